@@ -3,9 +3,14 @@
 256^3 uint8 bonsai (stand-in) at 1920x1080, dt_scale 0.5 ("512 steps/ray"), plus the achieved
 fraction of the HBM-read roofline (BASELINE.json / SURVEY.md 8d, config C2).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--batch B]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--batch B] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (typed without torchrun, `--gpus N` with N > 1 starts its own ranks as a child torch.distributed.run and relays the line)
+
+A plain run measures the headline alone: set-up, pre-roll and W warm-up steps, ONE window of exactly K timed steps, the line.  --full adds
+everything beside it: the window three times (median), the still-camera and tolerance-walk windows, `latency`, `extras` (C3, C4, C5, the
+compute twin, dense kernels), `cpu_baseline` and, at N > 1, the rotating root, the single-process group and C5 through the same driver.
+--dump-outputs DIR writes what the last timed step computed (its frames, as float32 .npy files) for output-for-output comparisons.
 
 A "step" is one LAUNCH: one pass of the raycast over a batch of `batch` frames, every frame its own camera (vk_render_batch; the
 reference keeps frames in flight through its queue, src/lib.rs:178-194).  K steps are timed, exactly.  At N = 1 the launch writes
@@ -19,8 +24,8 @@ value   = S_ref * M / t  [Mray-steps/s]: S_ref = loop iterations the reference s
           alpha >= 0.95 early-out), counted by the kernel itself in untimed counting launches (the mean over the
           launch's cameras) and equal to the oracle's count (tests).  Volume resident in HBM.  ONE contiguous timed
           window of exactly K steps (M = K * batch frames; `timed_frames`, `launches_per_region`), the same rule at
-          every N.  The window is repeated 3 times and the median reported (`repeats`, `repeat_ms_per_step` in run
-          order); an untimed pre-roll of the same path brings the GPU to its sustained clocks first (`preroll_frames`).
+          every N.  With --full the window is repeated 3 times and the median reported (`repeats`, `repeat_ms_per_step` in
+          run order); an untimed pre-roll of the same path brings the GPU to its sustained clocks first (`preroll_frames`).
           The frames of a launch are consecutive frames of an orbit around the config's camera (yaw step 2 pi / 1024),
           every frame its own camera; the same launch with ONE camera repeated is reported beside it (`still_camera`).
 roofline: algorithmic bytes of one launch = batch * (S_sampled * B_step + W*H * 8 B), B_step = 8 B (8 u8 taps) or 16 B
@@ -103,7 +108,15 @@ def parse():
     ap.add_argument("--no-rotate", action="store_true", help="N > 1: skip the second window with a rotating root (rotating_root in the JSON line)")
     ap.add_argument("--headline-only", action="store_true", help="only the headline's launches (no still-camera window, no single-frame launches): what tools/prof.sh profiles, so that a kernel's mean duration under rocprofv3 is the headline launch's")
     ap.add_argument("--force-dist", action="store_true", help="use the partition + gather driver even at N = 1 (the like-for-like baseline of the N > 1 lines)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also every side measurement (window repeated 3 times, still camera, tolerance walk, latency, "
+                                                        "extras, cpu_baseline, rotating root); without it a run times the headline window alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the frames of the last one to DIR/*.npy (float32, under 64 MB: "
+                                                          "the last frame, strided if large, and a fixed seeded sample of pixels over the whole step)")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run is the headline alone: every side measurement is off, as if each had been switched off by hand
+        args.headline_only = args.no_extras = args.no_cpu_baseline = args.no_rotate = True
+    return args
 
 
 def time_launches(ctx, fn, iters, warm=3, groups=3, min_warm_ms=40.0):
@@ -290,7 +303,7 @@ def c5_at_n(world, timeout_s=240):
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "GROUP_RANK", "GROUP_WORLD_SIZE", "ROLE_RANK", "ROLE_WORLD_SIZE", "ROLE_NAME",
                         "MASTER_ADDR", "MASTER_PORT", "VK_BENCH_TRANSPORT") and not k.startswith("TORCHELASTIC_")}
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--config", "c5", "--steps", "8", "--warmup", "2", "--no-extras", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--config", "c5", "--steps", "8", "--warmup", "2", "--full", "--no-extras", "--no-cpu-baseline"]
     try:
         proc = subprocess.Popen(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
         try:
@@ -607,7 +620,7 @@ def make_submitter(R):
     N > 1 (and --force-dist): BatchTileRenderer -- partition, gather, un-tile (R.btr: run_windows swaps it for the rotating-root renderer)."""
     BatchTileRenderer, H, V, W, batch, cam_list, ctx, dist, pipe = R.BatchTileRenderer, R.H, R.V, R.W, R.batch, R.cam_list, R.ctx, R.dist, R.pipe
     rehearsal, stream, torch, use_dist, world = R.rehearsal, R.stream, R.torch, R.use_dist, R.world
-    btr = transport = None
+    btr = transport = frames = None
     pipe_now = [pipe]      # (swapped for the tolerance-mode run)
     launch_ev = []  # (start, end) HIP events around every batch launch of the timed region
     if not use_dist:
@@ -663,6 +676,7 @@ def make_submitter(R):
             R.btr.flush()
             btr_i[0] = 0
     R.btr, R.cams_now, R.flush, R.launch_ev, R.pipe_now, R.submit, R.transport = btr, cams_now, flush, launch_ev, pipe_now, submit, transport
+    R.frames = frames  # N = 1: the launch's output buffer (N > 1: the renderer's, on the root)
 
 
 def make_timed_region(R):
@@ -718,8 +732,39 @@ def make_timed_region(R):
     R.timed_region = timed_region
 
 
+DUMP_FRAME_BYTES = 40 * 10**6  # the last frame, every s-th row and column for the least s that fits (s = 1 up to 1080p)
+DUMP_SAMPLE_PIXELS = 1 << 20   # 16.8 MB of float32 RGBA; with the frame, under 64 MB at every config
+
+
+def dump_outputs(R, out_dir):
+    """--dump-outputs: the frames of the last timed step as the caller of the timed path receives them (rgba16f; written as float32), for
+    comparing two builds output for output -- `last_frame.npy` [H/s, W/s, 4], the step's last frame, and `pixel_sample.npy` [2^20, 4], pixels
+    of all the step's frames at fixed positions (numpy default_rng(0x5EED), sorted flat indices into [batch, H, W]).  Rank 0 only; at N > 1
+    (and --force-dist) the frames the root assembled."""
+    import numpy as np
+
+    if R.rank != 0:
+        return
+    torch, frames = R.torch, R.frames
+    if frames is None:  # the partition + gather driver: the root's buffer that holds the last batch un-tiled
+        frames = R.btr.frames[max((0, 1), key=lambda s_: R.btr._frames_bid[s_])]
+    torch.cuda.synchronize()
+    B, H, W = frames.shape[:3]
+    s = 1
+    while -(-H // s) * -(-W // s) * 16 > DUMP_FRAME_BYTES:
+        s += 1
+    last = frames[B - 1, ::s, ::s].float().cpu().numpy()
+    n = B * H * W
+    idx = np.arange(n) if n <= DUMP_SAMPLE_PIXELS else np.sort(np.random.default_rng(0x5EED).integers(0, n, DUMP_SAMPLE_PIXELS))
+    sample = frames.reshape(n, 4).index_select(0, torch.from_numpy(idx).to(frames.device)).float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "last_frame.npy"), last)
+    np.save(os.path.join(out_dir, "pixel_sample.npy"), sample)
+
+
 def run_windows(R):
-    """Pre-roll, warm-up, the window of K steps (three times, median), and beside it the still-camera window, the tolerance walk, the rotating root."""
+    """Pre-roll, warm-up, the window of K steps (with --full three times, median, and beside it the still-camera window, the tolerance walk, the
+    rotating root); --dump-outputs writes the last step's frames."""
     BatchTileRenderer, K, V, args, batch, blob, btr, cam_list, cams_now = R.BatchTileRenderer, R.K, R.V, R.args, R.batch, R.blob, R.btr, R.cam_list, R.cams_now
     ctx, dist, flags, launch_ev, pipe, pipe_now = R.ctx, R.dist, R.flags, R.launch_ev, R.pipe, R.pipe_now
     rehearsal, timed_frames, timed_region = R.rehearsal, R.timed_frames, R.timed_region
@@ -737,9 +782,10 @@ def run_windows(R):
             timed_region(batch, False)
         preroll_frames = (2 + n_pre) * batch
     timed_region(args.warmup * batch, False) if args.warmup else None
-    # The window of `timed_frames` frames, three times (a single window is at the mercy of one host hiccup -- a default
-    # run on a busy box once reported 27.5 ms of wall time around 20.3 ms of launches); the median is reported.
-    repeats = 3
+    # The window of `timed_frames` frames; with --full three times (a single window is at the mercy of one host hiccup -- a default
+    # run on a busy box once reported 27.5 ms of wall time around 20.3 ms of launches) and the median is reported.  A plain run times
+    # exactly K steps, once.
+    repeats = 3 if args.full else 1
 
     def measure():
         runs = []
@@ -751,6 +797,8 @@ def run_windows(R):
         return runs[len(runs) // 2] + (order_ms,)
 
     elapsed, evs, run_order_ms = measure()
+    if args.dump_outputs:
+        dump_outputs(R, args.dump_outputs)  # before any other window overwrites the frames
     root_skip_fixed = btr.root_skip if use_dist else 0
     wire_info = {"format": "rgb" if btr.ch == 3 else "rgba", "bytes_per_pixel": ctx.wire_pixel_bytes, "slot_capacity": btr.cap,
                  "tile_bytes": TILE * TILE * ctx.wire_pixel_bytes} if use_dist else None

@@ -647,3 +647,38 @@ def test_fast_walk_tolerance_mode(V, O, golden, cameras, golden_volumes):
         ref, rsteps, _ = O.render(cam, v, W, H, dt_scale=dt)
         img, steps, _ = gpu_render(V, cam, v, W, H, dt=dt, layout=V.LAYOUT_PACKED, flags=fast)
         check(img, steps, ref, rsteps, (trial, dims, dt), px_bar=3e-2, steps_bar=0.01)
+
+
+def test_bench_plain_line_and_dumped_outputs(V, O, tmp_path):
+    """`bench.py --steps 2 --warmup 1 --dump-outputs DIR` at N = 1: a plain run times exactly K steps once and carries no side measurement,
+    and what it dumps is the last timed step's frames -- the last one bitwise the single-frame launch on that frame's orbit camera, the
+    seeded pixel sample consistent with it -- in float32, under 64 MB."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "VK_BENCH_REHEARSAL")}
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 2 and d["launches_per_region"] == 2 and d["repeats"] == 1 and d["value"] > 0 and d["unit"] == "Mray-steps/s"
+    assert abs(d["ms_per_step"] * d["steps"] * 1e-3 / d["timed_region_s"] - 1.0) < 1e-5
+    for key in ("metric", "higher_is_better", "dtype", "roofline"):
+        assert key in d, key
+    for key in ("still_camera", "fast_walk", "latency", "extras", "cpu_baseline"):
+        assert key not in d, key
+    last, sample = np.load(out / "last_frame.npy"), np.load(out / "pixel_sample.npy")
+    assert last.dtype == np.float32 and sample.dtype == np.float32 and last.nbytes + sample.nbytes < 64e6
+    B, W, H = d["frames_per_launch"], 1920, 1080
+    assert last.shape == (H, W, 4) and sample.shape == (1 << 20, 4)
+    cam = V.Camera(1.0, 0.5, 1.0 + 6.28318 * (B - 1) / 1024, (0.5, 0.5, 0.5), W / H).get_proj_view_matrix()
+    img16, _, _ = gpu_render(V, cam, O.volume_standin_u8(256), W, H, dt=0.5, out=V.OUT_RGBA16F, want_steps=False)
+    assert (last.astype(np.float16).view(np.uint16) == img16.view(np.uint16)).all()
+    idx = np.sort(np.random.default_rng(0x5EED).integers(0, B * H * W, 1 << 20))
+    f, y, x = idx // (H * W), (idx // W) % H, idx % W
+    mine = f == B - 1
+    assert mine.any() and (sample[mine] == last[y[mine], x[mine]]).all()

@@ -534,7 +534,7 @@ def test_bench_multi_rank_flow_rehearsal(V, O, how):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--no-extras", "--no-cpu-baseline"]
+    tail = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "VK_BENCH_REHEARSAL")}
     if how == "plain":
         cmd = [sys.executable] + tail
@@ -575,7 +575,7 @@ def test_bench_c5_two_rank_rehearsal(V, O, what):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline"]
     cmd += ["--config", "c5", "--no-extras"] if what == "config_c5" else ["--no-rotate"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "VK_BENCH_REHEARSAL")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=root)
