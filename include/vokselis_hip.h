@@ -154,6 +154,26 @@ int vk_volume_generate_xor(vk_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, f
 int vk_volume_empty_fraction(vk_ctx *ctx, double *fraction);
 int vk_volume_info(vk_ctx *ctx, uint32_t dims[3], int *format, int *layout, size_t *device_bytes);
 
+/* Runtime transfer function of VK_MODE_NAIVE_TRILINEAR: a context-wide RGBA table that replaces the built-in transfer and
+ * palette (min(0.9, v), smoothstep, the cosine "vertigo" palette: raycast_naive.wgsl:104-110) until it is reset.
+ * rgba: n entries of 4 floats (r, g, b, a), not premultiplied, alpha in [0, 1], spread evenly over the sample values
+ * [lo, hi] (R8 volumes: the normalised value, as the shader sees it; R16F: the value).  Per step, with x the filtered sample
+ * on the kernel's scale (R8: 0..255, S = 255; R16F: the value, S = 1) and k1 = (n-1) / ((hi-lo) S), k2 = -lo (n-1) / (hi-lo)
+ * rounded once to f32:  u = min(max(fma(x, k1, k2), 0), n-1);  i = min(floor(u), n-2);  c = lerp(T[i], T[i+1], u - i);
+ * w = (1 - A) c.a;  C += w c.rgb;  A += w  -- the early-out, the sRGB step and the miss colour as without a table.
+ * The skip maps and vk_volume_empty_fraction follow the table: a cell is empty iff its taps are finite and every entry
+ * from floor(u(min tap)) - 1 to floor(u(max tap)) + 2 has alpha 0.
+ * rgba == NULL resets to the built-in transfer.  VK_ERR_INVALID (the previous table stays in force): 2 <= n <=
+ * VK_TF_MAX_ENTRIES violated, a non-finite entry, a colour beyond +-VK_TF_MAX_COLOUR, an alpha outside [0, 1], !(lo < hi) or non-finite bounds, or a call
+ * between vk_frame_begin and vk_frame_end.  Otherwise the call drains every frame slot (as vk_ctx_sync), stores the table
+ * and rebuilds the skip maps of the current volume; frames recorded before it render with the old table.  The table stays
+ * in force across vk_volume_upload / _upload_device / vk_volume_generate.  Layouts: LINEAR, PACKED, PACKED_PAIRS; NAIVE
+ * renders of BRICKED / QUADS / STAGED volumes, and VK_RENDER_FAST_WALK, are VK_ERR_UNSUPPORTED while a table is set.
+ * COMPUTE_NEAREST and PROCEDURAL ignore it. */
+#define VK_TF_MAX_ENTRIES 256
+#define VK_TF_MAX_COLOUR 1e30f /* |r|, |g|, |b| at most this: the difference of two neighbouring entries stays finite */
+int vk_set_transfer_function(vk_ctx *ctx, const float *rgba, uint32_t n, float lo, float hi);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

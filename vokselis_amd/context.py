@@ -195,6 +195,21 @@ class Context:
     def sync(self):
         N.check(self._h, N.lib().vk_ctx_sync(self._h))
 
+    def set_transfer_function(self, table, domain=(0.0, 1.0)):
+        """Runtime transfer function of MODE_NAIVE_TRILINEAR (vk_set_transfer_function): `table` is an (n, 4) float32 array of RGBA
+        entries (not premultiplied, alpha in [0, 1], 2 <= n <= 256) spread evenly over the sample values `domain` = (lo, hi) -- normalised
+        values for R8 volumes, values for R16F.  It replaces the built-in transfer and palette (raycast_naive.wgsl:104-110) until
+        `table` is None, which resets.  Drains the frames in flight and rebuilds the skip maps of the current volume."""
+        L = N.lib()
+        if table is None:
+            N.check(self._h, L.vk_set_transfer_function(self._h, None, 0, 0.0, 1.0))
+            return
+        t = np.ascontiguousarray(table, dtype=np.float32)
+        if t.ndim != 2 or t.shape[1] != 4:
+            raise ValueError("transfer table: an (n, 4) array of RGBA entries")
+        lo, hi = domain
+        N.check(self._h, L.vk_set_transfer_function(self._h, t.ctypes.data_as(C.POINTER(C.c_float)), t.shape[0], float(lo), float(hi)))
+
     # -- frames in flight: the queue running ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain (src/context.rs:118,252)
     def frames_in_flight(self, k: int):
         """vk_ctx_frames_in_flight: a ring of k frame surfaces, each on its own stream (1: one surface, the default)."""
@@ -325,6 +340,19 @@ class Context:
         ms = C.c_float()
         N.check(self._h, N.lib().vk_timer_elapsed_ms(self._h, C.byref(ms)))
         return ms.value
+
+
+def transfer_table(points, n: int = 256) -> np.ndarray:
+    """A piecewise-linear (n, 4) float32 transfer table from control points (x, r, g, b, a), x in the table's domain mapped to
+    [0, 1] (entry j sits at x = j / (n - 1)); constant beyond the first and last point."""
+    p = np.asarray(points, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 5 or len(p) < 1:
+        raise ValueError("transfer_table: control points are rows (x, r, g, b, a)")
+    if not 2 <= n <= N.TF_MAX_ENTRIES:
+        raise ValueError("transfer_table: 2 <= n <= %d entries" % N.TF_MAX_ENTRIES)
+    p = p[np.argsort(p[:, 0], kind="stable")]
+    x = np.arange(n, dtype=np.float64) / (n - 1)
+    return np.stack([np.interp(x, p[:, 0], p[:, 1 + k]) for k in range(4)], axis=1).astype(np.float32)
 
 
 class VolumeTexture:

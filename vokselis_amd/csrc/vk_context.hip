@@ -137,6 +137,7 @@ int vk_ctx_destroy(vk_ctx *ctx) {
     ctx->fif_k = 1;
     comm_release(ctx);
     free_volume(ctx);
+    if (ctx->d_tf) (void)hipFree(ctx->d_tf);
     if (ctx->backbuffer) (void)hipFree(ctx->backbuffer);
     if (ctx->steps) (void)hipFree(ctx->steps);
     if (ctx->counters) (void)hipFree(ctx->counters);

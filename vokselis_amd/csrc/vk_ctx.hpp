@@ -7,6 +7,7 @@
 //   vk_render.hip          vk_render / vk_render_partition: argument checks, LaunchDesc, kernel choice
 //   vk_batch.hip           vk_render_batch: many frames, one launch
 //   vk_launch_cells.hip    instantiates the cell-layout march kernels      (vk_march.hpp)
+//   vk_launch_tf.hip       instantiates the cell march under a transfer table (vk_march.hpp)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)
@@ -15,6 +16,7 @@
 
 #include "../../include/vokselis_hip.h"
 #include "vk_common.hpp"
+#include "vk_tf.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>  // types only: the library is loaded on first use (vk_comm.hip)
@@ -47,6 +49,11 @@ struct vk_ctx {
     int vol_kind = -1;  // vk::VolKind
     double empty_fraction = 0.0;  // share of cells that are exactly transparent (packed layouts)
     vk::VolumeDesc vdesc{};
+    // runtime transfer function (vk_set_transfer_function): d_tf holds the n RGBA entries, then the n + 1 prefix counts of non-zero
+    // alphas the emptiness predicate reads (vk_tf.hpp); nullptr: the built-in transfer
+    float *d_tf = nullptr;
+    uint32_t tf_n = 0;
+    float tf_lo = 0.0f, tf_hi = 1.0f;
 
     // uniforms (host copies; passed to kernels by value)
     unsigned char uniform[48] = {0};
@@ -181,6 +188,7 @@ inline size_t px_bytes(int fmt) { return fmt == VK_OUT_RGBA16F ? 8 : 16; }
 inline size_t wire_px_bytes(int fmt, int wire) { return wire == VK_WIRE_RGB ? px_bytes(fmt) / 4 * 3 : px_bytes(fmt); }
 
 // ---- shared between translation units --------------------------------------------------------------------
+int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float lo, float hi);  // vk_volume.hip: the current volume's maps under a table (nullptr: built-in)
 int frames_drain(vk_ctx *ctx);   // vk_context.hip: wait for the work of every frame slot (one stream when fif_k == 1)
 void free_volume(vk_ctx *ctx);   // vk_volume.hip
 void comm_release(vk_ctx *ctx);  // vk_comm.hip
@@ -203,6 +211,7 @@ uint32_t launch_flags(const vk_ctx *ctx, uint32_t render_flags, bool batch);
 
 // the kernel-instantiating TUs: each launches on ctx->stream and returns; the caller checks hipGetLastError
 void launch_cells(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, bool skip, bool safe, int walk /* vk_march.hpp: WalkKind */);
+void launch_cells_tf(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_tf.hip
 void launch_staged(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, const float *cam);
 void launch_compute(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, bool records, bool skip);
 void launch_procedural(vk_ctx *ctx, const vk::LaunchDesc &L, uint32_t grid, bool count, float time, bool device_sine);

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "vk_common.hpp"
+#include "vk_tf.hpp"
 #include "vk_trips.hpp"
 
 namespace vk {
@@ -64,6 +65,18 @@ __device__ __forceinline__ int walk_steps_neg(float r, int nleft) {
     return k;
 }
 
+// The runtime transfer function (vk_tf.hpp): entries i and i + 1 of the table, lerped per channel.  The index is clamped to
+// [0, n - 2] whatever x is (a NaN reads entry 0): the two 16-byte loads stay inside the table.
+__device__ __forceinline__ void tf_lookup(const TfDesc &D, float x, float &cr, float &cg, float &cb, float &ca) {
+    const float u = tf_u(x, D.k1, D.k2, D.umax);
+    const int i = tf_index(u, D.imax);
+    const float f = u - (float)i;
+    const float4 *T = reinterpret_cast<const float4 *>(D.rgba);
+    const float4 t0 = T[i], t1 = T[i + 1];
+    cr = fmaf(f, t1.x - t0.x, t0.x); cg = fmaf(f, t1.y - t0.y, t0.y);
+    cb = fmaf(f, t1.z - t0.z, t0.z); ca = fmaf(f, t1.w - t0.w, t0.w);
+}
+
 // ---- the march, resumable ---------------------------------------------------------------------
 // Everything a ray needs to continue: the accumulators of the reference loop (p, alpha, colour sums), its per-ray constants and
 // where its pixel goes.  64 bytes.
@@ -118,9 +131,12 @@ enum WalkKind : int { WALK_LOOP = 0, WALK_FMA = 2 };
 // right after requesting its cell, locates the next position and requests its distance, then filters and composites.  One byte load is wasted
 // when the ray ends with that sample.  Walkers locate their new position at the end of their walk, as they did at the top of the next trip before.
 // Per ray the same operations in the same order on every variable.
-template <int VOL, bool SKIP, bool SAFE, bool COUNT, bool BOUNDED = false, int WALK = WALK_LOOP, bool AHEAD = false>
+//
+// TF (the table kernels of vk_launch_tf.hip): the runtime transfer function replaces transfer_alpha and the palette (tf_lookup).
+template <int VOL, bool SKIP, bool SAFE, bool COUNT, bool BOUNDED = false, int WALK = WALK_LOOP, bool AHEAD = false, bool TF = false>
 __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const uint32_t budget, Census &cs,
-                                      const uint32_t *lut = nullptr, const float walk_cap = __builtin_inff(), const float walk_cap_all = __builtin_inff()) {
+                                      const uint32_t *lut = nullptr, const float walk_cap = __builtin_inff(), const float walk_cap_all = __builtin_inff(),
+                                      const TfDesc *tfd = nullptr) {
     constexpr bool PACKED = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16);
     constexpr bool BRICK9 = (VOL == VOL_B9U8 || VOL == VOL_B9F16);
     static_assert(!AHEAD || (PACKED && SKIP && !SAFE && !BOUNDED), "probe-ahead: the skip kernels' fast path, unbounded");
@@ -334,7 +350,9 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
         }
         float c0 = fmaf(fy, c10 - c00, c00), c1 = fmaf(fy, c11 - c01, c01);
         float r = fmaf(fz, c1 - c0, c0);
-        const float a = transfer_alpha<(VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_LINEAR_U8 || VOL == VOL_B9U8) ? 1 : 0>(r);
+        float a, tr = 0.0f, tg = 0.0f, tb = 0.0f;
+        if constexpr (TF) tf_lookup(*tfd, r, tr, tg, tb, a);
+        else a = transfer_alpha<(VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_LINEAR_U8 || VOL == VOL_B9U8) ? 1 : 0>(r);
         if (COUNT && le) atomicAdd(le, (1u << 7) + (a != 0.0f ? 1u << 14 : 0u));
         if (SKIP) {
             // A cell is non-empty as soon as one of its 8 taps is above the threshold; the FILTERED value of a sample inside it
@@ -350,6 +368,17 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
                 }
                 continue;
             }
+        }
+        if constexpr (TF) {  // the table's colour, composited as below: C = sum w * c.rgb (no palette, no 0.5 A + 0.5 G at the end)
+            if (COUNT) { n_iter++; n_samp++; if (wave_leader()) w_sample++; }
+            const float w = (1.0f - A) * a;
+            Gr = fmaf(w, tr, Gr); Gg = fmaf(w, tg, Gg); Gb = fmaf(w, tb, Gb);
+            A = A + w;
+            if (!AHEAD) {
+                px = px + sx; py = py + sy; pz = pz + sz;  // :118
+                nleft += 1;
+            }
+            continue;
         }
         // vertigo(): cos(6.28318*(c*a + d)); v_cos_f32 takes revolutions
         constexpr double kk = 6.28318 / 6.283185307179586476925;
@@ -380,8 +409,9 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
 // The request one step past the ray's end reads a real (clamped) table entry and is never used.
 // CELL_LUT: the tables hold cell indices (the skip kernels' copy) instead of byte offsets; `budget` bounds the trips
 // (0xffffffff: none) so that the skip kernels can run stretches of it between probing windows.
-template <int VOL, bool COUNT, bool CELL_LUT = false>
-__device__ __forceinline__ bool march_stream(const VolumeDesc &V, RayState &r, Census &cs, const uint32_t *lut, uint32_t budget = 0xffffffffu) {
+template <int VOL, bool COUNT, bool CELL_LUT = false, bool TF = false>
+__device__ __forceinline__ bool march_stream(const VolumeDesc &V, RayState &r, Census &cs, const uint32_t *lut, uint32_t budget = 0xffffffffu,
+                                             const TfDesc *tfd = nullptr) {
     float px = r.px, py = r.py, pz = r.pz, A = r.A, Gr = r.Gr, Gg = r.Gg, Gb = r.Gb;
     uint32_t left = r.left;
     const float sx = r.sx, sy = r.sy, sz = r.sz;
@@ -407,6 +437,13 @@ __device__ __forceinline__ bool march_stream(const VolumeDesc &V, RayState &r, C
         xlerp_cell<VOL>(cur, fx, c00, c10, c01, c11);
         float l0 = fmaf(fy, c10 - c00, c00), l1 = fmaf(fy, c11 - c01, c01);
         float v = fmaf(fz, l1 - l0, l0);
+        if constexpr (TF) {
+            float cr, cg, cb, a;
+            tf_lookup(*tfd, v, cr, cg, cb, a);
+            const float w = (1.0f - A) * a;
+            Gr = fmaf(w, cr, Gr); Gg = fmaf(w, cg, Gg); Gb = fmaf(w, cb, Gb);
+            A = A + w;
+        } else {
         const float a = transfer_alpha<(VOL == VOL_P8 || VOL == VOL_P16) ? 1 : 0>(v);
         constexpr double kk = 6.28318 / 6.283185307179586476925;
         constexpr float pc0 = (float)(1.0 * kk), pc1 = (float)(1.7 * kk), pc2 = (float)(0.4 * kk);
@@ -417,6 +454,7 @@ __device__ __forceinline__ bool march_stream(const VolumeDesc &V, RayState &r, C
         const float w = (1.0f - A) * a;  // :112-114
         Gr = fmaf(w, cr, Gr); Gg = fmaf(w, cg, Gg); Gb = fmaf(w, cb, Gb);
         A = A + w;
+        }
         left -= 1u;  // :101
         fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);
         return left != 0u && A < 0.95f;
@@ -616,130 +654,9 @@ __device__ __forceinline__ void clear_inactive_strip(const LaunchDesc &L, uint32
 // AHEAD: the probe-ahead trip (march<..., AHEAD>), an instantiation of its own -- it needs six more registers, and the launches that fill the machine keep the leaner kernel
 template <int VOL, bool SKIP, bool SAFE, int WALK, bool AHEAD, int OUT, bool COUNT>
 __global__ __launch_bounds__(64) void raymarch_naive_kernel(const LaunchDesc L, const VolumeDesc V) {
-    static_assert(VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16 || (!SKIP && SAFE), "linear / bricked layouts: no skip map, clamped indices");
-    static_assert(SKIP || WALK == WALK_LOOP, "the closed-form walks are variants of the skip kernels");
-    static_assert(!AHEAD || (SKIP && !SAFE), "probe ahead: the skip kernels' fast path");
-    if (blockIdx.x >= L.grid_march) { clear_inactive_strip<OUT>(L, blockIdx.x - L.grid_march, threadIdx.x); return; }  // wave-uniform
-    const uint32_t lb = logical_block(blockIdx.x);
-    if (lb >= L.n_blocks) return;  // wave-uniform
-    const uint32_t lane = threadIdx.x;
-    unsigned long long t_start = 0;
-    if (COUNT) t_start = __builtin_amdgcn_s_memrealtime();
-    const FrameView fv = frame_view(L, lb);
-    const PixelMap pm = map_pixel(L, fv, lane);
-    {
-        // Screen-space cull (wave-uniform): an 8x8 block wholly outside the projected cube's bounding
-        // rectangle (host-computed, padded) holds only misses: clear colour, no ray set-up.
-        const int bx0 = pm.x - (int)(lane & 7u), by0 = pm.y - (int)(lane >> 3);
-        // ... and so does every block of a tile the box's silhouette cannot reach (the inactive tiles behind the order's
-        // active positions: a whole-frame launch covers them too, a partition never launches them)
-        if (pm.pos >= fv.n_active || bx0 + 8 <= fv.cull_x0 || bx0 >= fv.cull_x1 || by0 + 8 <= fv.cull_y0 || by0 >= fv.cull_y1) {
-            if (!pm.valid) return;
-            store_out<OUT>(L, pm, 0.0f, 0.0f, 0.0f);
-            if (COUNT && L.steps) L.steps[(size_t)pm.y * L.W + (size_t)pm.x] = 0;
-            return;
-        }
-    }
-    constexpr bool USE_LUT = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16) && !SAFE;
-    extern __shared__ uint32_t cell_lut[];
-    if (USE_LUT) {  // all 64 lanes are still here
-        load_cell_luts(V, cell_lut, lane);
-        __syncthreads();
-    }
-    if (!pm.valid) return;
-
-    // --- ray: SURVEY A.1 step 1 (replaces vs_main + rasteriser) ---
-    float fxp = (float)pm.x + 0.5f, fyp = (float)pm.y + 0.5f;
-    float ndcx = (2.0f * fxp) / (float)L.W - 1.0f;
-    float ndcy = 1.0f - (2.0f * fyp) / (float)L.H;
-    float q[4];
-    mat4_mul_vec4(fv.inv_proj, ndcx, ndcy, 1.0f, 1.0f, q);
-    const float eye[3] = {fv.eye[0], fv.eye[1], fv.eye[2]};
-    float dir[3] = {q[0] / q[3] - eye[0], q[1] / q[3] - eye[1], q[2] / q[3] - eye[2]};
-    normalize3(dir[0], dir[1], dir[2]);
-
-    float t0, t1;
-    intersect_box(eye, dir, 0.0f, 1.0f, t0, t1);
-    Census cs;
-    const bool trip_log = COUNT && L.trace && (L.flags & LF_TRIP_LOG);
-    if (trip_log) {
-        cs.log_cap = L.trip_log_cap;
-        cs.log = reinterpret_cast<uint32_t *>(L.trace) + (size_t)lb * cs.log_cap;
-    }
-    // colour is accumulated as G = sum w*cos(phase); C = 0.5*A + 0.5*G at the end (sum w == A)
-    float Gr = 0.0f, Gg = 0.0f, Gb = 0.0f, A = 0.0f;
-    float Cr = 0.0f, Cg = 0.0f, Cb = 0.0f;
-    if (!(t0 > t1)) {  // :91-93
-        t0 = fmaxf(t0, 0.0f);  // :94
-        const float fnx = (float)V.nx, fny = (float)V.ny, fnz = (float)V.nz;
-        float dtx = 1.0f / (fnx * fabsf(dir[0]));
-        float dty = 1.0f / (fny * fabsf(dir[1]));
-        float dtz = 1.0f / (fnz * fabsf(dir[2]));
-        const float dt = L.dt_scale * fminf(dtx, fminf(dty, dtz));  // :97-99
-        float px = eye[0] + t0 * dir[0], py = eye[1] + t0 * dir[1], pz = eye[2] + t0 * dir[2];  // :100
-        const float sx = dir[0] * dt, sy = dir[1] * dt, sz = dir[2] * dt;  // :118
-        RayState r;
-        r.left = min(count_trips(t0, t1, dt), 0x7fffffffu);  // :101
-        r.px = px; r.py = py; r.pz = pz; r.sx = sx; r.sy = sy; r.sz = sz;
-        r.A = 0.0f; r.Gr = 0.0f; r.Gg = 0.0f; r.Gb = 0.0f;  // colour sums: G = sum w*cos(phase); C = A/2 + G/2 (sum w == A)
-        r.out = (uint32_t)pm.out_index;
-        // (not in the skip kernels: a ray's nominal length says little about its work there -- C2 at 64 orbit frames per launch 0.06509 -> 0.06467 ms without)
-        if (!SKIP && (L.flags & LF_WAVE_PRIORITY)) set_wave_priority(true, r.left, fmaxf(fnx, fmaxf(fny, fnz)) / L.dt_scale);
-        if constexpr (USE_LUT && !SKIP) march_stream<VOL, COUNT>(V, r, cs, cell_lut);
-        else if constexpr (SKIP) {
-            if (L.flags & LF_ADAPTIVE_PROBING) {
-                // Adaptive probing (wave-uniform policy, any policy is exact: a sampled empty cell adds +0).  Probe for a
-                // window of 16 trips; if fewer than 1 in 8 of the wave's live rays skipped anything in it, the wave is in
-                // material that cannot be skipped: run the dense loop -- no distance look-up, and on the fast path
-                // software-pipelined -- for a stretch that doubles every time the next window confirms it (64 .. 512
-                // trips), then probe again.  Fog pays ~9 % of its trips at the probing price instead of all of them.
-                const uint32_t stretch0 = (L.flags & LF_LONG_STRETCHES) ? 256u : 64u;  // the census found (almost) nothing to skip
-                uint32_t stretch = stretch0;
-                for (;;) {
-                    cs.skips = 0;
-                    bool alive = march<VOL, true, SAFE, COUNT, true, WALK>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all);
-                    const unsigned long long live = __ballot(alive);
-                    if (live == 0ull) break;
-                    if (__popcll(__ballot(alive && cs.skips != 0u)) * 8 >= __popcll(live)) { stretch = stretch0; continue; }
-                    if constexpr (USE_LUT) alive = march_stream<VOL, COUNT, true>(V, r, cs, cell_lut, stretch);
-                    else alive = march<VOL, false, SAFE, COUNT, true>(V, r, stretch, cs, nullptr);
-                    if (__ballot(alive) == 0ull) break;
-                    stretch = min(stretch * 2u, 512u);
-                }
-            } else {
-                march<VOL, SKIP, SAFE, COUNT, false, WALK, AHEAD>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all);
-            }
-        }
-        else if constexpr (VOL == VOL_B9U8 || VOL == VOL_B9F16) march_b9_stream<VOL, COUNT>(V, r, cs);
-        else if constexpr (VOL == VOL_Q8 || VOL == VOL_QF16) march_quads_stream<VOL, COUNT>(V, r, cs);
-        else march<VOL, SKIP, SAFE, COUNT>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr);
-        A = r.A; Gr = r.Gr; Gg = r.Gg; Gb = r.Gb;
-        Cr = linear_to_srgb(fmaf(0.5f, Gr, 0.5f * A));  // :121-123
-        Cg = linear_to_srgb(fmaf(0.5f, Gg, 0.5f * A));
-        Cb = linear_to_srgb(fmaf(0.5f, Gb, 0.5f * A));
-    }
-    store_out<OUT>(L, pm, Cr, Cg, Cb);
-    if (COUNT) {
-        if (L.steps) L.steps[(size_t)pm.y * L.W + (size_t)pm.x] = (L.flags & LF_STEPS_ARE_TRIPS) ? cs.n_look : cs.n_iter;
-        if (L.counters) {
-            atomicAdd(&L.counters[0], (unsigned long long)cs.n_iter);
-            atomicAdd(&L.counters[1], (unsigned long long)cs.n_samp);
-            atomicAdd(&L.counters[2], (unsigned long long)cs.w_outer);
-            atomicAdd(&L.counters[3], (unsigned long long)cs.w_inner);
-            atomicAdd(&L.counters[4], (unsigned long long)cs.w_sample);
-            atomicAdd(&L.counters[5], (unsigned long long)cs.n_look);
-        }
-        if (L.trace && !trip_log) {  // stamps leave only through this debug buffer
-            unsigned long long t_end = __builtin_amdgcn_s_memrealtime();
-            atomicMin(&L.trace[4 * (size_t)lb], t_start);
-            atomicMax(&L.trace[4 * (size_t)lb + 1], t_end);
-            // where the wave ran: HW_ID (wave/simd/cu/sh/se fields) and XCC_ID
-            L.trace[4 * (size_t)lb + 2] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
-                                          ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
-            // wave-level work: march-loop trips | skip-walk trips << 20 | sample executions << 40
-            atomicAdd(&L.trace[4 * (size_t)lb + 3], (unsigned long long)cs.w_outer | ((unsigned long long)cs.w_inner << 20) | ((unsigned long long)cs.w_sample << 40));
-        }
-    }
+    constexpr bool TF = false;  // (the table kernels: vk_launch_tf.hip)
+    const TfDesc *tfd = nullptr;
+#include "vk_march_kernel_body.hpp"
 }
 
 }  // namespace vk

@@ -1,0 +1,133 @@
+// vk_march_kernel_body.hpp -- the body of the cell-march kernels, included inside them (no include guard): raymarch_naive_kernel
+// (vk_march.hpp) and raymarch_tf_kernel (vk_launch_tf.hip).  The including kernel defines the template parameters VOL, SKIP, SAFE, WALK,
+// AHEAD, OUT, COUNT, the constant TF (a runtime transfer function: vk_set_transfer_function) and `tfd`, its table (nullptr without one),
+// and takes its arguments L (LaunchDesc) and V (VolumeDesc) by value.  (Shared textually rather than as an inlined function: that
+// moved the register allocation of the existing kernels.)
+    static_assert(VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16 || (!SKIP && SAFE), "linear / bricked layouts: no skip map, clamped indices");
+    static_assert(SKIP || WALK == WALK_LOOP, "the closed-form walks are variants of the skip kernels");
+    static_assert(!AHEAD || (SKIP && !SAFE), "probe ahead: the skip kernels' fast path");
+    if (blockIdx.x >= L.grid_march) { clear_inactive_strip<OUT>(L, blockIdx.x - L.grid_march, threadIdx.x); return; }  // wave-uniform
+    const uint32_t lb = logical_block(blockIdx.x);
+    if (lb >= L.n_blocks) return;  // wave-uniform
+    const uint32_t lane = threadIdx.x;
+    unsigned long long t_start = 0;
+    if (COUNT) t_start = __builtin_amdgcn_s_memrealtime();
+    const FrameView fv = frame_view(L, lb);
+    const PixelMap pm = map_pixel(L, fv, lane);
+    {
+        // Screen-space cull (wave-uniform): an 8x8 block wholly outside the projected cube's bounding
+        // rectangle (host-computed, padded) holds only misses: clear colour, no ray set-up.
+        const int bx0 = pm.x - (int)(lane & 7u), by0 = pm.y - (int)(lane >> 3);
+        // ... and so does every block of a tile the box's silhouette cannot reach (the inactive tiles behind the order's
+        // active positions: a whole-frame launch covers them too, a partition never launches them)
+        if (pm.pos >= fv.n_active || bx0 + 8 <= fv.cull_x0 || bx0 >= fv.cull_x1 || by0 + 8 <= fv.cull_y0 || by0 >= fv.cull_y1) {
+            if (!pm.valid) return;
+            store_out<OUT>(L, pm, 0.0f, 0.0f, 0.0f);
+            if (COUNT && L.steps) L.steps[(size_t)pm.y * L.W + (size_t)pm.x] = 0;
+            return;
+        }
+    }
+    constexpr bool USE_LUT = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16) && !SAFE;
+    extern __shared__ uint32_t cell_lut[];
+    if (USE_LUT) {  // all 64 lanes are still here
+        load_cell_luts(V, cell_lut, lane);
+        __syncthreads();
+    }
+    if (!pm.valid) return;
+
+    // --- ray: SURVEY A.1 step 1 (replaces vs_main + rasteriser) ---
+    float fxp = (float)pm.x + 0.5f, fyp = (float)pm.y + 0.5f;
+    float ndcx = (2.0f * fxp) / (float)L.W - 1.0f;
+    float ndcy = 1.0f - (2.0f * fyp) / (float)L.H;
+    float q[4];
+    mat4_mul_vec4(fv.inv_proj, ndcx, ndcy, 1.0f, 1.0f, q);
+    const float eye[3] = {fv.eye[0], fv.eye[1], fv.eye[2]};
+    float dir[3] = {q[0] / q[3] - eye[0], q[1] / q[3] - eye[1], q[2] / q[3] - eye[2]};
+    normalize3(dir[0], dir[1], dir[2]);
+
+    float t0, t1;
+    intersect_box(eye, dir, 0.0f, 1.0f, t0, t1);
+    Census cs;
+    const bool trip_log = COUNT && L.trace && (L.flags & LF_TRIP_LOG);
+    if (trip_log) {
+        cs.log_cap = L.trip_log_cap;
+        cs.log = reinterpret_cast<uint32_t *>(L.trace) + (size_t)lb * cs.log_cap;
+    }
+    // colour is accumulated as G = sum w*cos(phase); C = 0.5*A + 0.5*G at the end (sum w == A)
+    float Gr = 0.0f, Gg = 0.0f, Gb = 0.0f, A = 0.0f;
+    float Cr = 0.0f, Cg = 0.0f, Cb = 0.0f;
+    if (!(t0 > t1)) {  // :91-93
+        t0 = fmaxf(t0, 0.0f);  // :94
+        const float fnx = (float)V.nx, fny = (float)V.ny, fnz = (float)V.nz;
+        float dtx = 1.0f / (fnx * fabsf(dir[0]));
+        float dty = 1.0f / (fny * fabsf(dir[1]));
+        float dtz = 1.0f / (fnz * fabsf(dir[2]));
+        const float dt = L.dt_scale * fminf(dtx, fminf(dty, dtz));  // :97-99
+        float px = eye[0] + t0 * dir[0], py = eye[1] + t0 * dir[1], pz = eye[2] + t0 * dir[2];  // :100
+        const float sx = dir[0] * dt, sy = dir[1] * dt, sz = dir[2] * dt;  // :118
+        RayState r;
+        r.left = min(count_trips(t0, t1, dt), 0x7fffffffu);  // :101
+        r.px = px; r.py = py; r.pz = pz; r.sx = sx; r.sy = sy; r.sz = sz;
+        r.A = 0.0f; r.Gr = 0.0f; r.Gg = 0.0f; r.Gb = 0.0f;  // colour sums: G = sum w*cos(phase); C = A/2 + G/2 (sum w == A)
+        r.out = (uint32_t)pm.out_index;
+        // (not in the skip kernels: a ray's nominal length says little about its work there -- C2 at 64 orbit frames per launch 0.06509 -> 0.06467 ms without)
+        if (!SKIP && (L.flags & LF_WAVE_PRIORITY)) set_wave_priority(true, r.left, fmaxf(fnx, fmaxf(fny, fnz)) / L.dt_scale);
+        if constexpr (USE_LUT && !SKIP) march_stream<VOL, COUNT, false, TF>(V, r, cs, cell_lut, 0xffffffffu, tfd);
+        else if constexpr (SKIP) {
+            if (L.flags & LF_ADAPTIVE_PROBING) {
+                // Adaptive probing (wave-uniform policy, any policy is exact: a sampled empty cell adds +0).  Probe for a
+                // window of 16 trips; if fewer than 1 in 8 of the wave's live rays skipped anything in it, the wave is in
+                // material that cannot be skipped: run the dense loop -- no distance look-up, and on the fast path
+                // software-pipelined -- for a stretch that doubles every time the next window confirms it (64 .. 512
+                // trips), then probe again.  Fog pays ~9 % of its trips at the probing price instead of all of them.
+                const uint32_t stretch0 = (L.flags & LF_LONG_STRETCHES) ? 256u : 64u;  // the census found (almost) nothing to skip
+                uint32_t stretch = stretch0;
+                for (;;) {
+                    cs.skips = 0;
+                    bool alive = march<VOL, true, SAFE, COUNT, true, WALK, false, TF>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd);
+                    const unsigned long long live = __ballot(alive);
+                    if (live == 0ull) break;
+                    if (__popcll(__ballot(alive && cs.skips != 0u)) * 8 >= __popcll(live)) { stretch = stretch0; continue; }
+                    if constexpr (USE_LUT) alive = march_stream<VOL, COUNT, true, TF>(V, r, cs, cell_lut, stretch, tfd);
+                    else alive = march<VOL, false, SAFE, COUNT, true, WALK_LOOP, false, TF>(V, r, stretch, cs, nullptr, __builtin_inff(), __builtin_inff(), tfd);
+                    if (__ballot(alive) == 0ull) break;
+                    stretch = min(stretch * 2u, 512u);
+                }
+            } else {
+                march<VOL, SKIP, SAFE, COUNT, false, WALK, AHEAD, TF>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd);
+            }
+        }
+        else if constexpr (VOL == VOL_B9U8 || VOL == VOL_B9F16) march_b9_stream<VOL, COUNT>(V, r, cs);
+        else if constexpr (VOL == VOL_Q8 || VOL == VOL_QF16) march_quads_stream<VOL, COUNT>(V, r, cs);
+        else march<VOL, SKIP, SAFE, COUNT, false, WALK_LOOP, false, TF>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, __builtin_inff(), __builtin_inff(), tfd);
+        A = r.A; Gr = r.Gr; Gg = r.Gg; Gb = r.Gb;
+        if constexpr (TF) {  // the table's colour sums are the colour
+            Cr = linear_to_srgb(Gr); Cg = linear_to_srgb(Gg); Cb = linear_to_srgb(Gb);
+        } else {
+            Cr = linear_to_srgb(fmaf(0.5f, Gr, 0.5f * A));  // :121-123
+            Cg = linear_to_srgb(fmaf(0.5f, Gg, 0.5f * A));
+            Cb = linear_to_srgb(fmaf(0.5f, Gb, 0.5f * A));
+        }
+    }
+    store_out<OUT>(L, pm, Cr, Cg, Cb);
+    if (COUNT) {
+        if (L.steps) L.steps[(size_t)pm.y * L.W + (size_t)pm.x] = (L.flags & LF_STEPS_ARE_TRIPS) ? cs.n_look : cs.n_iter;
+        if (L.counters) {
+            atomicAdd(&L.counters[0], (unsigned long long)cs.n_iter);
+            atomicAdd(&L.counters[1], (unsigned long long)cs.n_samp);
+            atomicAdd(&L.counters[2], (unsigned long long)cs.w_outer);
+            atomicAdd(&L.counters[3], (unsigned long long)cs.w_inner);
+            atomicAdd(&L.counters[4], (unsigned long long)cs.w_sample);
+            atomicAdd(&L.counters[5], (unsigned long long)cs.n_look);
+        }
+        if (L.trace && !trip_log) {  // stamps leave only through this debug buffer
+            unsigned long long t_end = __builtin_amdgcn_s_memrealtime();
+            atomicMin(&L.trace[4 * (size_t)lb], t_start);
+            atomicMax(&L.trace[4 * (size_t)lb + 1], t_end);
+            // where the wave ran: HW_ID (wave/simd/cu/sh/se fields) and XCC_ID
+            L.trace[4 * (size_t)lb + 2] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
+                                          ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
+            // wave-level work: march-loop trips | skip-walk trips << 20 | sample executions << 40
+            atomicAdd(&L.trace[4 * (size_t)lb + 3], (unsigned long long)cs.w_outer | ((unsigned long long)cs.w_inner << 20) | ((unsigned long long)cs.w_sample << 40));
+        }
+    }

@@ -75,6 +75,21 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
     const uint64_t n_blocks = L.n_blocks;
     uint32_t grid = (uint32_t)((n_blocks + 511) / 512 * 512);
     L.grid_march = grid;
+    // a runtime transfer function (vk_set_transfer_function) has kernels on the LINEAR / PACKED / PACKED_PAIRS layouts, walking with the loop
+    const bool tf = mode == VK_MODE_NAIVE_TRILINEAR && ctx->d_tf;
+    TfDesc T{};
+    if (tf) {
+        const int k = ctx->vol_kind;
+        if (k != VOL_LINEAR_U8 && k != VOL_LINEAR_F16 && k != VOL_P8 && k != VOL_P16 && k != VOL_PF16)
+            return fail(ctx, VK_ERR_UNSUPPORTED, "transfer function: NAIVE_TRILINEAR renders with a table need a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no table kernels; vk_set_transfer_function(NULL) resets)");
+        if (flags & VK_RENDER_FAST_WALK) return fail(ctx, VK_ERR_UNSUPPORTED, "transfer function: VK_RENDER_FAST_WALK has no table kernels");
+        float k1, k2;
+        tf_constants(ctx->tf_n, ctx->tf_lo, ctx->tf_hi, ctx->format == VK_FMT_R8_UNORM, k1, k2);
+        T.rgba = ctx->d_tf;
+        T.k1 = k1; T.k2 = k2;
+        T.umax = (float)(ctx->tf_n - 1u);
+        T.imax = (int32_t)ctx->tf_n - 2;
+    }
     if (mode != VK_MODE_NAIVE_TRILINEAR) L.clear_max_inactive = 0;  // (their kernels have no clearing blocks: every tile is active)
     // whole-frame batches: the strips that clear the inactive tiles ride behind the march blocks (clear_inactive_strip)
     const uint64_t clear_blocks = (uint64_t)L.clear_max_inactive * L.n_frames * ((L.ts * L.ts + 511u) / 512u);
@@ -115,6 +130,7 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
             if (V.max_off + 16 < (1ll << 32) && cell_lut_bytes(ctx->nx, ctx->ny, ctx->nz) <= 16384u && 64.0f * ulp < 0.25f / nmax && !(flags & VK_RENDER_SAFE)) safe = false;
         }
         if (ctx->vol_kind == VOL_S8U8 || ctx->vol_kind == VOL_S8F16) launch_staged(ctx, L, V, grid, count, reach_cam);
+        else if (tf) launch_cells_tf(ctx, L, V, T, grid, count, skip, safe);
         else launch_cells(ctx, L, V, grid, count, skip, safe, (flags & VK_RENDER_FAST_WALK) ? 2 : 0);  // (vk_march.hpp: WalkKind)
     }
     HIP_TRY(ctx, hipGetLastError());

@@ -1,0 +1,84 @@
+// vk_tf.hpp -- the runtime transfer function of NAIVE_TRILINEAR (vk_set_transfer_function): the table coordinate of a sample and the
+// emptiness predicate of a cell under the table, shared by the march kernels, the skip-map rebuild (vk_volume.hip) and the host
+// fuzz (tests/tf_fuzz.cpp, plain g++ under ASan / UBSan).
+//
+// x is the filtered sample on the kernel's own scale (R8: the filtered taps on 0..255; R16F: the value).  With k1, k2 from
+// tf_constants():  u = min(max(fma(x, k1, k2), 0), n - 1)  (a NaN sample reads entry 0),  i = min(floor(u), n - 2),  f = u - i,
+// c = fma(f, T[i+1] - T[i], T[i]) per channel.
+//
+// Why skipping stays exact.  Every f32 lerp of the filter, fma(f, b - a, a) with 0 <= f < 1, lies in [min(a, b), max(a, b)]: the
+// rounded difference times f stays below |b - a| in magnitude, and rounding to nearest never leaves an interval whose ends are
+// representable.  So a sample of a cell lies in [m, M], its smallest and largest taps; fma(x, k1, k2) with k1 > 0 rounds once and
+// is monotone, so floor(u(x)) is in [floor(u(m)), floor(u(M))] and the lookup reads entries of [floor(u(m)), floor(u(M)) + 1].
+// The predicate checks one guard entry more on each side.  If all of them have alpha 0, c.a = fma(f, +-0 - +-0, +-0) is +0, the
+// weight w = (1 - A) * 0 is +0 and the sample adds +0 to every accumulator: a skipped step and a sampled one leave the same bits.
+// (This needs finite colours in the lerp: vk_set_transfer_function refuses |r|, |g|, |b| > VK_TF_MAX_COLOUR = 1e30, so the difference of
+// two neighbours, and with it fma(+0, c, G) = G, stays finite.)
+// A cell with a non-finite tap is never empty.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define VK_TF_HD __host__ __device__ __forceinline__
+#else
+#define VK_TF_HD inline
+#endif
+
+namespace vk {
+
+constexpr int kTfMaxEntries = 256;
+
+// What the table kernels read (a kernel argument of their own: the kernels without a table keep their arguments as they are):
+// n RGBA f32 entries and the constants below, umax = n - 1, imax = n - 2.
+struct TfDesc {
+    const float *rgba;
+    float k1, k2, umax;
+    int32_t imax;
+};
+
+// k1 = (n-1) / ((hi-lo) S), k2 = -lo (n-1) / (hi-lo), each computed in double and rounded once to f32; S = 255 for R8 volumes, 1 for R16F
+inline void tf_constants(uint32_t n, float lo, float hi, bool r8, float &k1, float &k2) {
+    const double span = (double)hi - (double)lo, nm1 = (double)n - 1.0;
+    k1 = (float)(nm1 / (span * (r8 ? 255.0 : 1.0)));
+    k2 = (float)(-(double)lo * nm1 / span);
+}
+
+// the table coordinate u in [0, n - 1] (umax = n - 1)
+VK_TF_HD float tf_u(float x, float k1, float k2, float umax) { return fminf(fmaxf(fmaf(x, k1, k2), 0.0f), umax); }
+
+// the lower entry of the lerp (imax = n - 2)
+VK_TF_HD int tf_index(float u, int imax) {
+    const int i = (int)floorf(u);
+    return i < imax ? i : imax;
+}
+
+// prefix[j] = number of entries among T[0 .. j-1] whose alpha is not 0 (n + 1 values): the predicate is O(1) per cell
+inline void tf_alpha_prefix(const float *rgba, uint32_t n, uint32_t *prefix) {
+    prefix[0] = 0;
+    for (uint32_t j = 0; j < n; j++) prefix[j + 1] = prefix[j] + (rgba[4 * j + 3] != 0.0f ? 1u : 0u);
+}
+
+// Emptiness of a cell with finite taps in [m, M]: every entry of [max(floor(u(m)) - 1, 0), min(floor(u(M)) + 2, n - 1)] has alpha 0.
+VK_TF_HD bool tf_range_empty(float m, float M, const uint32_t *prefix, int n, float k1, float k2) {
+    const float umax = (float)(n - 1);
+    int lo = (int)floorf(tf_u(m, k1, k2, umax)) - 1, hi = (int)floorf(tf_u(M, k1, k2, umax)) + 2;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > n - 1 ? n - 1 : hi;
+    return prefix[hi + 1] == prefix[lo];
+}
+
+// The same for a cell's eight taps (f32 values on the kernel's scale); false as soon as one tap is not finite.
+VK_TF_HD bool tf_cell_empty(const float t[8], const uint32_t *prefix, int n, float k1, float k2) {
+    float m = t[0], M = t[0];
+    bool finite = true;
+    for (int b = 0; b < 8; b++) {
+        finite = finite && isfinite(t[b]);
+        m = fminf(m, t[b]);
+        M = fmaxf(M, t[b]);
+    }
+    return finite && tf_range_empty(m, M, prefix, n, k1, k2);
+}
+
+}  // namespace vk

@@ -81,6 +81,113 @@ static int commit_volume(vk_ctx *ctx, VolBuild &nb) {
     return VK_OK;
 }
 
+// ---- skip maps of the cell layouts -----------------------------------------------------------------
+// scratch of a map build: occupancy seed (0: the cell can contribute, 255: empty) + two pass buffers, one byte per cell each
+struct CellScratch {
+    uint8_t *occ = nullptr, *tx = nullptr, *txy = nullptr;
+    ~CellScratch() { (void)hipFree(occ); (void)hipFree(tx); (void)hipFree(txy); }
+};
+
+static int alloc_scratch(vk_ctx *ctx, CellScratch &sc, uint64_t n_cells) {
+    for (uint8_t **p : {&sc.occ, &sc.tx, &sc.txy}) {
+        hipError_t e = hipMalloc((void **)p, n_cells);
+        if (e != hipSuccess) { *p = nullptr; return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("re-layout scratch allocation failed: ") + hipGetErrorString(e)); }
+    }
+    return VK_OK;
+}
+
+// The seed of the skip maps under the runtime transfer function, read back from the cells (cell_occ_kernel), replacing the seed and the
+// census counter (ctx->counters[7]) pack_cells_kernel left.  prefix == nullptr: the built-in threshold.
+static int launch_cell_occ(vk_ctx *ctx, int kind, const void *cells, uint8_t *occ, uint64_t n_cells, uint32_t blocks, const uint32_t *prefix,
+                           uint32_t n, float lo, float hi) {
+    float k1 = 0.0f, k2 = 0.0f;
+    if (prefix) tf_constants(n, lo, hi, kind != VOL_PF16, k1, k2);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters + 7, 0, sizeof(unsigned long long), ctx->stream));
+    if (kind == VOL_PF16)
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_PF16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, n_cells, prefix, (int)n, k1, k2, ctx->counters + 7);
+    else if (kind == VOL_P16)
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_P16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, n_cells, prefix, (int)n, k1, k2, ctx->counters + 7);
+    else
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_P8>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, n_cells, prefix, (int)n, k1, k2, ctx->counters + 7);
+    return VK_OK;  // (launch errors: read_census)
+}
+
+// Share of empty cells from the census counter, after the seed's kernels (one synchronisation).
+static int read_census(vk_ctx *ctx, uint64_t n_cells, double *empty_fraction) {
+    unsigned long long ne = 0;
+    hipError_t le = hipGetLastError();
+    hipError_t ce = hipMemcpyAsync(&ne, ctx->counters + 7, sizeof(ne), hipMemcpyDeviceToHost, ctx->stream);
+    hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (le != hipSuccess || ce != hipSuccess || se != hipSuccess)
+        return fail(ctx, VK_ERR_HIP, std::string("volume re-layout: ") + hipGetErrorString(le != hipSuccess ? le : (ce != hipSuccess ? ce : se)));
+    *empty_fraction = (double)ne / (double)n_cells;
+    return VK_OK;
+}
+
+// Distance maps from the seed in sc.occ.  Eight one-sided maps (one per ray octant) when skipping will be on by default
+// or may well be forced on (>= 30 % empty cells) and they stay <= 2 GiB; otherwise one isotropic map serves every octant.
+// On success *dist (the caller's from then on), *oct_stride and *dist_bytes are set; on failure nothing is left allocated.
+static int build_skip_maps(vk_ctx *ctx, CellScratch &sc, uint32_t nbx, uint32_t nby, uint32_t nbz, uint64_t n_cells, double empty_fraction,
+                           uint8_t **dist, uint32_t *oct_stride, uint64_t *dist_bytes) {
+    const uint32_t blocks = (uint32_t)((n_cells + 255) / 256);
+    const bool octants = empty_fraction >= 0.30 && n_cells <= (1ull << 28);  // (the default policy skips from 45 %)
+    const uint64_t bytes = octants ? 8 * n_cells : n_cells;
+    uint8_t *d = nullptr;
+    hipError_t e = hipMalloc((void **)&d, bytes);
+    if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("distance map allocation failed: ") + hipGetErrorString(e));
+    auto pass = [&](const uint8_t *in, uint8_t *out, int axis, int dir, int last) {
+        hipLaunchKernelGGL(dist_pass_kernel, dim3(blocks), dim3(256), 0, ctx->stream, in, out, nbx, nby, nbz, axis, dir, last);
+    };
+    if (octants) {
+        for (int ux = 0; ux < 2; ux++) {
+            pass(sc.occ, sc.tx, 0, ux ? 1 : -1, 0);
+            for (int uy = 0; uy < 2; uy++) {
+                pass(sc.tx, sc.txy, 1, uy ? 1 : -1, 0);
+                for (int uz = 0; uz < 2; uz++) pass(sc.txy, d + (size_t)(ux | (uy << 1) | (uz << 2)) * n_cells, 2, uz ? 1 : -1, 1);
+            }
+        }
+    } else {
+        pass(sc.occ, sc.tx, 0, 0, 0);
+        pass(sc.tx, sc.txy, 1, 0, 0);
+        pass(sc.txy, d, 2, 0, 1);
+    }
+    hipError_t le = hipGetLastError();
+    hipError_t se = hipStreamSynchronize(ctx->stream);
+    if (le != hipSuccess || se != hipSuccess) {
+        (void)hipFree(d);
+        return fail(ctx, VK_ERR_HIP, std::string("distance maps: ") + hipGetErrorString(le != hipSuccess ? le : se));
+    }
+    *dist = d;
+    *oct_stride = octants ? (uint32_t)n_cells : 0u;
+    *dist_bytes = bytes;
+    return VK_OK;
+}
+
+// The current packed volume's seed, census and maps under the table (d_prefix: its prefix counts on the device; nullptr: the built-in
+// transfer), swapped in only when all of it has been built.  The caller has drained the frame slots.  Other layouts have no maps.
+int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float lo, float hi) {
+    const int kind = ctx->vol_kind;
+    if (ctx->format < 0 || (kind != VOL_P8 && kind != VOL_P16 && kind != VOL_PF16)) return VK_OK;
+    const uint64_t n_cells = (uint64_t)ctx->nbx * ctx->nby * ctx->nbz * kBrickCells;
+    const uint64_t cell_bytes = kind == VOL_P8 ? 8 : 16;
+    CellScratch sc;
+    int rc = alloc_scratch(ctx, sc, n_cells);
+    if (rc) return rc;
+    if ((rc = launch_cell_occ(ctx, kind, ctx->vol, sc.occ, n_cells, (uint32_t)((n_cells + 255) / 256), d_prefix, n, lo, hi))) return rc;
+    double ef = 0.0;
+    if ((rc = read_census(ctx, n_cells, &ef))) return rc;
+    uint8_t *dist = nullptr;
+    uint32_t stride = 0;
+    uint64_t dist_bytes = 0;
+    if ((rc = build_skip_maps(ctx, sc, ctx->nbx, ctx->nby, ctx->nbz, n_cells, ef, &dist, &stride, &dist_bytes))) return rc;
+    (void)hipFree(ctx->dist);
+    ctx->dist = dist;
+    ctx->vdesc.dist_oct_stride = stride;
+    ctx->vol_bytes = n_cells * cell_bytes + dist_bytes;
+    ctx->empty_fraction = ef;
+    return VK_OK;
+}
+
 static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, bool own_src, uint32_t nx,
                             uint32_t ny, uint32_t nz, int format, int layout) {
     // d_src is dense device memory; with own_src the LINEAR layout adopts it, every other layout frees it.
@@ -262,14 +369,8 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
     if (pack_blocks64 >= (1ull << 31)) return fail(ctx, VK_ERR_UNSUPPORTED, "volume too large for one launch");
     const uint32_t pack_blocks = (uint32_t)pack_blocks64;
     if ((rc = alloc(&nb.vol, n_cells * cell_bytes, "cell array"))) return rc;
-    // scratch: occupancy map + two pass buffers
-    struct Scratch {
-        uint8_t *occ = nullptr, *tx = nullptr, *txy = nullptr;
-        ~Scratch() { (void)hipFree(occ); (void)hipFree(tx); (void)hipFree(txy); }
-    } sc;
-    if ((rc = alloc((void **)&sc.occ, n_cells, "re-layout scratch")) || (rc = alloc((void **)&sc.tx, n_cells, "re-layout scratch")) ||
-        (rc = alloc((void **)&sc.txy, n_cells, "re-layout scratch")))
-        return rc;
+    CellScratch sc;  // occupancy map + two pass buffers
+    if ((rc = alloc_scratch(ctx, sc, n_cells))) return rc;
     nb.vol_kind = kind;
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters + 7, 0, sizeof(unsigned long long), ctx->stream));
     if (kind == VOL_PF16)
@@ -278,39 +379,13 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
         hipLaunchKernelGGL(pack_cells_kernel<VOL_P16>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
     else
         hipLaunchKernelGGL(pack_cells_kernel<VOL_P8>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
-    {
-        unsigned long long ne = 0;
-        hipError_t le = hipGetLastError();
-        hipError_t ce = hipMemcpyAsync(&ne, ctx->counters + 7, sizeof(ne), hipMemcpyDeviceToHost, ctx->stream);
-        hipError_t se = hipStreamSynchronize(ctx->stream);
-        if (le != hipSuccess || ce != hipSuccess || se != hipSuccess)
-            return fail(ctx, VK_ERR_HIP, std::string("volume re-layout: ") + hipGetErrorString(le != hipSuccess ? le : (ce != hipSuccess ? ce : se)));
-        nb.empty_fraction = (double)ne / (double)n_cells;
-    }
-    // Distance maps.  Eight one-sided maps (one per ray octant) when skipping will be on by default
-    // or may well be forced on (>= 30 % empty cells) and they stay <= 2 GiB; otherwise one isotropic map serves every octant.
-    const bool octants = nb.empty_fraction >= 0.30 && n_cells <= (1ull << 28);  // (the default policy skips from 45 %)
-    const uint64_t dist_bytes = octants ? 8 * n_cells : n_cells;
-    if ((rc = alloc((void **)&nb.dist, dist_bytes, "distance map"))) return rc;
+    // under a runtime transfer function the seed and the census follow its table (vk_set_transfer_function)
+    if (ctx->d_tf && (rc = launch_cell_occ(ctx, kind, nb.vol, sc.occ, n_cells, pack_blocks, reinterpret_cast<const uint32_t *>(ctx->d_tf + 4 * ctx->tf_n), ctx->tf_n, ctx->tf_lo, ctx->tf_hi)))
+        return rc;
+    if ((rc = read_census(ctx, n_cells, &nb.empty_fraction))) return rc;
+    uint64_t dist_bytes = 0;
+    if ((rc = build_skip_maps(ctx, sc, nb.nbx, nb.nby, nb.nbz, n_cells, nb.empty_fraction, &nb.dist, &nb.vdesc.dist_oct_stride, &dist_bytes))) return rc;
     nb.vol_bytes = n_cells * cell_bytes + dist_bytes;
-    nb.vdesc.dist_oct_stride = octants ? (uint32_t)n_cells : 0u;
-    auto pass = [&](const uint8_t *in, uint8_t *out, int axis, int dir, int last) {
-        hipLaunchKernelGGL(dist_pass_kernel, dim3(pack_blocks), dim3(256), 0, ctx->stream, in, out, nb.nbx, nb.nby, nb.nbz, axis, dir, last);
-    };
-    if (octants) {
-        for (int ux = 0; ux < 2; ux++) {
-            pass(sc.occ, sc.tx, 0, ux ? 1 : -1, 0);
-            for (int uy = 0; uy < 2; uy++) {
-                pass(sc.tx, sc.txy, 1, uy ? 1 : -1, 0);
-                for (int uz = 0; uz < 2; uz++) pass(sc.txy, nb.dist + (size_t)(ux | (uy << 1) | (uz << 2)) * n_cells, 2, uz ? 1 : -1, 1);
-            }
-        }
-    } else {
-        pass(sc.occ, sc.tx, 0, 0, 0);
-        pass(sc.tx, sc.txy, 1, 0, 0);
-        pass(sc.txy, nb.dist, 2, 0, 1);
-    }
-    if ((rc = finish("distance maps"))) return rc;
     {
         // per-axis cell-index tables of the fast path, two copies: cell units, byte offsets
         const uint32_t padded = cell_lut_entries(nx, ny, nz);
@@ -428,6 +503,47 @@ int vk_volume_empty_fraction(vk_ctx *ctx, double *fraction) {
     if (!ctx || !fraction) return VK_ERR_INVALID;
     if (ctx->format < 0) return fail(ctx, VK_ERR_INVALID, "no volume uploaded");
     *fraction = ctx->empty_fraction;
+    return VK_OK;
+}
+
+int vk_set_transfer_function(vk_ctx *ctx, const float *rgba, uint32_t n, float lo, float hi) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (ctx->fif_open) return fail(ctx, VK_ERR_INVALID, "vk_set_transfer_function: a frame is being recorded (call it outside vk_frame_begin / vk_frame_end)");
+    if (rgba) {
+        if (n < 2 || n > VK_TF_MAX_ENTRIES) return fail(ctx, VK_ERR_INVALID, "vk_set_transfer_function: 2 <= n <= VK_TF_MAX_ENTRIES entries");
+        if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) return fail(ctx, VK_ERR_INVALID, "vk_set_transfer_function: the domain needs finite lo < hi");
+        // |colour| <= VK_TF_MAX_COLOUR: the lerp's difference of two neighbours stays finite, so a sample whose alpha is +0 adds +0 (vk_tf.hpp)
+        for (uint32_t j = 0; j < 4 * n; j++)
+            if (!(std::fabs(rgba[j]) <= VK_TF_MAX_COLOUR)) return fail(ctx, VK_ERR_INVALID, "vk_set_transfer_function: entry " + std::to_string(j / 4) + " is not finite or beyond +-VK_TF_MAX_COLOUR");
+        for (uint32_t j = 0; j < n; j++)
+            if (!(rgba[4 * j + 3] >= 0.0f && rgba[4 * j + 3] <= 1.0f)) return fail(ctx, VK_ERR_INVALID, "vk_set_transfer_function: alpha of entry " + std::to_string(j) + " outside [0, 1]");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // every frame recorded so far renders with the table it was recorded under: drain them before anything they read changes
+    int rc = frames_drain(ctx);
+    if (rc) return rc;
+    if (!rgba) {
+        if (!ctx->d_tf) return VK_OK;
+        if ((rc = rebuild_skip_maps(ctx, nullptr, 0, 0.0f, 1.0f))) return rc;
+        (void)hipFree(ctx->d_tf);
+        ctx->d_tf = nullptr;
+        ctx->tf_n = 0;
+        return VK_OK;
+    }
+    // a new device copy (entries, then the prefix counts of non-zero alphas): the old one is freed only once the maps of the new one stand
+    std::vector<uint32_t> prefix(n + 1);
+    tf_alpha_prefix(rgba, n, prefix.data());
+    std::vector<unsigned char> blob((size_t)n * 16 + prefix.size() * 4);
+    std::memcpy(blob.data(), rgba, (size_t)n * 16);
+    std::memcpy(blob.data() + (size_t)n * 16, prefix.data(), prefix.size() * 4);
+    float *d = nullptr;
+    HIP_TRY(ctx, hipMalloc((void **)&d, blob.size()));
+    hipError_t e = hipMemcpy(d, blob.data(), blob.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); return fail(ctx, VK_ERR_HIP, std::string("vk_set_transfer_function: upload: ") + hipGetErrorString(e)); }
+    if ((rc = rebuild_skip_maps(ctx, reinterpret_cast<const uint32_t *>(d + 4 * n), n, lo, hi))) { (void)hipFree(d); return rc; }
+    (void)hipFree(ctx->d_tf);
+    ctx->d_tf = d;
+    ctx->tf_n = n; ctx->tf_lo = lo; ctx->tf_hi = hi;
     return VK_OK;
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "vk_common.hpp"
+#include "vk_tf.hpp"
 #include "vk_xor.hpp"
 
 namespace vk {
@@ -127,6 +128,41 @@ __global__ __launch_bounds__(256) void pack_cells_kernel(const void *__restrict_
     } else {
         reinterpret_cast<uint4 *>(dst)[id] = make_uint4(t[0] | (t[1] << 16), t[2] | (t[3] << 16), t[4] | (t[5] << 16), t[6] | (t[7] << 16));
     }
+}
+
+// The skip-map seed and census of a packed volume read back from its cells (the dense source is gone by then): each cell's 8 taps
+// (P8: u8 taps; P16: (tap, delta) pairs, tap + delta exact; PF16: f16 taps), tested by the runtime transfer function's emptiness
+// predicate (vk_tf.hpp; prefix: the table's prefix counts of non-zero alphas), or with prefix == nullptr by the built-in threshold
+// of pack_cells_kernel -- whose occ and census it then reproduces byte for byte.
+template <int VOL>
+__global__ __launch_bounds__(256) void cell_occ_kernel(const void *__restrict__ cells, uint8_t *__restrict__ occ, uint64_t n_cells,
+                                                       const uint32_t *__restrict__ prefix, int n, float k1, float k2,
+                                                       unsigned long long *__restrict__ n_empty) {
+    const uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= n_cells) return;  // (n_cells is a multiple of 64: whole waves)
+    float t[8];
+    if (VOL == VOL_P8) {
+        const uint2 c = reinterpret_cast<const uint2 *>(cells)[id];
+#pragma unroll
+        for (int b = 0; b < 4; b++) { t[b] = (float)((c.x >> (8 * b)) & 0xffu); t[4 + b] = (float)((c.y >> (8 * b)) & 0xffu); }
+    } else {
+        union { uint4 u; _Float16 h[8]; } c;
+        c.u = reinterpret_cast<const uint4 *>(cells)[id];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (VOL == VOL_P16) { t[2 * k] = (float)c.h[2 * k]; t[2 * k + 1] = (float)c.h[2 * k] + (float)c.h[2 * k + 1]; }
+            else { t[2 * k] = (float)c.h[2 * k]; t[2 * k + 1] = (float)c.h[2 * k + 1]; }
+        }
+    }
+    bool nonempty = false;
+    if (prefix) nonempty = !tf_cell_empty(t, prefix, n, k1, k2);
+    else {
+#pragma unroll
+        for (int b = 0; b < 8; b++) nonempty |= (VOL == VOL_PF16) ? !(t[b] <= 0.1f) : (t[b] > 25.0f);  // (pack_cells_kernel's threshold)
+    }
+    occ[id] = nonempty ? 0 : 255;
+    const unsigned long long m = __ballot(!nonempty);
+    if ((threadIdx.x & 63u) == 0 && m) atomicAdd(n_empty, (unsigned long long)__popcll(m));
 }
 
 // Dense voxels -> 9^3 bricks: one thread per stored voxel, brick b holds voxels [8b-1, 8b+7] per axis

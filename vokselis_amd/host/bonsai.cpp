@@ -6,6 +6,8 @@
 //                                                            store into GPU 0's frames themselves instead of gather + un-tile
 //          [--in-flight K] [--orbit] [--fuse-present] [--record]                        K frames in flight (vk_ctx_frames_in_flight); --orbit: the camera turns by 2 pi / 1024 every frame;
 //                                                            --record: capture_frame of every frame, K - 1 frames behind (the recorder, src/lib.rs:196-199)
+//          [--tf table.f32 [--tf-domain LO HI]]               runtime transfer function (vk_set_transfer_function): raw little-endian f32
+//                                                            RGBA rows, 2..256 of them, over the sample values [LO, HI] (default 0 1)
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -19,12 +21,28 @@ using namespace vokselis;
 static std::string g_raw;
 static float g_dt = 1.0f;
 static bool g_orbit = false;
+static std::vector<float> g_tf;  // --tf: n x 4 floats (empty: the built-in transfer)
+static float g_tf_lo = 0.0f, g_tf_hi = 1.0f;
+
+// --tf PATH: the whole file as little-endian f32 RGBA rows (the library checks n, finiteness and alpha)
+static std::vector<float> read_tf(const std::string &path) {
+    std::ifstream f(path, std::ios::binary | std::ios::ate);
+    if (!f) throw std::runtime_error("cannot open " + path);
+    const std::streamsize bytes = f.tellg();
+    if (bytes <= 0 || bytes % 16) throw std::runtime_error(path + ": expected whole RGBA rows of 4 f32 (16 bytes each)");
+    std::vector<float> t((size_t)bytes / 4);
+    f.seekg(0);
+    f.read(reinterpret_cast<char *>(t.data()), bytes);
+    if (f.gcount() != bytes) throw std::runtime_error(path + ": short read");
+    return t;
+}
 
 struct Bonsai : Demo {
     std::unique_ptr<VolumeTexture> volume_texture;
     RaycastPipeline pipeline;
     static std::unique_ptr<Bonsai> init(Context &ctx) {  // examples/bonsai/main.rs:16-25
         auto self = std::make_unique<Bonsai>();
+        if (!g_tf.empty()) ctx.set_transfer_function(g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi);
         if (!g_raw.empty()) self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::from_raw(ctx, g_raw));
         else self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, 256, 256, 256));
         self->pipeline = RaycastPipeline{VK_MODE_NAIVE_TRILINEAR, g_dt, 0};
@@ -54,6 +72,7 @@ static int run_group(int n_gpus, uint32_t frames, uint32_t batch, uint32_t w, ui
         for (int i = 0; i < n_gpus; i++) {
             vk_ctx *c = vk_group_ctx(g, i);
             check(c, vk_backbuffer_resize(c, w, h, VK_OUT_RGBA16F));
+            if (!g_tf.empty()) check(c, vk_set_transfer_function(c, g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi));
             if (!raw.empty()) check(c, vk_volume_upload(c, raw.data(), nullptr, 256, 256, 256, VK_FMT_R8_UNORM, VK_LAYOUT_AUTO));
             else check(c, vk_volume_generate(c, VK_GEN_BONSAI_STANDIN, 256, 256, 256, VK_FMT_R8_UNORM, 0x5EED0001u, 0, 1, VK_LAYOUT_AUTO));
         }
@@ -128,6 +147,10 @@ int main(int argc, char **argv) {
         else if (a == "--fuse-present") fuse_present = true;
         else if (a == "--record") record = true;
         else if (a == "--batch") batch = (uint32_t)std::max(1, std::atoi(next()));
+        else if (a == "--tf") {
+            try { g_tf = read_tf(next()); } catch (const std::exception &e) { std::fprintf(stderr, "bonsai: %s\n", e.what()); return 1; }
+        }
+        else if (a == "--tf-domain") { g_tf_lo = (float)std::atof(next()); g_tf_hi = (float)std::atof(next()); }
         else if (a == "--camera-blobs") { std::string in = next(); return dump_camera_blobs(in, next()); }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }

@@ -231,6 +231,11 @@ class Context {
     }
     void resize(uint32_t w, uint32_t h) { width = w; height = h; camera.set_aspect(w, h); }  // context.rs:238-249
     void sync() { check(ctx_, vk_ctx_sync(ctx_)); }
+    // Runtime transfer function of NAIVE_TRILINEAR (vk_set_transfer_function): n RGBA entries over the sample values [lo, hi];
+    // rgba == nullptr resets to the built-in transfer (raycast_naive.wgsl:104-110).
+    void set_transfer_function(const float *rgba, uint32_t n, float lo = 0.0f, float hi = 1.0f) {
+        check(ctx_, vk_set_transfer_function(ctx_, rgba, n, lo, hi));
+    }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
     void frames_in_flight(uint32_t k) { check(ctx_, vk_ctx_frames_in_flight(ctx_, k)); }
