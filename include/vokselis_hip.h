@@ -174,6 +174,30 @@ int vk_volume_info(vk_ctx *ctx, uint32_t dims[3], int *format, int *layout, size
 #define VK_TF_MAX_COLOUR 1e30f /* |r|, |g|, |b| at most this: the difference of two neighbouring entries stays finite */
 int vk_set_transfer_function(vk_ctx *ctx, const float *rgba, uint32_t n, float lo, float hi);
 
+/* Gradient lighting of the table march: shades each sample's table colour by the analytic gradient of the trilinear
+ * interpolant (two-sided Blinn-Phong).  It changes only the colour, never the alpha: trip counts,
+ * the early-out, skipping and vk_volume_empty_fraction are those of the unlit table.  Per sampled step, from the cell's
+ * taps t0..t7 (bit 0 = x, bit 1 = y, bit 2 = z), weights fx, fy, fz, x-lerps c00, c10, c01, c11 and y-lerps l0, l1,
+ * each operation rounded once:  e0 = fma(fy, (t3-t2) - (t1-t0), t1-t0);  e1 = fma(fy, (t7-t6) - (t5-t4), t5-t4);
+ * g = (fma(fz, e1 - e0, e0) nx, fma(fz, y1 - y0, y0) ny, (l1 - l0) nz) with y0 = c10 - c00, y1 = c11 - c01;
+ * q = g.g.  If q is finite and >= FLT_MIN: N = g rsqrt(q), diff = |N.L|, spec = |N.H|^shininess; otherwise (no
+ * gradient) diff = 1, spec = 0.  rgb' = c.rgb (ambient + diffuse diff) + specular spec, composited as c.rgb is.
+ * L = dir normalised (in double, rounded once per component), or -ray for a headlight; V = -ray; H = normalise(L + V)
+ * once per ray (V if L + V is zero).
+ * light == NULL turns lighting off.  VK_ERR_INVALID (the previous lighting stays in force): a field not finite, a
+ * zero-length dir with headlight == 0, ambient / diffuse / specular outside [0, 16], shininess outside [1, 1024].
+ * headlight != 0 puts the light at the eye (dir is then ignored).  Lighting is host state, taken into the kernel
+ * arguments when a render is recorded: the call needs no drain and no map rebuild, and it may be made at any time,
+ * between vk_frame_begin and vk_frame_end too (renders recorded before it keep the old lighting, renders after it
+ * take the new).  While lighting is set, NAIVE_TRILINEAR renders need a transfer function (VK_ERR_UNSUPPORTED
+ * otherwise); COMPUTE_NEAREST and PROCEDURAL ignore it. */
+typedef struct vk_lighting {
+    float dir[3];       /* towards the light, world space (the unit cube); ignored with headlight */
+    int32_t headlight;  /* != 0: the light sits at the eye, L = -ray direction */
+    float ambient, diffuse, specular, shininess;
+} vk_lighting; /* 32 bytes */
+int vk_set_lighting(vk_ctx *ctx, const vk_lighting *light);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

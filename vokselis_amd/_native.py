@@ -25,6 +25,15 @@ MAX_FRAMES_IN_FLIGHT = 4
 GEN_FOG, GEN_BONSAI_STANDIN, GEN_FOG_DENSE_CORE = 0, 1, 2
 TF_MAX_ENTRIES = 256
 
+
+class VkLighting(C.Structure):
+    """vk_lighting (32 bytes): the light's direction (towards the light), headlight, and the Blinn-Phong coefficients."""
+    _fields_ = [("dir", C.c_float * 3), ("headlight", C.c_int32), ("ambient", C.c_float), ("diffuse", C.c_float),
+                ("specular", C.c_float), ("shininess", C.c_float)]
+
+
+assert C.sizeof(VkLighting) == 32
+
 # every symbol include/vokselis_hip.h declares: name -> (restype, argtypes)
 _u32, _i32, _f32, _vp, _sz = C.c_uint32, C.c_int32, C.c_float, C.c_void_p, C.c_size_t
 SYMBOLS = {
@@ -41,6 +50,7 @@ SYMBOLS = {
     "vk_volume_generate_xor": (C.c_int, [_vp, _u32, _u32, _u32, _f32]),
     "vk_volume_empty_fraction": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "vk_set_transfer_function": (C.c_int, [_vp, C.POINTER(C.c_float), _u32, _f32, _f32]),
+    "vk_set_lighting": (C.c_int, [_vp, _vp]),  # const vk_lighting * (VkLighting below), NULL: off
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),
     "vk_set_uniform": (C.c_int, [_vp, _vp]),
     "vk_set_camera": (C.c_int, [_vp, _vp]),

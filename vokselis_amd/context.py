@@ -210,6 +210,28 @@ class Context:
         lo, hi = domain
         N.check(self._h, L.vk_set_transfer_function(self._h, t.ctypes.data_as(C.POINTER(C.c_float)), t.shape[0], float(lo), float(hi)))
 
+    def set_lighting(self, direction=None, ambient=0.3, diffuse=0.7, specular=0.2, shininess=32.0):
+        """Gradient lighting of the table march (vk_set_lighting): each sample's table colour is shaded by the gradient of the trilinear
+        interpolant, two-sided Blinn-Phong, rgb' = c.rgb (ambient + diffuse |N.L|) + specular |N.H|^shininess; alpha is untouched.
+        `direction`: (x, y, z) towards the light in world space, "headlight" for a light at the eye, or None to turn lighting off.
+        Needs a transfer function (set_transfer_function) for NAIVE_TRILINEAR renders; takes effect from the next recorded render."""
+        L = N.lib()
+        if direction is None:
+            N.check(self._h, L.vk_set_lighting(self._h, None))
+            return
+        li = N.VkLighting()
+        if isinstance(direction, str):
+            if direction != "headlight":
+                raise ValueError('set_lighting: direction is None, (x, y, z) or "headlight"')
+            li.headlight = 1
+        else:
+            d = tuple(float(v) for v in direction)
+            if len(d) != 3:
+                raise ValueError("set_lighting: direction needs three components")
+            li.dir[0], li.dir[1], li.dir[2] = d
+        li.ambient, li.diffuse, li.specular, li.shininess = float(ambient), float(diffuse), float(specular), float(shininess)
+        N.check(self._h, L.vk_set_lighting(self._h, C.byref(li)))
+
     # -- frames in flight: the queue running ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain (src/context.rs:118,252)
     def frames_in_flight(self, k: int):
         """vk_ctx_frames_in_flight: a ring of k frame surfaces, each on its own stream (1: one surface, the default)."""

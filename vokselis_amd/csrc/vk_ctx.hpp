@@ -8,6 +8,7 @@
 //   vk_batch.hip           vk_render_batch: many frames, one launch
 //   vk_launch_cells.hip    instantiates the cell-layout march kernels      (vk_march.hpp)
 //   vk_launch_tf.hip       instantiates the cell march under a transfer table (vk_march.hpp)
+//   vk_launch_lit.hip      instantiates the table march with gradient lighting (vk_march.hpp, vk_light.hpp)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)
@@ -16,6 +17,7 @@
 
 #include "../../include/vokselis_hip.h"
 #include "vk_common.hpp"
+#include "vk_light.hpp"
 #include "vk_tf.hpp"
 
 #include <hip/hip_runtime.h>
@@ -54,6 +56,9 @@ struct vk_ctx {
     float *d_tf = nullptr;
     uint32_t tf_n = 0;
     float tf_lo = 0.0f, tf_hi = 1.0f;
+    // gradient lighting of the table march (vk_set_lighting): host state, passed by value to the lit kernels
+    bool lit = false;
+    vk::LightDesc light{};
 
     // uniforms (host copies; passed to kernels by value)
     unsigned char uniform[48] = {0};
@@ -212,6 +217,8 @@ uint32_t launch_flags(const vk_ctx *ctx, uint32_t render_flags, bool batch);
 // the kernel-instantiating TUs: each launches on ctx->stream and returns; the caller checks hipGetLastError
 void launch_cells(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, bool skip, bool safe, int walk /* vk_march.hpp: WalkKind */);
 void launch_cells_tf(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_tf.hip
+void launch_cells_lit(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::LightDesc &Lt, uint32_t grid, bool count, bool skip,
+                      bool safe);  // vk_launch_lit.hip
 void launch_staged(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, const float *cam);
 void launch_compute(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, bool records, bool skip);
 void launch_procedural(vk_ctx *ctx, const vk::LaunchDesc &L, uint32_t grid, bool count, float time, bool device_sine);

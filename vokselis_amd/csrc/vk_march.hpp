@@ -3,6 +3,7 @@
 #pragma once
 
 #include "vk_common.hpp"
+#include "vk_light.hpp"
 #include "vk_tf.hpp"
 #include "vk_trips.hpp"
 
@@ -54,6 +55,35 @@ __device__ __forceinline__ void xlerp_cell(const CellBits<VOL> &cb, float fx, fl
             float a4 = (float)c.h[2].x, a5 = (float)c.h[2].y, a6 = (float)c.h[3].x, a7 = (float)c.h[3].y;
             c00 = fmaf(fx, a1 - a0, a0); c10 = fmaf(fx, a3 - a2, a2);
             c01 = fmaf(fx, a5 - a4, a4); c11 = fmaf(fx, a7 - a6, a6);
+        }
+    }
+}
+
+// xlerp_cell that also returns the four x-differences t1 - t0, t3 - t2, t5 - t4, t7 - t6 (the lit kernels' gradient, vk_light.hpp); PACKED_PAIRS
+// returns its stored deltas, which are those differences exactly for u8 data
+template <int VOL>
+__device__ __forceinline__ void xlerp_cell_dx(const CellBits<VOL> &cb, float fx, float &c00, float &c10, float &c01, float &c11,
+                                              float &dx00, float &dx10, float &dx01, float &dx11) {
+    if constexpr (VOL == VOL_P8) {
+        const uint32_t lo = cb.v.x, hi = cb.v.y;
+        float t0_ = (float)(lo & 0xffu), t1_ = (float)((lo >> 8) & 0xffu), t2_ = (float)((lo >> 16) & 0xffu), t3_ = (float)(lo >> 24);
+        float t4_ = (float)(hi & 0xffu), t5_ = (float)((hi >> 8) & 0xffu), t6_ = (float)((hi >> 16) & 0xffu), t7_ = (float)(hi >> 24);
+        dx00 = t1_ - t0_; dx10 = t3_ - t2_; dx01 = t5_ - t4_; dx11 = t7_ - t6_;
+        c00 = fmaf(fx, dx00, t0_); c10 = fmaf(fx, dx10, t2_);
+        c01 = fmaf(fx, dx01, t4_); c11 = fmaf(fx, dx11, t6_);
+    } else {
+        union { u32x4_t u; half2_t h[4]; } c;
+        c.u = cb.v;
+        if constexpr (VOL == VOL_P16) {
+            dx00 = (float)c.h[0].y; dx10 = (float)c.h[1].y; dx01 = (float)c.h[2].y; dx11 = (float)c.h[3].y;
+            c00 = fmaf(fx, dx00, (float)c.h[0].x); c10 = fmaf(fx, dx10, (float)c.h[1].x);
+            c01 = fmaf(fx, dx01, (float)c.h[2].x); c11 = fmaf(fx, dx11, (float)c.h[3].x);
+        } else {
+            float a0 = (float)c.h[0].x, a1 = (float)c.h[0].y, a2 = (float)c.h[1].x, a3 = (float)c.h[1].y;
+            float a4 = (float)c.h[2].x, a5 = (float)c.h[2].y, a6 = (float)c.h[3].x, a7 = (float)c.h[3].y;
+            dx00 = a1 - a0; dx10 = a3 - a2; dx01 = a5 - a4; dx11 = a7 - a6;
+            c00 = fmaf(fx, dx00, a0); c10 = fmaf(fx, dx10, a2);
+            c01 = fmaf(fx, dx01, a4); c11 = fmaf(fx, dx11, a6);
         }
     }
 }
@@ -133,10 +163,13 @@ enum WalkKind : int { WALK_LOOP = 0, WALK_FMA = 2 };
 // Per ray the same operations in the same order on every variable.
 //
 // TF (the table kernels of vk_launch_tf.hip): the runtime transfer function replaces transfer_alpha and the palette (tf_lookup).
-template <int VOL, bool SKIP, bool SAFE, bool COUNT, bool BOUNDED = false, int WALK = WALK_LOOP, bool AHEAD = false, bool TF = false>
+// LIT (vk_launch_lit.hip; needs TF): the table colour is shaded by the sample's gradient (vk_light.hpp: lit_gradient, lit_shade) before it is
+// composited; alpha, and with it every trip, walk and exit, is the table's.
+template <int VOL, bool SKIP, bool SAFE, bool COUNT, bool BOUNDED = false, int WALK = WALK_LOOP, bool AHEAD = false, bool TF = false, bool LIT = false>
 __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const uint32_t budget, Census &cs,
                                       const uint32_t *lut = nullptr, const float walk_cap = __builtin_inff(), const float walk_cap_all = __builtin_inff(),
-                                      const TfDesc *tfd = nullptr) {
+                                      const TfDesc *tfd = nullptr, const LightDesc *ld = nullptr, const LitRay *lr = nullptr) {
+    static_assert(!LIT || TF, "lighting shades the table's colour");
     constexpr bool PACKED = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16);
     constexpr bool BRICK9 = (VOL == VOL_B9U8 || VOL == VOL_B9F16);
     static_assert(!AHEAD || (PACKED && SKIP && !SAFE && !BOUNDED), "probe-ahead: the skip kernels' fast path, unbounded");
@@ -203,6 +236,7 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
         int ix = AHEAD ? 0 : cvt_floor_i32(ux), iy = AHEAD ? 0 : cvt_floor_i32(uy), iz = AHEAD ? 0 : cvt_floor_i32(uz);
         float fx = AHEAD ? a_fx : __builtin_amdgcn_fractf(ux), fy = AHEAD ? a_fy : __builtin_amdgcn_fractf(uy), fz = AHEAD ? a_fz : __builtin_amdgcn_fractf(uz);
         float c00, c10, c01, c11;  // x-lerped corners
+        float dx00 = 0.0f, dx10 = 0.0f, dx01 = 0.0f, dx11 = 0.0f;  // LIT: the x-differences of the taps
         if (PACKED) {
             if (SAFE) { ix = med3_i32(ix, -1, mx); iy = med3_i32(iy, -1, my); iz = med3_i32(iz, -1, mz); }
             const int bx = ix >> 2, by = iy >> 2, bz = iz >> 2;
@@ -303,7 +337,8 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
                 nleft += 1;
                 locate(px, py, pz);
             }
-            xlerp_cell<VOL>(cb, fx, c00, c10, c01, c11);
+            if constexpr (LIT) xlerp_cell_dx<VOL>(cb, fx, c00, c10, c01, c11, dx00, dx10, dx01, dx11);
+            else xlerp_cell<VOL>(cb, fx, c00, c10, c01, c11);
         } else if (BRICK9) {
             // cell coords c = i + 1 in [0, n]; brick c >> 3, local c & 7; the taps sit at local
             // (l, l+1) per axis of the 9^3 brick: offsets {0,1} + {0,9} + {0,81} from one base
@@ -345,6 +380,7 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
                 tp[0] = h2f(v[r00 + x0]); tp[1] = h2f(v[r00 + x1]); tp[2] = h2f(v[r10 + x0]); tp[3] = h2f(v[r10 + x1]);
                 tp[4] = h2f(v[r01 + x0]); tp[5] = h2f(v[r01 + x1]); tp[6] = h2f(v[r11 + x0]); tp[7] = h2f(v[r11 + x1]);
             }
+            if constexpr (LIT) { dx00 = tp[1] - tp[0]; dx10 = tp[3] - tp[2]; dx01 = tp[5] - tp[4]; dx11 = tp[7] - tp[6]; }
             c00 = fmaf(fx, tp[1] - tp[0], tp[0]); c10 = fmaf(fx, tp[3] - tp[2], tp[2]);
             c01 = fmaf(fx, tp[5] - tp[4], tp[4]); c11 = fmaf(fx, tp[7] - tp[6], tp[6]);
         }
@@ -371,6 +407,11 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
         }
         if constexpr (TF) {  // the table's colour, composited as below: C = sum w * c.rgb (no palette, no 0.5 A + 0.5 G at the end)
             if (COUNT) { n_iter++; n_samp++; if (wave_leader()) w_sample++; }
+            if constexpr (LIT) {
+                float gx, gy, gz;
+                lit_gradient(dx00, dx10, dx01, dx11, c00, c10, c01, c11, c0, c1, fy, fz, fnx, fny, fnz, gx, gy, gz);
+                lit_shade(*ld, *lr, gx, gy, gz, tr, tg, tb);
+            }
             const float w = (1.0f - A) * a;
             Gr = fmaf(w, tr, Gr); Gg = fmaf(w, tg, Gg); Gb = fmaf(w, tb, Gb);
             A = A + w;
@@ -409,9 +450,10 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
 // The request one step past the ray's end reads a real (clamped) table entry and is never used.
 // CELL_LUT: the tables hold cell indices (the skip kernels' copy) instead of byte offsets; `budget` bounds the trips
 // (0xffffffff: none) so that the skip kernels can run stretches of it between probing windows.
-template <int VOL, bool COUNT, bool CELL_LUT = false, bool TF = false>
+template <int VOL, bool COUNT, bool CELL_LUT = false, bool TF = false, bool LIT = false>
 __device__ __forceinline__ bool march_stream(const VolumeDesc &V, RayState &r, Census &cs, const uint32_t *lut, uint32_t budget = 0xffffffffu,
-                                             const TfDesc *tfd = nullptr) {
+                                             const TfDesc *tfd = nullptr, const LightDesc *ld = nullptr, const LitRay *lr = nullptr) {
+    static_assert(!LIT || TF, "lighting shades the table's colour");
     float px = r.px, py = r.py, pz = r.pz, A = r.A, Gr = r.Gr, Gg = r.Gg, Gb = r.Gb;
     uint32_t left = r.left;
     const float sx = r.sx, sy = r.sy, sz = r.sz;
@@ -434,12 +476,19 @@ __device__ __forceinline__ bool march_stream(const VolumeDesc &V, RayState &r, C
         const float ux = fmaf(px, fnx, -0.5f), uy = fmaf(py, fny, -0.5f), uz = fmaf(pz, fnz, -0.5f);
         nxt = load_cell<VOL>(cells, (lut[cvt_floor_i32(ux) + 2] + luty[cvt_floor_i32(uy) + 2] + lutz[cvt_floor_i32(uz) + 2]) << lsh);
         float c00, c10, c01, c11;
-        xlerp_cell<VOL>(cur, fx, c00, c10, c01, c11);
+        float dx00, dx10, dx01, dx11;
+        if constexpr (LIT) xlerp_cell_dx<VOL>(cur, fx, c00, c10, c01, c11, dx00, dx10, dx01, dx11);
+        else xlerp_cell<VOL>(cur, fx, c00, c10, c01, c11);
         float l0 = fmaf(fy, c10 - c00, c00), l1 = fmaf(fy, c11 - c01, c01);
         float v = fmaf(fz, l1 - l0, l0);
         if constexpr (TF) {
             float cr, cg, cb, a;
             tf_lookup(*tfd, v, cr, cg, cb, a);
+            if constexpr (LIT) {
+                float gx, gy, gz;
+                lit_gradient(dx00, dx10, dx01, dx11, c00, c10, c01, c11, l0, l1, fy, fz, fnx, fny, fnz, gx, gy, gz);
+                lit_shade(*ld, *lr, gx, gy, gz, cr, cg, cb);
+            }
             const float w = (1.0f - A) * a;
             Gr = fmaf(w, cr, Gr); Gg = fmaf(w, cg, Gg); Gb = fmaf(w, cb, Gb);
             A = A + w;
@@ -654,8 +703,9 @@ __device__ __forceinline__ void clear_inactive_strip(const LaunchDesc &L, uint32
 // AHEAD: the probe-ahead trip (march<..., AHEAD>), an instantiation of its own -- it needs six more registers, and the launches that fill the machine keep the leaner kernel
 template <int VOL, bool SKIP, bool SAFE, int WALK, bool AHEAD, int OUT, bool COUNT>
 __global__ __launch_bounds__(64) void raymarch_naive_kernel(const LaunchDesc L, const VolumeDesc V) {
-    constexpr bool TF = false;  // (the table kernels: vk_launch_tf.hip)
+    constexpr bool TF = false, LIT = false;  // (the table kernels: vk_launch_tf.hip; lit: vk_launch_lit.hip)
     const TfDesc *tfd = nullptr;
+    const LightDesc *ldp = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

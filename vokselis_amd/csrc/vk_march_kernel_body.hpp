@@ -1,7 +1,8 @@
 // vk_march_kernel_body.hpp -- the body of the cell-march kernels, included inside them (no include guard): raymarch_naive_kernel
-// (vk_march.hpp) and raymarch_tf_kernel (vk_launch_tf.hip).  The including kernel defines the template parameters VOL, SKIP, SAFE, WALK,
-// AHEAD, OUT, COUNT, the constant TF (a runtime transfer function: vk_set_transfer_function) and `tfd`, its table (nullptr without one),
-// and takes its arguments L (LaunchDesc) and V (VolumeDesc) by value.  (Shared textually rather than as an inlined function: that
+// (vk_march.hpp), raymarch_tf_kernel (vk_launch_tf.hip) and raymarch_lit_kernel (vk_launch_lit.hip).  The including kernel defines the
+// template parameters VOL, SKIP, SAFE, WALK, AHEAD, OUT, COUNT, the constants TF (a runtime transfer function: vk_set_transfer_function)
+// and LIT (gradient lighting: vk_set_lighting), `tfd`, its table (nullptr without one), and `ldp`, its lighting (nullptr without), and
+// takes its arguments L (LaunchDesc) and V (VolumeDesc) by value.  (Shared textually rather than as an inlined function: that
 // moved the register allocation of the existing kernels.)
     static_assert(VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16 || (!SKIP && SAFE), "linear / bricked layouts: no skip map, clamped indices");
     static_assert(SKIP || WALK == WALK_LOOP, "the closed-form walks are variants of the skip kernels");
@@ -70,9 +71,11 @@
         r.px = px; r.py = py; r.pz = pz; r.sx = sx; r.sy = sy; r.sz = sz;
         r.A = 0.0f; r.Gr = 0.0f; r.Gg = 0.0f; r.Gb = 0.0f;  // colour sums: G = sum w*cos(phase); C = A/2 + G/2 (sum w == A)
         r.out = (uint32_t)pm.out_index;
+        LitRay lr;  // LIT: the ray's light and half vectors (vk_light.hpp; left unset in the other kernels, which never read it)
+        if constexpr (LIT) lr = lit_ray(*ldp, dir);
         // (not in the skip kernels: a ray's nominal length says little about its work there -- C2 at 64 orbit frames per launch 0.06509 -> 0.06467 ms without)
         if (!SKIP && (L.flags & LF_WAVE_PRIORITY)) set_wave_priority(true, r.left, fmaxf(fnx, fmaxf(fny, fnz)) / L.dt_scale);
-        if constexpr (USE_LUT && !SKIP) march_stream<VOL, COUNT, false, TF>(V, r, cs, cell_lut, 0xffffffffu, tfd);
+        if constexpr (USE_LUT && !SKIP) march_stream<VOL, COUNT, false, TF, LIT>(V, r, cs, cell_lut, 0xffffffffu, tfd, ldp, &lr);
         else if constexpr (SKIP) {
             if (L.flags & LF_ADAPTIVE_PROBING) {
                 // Adaptive probing (wave-uniform policy, any policy is exact: a sampled empty cell adds +0).  Probe for a
@@ -84,22 +87,22 @@
                 uint32_t stretch = stretch0;
                 for (;;) {
                     cs.skips = 0;
-                    bool alive = march<VOL, true, SAFE, COUNT, true, WALK, false, TF>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd);
+                    bool alive = march<VOL, true, SAFE, COUNT, true, WALK, false, TF, LIT>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd, ldp, &lr);
                     const unsigned long long live = __ballot(alive);
                     if (live == 0ull) break;
                     if (__popcll(__ballot(alive && cs.skips != 0u)) * 8 >= __popcll(live)) { stretch = stretch0; continue; }
-                    if constexpr (USE_LUT) alive = march_stream<VOL, COUNT, true, TF>(V, r, cs, cell_lut, stretch, tfd);
-                    else alive = march<VOL, false, SAFE, COUNT, true, WALK_LOOP, false, TF>(V, r, stretch, cs, nullptr, __builtin_inff(), __builtin_inff(), tfd);
+                    if constexpr (USE_LUT) alive = march_stream<VOL, COUNT, true, TF, LIT>(V, r, cs, cell_lut, stretch, tfd, ldp, &lr);
+                    else alive = march<VOL, false, SAFE, COUNT, true, WALK_LOOP, false, TF, LIT>(V, r, stretch, cs, nullptr, __builtin_inff(), __builtin_inff(), tfd, ldp, &lr);
                     if (__ballot(alive) == 0ull) break;
                     stretch = min(stretch * 2u, 512u);
                 }
             } else {
-                march<VOL, SKIP, SAFE, COUNT, false, WALK, AHEAD, TF>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd);
+                march<VOL, SKIP, SAFE, COUNT, false, WALK, AHEAD, TF, LIT>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd, ldp, &lr);
             }
         }
         else if constexpr (VOL == VOL_B9U8 || VOL == VOL_B9F16) march_b9_stream<VOL, COUNT>(V, r, cs);
         else if constexpr (VOL == VOL_Q8 || VOL == VOL_QF16) march_quads_stream<VOL, COUNT>(V, r, cs);
-        else march<VOL, SKIP, SAFE, COUNT, false, WALK_LOOP, false, TF>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, __builtin_inff(), __builtin_inff(), tfd);
+        else march<VOL, SKIP, SAFE, COUNT, false, WALK_LOOP, false, TF, LIT>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, __builtin_inff(), __builtin_inff(), tfd, ldp, &lr);
         A = r.A; Gr = r.Gr; Gg = r.Gg; Gb = r.Gb;
         if constexpr (TF) {  // the table's colour sums are the colour
             Cr = linear_to_srgb(Gr); Cg = linear_to_srgb(Gg); Cb = linear_to_srgb(Gb);

@@ -77,6 +77,9 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
     L.grid_march = grid;
     // a runtime transfer function (vk_set_transfer_function) has kernels on the LINEAR / PACKED / PACKED_PAIRS layouts, walking with the loop
     const bool tf = mode == VK_MODE_NAIVE_TRILINEAR && ctx->d_tf;
+    // gradient lighting (vk_set_lighting) shades the table's colour: it has no kernels without a table
+    if (mode == VK_MODE_NAIVE_TRILINEAR && ctx->lit && !tf)
+        return fail(ctx, VK_ERR_UNSUPPORTED, "lighting: NAIVE_TRILINEAR renders with lighting need a transfer function (set a table with vk_set_transfer_function, or turn lighting off with vk_set_lighting(NULL))");
     TfDesc T{};
     if (tf) {
         const int k = ctx->vol_kind;
@@ -130,6 +133,7 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
             if (V.max_off + 16 < (1ll << 32) && cell_lut_bytes(ctx->nx, ctx->ny, ctx->nz) <= 16384u && 64.0f * ulp < 0.25f / nmax && !(flags & VK_RENDER_SAFE)) safe = false;
         }
         if (ctx->vol_kind == VOL_S8U8 || ctx->vol_kind == VOL_S8F16) launch_staged(ctx, L, V, grid, count, reach_cam);
+        else if (tf && ctx->lit) launch_cells_lit(ctx, L, V, T, ctx->light, grid, count, skip, safe);
         else if (tf) launch_cells_tf(ctx, L, V, T, grid, count, skip, safe);
         else launch_cells(ctx, L, V, grid, count, skip, safe, (flags & VK_RENDER_FAST_WALK) ? 2 : 0);  // (vk_march.hpp: WalkKind)
     }
@@ -234,6 +238,22 @@ static int render_common(vk_ctx *ctx, int mode, int32_t ox, int32_t oy, uint32_t
 }
 
 extern "C" {
+
+// Lighting is host state read by dispatch_march when a render is recorded: nothing on the device changes, so no drain, no map rebuild, and no
+// restriction to the outside of vk_frame_begin / vk_frame_end.
+int vk_set_lighting(vk_ctx *ctx, const vk_lighting *light) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (!light) {
+        ctx->lit = false;
+        return VK_OK;
+    }
+    LightDesc D{};
+    if (const char *why = light_desc(light->dir, light->headlight, light->ambient, light->diffuse, light->specular, light->shininess, D))
+        return fail(ctx, VK_ERR_INVALID, std::string("vk_set_lighting: ") + why);
+    ctx->light = D;
+    ctx->lit = true;
+    return VK_OK;
+}
 
 int vk_render(vk_ctx *ctx, int mode, int32_t tile_x, int32_t tile_y, uint32_t tile_w, uint32_t tile_h, float dt_scale,
               uint32_t flags) {

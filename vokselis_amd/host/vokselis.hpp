@@ -236,6 +236,8 @@ class Context {
     void set_transfer_function(const float *rgba, uint32_t n, float lo = 0.0f, float hi = 1.0f) {
         check(ctx_, vk_set_transfer_function(ctx_, rgba, n, lo, hi));
     }
+    // Gradient lighting of the table march (vk_set_lighting); nullptr turns it off.
+    void set_lighting(const vk_lighting *light) { check(ctx_, vk_set_lighting(ctx_, light)); }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
     void frames_in_flight(uint32_t k) { check(ctx_, vk_ctx_frames_in_flight(ctx_, k)); }
