@@ -54,8 +54,9 @@ def intersect_box(o, d, lo, hi):
     return t0, t1
 
 
-def sample_trilinear(vol: np.ndarray, p, raw=False):
-    """Linear, clamp-to-edge sample of a [nz,ny,nx] u8 (R8Unorm) or f16 volume at p in [0,1]^3."""
+def sample_trilinear(vol: np.ndarray, p, raw=False, taps=False):
+    """Linear, clamp-to-edge sample of a [nz,ny,nx] u8 (R8Unorm) or f16 volume at p in [0,1]^3.  taps: also return the eight
+    f32 taps (bit 0 = x, bit 1 = y, bit 2 = z) and the three f32 weights (fx, fy, fz)."""
     nz, ny, nx = vol.shape
     dims = (nx, ny, nz)
     fr, i0, i1 = [], [], []
@@ -88,6 +89,8 @@ def sample_trilinear(vol: np.ndarray, p, raw=False):
     r = lerp(c0, c1, fr[2])
     if is_u8 and not raw:  # raw: the filtered taps stay on their 0..255 scale (the march: transfer_alpha carries the 1/255)
         r = (r * (f32(1.0) / f32(255.0))).astype(np.float32)
+    if taps:
+        return r, nonempty, t, fr
     return r, nonempty
 
 
@@ -117,20 +120,18 @@ def linear_to_srgb(x):
     return np.where(x <= f32(0.0031308), (f32(12.92) * x).astype(np.float32), hi)
 
 
-def render_naive(camera_blob: bytes, vol: np.ndarray, W: int, H: int, dt_scale: float = 1.0, tile=None):
-    """fs_main of raycast_naive.wgsl for every pixel of `tile` (default: the full frame).
-    Returns (rgba [H,W,4] f32, steps [H,W] u32, sampled [H,W] u32)."""
+def naive_rays(camera_blob: bytes, dims, W: int, H: int, dt_scale: float = 1.0, tile=None):
+    """The ray set-up of fs_main (raycast_naive.wgsl:80-100) for every pixel of `tile` (default: the full frame), dims = (nx, ny, nz).
+    Returns None for an empty tile, else a dict: xs, ys (the pixel columns and rows), d (unit direction), hit, t0 (clamped to 0),
+    t1, dt, p (the first position) and st (the step d * dt), each a list of three or one f32 array over the rays (row-major)."""
     cam = np.frombuffer(camera_blob, np.float32)
     eye = [cam[0], cam[1], cam[2]]
     inv_proj = cam[20:36]
     tx, ty, tw, th = (0, 0, W, H) if tile is None else tile
     xs = np.arange(max(tx, 0), min(tx + tw, W))
     ys = np.arange(max(ty, 0), min(ty + th, H))
-    rgba = np.zeros((H, W, 4), np.float32)
-    steps = np.zeros((H, W), np.uint32)
-    sampled = np.zeros((H, W), np.uint32)
     if xs.size == 0 or ys.size == 0:
-        return rgba, steps, sampled
+        return None
     X, Y = np.meshgrid(xs, ys)
     fx = (X.astype(np.float32) + f32(0.5)).ravel()
     fy = (Y.astype(np.float32) + f32(0.5)).ravel()
@@ -143,13 +144,26 @@ def render_naive(camera_blob: bytes, vol: np.ndarray, W: int, H: int, dt_scale: 
     t0, t1 = intersect_box(o, d, 0.0, 1.0)
     hit = ~(t0 > t1)
     t0 = np.fmax(t0, f32(0.0))
-    nz, ny, nx = vol.shape
     with np.errstate(divide="ignore"):
-        dtv = [(f32(1.0) / (f32(n) * np.abs(d[i])).astype(np.float32)).astype(np.float32) for i, n in enumerate((nx, ny, nz))]
+        dtv = [(f32(1.0) / (f32(n) * np.abs(d[i])).astype(np.float32)).astype(np.float32) for i, n in enumerate(dims)]
     dt = (f32(dt_scale) * np.fmin(dtv[0], np.fmin(dtv[1], dtv[2]))).astype(np.float32)
     p = [(o[i] + (t0 * d[i]).astype(np.float32)).astype(np.float32) for i in range(3)]
     st = [(d[i] * dt).astype(np.float32) for i in range(3)]
-    n = ndcx.size
+    return dict(xs=xs, ys=ys, d=d, hit=hit, t0=t0, t1=t1, dt=dt, p=p, st=st)
+
+
+def render_naive(camera_blob: bytes, vol: np.ndarray, W: int, H: int, dt_scale: float = 1.0, tile=None):
+    """fs_main of raycast_naive.wgsl for every pixel of `tile` (default: the full frame).
+    Returns (rgba [H,W,4] f32, steps [H,W] u32, sampled [H,W] u32)."""
+    rgba = np.zeros((H, W, 4), np.float32)
+    steps = np.zeros((H, W), np.uint32)
+    sampled = np.zeros((H, W), np.uint32)
+    nz, ny, nx = vol.shape
+    ray = naive_rays(camera_blob, (nx, ny, nz), W, H, dt_scale, tile)
+    if ray is None:
+        return rgba, steps, sampled
+    xs, ys, hit, t0, t1, dt, p, st = (ray[k] for k in ("xs", "ys", "hit", "t0", "t1", "dt", "p", "st"))
+    n = hit.size
     C = [np.zeros(n, np.float32) for _ in range(3)]
     A = np.zeros(n, np.float32)
     t = t0.copy()
