@@ -150,7 +150,8 @@ int vk_volume_generate(vk_ctx *ctx, int kind, uint32_t nx, uint32_t ny, uint32_t
  * un.time = time (0 in the reference: the pass runs before the first Context::update),
  * filling the two rgba16float storage textures (density, normals) the compute raycast reads. */
 int vk_volume_generate_xor(vk_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, float time);
-/* Share of the cells that are exactly transparent under the transfer function (packed layouts). */
+/* Share of the cells that are exactly transparent under the transfer function (packed layouts).  Built-in transfer: a cell
+ * is empty iff each of its 8 taps is (R8: <= 25; R16F: finite and <= 0.1 -- a NaN or infinite tap is never empty). */
 int vk_volume_empty_fraction(vk_ctx *ctx, double *fraction);
 int vk_volume_info(vk_ctx *ctx, uint32_t dims[3], int *format, int *layout, size_t *device_bytes);
 

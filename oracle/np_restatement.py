@@ -76,9 +76,11 @@ def sample_trilinear(vol: np.ndarray, p, raw=False, taps=False):
 
     t = [tap(i0[0], i0[1], i0[2]), tap(i1[0], i0[1], i0[2]), tap(i0[0], i1[1], i0[2]), tap(i1[0], i1[1], i0[2]),
          tap(i0[0], i0[1], i1[2]), tap(i1[0], i0[1], i1[2]), tap(i0[0], i1[1], i1[2]), tap(i1[0], i1[1], i1[2])]
+    # a cell is empty when every tap is: u8 <= 25; f16 finite and <= 0.1 (a NaN or infinite tap filters to NaN, and
+    # transfer_alpha(NaN) = smoothstep of min(NaN, 0.9) = 0.9: never empty, -inf included)
     nonempty = np.zeros(p[0].shape, bool)
     for k in range(8):
-        nonempty |= (t[k] > 25) if is_u8 else (t[k] > f32(0.1))
+        nonempty |= (t[k] > 25) if is_u8 else ~(np.isfinite(t[k]) & (t[k] <= f32(0.1)))
 
     def lerp(a, b, f):
         return fma(f, (b - a).astype(np.float32), a)

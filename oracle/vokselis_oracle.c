@@ -259,7 +259,9 @@ float vo_sample_trilinear(const void *vol, uint32_t nx, uint32_t ny, uint32_t nz
         const uint16_t *v = (const uint16_t *)vol;
         for (int k = 0; k < 8; k++) {
             t[k] = vo_f16_to_f32(v[idx[k]]);
-            nonempty |= (t[k] > 0.1f);
+            /* empty: finite and <= 0.1f.  A NaN or infinite tap is never empty: the lerps turn it into NaN (inf - inf, 0 * inf) and
+             * vo_transfer_alpha(NaN) takes min(NaN, 0.9) = 0.9, alpha ~0.817, for -inf as for +inf */
+            nonempty |= !(isfinite(t[k]) && t[k] <= 0.1f);
         }
     }
     if (any_nonempty) *any_nonempty = nonempty;

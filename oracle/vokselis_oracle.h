@@ -83,7 +83,7 @@ typedef struct vo_render_args {
     int threads;                 /* OpenMP threads, <=0: runtime default */
     float *out_rgba;             /* [height][width][4] f32, only tile pixels written */
     uint32_t *out_steps;         /* optional [height][width]: loop iterations executed */
-    uint32_t *out_sampled;       /* optional: iterations with at least one tap > 25 (u8) */
+    uint32_t *out_sampled;       /* optional: iterations in a non-empty cell (a tap > 25, u8; a tap not finite or > 0.1, f16) */
     float proc_time;             /* PROCEDURAL: un.time of noise_volume (the reference runs it at 0) */
 } vo_render_args;
 

@@ -81,4 +81,18 @@ VK_TF_HD bool tf_cell_empty(const float t[8], const uint32_t *prefix, int n, flo
     return finite && tf_range_empty(m, M, prefix, n, k1, k2);
 }
 
+// The emptiness predicate of the built-in transfer (no table): a tap is empty when transfer_alpha gives +0 for every sample that lerps it
+// with other empty taps.  u8 (the tap's value 0..255): t <= 25, since 25/255 < 0.1 <= 26/255.  f16: t finite and t <= 0.1f.  A NaN or an
+// infinite tap is never empty: the filter's fma(f, b - a, a) turns an infinite tap into NaN (inf - inf, 0 * inf) and
+// transfer_alpha(NaN) = smoothstep of min(NaN, 0.9) = 0.9, alpha ~0.817 -- the same for -inf as for +inf.  Shared by pack_cells_kernel,
+// cell_occ_kernel's built-in branch and the host fuzz (tests/builtin_fuzz.cpp); the oracle and the numpy restatement state it again.
+VK_TF_HD bool builtin_tap_empty(float t, bool f16) { return f16 ? (isfinite(t) && t <= 0.1f) : (t <= 25.0f); }
+
+// The same for a cell's eight taps (f32 values: u8 taps on 0..255, f16 taps as values): empty when every tap is.
+VK_TF_HD bool builtin_cell_empty(const float t[8], bool f16) {
+    bool empty = true;
+    for (int b = 0; b < 8; b++) empty = empty && builtin_tap_empty(t[b], f16);
+    return empty;
+}
+
 }  // namespace vk

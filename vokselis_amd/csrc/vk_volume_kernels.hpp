@@ -103,11 +103,12 @@ __global__ __launch_bounds__(256) void pack_cells_kernel(const void *__restrict_
         t[b] = (VOL == VOL_PF16) ? (uint32_t)reinterpret_cast<const uint16_t *>(src)[idx]
                                  : (uint32_t)reinterpret_cast<const uint8_t *>(src)[idx];
     }
-    // occ = 0 if any tap is above the transfer function's zero threshold (u8 > 25: 25/255 < 0.1 <=
-    // 26/255; f16 > 0.1f or NaN), else 255 ("no contributing cell seen yet")
-    bool nonempty = false;
+    // occ = 0 unless every tap is empty under the built-in transfer (vk_tf.hpp: builtin_cell_empty -- u8 <= 25; f16 finite and
+    // <= 0.1f), else 255 ("no contributing cell seen yet")
+    float tv[8];
 #pragma unroll
-    for (int b = 0; b < 8; b++) nonempty |= (VOL == VOL_PF16) ? !(h2f(t[b]) <= 0.1f) : (t[b] > 25u);
+    for (int b = 0; b < 8; b++) tv[b] = (VOL == VOL_PF16) ? h2f(t[b]) : (float)t[b];
+    const bool nonempty = !builtin_cell_empty(tv, VOL == VOL_PF16);
     occ[id] = nonempty ? 0 : 255;
     {   // census of exactly-transparent cells (one atomic per wave): decides whether skipping can pay
         const unsigned long long m = __ballot(!nonempty);
@@ -154,12 +155,7 @@ __global__ __launch_bounds__(256) void cell_occ_kernel(const void *__restrict__ 
             else { t[2 * k] = (float)c.h[2 * k]; t[2 * k + 1] = (float)c.h[2 * k + 1]; }
         }
     }
-    bool nonempty = false;
-    if (prefix) nonempty = !tf_cell_empty(t, prefix, n, k1, k2);
-    else {
-#pragma unroll
-        for (int b = 0; b < 8; b++) nonempty |= (VOL == VOL_PF16) ? !(t[b] <= 0.1f) : (t[b] > 25.0f);  // (pack_cells_kernel's threshold)
-    }
+    const bool nonempty = prefix ? !tf_cell_empty(t, prefix, n, k1, k2) : !builtin_cell_empty(t, VOL == VOL_PF16);  // (pack_cells_kernel's predicate)
     occ[id] = nonempty ? 0 : 255;
     const unsigned long long m = __ballot(!nonempty);
     if ((threadIdx.x & 63u) == 0 && m) atomicAdd(n_empty, (unsigned long long)__popcll(m));
