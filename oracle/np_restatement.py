@@ -217,18 +217,18 @@ def _dot3(a, b):
     return (((a[0] * b[0]).astype(np.float32) + (a[1] * b[1]).astype(np.float32)).astype(np.float32) + (a[2] * b[2]).astype(np.float32)).astype(np.float32)
 
 
-def render_compute(camera_blob: bytes, density: np.ndarray, normals: np.ndarray, W: int, H: int, dt_scale: float = 1.0,
-                   tile=None):
-    """`single` / `tile` of raycast_compute.wgsl (render + get_col2).  density/normals: f16 [nz,ny,nx,4]."""
+def compute_rays(camera_blob: bytes, dims, W: int, H: int, dt_scale: float = 1.0, tile=None):
+    """The ray set-up of render / get_col2 (raycast_compute.wgsl:62-68,99-127) for every pixel of `tile` (default: the full frame),
+    dims = (nx, ny, nz).  Returns None for an empty tile, else a dict: xs, ys (the pixel columns and rows), eye (the near-plane point) and
+    d (unit direction), hit (t0 < t1), t0 (clamped to 0), t1, dt (with the 0.01 floor) and hb (the half dims), each a list of three or one
+    f32 array over the rays (row-major; hb: three f32 scalars)."""
     cam = np.frombuffer(camera_blob, np.float32)
     inv_proj = cam[20:36]
     tx, ty, tw, th = (0, 0, W, H) if tile is None else tile
     xs = np.arange(max(tx, 0), min(tx + tw, W))
     ys = np.arange(max(ty, 0), min(ty + th, H))
-    rgba = np.zeros((H, W, 4), np.float32)
-    steps = np.zeros((H, W), np.uint32)
     if xs.size == 0 or ys.size == 0:
-        return rgba, steps
+        return None
     X, Y = np.meshgrid(xs, ys)
     cx, cy = X.astype(np.float32).ravel(), Y.astype(np.float32).ravel()
     dx, dy = f32(W), f32(H)
@@ -241,20 +241,32 @@ def render_compute(camera_blob: bytes, density: np.ndarray, normals: np.ndarray,
     vt = _mat_vec(inv_proj, [sx, sy, one, one])
     eye = [(vp[i] / vp[3]).astype(np.float32) for i in range(3)]
     d = _normalize([((vt[i] / vt[3]).astype(np.float32) - eye[i]).astype(np.float32) for i in range(3)])
-    clear = (f32(0.023), f32(0.02), f32(0.02))
     t0, t1 = intersect_box(eye, d, -1.0, 1.0)
     with np.errstate(invalid="ignore"):
         hit = t0 < t1
     t0 = np.fmax(t0, f32(0.0))
-    nz, ny, nx = density.shape[:3]
-    bs = (f32(nx), f32(ny), f32(nz))
+    bs = tuple(f32(n) for n in dims)
     with np.errstate(divide="ignore"):
         dtv = [(f32(1.0) / (bs[i] * np.abs(d[i])).astype(np.float32)).astype(np.float32) for i in range(3)]
     dt = (f32(dt_scale) * np.fmax(np.fmin(dtv[0], np.fmin(dtv[1], dtv[2])), f32(0.01))).astype(np.float32)
     hb = [b / f32(2.0) for b in bs]
+    return dict(xs=xs, ys=ys, eye=eye, d=d, hit=hit, t0=t0, t1=t1, dt=dt, hb=hb)
+
+
+def render_compute(camera_blob: bytes, density: np.ndarray, normals: np.ndarray, W: int, H: int, dt_scale: float = 1.0,
+                   tile=None):
+    """`single` / `tile` of raycast_compute.wgsl (render + get_col2).  density/normals: f16 [nz,ny,nx,4]."""
+    rgba = np.zeros((H, W, 4), np.float32)
+    steps = np.zeros((H, W), np.uint32)
+    nz, ny, nx = density.shape[:3]
+    ray = compute_rays(camera_blob, (nx, ny, nz), W, H, dt_scale, tile)
+    if ray is None:
+        return rgba, steps
+    xs, ys, eye, d, hit, t0, t1, dt, hb = (ray[k] for k in ("xs", "ys", "eye", "d", "hit", "t0", "t1", "dt", "hb"))
+    clear = (f32(0.023), f32(0.02), f32(0.02))
     l1 = _normalize([np.array(f32(-2.0)), np.array(f32(-2.0)), np.array(f32(-1.0))])
     l2 = _normalize([np.array(f32(1.0)), np.array(f32(1.0)), np.array(f32(-1.0))])
-    n = sx.size
+    n = hit.size
     C = [np.full(n, clear[k], np.float32) for k in range(3)]
     A = np.full(n, f32(0.1), np.float32)
     t = t0.copy()

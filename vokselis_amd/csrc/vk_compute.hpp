@@ -13,10 +13,11 @@ namespace vk {
 // cache-miss latency per step (<= 346 dependent steps per ray).
 //
 // SKIP (round 4): exact empty-space skipping, as the cell march has it.  A record whose opacity smoothstep(0, 0.7, a^3) is exactly 0 gives
-// w = 0: every accumulator takes +0 (the max / min of the shading launder a NaN normal, so the product is 0 x finite), A does not move, and
-// the loop's only other state is t.  Such a step need not be shaded -- provided t still takes the same sequence of rounded additions (:69) and
-// every skipped iteration passed the reference's own `t < t1` on the very same t.  The record carries, in the half get_col2 never reads
-// (normals.w), its Chebyshev distance d in voxels to the nearest record that can contribute: the samples of the next
+// w = +0: every accumulator takes +-0 provided colour and shade are finite (the max / min of the shading launder a NaN normal; a non-finite
+// colour or a -inf normal component makes the product 0 x inf = NaN, so such a record counts as one that can contribute: vk_pair.hpp),
+// A does not move, and the loop's only other state is t.  Such a step need not be shaded -- provided t still takes the same sequence of
+// rounded additions (:69) and every skipped iteration passed the reference's own `t < t1` on the very same t.  The record carries, in the
+// half get_col2 never reads (normals.w), its Chebyshev distance d in voxels to the nearest record that can contribute: the samples of the next
 // m = 1 + floor((d - 2) / (voxels per step)) iterations truncate to voxels inside that empty range, so they are walked (one addition each)
 // instead of fetched and shaded.  The xor example's blob fills half of its cube and a ray leaves it by the opacity early-out or crosses
 // empty space before and after it.  Frames and per-pixel iteration counts do not change by a bit (tests: SKIP == !SKIP == the literal twin).
@@ -71,7 +72,20 @@ __global__ __launch_bounds__(64) void raymarch_compute_records_kernel(const Laun
         // steps per voxel of Chebyshev distance: after i steps a sample's voxel differs from this one's by at most floor(i * u) + 1 on every axis
         // (u = voxels per step on the fastest axis; the + 1 is the truncation), which stays inside the empty range d - 1 for i <= (d - 2) / u;
         // 0.01 voxel covers the rounding of p = eye + t * dir (~1e-5 voxel).  rcp: 1 ulp, far inside that margin.
+        // That takes every t = t + dt to move exactly dt.  It moves dt + e, |e| <= ulp(t) / 2 <= |t1| 2^-24 (a walked t is below t1), and at a
+        // far eye e has the same sign step after step: at t ~ 150 and the smallest dt the library accepts, each step moves 1.03 dt, and a
+        // 60-voxel hop ends 1.7 voxels further on than planned.  Over the hop's at most (d - 2.01) / u steps the sample runs at most
+        // (d - 2.01) |t1| 2^-24 / dt voxels ahead; `drift` is twice that per voxel of d.  The plan above already keeps a voxel spare: the sample
+        // leaves the empty range only after i * u >= d - 1 (worst: a sample at the far side of its voxel), not d - 2.  So a hop is shortened by
+        // what d * drift takes beyond one voxel, which keeps at least half a voxel spare either way.  At the examples' eyes (t1 * 2^-23 / dt
+        // ~ 5e-5, d <= 61) d * drift stays far below 1: their walks do not change.
         const float inv_u = SKIP ? __builtin_amdgcn_rcpf(dt * fmaxf(fabsf(dir[0]) * hbx, fmaxf(fabsf(dir[1]) * hby, fabsf(dir[2]) * hbz))) : 0.0f;
+        const float drift = SKIP ? fabsf(t1) * 0x1p-23f / dt : 0.0f;
+        // iterations, this one included, whose samples cannot contribute, at a record dvox voxels (Chebyshev) from the nearest that can
+        auto clear_steps = [&](uint32_t dvox) -> float {
+            const float dv = (float)dvox;
+            return __builtin_floorf(fmaf(dv, inv_u, -2.01f * inv_u) - fmaxf(fmaf(dv, drift, -1.0f), 0.0f) * inv_u) + 1.0f;
+        };
         struct Req { float px, py, pz; u32x4_t r; };
         auto request = [&](float t) -> Req {
             Req q;
@@ -104,7 +118,7 @@ __global__ __launch_bounds__(64) void raymarch_compute_records_kernel(const Laun
             if (SKIP) {  // ---- WALK
                 while (alive) {
                     const uint32_t dvox = q.r.w >> 16;
-                    const float m = __builtin_floorf(fmaf((float)dvox, inv_u, -2.01f * inv_u)) + 1.0f;  // iterations, this one included, whose samples cannot contribute
+                    const float m = clear_steps(dvox);
                     if (dvox == 0u || m < 2.0f) break;
                     float c = 0.0f;
                     do { t = t + dt; c += 1.0f; } while (c < m && t < t1);
@@ -132,7 +146,7 @@ __global__ __launch_bounds__(64) void raymarch_compute_records_kernel(const Laun
             auto leave = [&](const Req &cur) -> bool {
                 if (SKIP) {
                     const uint32_t dvox = cur.r.w >> 16;  // (an out-of-range load returns zeros: distance 0 -- it is shaded and adds +0)
-                    const bool deep = fmaf((float)dvox, inv_u, -2.01f * inv_u) + 1.0f >= walk_min;
+                    const bool deep = clear_steps(dvox) >= walk_min;  // (WALK's own m: a lane that is deep hops at least once)
                     return __ballot(alive && !deep) == 0ull;  // every live lane may walk (or none is left)
                 }
                 return __ballot(alive) == 0ull;
@@ -150,9 +164,11 @@ __global__ __launch_bounds__(64) void raymarch_compute_records_kernel(const Laun
                     // The shader's literal expressions (kept word for word in raymarch_compute_kernel below, which the tests hold
                     // this kernel to bit for bit) carry terms that are zero for every finite record: dot((0,-1,0), n) is -n.y,
                     // mix(shade, bl * (0,0,0.6), 0.2) has zero red and green contributions from bl, and clear.rgb * clear.a * (1 - a)
-                    // is 0 * (1 - a).  IEEE arithmetic forbids the compiler to drop them (0 * x is NaN for an infinite x); with finite
-                    // taps they only ever add a zero to a non-zero accumulator, so leaving them out changes no bit: 15 of the step's
-                    // 85 instructions.  A volume with infinities or NaNs renders differently from the literal form.
+                    // is 0 * (1 - a).  IEEE arithmetic forbids the compiler to drop them (0 * x is NaN for an infinite x), but bl and
+                    // a are always finite, so the last two only ever add a zero to a non-zero accumulator, and dot((0,-1,0), n) is
+                    // -n.y whenever n.x and n.z are finite: leaving them out changes no bit there, and saves 15 of the step's 85
+                    // instructions.  The one input that renders differently from the literal form: a record whose n.x or n.z is +-inf
+                    // or NaN while n.y < 0 (the literal dot is NaN and max(0, .) makes the shade 0; here it is -n.y).
                     float sh = fmaxf(0.0f, -n1);
                     float va = (vc3 * vc3) * vc3;
                     va = smoothstepf(0.0f, 0.7f, va);

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "vk_common.hpp"
+#include "vk_pair.hpp"
 #include "vk_tf.hpp"
 #include "vk_xor.hpp"
 
@@ -42,8 +43,9 @@ __global__ __launch_bounds__(256) void build_pair_luts_kernel(uint32_t *__restri
 }
 
 // dense x-fastest (density, normals) -> bricked 16-byte records
-// occ[id] = 0 where the record can contribute -- the shader's own opacity smoothstep(0, 0.7, a^3) (raycast_compute.wgsl:78-79) is not exactly
-// 0 -- else 255: the seed of the records' skip map (embed_pair_dist_kernel).
+// occ[id] = 0 where shading the record could change an accumulator -- vk_pair.hpp: pair_record_empty is false: the shader's own opacity
+// smoothstep(0, 0.7, a^3) (raycast_compute.wgsl:78-79) is not exactly 0, or the colour is not finite, or a normal component is -inf --
+// else 255: the seed of the records' skip map (embed_pair_dist_kernel).
 __global__ __launch_bounds__(256) void pack_pairs_kernel(const uint2 *__restrict__ den, const uint2 *__restrict__ nrm, uint4 *__restrict__ dst,
                                                          uint32_t nx, uint32_t ny, uint32_t nz, uint32_t nbx, uint32_t nby, uint64_t n_rec,
                                                          uint8_t *__restrict__ occ) {
@@ -61,8 +63,9 @@ __global__ __launch_bounds__(256) void pack_pairs_kernel(const uint2 *__restrict
             r = make_uint4(d.x, d.y, n.x, n.y);
         }
         dst[id] = r;
-        const float a = h2f(r.y >> 16);
-        occ[id] = smoothstepf(0.0f, 0.7f, (a * a) * a) != 0.0f ? 0 : 255;  // (a NaN opacity compares unequal: kept)
+        const float rgba[4] = {h2f(r.x & 0xffffu), h2f(r.x >> 16), h2f(r.y & 0xffffu), h2f(r.y >> 16)};
+        const float n[3] = {h2f(r.z & 0xffffu), h2f(r.z >> 16), h2f(r.w & 0xffffu)};
+        occ[id] = pair_record_empty(rgba, n) ? 255 : 0;  // (a NaN opacity gives smoothstep 0: empty when the rest allows)
     }
 }
 
