@@ -393,7 +393,20 @@ int vk_device_download(vk_ctx *ctx, void *dst_host, const void *src_device, size
 /* Context::render's present pass (src/context.rs:251-297, shaders/present.wgsl:23-35,111-119): bilinear
  * resample of the backbuffer to width x height (the window size), ACESFilm, linear_to_srgb, into the
  * context-owned Rgba8Unorm target (and a Bgra8Unorm "surface" copy when also_bgra != 0).  Asynchronous. */
+/* What it computes, per pixel (x, y) of the window and per channel (tests/np_present_reference.py restates this in float64):
+ *   - the sample position and weights are this f32 chain: uv = (x + 0.5) / width, u = fma(uv, backbuffer_width, -0.5), texel floor(u) and
+ *     floor(u) + 1 clamped to the edge, weight fract(u) (below 1); the same in y.  They are part of the specification.
+ *   - a sample whose two weights are both exactly 0 is that texel's value, whatever its neighbours hold; otherwise the bilinear blend
+ *     a + fx (b - a) follows IEEE: a NaN tap, or inf - inf, makes NaN.
+ *   - colour = linear_to_srgb(ACESFilm(v)) as real functions of present.wgsl:23-35 (exponent 0.41666, threshold 0.0031308), ACESFilm extended
+ *     by its limits: huge finite values and +-inf map to 1.  Alpha is v itself.  NaN maps to 0 in every channel, alpha included.
+ *   - clamp to [0, 1], times 255, round half up.  Bgra8 is Rgba8 with bytes 0 and 2 exchanged. */
 int vk_present(vk_ctx *ctx, uint32_t width, uint32_t height, int also_bgra);
+/* The current frame slot's present targets, device pointers to width x height tightly packed 4-byte pixels: the Rgba8Unorm image
+ * vk_capture_frame reads and the Bgra8Unorm surface copy (NULL when no present has asked for one at this size; it holds the last present
+ * that did).  Every out-pointer is optional.  VK_ERR_INVALID before anything was presented.  Does not synchronise: order reads after the
+ * context's stream (vk_ctx_sync, vk_device_download). */
+int vk_present_info(vk_ctx *ctx, uint32_t *width, uint32_t *height, void **rgba8, void **bgra8);
 /* Context::capture_frame (src/context.rs:299-302, src/context/screenshot.rs:37-77): the presented Rgba8
  * image with the reference's ImageDimentions: even-rounded size, rows padded to 256 B.  dst == NULL only
  * queries the three sizes.  Blocking. */

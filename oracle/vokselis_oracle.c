@@ -758,7 +758,10 @@ void vo_volume_xor(uint32_t nx, uint32_t ny, uint32_t nz, float time, uint16_t *
 static inline float aces_film(float x) { /* present.wgsl:33-35 */
     float num = x * (2.51f * x + 0.03f);
     float den = x * (2.43f * x + 0.59f) + 0.14f;
-    return vmin(vmax(num / den, 0.0f), 1.0f);
+    /* the curve's limit at +-inf is 2.51 / 2.43 > 1 and it exceeds 1 beyond |x| ~ 7.3: from 1024 on the answer is the clamp's 1, also where
+     * both quadratics overflow in f32 (|x| > ~1.16e19, +-inf) and num / den would be NaN, hence 0.  NaN compares false and presents as 0. */
+    float q = fabsf(x) >= 1024.0f ? 1.0f : num / den;
+    return vmin(vmax(q, 0.0f), 1.0f);
 }
 
 static inline float present_srgb(float c) { /* present.wgsl:23-30: branch-free, exponent 0.41666 */
@@ -788,10 +791,13 @@ void vo_present(const float *bb, uint32_t bw, uint32_t bh, uint32_t w, uint32_t 
             for (int c = 0; c < 4; c++) {
                 float t00 = bb[4 * ((size_t)y0 * bw + x0) + c], t10 = bb[4 * ((size_t)y0 * bw + x1) + c];
                 float t01 = bb[4 * ((size_t)y1 * bw + x0) + c], t11 = bb[4 * ((size_t)y1 * bw + x1) + c];
-                float a = lerp_fma(t00, t10, fx), b = lerp_fma(t01, t11, fx);
-                float v = lerp_fma(a, b, fy);
+                float v = t00; /* both weights exactly 0: the texel alone, whatever its neighbours hold (fma(0, inf, a) is NaN) */
+                if (fx != 0.0f || fy != 0.0f) {
+                    float a = lerp_fma(t00, t10, fx), b = lerp_fma(t01, t11, fx);
+                    v = lerp_fma(a, b, fy);
+                }
                 if (c < 3) v = present_srgb(aces_film(v));
-                v = vmin(vmax(v, 0.0f), 1.0f);
+                v = v != v ? 0.0f : vmin(vmax(v, 0.0f), 1.0f); /* NaN presents as 0 (libm's fmaxf hands a signalling NaN on) */
                 o[c] = (uint8_t)floorf(v * 255.0f + 0.5f);
             }
         }

@@ -145,7 +145,9 @@ void vo_volume_xor(uint32_t nx, uint32_t ny, uint32_t nz, float time, uint16_t *
 /* Present pass (next row N1): shaders/present.wgsl:23-35,111-119 with the linear clamp-to-edge sampler of
  * src/context/present_pipeline.rs:95-104.  backbuffer: [bh][bw][4] f32 (already rounded through f16
  * by the caller when the surface is rgba16float); out: [h][w][4] u8 in RGBA order (the Rgba8Unorm
- * copy that capture_frame reads, src/context.rs:339-359).  unorm8 = floor(c*255 + 0.5). */
+ * copy that capture_frame reads, src/context.rs:339-359).  unorm8 = floor(c*255 + 0.5).
+ * As vk_present specifies it (include/vokselis_hip.h): a sample whose two weights are exactly 0 is that texel alone; ACESFilm is extended
+ * by its limits (|x| >= 1024, +-inf included, gives 1); NaN presents as 0 in every channel. */
 void vo_present(const float *backbuffer, uint32_t bw, uint32_t bh, uint32_t w, uint32_t h, uint8_t *out_rgba8);
 
 /* src/utils/mod.rs:15-18 and :99-117 */

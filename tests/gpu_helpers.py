@@ -48,6 +48,13 @@ def gpu_render(V, cam_blob, vol, W, H, *, dt=1.0, layout=None, flags=0, out=None
         ctx.close()
 
 
+class _DevicePtr:
+    """A raw device pointer as something torch.as_tensor reads without copying."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "version": 2}
+
+
 def _synced(t):
     """A tensor torch has just filled on ITS current stream, handed to the library, which writes on a non-blocking stream of
     its own: without a synchronisation nothing orders the fill before the library's kernels (torch's streams and the

@@ -7,6 +7,9 @@ written again before the frame K later begins; error codes, never crashes, for m
 import numpy as np
 import pytest
 
+import np_present_reference as P
+import present_cases as PC
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
@@ -328,6 +331,11 @@ def test_present_fused_equals_render_then_present(V, O):
                 want = O.present(bb0.astype(np.float32), w, h)[:fused.shape[0], :fused.shape[1]].astype(np.int32)
                 do = np.abs(fused.astype(np.int32) - want)
                 assert do.max() <= 1 and (do == 0).mean() > 0.995, (name, fmt, do.max(), (do == 0).mean())
+                # ... and byte for byte the float64 specification's at texel centres (the stored value itself), but where q + 0.5 lies
+                # within DELTA of an integer
+                q = np.concatenate([P.tone_q(bb0[..., :3]), P.tone_q(bb0[..., 3:], alpha=True)], axis=2)[:fused.shape[0], :fused.shape[1]]
+                wrong, _ = P.judge(fused, q, PC.DELTA)
+                assert not wrong.any(), (name, fmt, int(wrong.sum()))
                 assert (fused[..., 3] == 255).all() and fused[..., :3].max() > 30
                 # PRESENT_ONLY: the backbuffer keeps what it held
                 V.native.check(ctx.handle, V.native.lib().vk_backbuffer_clear(ctx.handle))

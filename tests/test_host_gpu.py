@@ -5,6 +5,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import np_present_reference as P
+import present_cases as PC
+
 from gpu_helpers import TOL, V, _captured_rgb, _holes_volume, _orbit_cameras, _render_with_params, _synced, gpu_render, layouts  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -147,6 +150,9 @@ def test_present_pass_and_capture_frame(V, O):
                 want = O.present(ctx.read_backbuffer().astype(np.float32), w, h)[:dims.height, :dims.width].astype(np.int32)
                 d = np.abs(got - want)
                 assert d.max() <= 1 and (d == 0).mean() > 0.995, ((bw, bh), (w, h), fmt, d.max(), (d == 0).mean())
+                # ... and byte for byte the float64 specification's, but where its q + 0.5 lies within DELTA of an integer
+                wrong, _ = P.judge(got, P.present_q(ctx.read_backbuffer(), w, h)[:dims.height, :dims.width], PC.DELTA)
+                assert not wrong.any(), ((bw, bh), (w, h), fmt, int(wrong.sum()))
                 assert (got[..., 3] == 255).all()
             finally:
                 ctx.close()

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from gpu_helpers import V, _synced  # noqa: F401  (V: fixture)
+from gpu_helpers import V, _DevicePtr, _synced  # noqa: F401  (V: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -16,13 +16,6 @@ def _fog(n, seed=11):
 
 def _camera(V, W, H, k=0):
     return V.Camera(1.0 + 0.1 * k, 0.5, 1.1, (0.5, 0.5, 0.5), W / H).get_proj_view_matrix()
-
-
-class _DevicePtr:
-    """A raw device pointer as something torch.as_tensor reads without copying."""
-
-    def __init__(self, ptr, shape, typestr):
-        self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "version": 2}
 
 
 def test_backbuffer_info_follows_the_surface(V):

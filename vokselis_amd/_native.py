@@ -97,6 +97,7 @@ SYMBOLS = {
     "vk_device_free": (C.c_int, [_vp, _vp]),
     "vk_device_download": (C.c_int, [_vp, _vp, _vp, _sz]),
     "vk_present": (C.c_int, [_vp, _u32, _u32, C.c_int]),
+    "vk_present_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_vp), C.POINTER(_vp)]),
     "vk_capture_frame": (C.c_int, [_vp, _vp, _sz, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "vk_readback": (C.c_int, [_vp, _vp, _sz]),
     "vk_step_counts": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -307,6 +307,20 @@ class Context:
             return
         N.check(self._h, N.lib().vk_present(self._h, self.width, self.height, 0))
 
+    def present_targets(self):
+        """vk_present_info: the current slot's presented images as [h, w, 4] uint8 arrays, (Rgba8, Bgra8 or None).  Waits for the context's
+        stream."""
+        w, h, r8, b8 = C.c_uint32(), C.c_uint32(), C.c_void_p(), C.c_void_p()
+        N.check(self._h, N.lib().vk_present_info(self._h, C.byref(w), C.byref(h), C.byref(r8), C.byref(b8)))
+        out = []
+        for p in (r8.value, b8.value):
+            img = None
+            if p:
+                img = np.empty((h.value, w.value, 4), np.uint8)
+                N.check(self._h, N.lib().vk_device_download(self._h, img.ctypes.data, p, img.size))
+            out.append(img)
+        return tuple(out)
+
     def capture_frame(self):
         """Context::capture_frame (src/context.rs:299-302, screenshot.rs:37-77): the presented Rgba8
         frame as padded rows + its ImageDimentions."""

@@ -248,9 +248,15 @@ __device__ __forceinline__ void store_pixel(void *out, size_t idx, float r, floa
 }
 
 // ---- present pass arithmetic (shaders/present.wgsl:23-35,111-119), shared by present_kernel (vk_post.hpp) and the fused epilogue ----
+// ACESFilm is a ratio of two quadratics with limit 2.51 / 2.43 > 1 at +-inf; it exceeds 1 for every x > 7.3 and every x < -0.25.  Beyond
+// |x| ~ 1.16e19 both quadratics overflow in f32 and the quotient is inf / inf = NaN, which the clamp would turn into 0: the brightest pixels
+// (every overexposed pixel of an rgba16f surface is +inf) would come out black.  So |x| >= kAcesSaturated takes the limit's clamp, 1, which
+// is what the quotient gives for every finite x from there up to the overflow point.  NaN compares false and stays NaN -> 0.
+constexpr float kAcesSaturated = 1024.0f;
 __device__ __forceinline__ float aces_film(float x) {
     float num = x * (2.51f * x + 0.03f), den = x * (2.43f * x + 0.59f) + 0.14f;
-    return fminf(fmaxf(num / den, 0.0f), 1.0f);
+    float q = fabsf(x) >= kAcesSaturated ? 1.0f : num / den;
+    return fminf(fmaxf(q, 0.0f), 1.0f);
 }
 __device__ __forceinline__ float present_srgb(float c) {
     float sel = ceilf(c - 0.0031308f);

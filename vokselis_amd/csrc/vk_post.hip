@@ -137,6 +137,16 @@ int vk_present(vk_ctx *ctx, uint32_t width, uint32_t height, int also_bgra) {
     return VK_OK;
 }
 
+int vk_present_info(vk_ctx *ctx, uint32_t *width, uint32_t *height, void **rgba8, void **bgra8) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (!ctx->rgba8) return fail(ctx, VK_ERR_INVALID, "vk_present_info: nothing presented yet (vk_present)");
+    if (width) *width = ctx->present_w;
+    if (height) *height = ctx->present_h;
+    if (rgba8) *rgba8 = ctx->rgba8;
+    if (bgra8) *bgra8 = ctx->bgra8;
+    return VK_OK;
+}
+
 int vk_capture_frame(vk_ctx *ctx, void *dst, size_t dst_bytes, uint32_t *out_width, uint32_t *out_height,
                      uint32_t *out_padded_bytes_per_row) {
     if (!ctx) return VK_ERR_INVALID;

@@ -38,7 +38,8 @@ __global__ __launch_bounds__(256) void present_kernel(const void *__restrict__ b
     float px[4] = {t00.x, t00.y, t00.z, t00.w};
     if (fx != 0.0f || fy != 0.0f) {
         // (a sample on a texel centre -- nearly every pixel when the backbuffer has the window's size -- has weights
-        // exactly (1, 0, 0, 0): fma(0, b - a, a) is a for finite taps, so the other three are not fetched)
+        // exactly (1, 0, 0, 0).  By specification it is that texel's value whatever its neighbours hold -- fma(0, b - a, a)
+        // would be NaN beside an inf or NaN texel -- so the other three are not fetched: include/vokselis_hip.h, vk_present)
         const float4 t10 = load_px(bb, fmt, (size_t)y0 * bw + x1), t01 = load_px(bb, fmt, (size_t)y1 * bw + x0), t11 = load_px(bb, fmt, (size_t)y1 * bw + x1);
         const float a1[4] = {t10.x, t10.y, t10.z, t10.w}, b0[4] = {t01.x, t01.y, t01.z, t01.w}, b1[4] = {t11.x, t11.y, t11.z, t11.w};
 #pragma unroll
