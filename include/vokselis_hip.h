@@ -199,6 +199,26 @@ typedef struct vk_lighting {
 } vk_lighting; /* 32 bytes */
 int vk_set_lighting(vk_ctx *ctx, const vk_lighting *light);
 
+/* Projection of VK_MODE_NAIVE_TRILINEAR: VK_PROJ_COMPOSITE (default), the front-to-back compositing of the reference, or
+ * VK_PROJ_MAX, a maximum-intensity projection over the window [lo, hi] of the table in force.  Under
+ * VK_PROJ_MAX a ray that hits the box carries U = +0 and takes, per iteration of the reference's loop, with x the filtered
+ * sample and k1, k2 as under vk_set_transfer_function:  U = max(U, min(max(fma(x, k1, k2), 0), n-1))  (a NaN sample counts as 0;
+ * U is +0 whenever it compares equal to zero);  the ray ends after the iteration in which U reaches n-1.  The pixel is
+ * i = min(floor(U), n-2);  c = lerp(T[i], T[i+1], U - i);  (srgb(c.r), srgb(c.g), srgb(c.b), 1): the table is read once per
+ * ray and its alpha column not at all.  Without a table the implicit grey ramp {(0,0,0), (1,1,1)} over [0, 1] is used (n = 2),
+ * bit for bit the frame of that table set explicitly.  Misses are (0,0,0,1).  Lighting (vk_set_lighting) is ignored under
+ * VK_PROJ_MAX, with or without a table.  The skip maps and vk_volume_empty_fraction follow the projection: a cell is empty iff
+ * its 8 taps are finite and its largest tap M has min(max(fma(M, k1, k2), 0), n-1) == 0.
+ * The call drains every frame slot (as vk_ctx_sync), stores the value and rebuilds the skip maps of the current volume under
+ * the (projection, table) pair now in force; the order of vk_set_projection and vk_set_transfer_function does not matter.
+ * VK_ERR_INVALID (the previous projection stays in force): an unknown value, or a call between vk_frame_begin and
+ * vk_frame_end.  The projection stays in force across vk_volume_upload / _upload_device / vk_volume_generate.  Layouts under
+ * VK_PROJ_MAX: LINEAR, PACKED, PACKED_PAIRS; NAIVE renders of BRICKED / QUADS / STAGED volumes, and VK_RENDER_FAST_WALK, are
+ * VK_ERR_UNSUPPORTED.  COMPUTE_NEAREST and PROCEDURAL ignore it. */
+enum vk_projection { VK_PROJ_COMPOSITE = 0, VK_PROJ_MAX = 1 };
+int vk_set_projection(vk_ctx *ctx, int projection);
+int vk_get_projection(vk_ctx *ctx, int *projection);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

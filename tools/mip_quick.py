@@ -1,0 +1,95 @@
+"""The maximum-intensity projection on the C2 shape (256^3 bonsai stand-in, 1080p, dt 0.5, f16 out): ms per frame, one frame per launch and
+128 orbit frames per launch, interleaved, best of three groups per repetition, for
+  composite          the built-in transfer, composited
+  composite_table    `builtin_table` (the built-in transfer and palette sampled into 256 entries), composited
+  max_table          VK_PROJ_MAX over the window [0.1, 1] with `builtin_table`: the census of the two above, so the same skip policy
+  max_grey           VK_PROJ_MAX with no table: the grey ramp over [0, 1]
+plus every configuration's empty fraction, S_ref, S_sampled and ms per million sampled steps.  The comparison that prices the new loop is
+max_table against composite_table per sampled step: MIP rays run longer than composited ones.  S_ref - S_sampled of the MAX rows is
+also the room a skip driven by the running maximum would have (out of scope: DESIGN.md section 12).
+usage: tools/mip_quick.py [--reps N]"""
+import ctypes as C
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+import vokselis_amd as V
+from vokselis_amd import _native as N
+
+W, H, DT, B = 1920, 1080, 0.5, 128
+reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 3
+
+
+def builtin_table(n=256):
+    """raycast_naive.wgsl:104-110 sampled at n values: alpha = smoothstep(0.1, 1.2, min(v, 0.9)), colour = the vertigo palette of alpha."""
+    x = np.arange(n) / (n - 1)
+    s = np.clip((np.minimum(x, 0.9) - 0.1) / 1.1, 0.0, 1.0)
+    a = s * s * (3.0 - 2.0 * s)
+    rgb = np.stack([0.5 + 0.5 * np.cos(6.28318 * (c * a + d)) for c, d in ((1.0, 0.0), (1.7, 0.15), (0.4, 0.20))], axis=1)
+    return np.concatenate([rgb, a[:, None]], axis=1).astype(np.float32)
+
+
+def t(ctx, fn, iters, groups=3):
+    for _ in range(2):
+        fn()
+    ctx.sync()
+    best = 1e9
+    for _ in range(groups):
+        ctx.timer_begin()
+        for _ in range(iters):
+            fn()
+        ctx.timer_end()
+        best = min(best, ctx.timer_elapsed_ms() / iters)
+    return best
+
+
+def empty_fraction(ctx):
+    f = C.c_double()
+    N.check(ctx.handle, N.lib().vk_volume_empty_fraction(ctx.handle, C.byref(f)))
+    return f.value
+
+
+cam = V.Camera(1.0, 0.5, 1.0, (0.5, 0.5, 0.5), W / H)
+orbit = [V.Camera(1.0, 0.5, 1.0 + 6.28318 * j / 1024, (0.5, 0.5, 0.5), W / H).get_proj_view_matrix() for j in range(B)]
+configs = [("composite", None, (0.0, 1.0), None), ("composite_table", builtin_table(), (0.0, 1.0), None),
+           ("max_table", builtin_table(), (0.1, 1.0), "max"), ("max_grey", None, (0.0, 1.0), "max")]
+ctxs = {}
+out = {}
+for name, table, window, proj in configs:
+    ctx = V.Context(W, H, cam, backbuffer=(W, H), out_format=V.OUT_RGBA16F)
+    if table is not None:
+        ctx.set_transfer_function(table, window)
+    ctx.set_projection(proj)
+    V.VolumeTexture.generate_standin(ctx, (256,) * 3)
+    ctx.update()
+    ctx.reset_step_counts()
+    V.RaycastPipeline(dt_scale=DT, flags=V.RENDER_COUNT).record(ctx)
+    s_ref, s_sampled = ctx.step_counts()
+    out[name + "_empty_fraction"] = round(empty_fraction(ctx), 4)
+    out[name + "_s_ref"], out[name + "_s_sampled"] = int(s_ref), int(s_sampled)
+    ctxs[name] = ctx
+frames = torch.empty((B, H, W, 4), dtype=torch.float16, device="cuda")
+pipe = V.RaycastPipeline(dt_scale=DT)
+for name, ctx in ctxs.items():
+    for _ in range(200):
+        pipe.record(ctx)
+    ctx.sync()
+for rep in range(reps):
+    for name, ctx in ctxs.items():
+        out.setdefault(name + "_single_ms", []).append(round(t(ctx, lambda: pipe.record(ctx), 50), 4))
+        out.setdefault(name + "_orbit128_ms_per_frame", []).append(
+            round(t(ctx, lambda: V.render_batch(ctx, pipe, orbit, frames.data_ptr(), tile_size=64), 3) / B, 5))
+for name in ctxs:
+    for k in ("single_ms", "orbit128_ms_per_frame"):
+        out[name + "_" + k + "_per_Msampled"] = round(min(out[name + "_" + k]) / (out[name + "_s_sampled"] / 1e6), 5)
+for k in ("single_ms", "orbit128_ms_per_frame"):
+    out["max_table_over_composite_table_" + k] = round(min(out["max_table_" + k]) / min(out["composite_table_" + k]), 3)
+    out["max_table_over_composite_table_per_sampled_step_" + k] = round(out["max_table_" + k + "_per_Msampled"] / out["composite_table_" + k + "_per_Msampled"], 3)
+    out["max_grey_over_composite_" + k] = round(min(out["max_grey_" + k]) / min(out["composite_" + k]), 3)
+for ctx in ctxs.values():
+    ctx.close()
+print(json.dumps(out), flush=True)

@@ -24,6 +24,7 @@ WIRE_RGBA, WIRE_RGB = 0, 1
 MAX_FRAMES_IN_FLIGHT = 4
 GEN_FOG, GEN_BONSAI_STANDIN, GEN_FOG_DENSE_CORE = 0, 1, 2
 TF_MAX_ENTRIES = 256
+PROJ_COMPOSITE, PROJ_MAX = 0, 1
 
 
 class VkLighting(C.Structure):
@@ -51,6 +52,8 @@ SYMBOLS = {
     "vk_volume_empty_fraction": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "vk_set_transfer_function": (C.c_int, [_vp, C.POINTER(C.c_float), _u32, _f32, _f32]),
     "vk_set_lighting": (C.c_int, [_vp, _vp]),  # const vk_lighting * (VkLighting below), NULL: off
+    "vk_set_projection": (C.c_int, [_vp, C.c_int]),
+    "vk_get_projection": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),
     "vk_set_uniform": (C.c_int, [_vp, _vp]),
     "vk_set_camera": (C.c_int, [_vp, _vp]),

@@ -210,6 +210,25 @@ class Context:
         lo, hi = domain
         N.check(self._h, L.vk_set_transfer_function(self._h, t.ctypes.data_as(C.POINTER(C.c_float)), t.shape[0], float(lo), float(hi)))
 
+    def set_projection(self, projection):
+        """Projection of MODE_NAIVE_TRILINEAR (vk_set_projection): "max" for a maximum-intensity projection over the window of the
+        table in force (without a table: a grey ramp over [0, 1]), None or "composite" for the front-to-back compositing (the default).
+        Drains the frames in flight and rebuilds the skip maps of the current volume; lighting is ignored under "max"."""
+        if projection in (None, "composite", N.PROJ_COMPOSITE):
+            value = N.PROJ_COMPOSITE
+        elif projection in ("max", N.PROJ_MAX):
+            value = N.PROJ_MAX
+        else:
+            raise ValueError('set_projection: "max", "composite" or None')
+        N.check(self._h, N.lib().vk_set_projection(self._h, value))
+
+    @property
+    def projection(self):
+        """The projection in force: "max", or None for the compositing default (vk_get_projection)."""
+        v = C.c_int(0)
+        N.check(self._h, N.lib().vk_get_projection(self._h, C.byref(v)))
+        return "max" if v.value == N.PROJ_MAX else None
+
     def set_lighting(self, direction=None, ambient=0.3, diffuse=0.7, specular=0.2, shininess=32.0):
         """Gradient lighting of the table march (vk_set_lighting): each sample's table colour is shaded by the gradient of the trilinear
         interpolant, two-sided Blinn-Phong, rgb' = c.rgb (ambient + diffuse |N.L|) + specular |N.H|^shininess; alpha is untouched.

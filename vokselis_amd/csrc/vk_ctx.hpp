@@ -9,6 +9,7 @@
 //   vk_launch_cells.hip    instantiates the cell-layout march kernels      (vk_march.hpp)
 //   vk_launch_tf.hip       instantiates the cell march under a transfer table (vk_march.hpp)
 //   vk_launch_lit.hip      instantiates the table march with gradient lighting (vk_march.hpp, vk_light.hpp)
+//   vk_launch_mip.hip      the cell march under the maximum-intensity projection (its own loops and kernel)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)
@@ -56,6 +57,8 @@ struct vk_ctx {
     float *d_tf = nullptr;
     uint32_t tf_n = 0;
     float tf_lo = 0.0f, tf_hi = 1.0f;
+    // projection of NAIVE_TRILINEAR (vk_set_projection): compositing, or the maximum over the table's window (vk_launch_mip.hip)
+    int proj = VK_PROJ_COMPOSITE;
     // gradient lighting of the table march (vk_set_lighting): host state, passed by value to the lit kernels
     bool lit = false;
     vk::LightDesc light{};
@@ -193,7 +196,7 @@ inline size_t px_bytes(int fmt) { return fmt == VK_OUT_RGBA16F ? 8 : 16; }
 inline size_t wire_px_bytes(int fmt, int wire) { return wire == VK_WIRE_RGB ? px_bytes(fmt) / 4 * 3 : px_bytes(fmt); }
 
 // ---- shared between translation units --------------------------------------------------------------------
-int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float lo, float hi);  // vk_volume.hip: the current volume's maps under a table (nullptr: built-in)
+int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float lo, float hi, int projection);  // vk_volume.hip: the current volume's maps under a table (nullptr: built-in) and a projection
 int frames_drain(vk_ctx *ctx);   // vk_context.hip: wait for the work of every frame slot (one stream when fif_k == 1)
 void free_volume(vk_ctx *ctx);   // vk_volume.hip
 void comm_release(vk_ctx *ctx);  // vk_comm.hip
@@ -219,6 +222,7 @@ void launch_cells(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V,
 void launch_cells_tf(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_tf.hip
 void launch_cells_lit(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::LightDesc &Lt, uint32_t grid, bool count, bool skip,
                       bool safe);  // vk_launch_lit.hip
+void launch_cells_mip(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_mip.hip (T.rgba == nullptr: the grey ramp)
 void launch_staged(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, const float *cam);
 void launch_compute(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, bool records, bool skip);
 void launch_procedural(vk_ctx *ctx, const vk::LaunchDesc &L, uint32_t grid, bool count, float time, bool device_sine);

@@ -77,11 +77,24 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
     L.grid_march = grid;
     // a runtime transfer function (vk_set_transfer_function) has kernels on the LINEAR / PACKED / PACKED_PAIRS layouts, walking with the loop
     const bool tf = mode == VK_MODE_NAIVE_TRILINEAR && ctx->d_tf;
+    // the maximum-intensity projection (vk_set_projection): kernels of its own with the table kernels' coverage; lighting is ignored under it
+    const bool mip = mode == VK_MODE_NAIVE_TRILINEAR && ctx->proj == VK_PROJ_MAX;
     // gradient lighting (vk_set_lighting) shades the table's colour: it has no kernels without a table
-    if (mode == VK_MODE_NAIVE_TRILINEAR && ctx->lit && !tf)
+    if (mode == VK_MODE_NAIVE_TRILINEAR && ctx->lit && !tf && !mip)
         return fail(ctx, VK_ERR_UNSUPPORTED, "lighting: NAIVE_TRILINEAR renders with lighting need a transfer function (set a table with vk_set_transfer_function, or turn lighting off with vk_set_lighting(NULL))");
     TfDesc T{};
-    if (tf) {
+    if (mip) {
+        const int k = ctx->vol_kind;
+        if (k != VOL_LINEAR_U8 && k != VOL_LINEAR_F16 && k != VOL_P8 && k != VOL_P16 && k != VOL_PF16)
+            return fail(ctx, VK_ERR_UNSUPPORTED, "projection: NAIVE_TRILINEAR renders under VK_PROJ_MAX need a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no maximum-projection kernels; vk_set_projection(VK_PROJ_COMPOSITE) resets)");
+        if (flags & VK_RENDER_FAST_WALK) return fail(ctx, VK_ERR_UNSUPPORTED, "projection: VK_RENDER_FAST_WALK has no maximum-projection kernels (VK_PROJ_MAX)");
+        // the window of the table in force; without one the implicit grey ramp, two entries over [0, 1] (T.rgba stays NULL)
+        const uint32_t n = tf ? ctx->tf_n : 2u;
+        tf_constants(n, tf ? ctx->tf_lo : 0.0f, tf ? ctx->tf_hi : 1.0f, ctx->format == VK_FMT_R8_UNORM, T.k1, T.k2);
+        T.rgba = tf ? ctx->d_tf : nullptr;
+        T.umax = (float)(n - 1u);
+        T.imax = (int32_t)n - 2;
+    } else if (tf) {
         const int k = ctx->vol_kind;
         if (k != VOL_LINEAR_U8 && k != VOL_LINEAR_F16 && k != VOL_P8 && k != VOL_P16 && k != VOL_PF16)
             return fail(ctx, VK_ERR_UNSUPPORTED, "transfer function: NAIVE_TRILINEAR renders with a table need a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no table kernels; vk_set_transfer_function(NULL) resets)");
@@ -133,6 +146,7 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
             if (V.max_off + 16 < (1ll << 32) && cell_lut_bytes(ctx->nx, ctx->ny, ctx->nz) <= 16384u && 64.0f * ulp < 0.25f / nmax && !(flags & VK_RENDER_SAFE)) safe = false;
         }
         if (ctx->vol_kind == VOL_S8U8 || ctx->vol_kind == VOL_S8F16) launch_staged(ctx, L, V, grid, count, reach_cam);
+        else if (mip) launch_cells_mip(ctx, L, V, T, grid, count, skip, safe);
         else if (tf && ctx->lit) launch_cells_lit(ctx, L, V, T, ctx->light, grid, count, skip, safe);
         else if (tf) launch_cells_tf(ctx, L, V, T, grid, count, skip, safe);
         else launch_cells(ctx, L, V, grid, count, skip, safe, (flags & VK_RENDER_FAST_WALK) ? 2 : 0);  // (vk_march.hpp: WalkKind)

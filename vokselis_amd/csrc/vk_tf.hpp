@@ -95,4 +95,28 @@ VK_TF_HD bool builtin_cell_empty(const float t[8], bool f16) {
     return empty;
 }
 
+// ---- maximum-intensity projection (vk_set_projection(VK_PROJ_MAX)) ----
+// One step of the running maximum in table coordinates: U' = fmaxf(U, tf_u(x)) with the rule that a U comparing equal to zero is +0.
+// Written as a select: with 0 <= U <= umax (U starts at +0), u = fma(x, k1, k2) replaces U only when u > U, which is never the case
+// for u <= 0, u = -0 or a NaN u (a NaN sample reads as the minimum); the result is clamped to umax.  For u > U >= 0 that is
+// min(max(u, 0), umax) = tf_u(x), otherwise U: the specification's value, and U never carries a -0.
+VK_TF_HD float mip_update(float U, float x, float k1, float k2, float umax) {
+    const float u = fmaf(x, k1, k2);
+    return fminf(u > U ? u : U, umax);
+}
+
+// Emptiness of a cell under the maximum projection: its 8 taps are finite and tf_u(M) == 0 for its largest tap M.  Why skipping stays
+// exact: a sample of the cell lies in [m, M] (the lerp argument at the top of this file), fma(x, k1, k2) with k1 > 0 rounds once and
+// is monotone in x, so u(x) <= u(M) <= 0 and mip_update leaves U with the bits it had -- a skipped step and a sampled one agree.
+// A cell with a non-finite tap is never empty (its samples can be NaN or +inf).
+VK_TF_HD bool mip_cell_empty(const float t[8], float k1, float k2, float umax) {
+    float M = t[0];
+    bool finite = true;
+    for (int b = 0; b < 8; b++) {
+        finite = finite && isfinite(t[b]);
+        M = fmaxf(M, t[b]);
+    }
+    return finite && tf_u(M, k1, k2, umax) == 0.0f;
+}
+
 }  // namespace vk

@@ -98,17 +98,21 @@ static int alloc_scratch(vk_ctx *ctx, CellScratch &sc, uint64_t n_cells) {
 
 // The seed of the skip maps under the runtime transfer function, read back from the cells (cell_occ_kernel), replacing the seed and the
 // census counter (ctx->counters[7]) pack_cells_kernel left.  prefix == nullptr: the built-in threshold.
+// mip (VK_PROJ_MAX): the predicate of the maximum projection over the table's window (mip_cell_empty; its alphas, and with them prefix, are
+// not read), n == 0: over the implicit grey ramp's, two entries on [0, 1].
 static int launch_cell_occ(vk_ctx *ctx, int kind, const void *cells, uint8_t *occ, uint64_t n_cells, uint32_t blocks, const uint32_t *prefix,
-                           uint32_t n, float lo, float hi) {
+                           uint32_t n, float lo, float hi, bool mip) {
     float k1 = 0.0f, k2 = 0.0f;
-    if (prefix) tf_constants(n, lo, hi, kind != VOL_PF16, k1, k2);
+    if (mip && n == 0) { n = 2; lo = 0.0f; hi = 1.0f; }
+    if (mip) prefix = nullptr;
+    if (prefix || mip) tf_constants(n, lo, hi, kind != VOL_PF16, k1, k2);
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters + 7, 0, sizeof(unsigned long long), ctx->stream));
     if (kind == VOL_PF16)
-        hipLaunchKernelGGL(cell_occ_kernel<VOL_PF16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, n_cells, prefix, (int)n, k1, k2, ctx->counters + 7);
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_PF16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, n_cells, prefix, (int)n, k1, k2, mip ? 1 : 0, ctx->counters + 7);
     else if (kind == VOL_P16)
-        hipLaunchKernelGGL(cell_occ_kernel<VOL_P16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, n_cells, prefix, (int)n, k1, k2, ctx->counters + 7);
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_P16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, n_cells, prefix, (int)n, k1, k2, mip ? 1 : 0, ctx->counters + 7);
     else
-        hipLaunchKernelGGL(cell_occ_kernel<VOL_P8>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, n_cells, prefix, (int)n, k1, k2, ctx->counters + 7);
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_P8>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, n_cells, prefix, (int)n, k1, k2, mip ? 1 : 0, ctx->counters + 7);
     return VK_OK;  // (launch errors: read_census)
 }
 
@@ -164,8 +168,9 @@ static int build_skip_maps(vk_ctx *ctx, CellScratch &sc, uint32_t nbx, uint32_t 
 }
 
 // The current packed volume's seed, census and maps under the table (d_prefix: its prefix counts on the device; nullptr: the built-in
-// transfer), swapped in only when all of it has been built.  The caller has drained the frame slots.  Other layouts have no maps.
-int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float lo, float hi) {
+// transfer) and the projection, swapped in only when all of it has been built.  The caller has drained the frame slots.  Other layouts
+// have no maps.
+int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float lo, float hi, int projection) {
     const int kind = ctx->vol_kind;
     if (ctx->format < 0 || (kind != VOL_P8 && kind != VOL_P16 && kind != VOL_PF16)) return VK_OK;
     const uint64_t n_cells = (uint64_t)ctx->nbx * ctx->nby * ctx->nbz * kBrickCells;
@@ -173,7 +178,7 @@ int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float l
     CellScratch sc;
     int rc = alloc_scratch(ctx, sc, n_cells);
     if (rc) return rc;
-    if ((rc = launch_cell_occ(ctx, kind, ctx->vol, sc.occ, n_cells, (uint32_t)((n_cells + 255) / 256), d_prefix, n, lo, hi))) return rc;
+    if ((rc = launch_cell_occ(ctx, kind, ctx->vol, sc.occ, n_cells, (uint32_t)((n_cells + 255) / 256), d_prefix, n, lo, hi, projection == VK_PROJ_MAX))) return rc;
     double ef = 0.0;
     if ((rc = read_census(ctx, n_cells, &ef))) return rc;
     uint8_t *dist = nullptr;
@@ -379,8 +384,10 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
         hipLaunchKernelGGL(pack_cells_kernel<VOL_P16>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
     else
         hipLaunchKernelGGL(pack_cells_kernel<VOL_P8>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
-    // under a runtime transfer function the seed and the census follow its table (vk_set_transfer_function)
-    if (ctx->d_tf && (rc = launch_cell_occ(ctx, kind, nb.vol, sc.occ, n_cells, pack_blocks, reinterpret_cast<const uint32_t *>(ctx->d_tf + 4 * ctx->tf_n), ctx->tf_n, ctx->tf_lo, ctx->tf_hi)))
+    // under a runtime transfer function the seed and the census follow its table (vk_set_transfer_function), under the maximum projection its predicate (vk_set_projection)
+    if ((ctx->d_tf || ctx->proj == VK_PROJ_MAX) &&
+        (rc = launch_cell_occ(ctx, kind, nb.vol, sc.occ, n_cells, pack_blocks, ctx->d_tf ? reinterpret_cast<const uint32_t *>(ctx->d_tf + 4 * ctx->tf_n) : nullptr,
+                              ctx->d_tf ? ctx->tf_n : 0u, ctx->tf_lo, ctx->tf_hi, ctx->proj == VK_PROJ_MAX)))
         return rc;
     if ((rc = read_census(ctx, n_cells, &nb.empty_fraction))) return rc;
     uint64_t dist_bytes = 0;
@@ -524,7 +531,7 @@ int vk_set_transfer_function(vk_ctx *ctx, const float *rgba, uint32_t n, float l
     if (rc) return rc;
     if (!rgba) {
         if (!ctx->d_tf) return VK_OK;
-        if ((rc = rebuild_skip_maps(ctx, nullptr, 0, 0.0f, 1.0f))) return rc;
+        if ((rc = rebuild_skip_maps(ctx, nullptr, 0, 0.0f, 1.0f, ctx->proj))) return rc;
         (void)hipFree(ctx->d_tf);
         ctx->d_tf = nullptr;
         ctx->tf_n = 0;
@@ -540,10 +547,33 @@ int vk_set_transfer_function(vk_ctx *ctx, const float *rgba, uint32_t n, float l
     HIP_TRY(ctx, hipMalloc((void **)&d, blob.size()));
     hipError_t e = hipMemcpy(d, blob.data(), blob.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d); return fail(ctx, VK_ERR_HIP, std::string("vk_set_transfer_function: upload: ") + hipGetErrorString(e)); }
-    if ((rc = rebuild_skip_maps(ctx, reinterpret_cast<const uint32_t *>(d + 4 * n), n, lo, hi))) { (void)hipFree(d); return rc; }
+    if ((rc = rebuild_skip_maps(ctx, reinterpret_cast<const uint32_t *>(d + 4 * n), n, lo, hi, ctx->proj))) { (void)hipFree(d); return rc; }
     (void)hipFree(ctx->d_tf);
     ctx->d_tf = d;
     ctx->tf_n = n; ctx->tf_lo = lo; ctx->tf_hi = hi;
+    return VK_OK;
+}
+
+int vk_set_projection(vk_ctx *ctx, int projection) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (projection != VK_PROJ_COMPOSITE && projection != VK_PROJ_MAX) return fail(ctx, VK_ERR_INVALID, "vk_set_projection: unknown projection");
+    if (ctx->fif_open) return fail(ctx, VK_ERR_INVALID, "vk_set_projection: a frame is being recorded (call it outside vk_frame_begin / vk_frame_end)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // every frame recorded so far renders under the projection it was recorded under, with that projection's maps: drain them first
+    int rc = frames_drain(ctx);
+    if (rc) return rc;
+    if (projection == ctx->proj) return VK_OK;
+    // the maps of the (projection, table) pair now in force, whichever setter came first
+    if ((rc = rebuild_skip_maps(ctx, ctx->d_tf ? reinterpret_cast<const uint32_t *>(ctx->d_tf + 4 * ctx->tf_n) : nullptr, ctx->d_tf ? ctx->tf_n : 0u,
+                                ctx->d_tf ? ctx->tf_lo : 0.0f, ctx->d_tf ? ctx->tf_hi : 1.0f, projection)))
+        return rc;
+    ctx->proj = projection;
+    return VK_OK;
+}
+
+int vk_get_projection(vk_ctx *ctx, int *projection) {
+    if (!ctx || !projection) return VK_ERR_INVALID;
+    *projection = ctx->proj;
     return VK_OK;
 }
 

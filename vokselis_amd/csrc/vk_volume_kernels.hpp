@@ -137,10 +137,11 @@ __global__ __launch_bounds__(256) void pack_cells_kernel(const void *__restrict_
 // The skip-map seed and census of a packed volume read back from its cells (the dense source is gone by then): each cell's 8 taps
 // (P8: u8 taps; P16: (tap, delta) pairs, tap + delta exact; PF16: f16 taps), tested by the runtime transfer function's emptiness
 // predicate (vk_tf.hpp; prefix: the table's prefix counts of non-zero alphas), or with prefix == nullptr by the built-in threshold
-// of pack_cells_kernel -- whose occ and census it then reproduces byte for byte.
+// of pack_cells_kernel -- whose occ and census it then reproduces byte for byte.  mip != 0 (vk_set_projection(VK_PROJ_MAX)): the predicate
+// of the maximum projection over the window behind k1, k2 and its n entries (vk_tf.hpp: mip_cell_empty).
 template <int VOL>
 __global__ __launch_bounds__(256) void cell_occ_kernel(const void *__restrict__ cells, uint8_t *__restrict__ occ, uint64_t n_cells,
-                                                       const uint32_t *__restrict__ prefix, int n, float k1, float k2,
+                                                       const uint32_t *__restrict__ prefix, int n, float k1, float k2, int mip,
                                                        unsigned long long *__restrict__ n_empty) {
     const uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= n_cells) return;  // (n_cells is a multiple of 64: whole waves)
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(256) void cell_occ_kernel(const void *__restrict__ 
             else { t[2 * k] = (float)c.h[2 * k]; t[2 * k + 1] = (float)c.h[2 * k + 1]; }
         }
     }
-    const bool nonempty = prefix ? !tf_cell_empty(t, prefix, n, k1, k2) : !builtin_cell_empty(t, VOL == VOL_PF16);  // (pack_cells_kernel's predicate)
+    const bool nonempty = mip ? !mip_cell_empty(t, k1, k2, (float)(n - 1)) : prefix ? !tf_cell_empty(t, prefix, n, k1, k2) : !builtin_cell_empty(t, VOL == VOL_PF16);  // (pack_cells_kernel's predicate)
     occ[id] = nonempty ? 0 : 255;
     const unsigned long long m = __ballot(!nonempty);
     if ((threadIdx.x & 63u) == 0 && m) atomicAdd(n_empty, (unsigned long long)__popcll(m));

@@ -10,6 +10,8 @@
 //                                                            RGBA rows, 2..256 of them, over the sample values [LO, HI] (default 0 1)
 //          [--light X Y Z | --headlight] [--light-params KA KD KS N]   gradient lighting of the table (vk_set_lighting; needs --tf): a light
 //                                                            towards (X, Y, Z) or at the eye; ambient, diffuse, specular, shininess (default 0.3 0.7 0.2 32)
+//          [--mip]                                            maximum-intensity projection (vk_set_projection(VK_PROJ_MAX)) over the table's window,
+//                                                            without --tf a grey ramp over [0, 1]
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -26,6 +28,7 @@ static bool g_orbit = false;
 static std::vector<float> g_tf;  // --tf: n x 4 floats (empty: the built-in transfer)
 static float g_tf_lo = 0.0f, g_tf_hi = 1.0f;
 static bool g_lit = false;  // --light / --headlight: gradient lighting (the library checks the parameters)
+static bool g_mip = false;  // --mip: maximum-intensity projection
 static vk_lighting g_light = {{0.0f, 0.0f, 0.0f}, 0, 0.3f, 0.7f, 0.2f, 32.0f};
 
 // --tf PATH: the whole file as little-endian f32 RGBA rows (the library checks n, finiteness and alpha)
@@ -48,6 +51,7 @@ struct Bonsai : Demo {
         auto self = std::make_unique<Bonsai>();
         if (!g_tf.empty()) ctx.set_transfer_function(g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi);
         if (g_lit) ctx.set_lighting(&g_light);
+        if (g_mip) ctx.set_projection(VK_PROJ_MAX);
         if (!g_raw.empty()) self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::from_raw(ctx, g_raw));
         else self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, 256, 256, 256));
         self->pipeline = RaycastPipeline{VK_MODE_NAIVE_TRILINEAR, g_dt, 0};
@@ -79,6 +83,7 @@ static int run_group(int n_gpus, uint32_t frames, uint32_t batch, uint32_t w, ui
             check(c, vk_backbuffer_resize(c, w, h, VK_OUT_RGBA16F));
             if (!g_tf.empty()) check(c, vk_set_transfer_function(c, g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi));
             if (g_lit) check(c, vk_set_lighting(c, &g_light));
+            if (g_mip) check(c, vk_set_projection(c, VK_PROJ_MAX));
             if (!raw.empty()) check(c, vk_volume_upload(c, raw.data(), nullptr, 256, 256, 256, VK_FMT_R8_UNORM, VK_LAYOUT_AUTO));
             else check(c, vk_volume_generate(c, VK_GEN_BONSAI_STANDIN, 256, 256, 256, VK_FMT_R8_UNORM, 0x5EED0001u, 0, 1, VK_LAYOUT_AUTO));
         }
@@ -157,6 +162,7 @@ int main(int argc, char **argv) {
             try { g_tf = read_tf(next()); } catch (const std::exception &e) { std::fprintf(stderr, "bonsai: %s\n", e.what()); return 1; }
         }
         else if (a == "--tf-domain") { g_tf_lo = (float)std::atof(next()); g_tf_hi = (float)std::atof(next()); }
+        else if (a == "--mip") g_mip = true;
         else if (a == "--light") { g_lit = true; g_light.headlight = 0; for (int k = 0; k < 3; k++) g_light.dir[k] = (float)std::atof(next()); }
         else if (a == "--headlight") { g_lit = true; g_light.headlight = 1; }
         else if (a == "--light-params") {

@@ -236,6 +236,9 @@ class Context {
     void set_transfer_function(const float *rgba, uint32_t n, float lo = 0.0f, float hi = 1.0f) {
         check(ctx_, vk_set_transfer_function(ctx_, rgba, n, lo, hi));
     }
+    // Projection of NAIVE_TRILINEAR (vk_set_projection): VK_PROJ_MAX, a maximum-intensity projection over the table's window, or VK_PROJ_COMPOSITE.
+    void set_projection(int projection) { check(ctx_, vk_set_projection(ctx_, projection)); }
+    int projection() const { int p = VK_PROJ_COMPOSITE; check(ctx_, vk_get_projection(ctx_, &p)); return p; }
     // Gradient lighting of the table march (vk_set_lighting); nullptr turns it off.
     void set_lighting(const vk_lighting *light) { check(ctx_, vk_set_lighting(ctx_, light)); }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
