@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from gpu_helpers import V, _DevicePtr, _synced  # noqa: F401  (V: fixture)
+from tf_helpers import zero_band_table
 
 pytestmark = pytest.mark.gpu
 
@@ -212,6 +213,43 @@ def test_wave_trace_stamps_every_marched_block(V):
         # the wave-level trips of a block are at least its longest ray's iterations
         assert int(trips.sum()) >= int(steps.reshape(H // 8, 8, W // 8, 8).max(axis=(1, 3)).sum())
         assert lib.vk_debug_wave_trace(ctx.handle, 0, out, 10 ** 9) != 0  # more blocks than were traced
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("family", ["builtin", "table", "lit", "mip"])
+def test_wave_trace_and_counters_in_every_cell_kernel_family(V, family):
+    """The stamps, the wave-level counters and the step counters leave every family of cell kernels the same way: the built-in march,
+    the table march, the lit table march and the maximum projection, probing adaptively and without skipping."""
+    lib, W, H = V.native.lib(), 128, 128
+    ctx = V.Context(W, H, backbuffer=(W, H), out_format=V.OUT_RGBA32F)
+    try:
+        if family != "builtin":
+            ctx.set_transfer_function(zero_band_table())
+        if family == "lit":
+            ctx.set_lighting(direction="headlight")
+        if family == "mip":
+            ctx.set_projection("max")
+        V.VolumeTexture(ctx, _fog(48), layout=V.LAYOUT_PACKED)
+        ctx.set_camera_blob(_camera(V, W, H))
+        n_blocks = (W // 8) * (H // 8)
+        out = (C.c_uint64 * (4 * n_blocks))()
+        for flags in (V.RENDER_COUNT | V.RENDER_FORCE_SKIP, V.RENDER_COUNT | V.RENDER_NO_SKIP):
+            V.native.check(ctx.handle, lib.vk_debug_wave_trace(ctx.handle, 1, None, 0))
+            ctx.reset_step_counts()
+            V.RaycastPipeline(dt_scale=0.5, flags=flags).record(ctx)
+            steps = ctx.read_steps()
+            V.native.check(ctx.handle, lib.vk_debug_wave_trace(ctx.handle, 0, out, n_blocks))
+            rec = np.frombuffer(out, np.uint64).reshape(n_blocks, 4)
+            stamped = rec[:, 0] != np.uint64(0xFFFFFFFFFFFFFFFF)
+            marched = int((steps.reshape(H // 8, 8, W // 8, 8).sum(axis=(1, 3)) > 0).sum())
+            assert 0 < marched <= int(stamped.sum()) <= n_blocks  # every block whose rays marched is stamped
+            r = rec[stamped]
+            assert (r[:, 0] <= r[:, 1]).all()  # start <= end
+            assert ((r[:, 2] >> np.uint64(32)) < 8).all()  # XCC_ID: 8 XCDs
+            trips = r[:, 3] & np.uint64((1 << 20) - 1)
+            assert int((trips > 0).sum()) == marched  # wave-level march-loop trips: exactly the blocks with a ray that iterated
+            assert ctx.step_counts()[0] == int(steps.sum(dtype=np.uint64))
     finally:
         ctx.close()
 

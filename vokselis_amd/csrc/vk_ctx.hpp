@@ -9,7 +9,7 @@
 //   vk_launch_cells.hip    instantiates the cell-layout march kernels      (vk_march.hpp)
 //   vk_launch_tf.hip       instantiates the cell march under a transfer table (vk_march.hpp)
 //   vk_launch_lit.hip      instantiates the table march with gradient lighting (vk_march.hpp, vk_light.hpp)
-//   vk_launch_mip.hip      the cell march under the maximum-intensity projection (its own loops and kernel)
+//   vk_launch_mip.hip      instantiates the cell march under the maximum-intensity projection (vk_march.hpp, vk_march_mip.hpp)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)

@@ -1,0 +1,60 @@
+// vk_launch.hpp -- host side of the vk_launch_*.hip files (included by them only): the runtime choices that select a kernel instantiation,
+// each written once.  A helper turns its runtime values into compile-time tags and hands them to a generic lambda that names the kernel:
+//     with_out_count(ctx, count, [&](auto OUT, auto COUNT) { hipLaunchKernelGGL((kernel<..., OUT(), COUNT()>), ...); });
+// A helper calls its lambda with exactly the combinations the ladder it replaces spelled out: the set of instantiated kernels is the same.
+#pragma once
+
+#include "vk_ctx.hpp"
+
+#include <type_traits>
+
+namespace vk {
+
+template <int I>
+using int_tag = std::integral_constant<int, I>;
+template <bool B>
+using bool_tag = std::integral_constant<bool, B>;
+
+// f(OUT): the context's output format
+template <class F>
+void with_out(const vk_ctx *ctx, F &&f) {
+    if (ctx->out_format == VK_OUT_RGBA16F) f(int_tag<OUT_RGBA16F>()); else f(int_tag<OUT_RGBA32F>());
+}
+
+// f(OUT, COUNT)
+template <class F>
+void with_out_count(const vk_ctx *ctx, bool count, F &&f) {
+    with_out(ctx, [&](auto OUT) { if (count) f(OUT, bool_tag<true>()); else f(OUT, bool_tag<false>()); });
+}
+
+// f(SKIP, SAFE)
+template <class F>
+void with_skip_safe(bool skip, bool safe, F &&f) {
+    if (skip) { if (safe) f(bool_tag<true>(), bool_tag<true>()); else f(bool_tag<true>(), bool_tag<false>()); }
+    else { if (safe) f(bool_tag<false>(), bool_tag<true>()); else f(bool_tag<false>(), bool_tag<false>()); }
+}
+
+// f(VOL, SKIP, SAFE) over the layouts that have table kernels (dispatch_march has refused the others): the cell layouts in all four
+// variants, the LINEAR layouts without a skip map and with clamped indices only.
+template <class F>
+void with_table_layout(const vk_ctx *ctx, bool skip, bool safe, F &&f) {
+    auto cells = [&](auto VOL) { with_skip_safe(skip, safe, [&](auto SKIP, auto SAFE) { f(VOL, SKIP, SAFE); }); };
+    switch (ctx->vol_kind) {
+        case VOL_P8: cells(int_tag<VOL_P8>()); break;
+        case VOL_P16: cells(int_tag<VOL_P16>()); break;
+        case VOL_PF16: cells(int_tag<VOL_PF16>()); break;
+        case VOL_LINEAR_F16: f(int_tag<VOL_LINEAR_F16>(), bool_tag<false>(), bool_tag<true>()); break;
+        default: f(int_tag<VOL_LINEAR_U8>(), bool_tag<false>(), bool_tag<true>()); break;
+    }
+}
+
+// Dynamic LDS of a cell kernel (vk_march_kernel_body.hpp) -- the fast path of the cell layouts keeps its per-axis index tables there
+// (vk_march.hpp: load_cell_luts) -- and, for the variants without skipping, V.lut moved on to the byte-offset copy of the tables.
+template <int VOL, bool SKIP, bool SAFE>
+uint32_t cell_kernel_lds(const vk_ctx *ctx, VolumeDesc &V) {
+    if (!SKIP && V.lut) V.lut += cell_lut_entries(V.nx, V.ny, V.nz);
+    constexpr bool lut = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16) && !SAFE;
+    return (lut ? cell_lut_bytes(V.nx, V.ny, V.nz) : 0u) + ctx->naive_lds_pad;  // (pad: occupancy experiments, vk_debug_set_param)
+}
+
+}  // namespace vk

@@ -1,24 +1,15 @@
 // vk_launch_cells.hip -- instantiates raymarch_naive_kernel (vk_march.hpp) for every cell / comparison layout.
-#include "vk_ctx.hpp"
+#include "vk_launch.hpp"
 #include "vk_march.hpp"
 
 using namespace vk;
 
 template <int VOL, bool SKIP, bool SAFE, int WALK = WALK_LOOP, bool AHEAD = false>
-static void launch_naive(vk_ctx *ctx, const LaunchDesc &L, const VolumeDesc &V_in, uint32_t grid, bool count) {
-    const bool f16 = ctx->out_format == VK_OUT_RGBA16F;
-    VolumeDesc V = V_in;
-    if (!SKIP && V.lut) V.lut += cell_lut_entries(V.nx, V.ny, V.nz);  // byte-offset copy of the tables
-    // the fast path of the cell layouts keeps its per-axis index tables in LDS (vk_march.hpp: load_cell_luts)
-    constexpr bool lut = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16) && !SAFE;
-    const uint32_t lds = (lut ? cell_lut_bytes(V.nx, V.ny, V.nz) : 0u) + ctx->naive_lds_pad;  // (pad: occupancy experiments, vk_debug_set_param)
-    if (f16) {
-        if (count) hipLaunchKernelGGL((raymarch_naive_kernel<VOL, SKIP, SAFE, WALK, AHEAD, OUT_RGBA16F, true>), dim3(grid), dim3(64), lds, ctx->stream, L, V);
-        else hipLaunchKernelGGL((raymarch_naive_kernel<VOL, SKIP, SAFE, WALK, AHEAD, OUT_RGBA16F, false>), dim3(grid), dim3(64), lds, ctx->stream, L, V);
-    } else {
-        if (count) hipLaunchKernelGGL((raymarch_naive_kernel<VOL, SKIP, SAFE, WALK, AHEAD, OUT_RGBA32F, true>), dim3(grid), dim3(64), lds, ctx->stream, L, V);
-        else hipLaunchKernelGGL((raymarch_naive_kernel<VOL, SKIP, SAFE, WALK, AHEAD, OUT_RGBA32F, false>), dim3(grid), dim3(64), lds, ctx->stream, L, V);
-    }
+static void launch_naive(vk_ctx *ctx, const LaunchDesc &L, VolumeDesc V, uint32_t grid, bool count) {
+    const uint32_t lds = cell_kernel_lds<VOL, SKIP, SAFE>(ctx, V);
+    with_out_count(ctx, count, [&](auto OUT, auto COUNT) {
+        hipLaunchKernelGGL((raymarch_naive_kernel<VOL, SKIP, SAFE, WALK, AHEAD, OUT(), COUNT()>), dim3(grid), dim3(64), lds, ctx->stream, L, V);
+    });
 }
 
 template <int VOL>

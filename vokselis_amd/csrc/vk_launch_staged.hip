@@ -1,5 +1,5 @@
 // vk_launch_staged.hip -- instantiates the LDS-staged march (vk_staged.hpp) and picks its LDS budget from the view.
-#include "vk_ctx.hpp"
+#include "vk_launch.hpp"
 #include "vk_staged.hpp"
 
 #include <algorithm>
@@ -65,7 +65,6 @@ static void launch_staged_t(vk_ctx *ctx, const LaunchDesc &L, const VolumeDesc &
     D.row_pad = ctx->stage_row_pad == 1u ? 1u : 0u;
     // u8 (at the issue-slot limit): every 4th round -- C5 10.40 -> 10.12 ms, other views +-1 %; f16 (waiting on fills, not on slots): every round
     D.grow_every = ctx->stage_grow_every ? ctx->stage_grow_every : (VOL == VOL_S8U8 ? 4u : 1u);
-    const bool f16 = ctx->out_format == VK_OUT_RGBA16F;
     // One window for the four waves of a 256-thread group (2 x 2 neighbouring 8x8 blocks) instead of one per wave: the rays of 16 x 16 pixels
     // sweep far less than four 8 x 8 boxes, so the slab is ~twice as thick and a ray meets half as many rounds -- against two barriers
     // per round.  Measured (docs/archive/tools/staged_group.py, staged_group_sweep.py; frames bitwise equal): it pays where the wave is starved of LDS --
@@ -85,22 +84,14 @@ static void launch_staged_t(vk_ctx *ctx, const LaunchDesc &L, const VolumeDesc &
         const uint32_t lds = std::min(D.cap_bytes * kGroupWaves, 65536u) & ~15u;  // four waves' LDS, less the exchange block
         D.cap_bytes = lds - kGroupExchBytes;
         const uint32_t groups = (grid + kGroupWaves - 1u) / kGroupWaves;
-        if (f16) {
-            if (count) hipLaunchKernelGGL((raymarch_staged_group_kernel<VOL, OUT_RGBA16F, true>), dim3(groups), dim3(256), lds, ctx->stream, L, V, D);
-            else hipLaunchKernelGGL((raymarch_staged_group_kernel<VOL, OUT_RGBA16F, false>), dim3(groups), dim3(256), lds, ctx->stream, L, V, D);
-        } else {
-            if (count) hipLaunchKernelGGL((raymarch_staged_group_kernel<VOL, OUT_RGBA32F, true>), dim3(groups), dim3(256), lds, ctx->stream, L, V, D);
-            else hipLaunchKernelGGL((raymarch_staged_group_kernel<VOL, OUT_RGBA32F, false>), dim3(groups), dim3(256), lds, ctx->stream, L, V, D);
-        }
+        with_out_count(ctx, count, [&](auto OUT, auto COUNT) {
+            hipLaunchKernelGGL((raymarch_staged_group_kernel<VOL, OUT(), COUNT()>), dim3(groups), dim3(256), lds, ctx->stream, L, V, D);
+        });
         return;
     }
-    if (f16) {
-        if (count) hipLaunchKernelGGL((raymarch_staged_kernel<VOL, OUT_RGBA16F, true>), dim3(grid), dim3(64), D.cap_bytes, ctx->stream, L, V, D);
-        else hipLaunchKernelGGL((raymarch_staged_kernel<VOL, OUT_RGBA16F, false>), dim3(grid), dim3(64), D.cap_bytes, ctx->stream, L, V, D);
-    } else {
-        if (count) hipLaunchKernelGGL((raymarch_staged_kernel<VOL, OUT_RGBA32F, true>), dim3(grid), dim3(64), D.cap_bytes, ctx->stream, L, V, D);
-        else hipLaunchKernelGGL((raymarch_staged_kernel<VOL, OUT_RGBA32F, false>), dim3(grid), dim3(64), D.cap_bytes, ctx->stream, L, V, D);
-    }
+    with_out_count(ctx, count, [&](auto OUT, auto COUNT) {
+        hipLaunchKernelGGL((raymarch_staged_kernel<VOL, OUT(), COUNT()>), dim3(grid), dim3(64), D.cap_bytes, ctx->stream, L, V, D);
+    });
 }
 
 void launch_staged(vk_ctx *ctx, const LaunchDesc &L, const VolumeDesc &V, uint32_t grid, bool count, const float *cam) {

@@ -700,10 +700,16 @@ __device__ __forceinline__ void clear_inactive_strip(const LaunchDesc &L, uint32
     }
 }
 
+}  // namespace vk
+
+#include "vk_march_mip.hpp"  // march_mip, march_mip_stream: the loops of the maximum projection, which the kernel body calls under MIP
+
+namespace vk {
+
 // AHEAD: the probe-ahead trip (march<..., AHEAD>), an instantiation of its own -- it needs six more registers, and the launches that fill the machine keep the leaner kernel
 template <int VOL, bool SKIP, bool SAFE, int WALK, bool AHEAD, int OUT, bool COUNT>
 __global__ __launch_bounds__(64) void raymarch_naive_kernel(const LaunchDesc L, const VolumeDesc V) {
-    constexpr bool TF = false, LIT = false;  // (the table kernels: vk_launch_tf.hip; lit: vk_launch_lit.hip)
+    constexpr bool TF = false, LIT = false, MIP = false;  // (the table kernels: vk_launch_tf.hip; lit: vk_launch_lit.hip; the maximum projection: vk_launch_mip.hip)
     const TfDesc *tfd = nullptr;
     const LightDesc *ldp = nullptr;
 #include "vk_march_kernel_body.hpp"

@@ -1,12 +1,20 @@
 // vk_march_kernel_body.hpp -- the body of the cell-march kernels, included inside them (no include guard): raymarch_naive_kernel
-// (vk_march.hpp), raymarch_tf_kernel (vk_launch_tf.hip) and raymarch_lit_kernel (vk_launch_lit.hip).  The including kernel defines the
-// template parameters VOL, SKIP, SAFE, WALK, AHEAD, OUT, COUNT, the constants TF (a runtime transfer function: vk_set_transfer_function)
-// and LIT (gradient lighting: vk_set_lighting), `tfd`, its table (nullptr without one), and `ldp`, its lighting (nullptr without), and
-// takes its arguments L (LaunchDesc) and V (VolumeDesc) by value.  (Shared textually rather than as an inlined function: that
-// moved the register allocation of the existing kernels.)
+// (vk_march.hpp), raymarch_tf_kernel (vk_launch_tf.hip), raymarch_lit_kernel (vk_launch_lit.hip) and raymarch_mip_kernel
+// (vk_launch_mip.hip).  The including kernel defines the template parameters VOL, SKIP, SAFE, WALK, AHEAD, OUT, COUNT, the constants TF
+// (a runtime transfer function: vk_set_transfer_function), LIT (gradient lighting: vk_set_lighting) and MIP (the maximum-intensity
+// projection: vk_set_projection), `tfd`, its table (nullptr without one; under MIP the window, whose rgba is nullptr for the grey ramp),
+// and `ldp`, its lighting (nullptr without), and takes its arguments L (LaunchDesc) and V (VolumeDesc) by value.  (Shared textually
+// rather than as an inlined function: that moved the register allocation of the existing kernels.)
+// Shared by all four families: the block and pixel mapping, the cull, the index tables in LDS, the ray set-up, the wave priority, the
+// adaptive-probing policy, the step image, the counters and the trace.  A family's own: its loops -- march / march_stream (vk_march.hpp), or under MIP
+// march_mip / march_mip_stream (vk_march_mip.hpp), which take the window's k1, k2 and umax from *tfd and carry the running maximum U in
+// RayState::A; selected at each call site, since a forwarding wrapper moved registers in the COUNT kernels -- and what the epilogue
+// makes of the ray's sums.
     static_assert(VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16 || (!SKIP && SAFE), "linear / bricked layouts: no skip map, clamped indices");
     static_assert(SKIP || WALK == WALK_LOOP, "the closed-form walks are variants of the skip kernels");
     static_assert(!AHEAD || (SKIP && !SAFE), "probe ahead: the skip kernels' fast path");
+    static_assert(!MIP || (!TF && !LIT && WALK == WALK_LOOP && !AHEAD), "the maximum projection: loops of its own, walking with the loop; the table is looked up in the epilogue");
+    static_assert(!MIP || (VOL != VOL_B9U8 && VOL != VOL_B9F16 && VOL != VOL_Q8 && VOL != VOL_QF16), "the maximum projection: LINEAR and cell layouts");
     if (blockIdx.x >= L.grid_march) { clear_inactive_strip<OUT>(L, blockIdx.x - L.grid_march, threadIdx.x); return; }  // wave-uniform
     const uint32_t lb = logical_block(blockIdx.x);
     if (lb >= L.n_blocks) return;  // wave-uniform
@@ -50,7 +58,7 @@
     intersect_box(eye, dir, 0.0f, 1.0f, t0, t1);
     Census cs;
     const bool trip_log = COUNT && L.trace && (L.flags & LF_TRIP_LOG);
-    if (trip_log) {
+    if (trip_log) {  // (the loops of the maximum projection keep no log: such a launch writes neither a log nor stamps)
         cs.log_cap = L.trip_log_cap;
         cs.log = reinterpret_cast<uint32_t *>(L.trace) + (size_t)lb * cs.log_cap;
     }
@@ -69,13 +77,16 @@
         RayState r;
         r.left = min(count_trips(t0, t1, dt), 0x7fffffffu);  // :101
         r.px = px; r.py = py; r.pz = pz; r.sx = sx; r.sy = sy; r.sz = sz;
-        r.A = 0.0f; r.Gr = 0.0f; r.Gg = 0.0f; r.Gb = 0.0f;  // colour sums: G = sum w*cos(phase); C = A/2 + G/2 (sum w == A)
+        r.A = 0.0f; r.Gr = 0.0f; r.Gg = 0.0f; r.Gb = 0.0f;  // colour sums: G = sum w*cos(phase); C = A/2 + G/2 (sum w == A); MIP: A is U, the running maximum
         r.out = (uint32_t)pm.out_index;
         LitRay lr;  // LIT: the ray's light and half vectors (vk_light.hpp; left unset in the other kernels, which never read it)
         if constexpr (LIT) lr = lit_ray(*ldp, dir);
         // (not in the skip kernels: a ray's nominal length says little about its work there -- C2 at 64 orbit frames per launch 0.06509 -> 0.06467 ms without)
         if (!SKIP && (L.flags & LF_WAVE_PRIORITY)) set_wave_priority(true, r.left, fmaxf(fnx, fmaxf(fny, fnz)) / L.dt_scale);
-        if constexpr (USE_LUT && !SKIP) march_stream<VOL, COUNT, false, TF, LIT>(V, r, cs, cell_lut, 0xffffffffu, tfd, ldp, &lr);
+        if constexpr (USE_LUT && !SKIP) {
+            if constexpr (MIP) march_mip_stream<VOL, COUNT, false>(V, r, cs, cell_lut, 0xffffffffu, tfd->k1, tfd->k2, tfd->umax);
+            else march_stream<VOL, COUNT, false, TF, LIT>(V, r, cs, cell_lut, 0xffffffffu, tfd, ldp, &lr);
+        }
         else if constexpr (SKIP) {
             if (L.flags & LF_ADAPTIVE_PROBING) {
                 // Adaptive probing (wave-uniform policy, any policy is exact: a sampled empty cell adds +0).  Probe for a
@@ -87,24 +98,44 @@
                 uint32_t stretch = stretch0;
                 for (;;) {
                     cs.skips = 0;
-                    bool alive = march<VOL, true, SAFE, COUNT, true, WALK, false, TF, LIT>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd, ldp, &lr);
+                    bool alive;
+                    if constexpr (MIP) alive = march_mip<VOL, true, SAFE, COUNT, true>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd->k1, tfd->k2, tfd->umax);
+                    else alive = march<VOL, true, SAFE, COUNT, true, WALK, false, TF, LIT>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd, ldp, &lr);
                     const unsigned long long live = __ballot(alive);
                     if (live == 0ull) break;
                     if (__popcll(__ballot(alive && cs.skips != 0u)) * 8 >= __popcll(live)) { stretch = stretch0; continue; }
-                    if constexpr (USE_LUT) alive = march_stream<VOL, COUNT, true, TF, LIT>(V, r, cs, cell_lut, stretch, tfd, ldp, &lr);
+                    if constexpr (MIP && USE_LUT) alive = march_mip_stream<VOL, COUNT, true>(V, r, cs, cell_lut, stretch, tfd->k1, tfd->k2, tfd->umax);
+                    else if constexpr (MIP) alive = march_mip<VOL, false, SAFE, COUNT, true>(V, r, stretch, cs, nullptr, __builtin_inff(), __builtin_inff(), tfd->k1, tfd->k2, tfd->umax);
+                    else if constexpr (USE_LUT) alive = march_stream<VOL, COUNT, true, TF, LIT>(V, r, cs, cell_lut, stretch, tfd, ldp, &lr);
                     else alive = march<VOL, false, SAFE, COUNT, true, WALK_LOOP, false, TF, LIT>(V, r, stretch, cs, nullptr, __builtin_inff(), __builtin_inff(), tfd, ldp, &lr);
                     if (__ballot(alive) == 0ull) break;
                     stretch = min(stretch * 2u, 512u);
                 }
+            } else if constexpr (MIP) {
+                march_mip<VOL, true, SAFE, COUNT, false>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd->k1, tfd->k2, tfd->umax);
             } else {
                 march<VOL, SKIP, SAFE, COUNT, false, WALK, AHEAD, TF, LIT>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd, ldp, &lr);
             }
         }
         else if constexpr (VOL == VOL_B9U8 || VOL == VOL_B9F16) march_b9_stream<VOL, COUNT>(V, r, cs);
         else if constexpr (VOL == VOL_Q8 || VOL == VOL_QF16) march_quads_stream<VOL, COUNT>(V, r, cs);
+        else if constexpr (MIP) march_mip<VOL, false, SAFE, COUNT, false>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, __builtin_inff(), __builtin_inff(), tfd->k1, tfd->k2, tfd->umax);
         else march<VOL, SKIP, SAFE, COUNT, false, WALK_LOOP, false, TF, LIT>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, __builtin_inff(), __builtin_inff(), tfd, ldp, &lr);
         A = r.A; Gr = r.Gr; Gg = r.Gg; Gb = r.Gb;
-        if constexpr (TF) {  // the table's colour sums are the colour
+        if constexpr (MIP) {
+            // the table path's lookup at U, once per ray.  No table: the implicit two-entry grey ramp {(0,0,0), (1,1,1)}, whose lerp
+            // fma(U, 1 - 0, 0) is U itself, bit for bit (U is +0 or positive)
+            const float U = r.A;
+            float cr = U, cg = U, cb = U;
+            if (tfd->rgba) {
+                const int i = tf_index(U, tfd->imax);
+                const float f = U - (float)i;
+                const float4 *E = reinterpret_cast<const float4 *>(tfd->rgba);
+                const float4 e0 = E[i], e1 = E[i + 1];
+                cr = fmaf(f, e1.x - e0.x, e0.x); cg = fmaf(f, e1.y - e0.y, e0.y); cb = fmaf(f, e1.z - e0.z, e0.z);
+            }
+            Cr = linear_to_srgb(cr); Cg = linear_to_srgb(cg); Cb = linear_to_srgb(cb);
+        } else if constexpr (TF) {  // the table's colour sums are the colour
             Cr = linear_to_srgb(Gr); Cg = linear_to_srgb(Gg); Cb = linear_to_srgb(Gb);
         } else {
             Cr = linear_to_srgb(fmaf(0.5f, Gr, 0.5f * A));  // :121-123

@@ -83,28 +83,19 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
     if (mode == VK_MODE_NAIVE_TRILINEAR && ctx->lit && !tf && !mip)
         return fail(ctx, VK_ERR_UNSUPPORTED, "lighting: NAIVE_TRILINEAR renders with lighting need a transfer function (set a table with vk_set_transfer_function, or turn lighting off with vk_set_lighting(NULL))");
     TfDesc T{};
-    if (mip) {
+    if (mip || tf) {
         const int k = ctx->vol_kind;
         if (k != VOL_LINEAR_U8 && k != VOL_LINEAR_F16 && k != VOL_P8 && k != VOL_P16 && k != VOL_PF16)
-            return fail(ctx, VK_ERR_UNSUPPORTED, "projection: NAIVE_TRILINEAR renders under VK_PROJ_MAX need a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no maximum-projection kernels; vk_set_projection(VK_PROJ_COMPOSITE) resets)");
-        if (flags & VK_RENDER_FAST_WALK) return fail(ctx, VK_ERR_UNSUPPORTED, "projection: VK_RENDER_FAST_WALK has no maximum-projection kernels (VK_PROJ_MAX)");
-        // the window of the table in force; without one the implicit grey ramp, two entries over [0, 1] (T.rgba stays NULL)
+            return fail(ctx, VK_ERR_UNSUPPORTED, mip ? "projection: NAIVE_TRILINEAR renders under VK_PROJ_MAX need a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no maximum-projection kernels; vk_set_projection(VK_PROJ_COMPOSITE) resets)"
+                                                     : "transfer function: NAIVE_TRILINEAR renders with a table need a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no table kernels; vk_set_transfer_function(NULL) resets)");
+        if (flags & VK_RENDER_FAST_WALK)
+            return fail(ctx, VK_ERR_UNSUPPORTED, mip ? "projection: VK_RENDER_FAST_WALK has no maximum-projection kernels (VK_PROJ_MAX)" : "transfer function: VK_RENDER_FAST_WALK has no table kernels");
+        // the window of the table in force; under VK_PROJ_MAX without one the implicit grey ramp, two entries over [0, 1] (T.rgba stays NULL)
         const uint32_t n = tf ? ctx->tf_n : 2u;
         tf_constants(n, tf ? ctx->tf_lo : 0.0f, tf ? ctx->tf_hi : 1.0f, ctx->format == VK_FMT_R8_UNORM, T.k1, T.k2);
         T.rgba = tf ? ctx->d_tf : nullptr;
         T.umax = (float)(n - 1u);
         T.imax = (int32_t)n - 2;
-    } else if (tf) {
-        const int k = ctx->vol_kind;
-        if (k != VOL_LINEAR_U8 && k != VOL_LINEAR_F16 && k != VOL_P8 && k != VOL_P16 && k != VOL_PF16)
-            return fail(ctx, VK_ERR_UNSUPPORTED, "transfer function: NAIVE_TRILINEAR renders with a table need a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no table kernels; vk_set_transfer_function(NULL) resets)");
-        if (flags & VK_RENDER_FAST_WALK) return fail(ctx, VK_ERR_UNSUPPORTED, "transfer function: VK_RENDER_FAST_WALK has no table kernels");
-        float k1, k2;
-        tf_constants(ctx->tf_n, ctx->tf_lo, ctx->tf_hi, ctx->format == VK_FMT_R8_UNORM, k1, k2);
-        T.rgba = ctx->d_tf;
-        T.k1 = k1; T.k2 = k2;
-        T.umax = (float)(ctx->tf_n - 1u);
-        T.imax = (int32_t)ctx->tf_n - 2;
     }
     if (mode != VK_MODE_NAIVE_TRILINEAR) L.clear_max_inactive = 0;  // (their kernels have no clearing blocks: every tile is active)
     // whole-frame batches: the strips that clear the inactive tiles ride behind the march blocks (clear_inactive_strip)
