@@ -9,6 +9,11 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import zlib
+
+import variant
+
+variant.use_variant_from_env()  # tools/ab.py: VK_LIB
 import torch
 
 import vokselis_amd as V
@@ -46,7 +51,7 @@ cam = V.Camera(1.0, 0.5, 1.0, (0.5, 0.5, 0.5), W / H)
 orbit = [V.Camera(1.0, 0.5, 1.0 + 6.28318 * j / 1024, (0.5, 0.5, 0.5), W / H).get_proj_view_matrix() for j in range(B)]
 variants = [("unlit", None), ("headlight", dict(direction="headlight")), ("world", dict(direction=(0.4, -0.8, 0.45), ambient=0.1, diffuse=0.9, specular=0.6, shininess=64.0))]
 ctxs = {}
-out = {}
+out = {"lib": os.environ.get("VK_LIB", "product")}
 for name, light in variants:
     ctx = V.Context(W, H, cam, backbuffer=(W, H), out_format=V.OUT_RGBA16F)
     ctx.set_transfer_function(builtin_table())
@@ -56,6 +61,8 @@ for name, light in variants:
     ctx.update()
     ctx.reset_step_counts()
     V.RaycastPipeline(dt_scale=DT, flags=V.RENDER_COUNT).record(ctx)
+    out[name + "_crc"] = "%08x" % zlib.crc32(ctx.read_backbuffer().tobytes())  # the frame, for A/B runs: both sides must agree
+    out[name + "_steps_crc"] = "%08x" % zlib.crc32(ctx.read_steps().tobytes())
     out[name + "_s_ref"], out[name + "_s_sampled"] = (int(v) for v in ctx.step_counts())
     ctxs[name] = ctx
 assert len({out[n + "_s_sampled"] for n, _ in variants}) == 1, out  # lighting never changes the steps

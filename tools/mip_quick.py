@@ -14,6 +14,12 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import zlib
+
+import variant
+
+variant.use_variant_from_env()  # tools/ab.py: VK_LIB
 import numpy as np
 import torch
 
@@ -58,7 +64,7 @@ orbit = [V.Camera(1.0, 0.5, 1.0 + 6.28318 * j / 1024, (0.5, 0.5, 0.5), W / H).ge
 configs = [("composite", None, (0.0, 1.0), None), ("composite_table", builtin_table(), (0.0, 1.0), None),
            ("max_table", builtin_table(), (0.1, 1.0), "max"), ("max_grey", None, (0.0, 1.0), "max")]
 ctxs = {}
-out = {}
+out = {"lib": os.environ.get("VK_LIB", "product")}
 for name, table, window, proj in configs:
     ctx = V.Context(W, H, cam, backbuffer=(W, H), out_format=V.OUT_RGBA16F)
     if table is not None:
@@ -68,6 +74,8 @@ for name, table, window, proj in configs:
     ctx.update()
     ctx.reset_step_counts()
     V.RaycastPipeline(dt_scale=DT, flags=V.RENDER_COUNT).record(ctx)
+    out[name + "_crc"] = "%08x" % zlib.crc32(ctx.read_backbuffer().tobytes())  # the frame, for A/B runs: both sides must agree
+    out[name + "_steps_crc"] = "%08x" % zlib.crc32(ctx.read_steps().tobytes())
     s_ref, s_sampled = ctx.step_counts()
     out[name + "_empty_fraction"] = round(empty_fraction(ctx), 4)
     out[name + "_s_ref"], out[name + "_s_sampled"] = int(s_ref), int(s_sampled)

@@ -2,6 +2,9 @@
 
     python tools/variant.py NAME -DVK_EXP_SOMETHING=1 ...     ->  tools/_variants/NAME/libvokselis_hip.so
 
+    python tools/variant.py NAME --tree DIR [-D...]            ->  the same, from the sources of another checkout (a `git worktree` of
+                                                                   the parent, say), so that tools/ab.py times parent against new on one box
+
 and run any tool against it with VK_LIB=tools/_variants/NAME/libvokselis_hip.so (tools/ab.py does both sides in child processes).
 The product never reads VK_LIB: only tools that call use_variant_from_env() below do."""
 import os
@@ -13,12 +16,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def build_variant(name, defines):
+def build_variant(name, defines, tree=None):
     import __graft_entry__ as g
 
     out = os.path.join(ROOT, "tools", "_variants", name)
     os.makedirs(out, exist_ok=True)
     tus, _ = g.hip_sources()
+    if tree:  # the other checkout's translation units (its headers are found beside them); this tree's flags
+        csrc = os.path.join(os.path.abspath(tree), "vokselis_amd", "csrc")
+        tus = sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hip"))
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
     def one(tu):
@@ -47,4 +53,9 @@ def use_variant_from_env():
 
 
 if __name__ == "__main__":
-    print(build_variant(sys.argv[1], sys.argv[2:]))
+    args, tree = sys.argv[2:], None
+    if "--tree" in args:
+        i = args.index("--tree")
+        tree = args[i + 1]
+        del args[i:i + 2]
+    print(build_variant(sys.argv[1], args, tree))

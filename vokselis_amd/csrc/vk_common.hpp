@@ -369,17 +369,6 @@ __device__ __forceinline__ float transfer_alpha(float x) {
     return (s * s) * fmaf(-2.0f, s, 3.0f);
 }
 
-// raycast_naive.wgsl:70-81: 0.5 + 0.5*cos(6.28318*(c*a + d)).  v_cos_f32 takes its argument in
-// revolutions, so the phase is a single fma with constants pre-divided by 2*pi.
-__device__ __forceinline__ void vertigo(float a, float &r, float &g, float &b) {
-    constexpr double k = 6.28318 / 6.283185307179586476925;
-    constexpr float c0 = (float)(1.0 * k), c1 = (float)(1.7 * k), c2 = (float)(0.4 * k);
-    constexpr float d1 = (float)(0.15 * k), d2 = (float)(0.20 * k);
-    r = fmaf(0.5f, __builtin_amdgcn_cosf(a * c0), 0.5f);
-    g = fmaf(0.5f, __builtin_amdgcn_cosf(fmaf(a, c1, d1)), 0.5f);
-    b = fmaf(0.5f, __builtin_amdgcn_cosf(fmaf(a, c2, d2)), 0.5f);
-}
-
 __device__ __forceinline__ float h2f(uint32_t bits16) {
     union { uint16_t u; _Float16 h; } c;
     c.u = (uint16_t)bits16;

@@ -1,8 +1,13 @@
 // vk_march.hpp -- NAIVE_TRILINEAR (raycast_naive.wgsl:83-125) on the cell layouts (and the LINEAR / 9^3 / quad comparison layouts).
-// Included by vk_launch_cells.hip only (and, for RayState / Census / clear_inactive_strip, by vk_staged.hpp).
+// The loops march / march_stream / march_dense_stream, RayState, Census, and raymarch_naive_kernel around the shared kernel body
+// (vk_march_kernel_body.hpp).  Included by vk_launch_cells.hip for that kernel, by vk_launch_tf.hip and vk_launch_lit.hip, whose
+// kernels instantiate the same loops with TF / LIT, by vk_launch_mip.hip for the loops of vk_march_mip.hpp (included below), and by
+// vk_staged.hpp (vk_launch_staged.hip) for RayState, Census, clear_inactive_strip and the palette.  The statement groups the loops
+// share are vk_march_parts.hpp's.
 #pragma once
 
 #include "vk_common.hpp"
+#include "vk_march_parts.hpp"
 #include "vk_light.hpp"
 #include "vk_tf.hpp"
 #include "vk_trips.hpp"
@@ -16,76 +21,6 @@ __device__ __forceinline__ void load_cell_luts(const VolumeDesc &V, uint32_t *lu
     const uint4 *src = reinterpret_cast<const uint4 *>(V.lut);
     uint4 *dst = reinterpret_cast<uint4 *>(lut);
     for (uint32_t e = lane; e < n4; e += 64u) dst[e] = src[e];
-}
-
-// x-lerps of one cell: c00, c10, c01, c11 (the four x edges of the footprint)
-template <int VOL>
-struct CellBits { u32x4_t v; };
-template <>
-struct CellBits<VOL_P8> { u32x2_t v; };
-
-// PIN: mark the load volatile (aux bit 31: compiler-only, nothing changes in the encoding) so that it
-// is issued where it is written -- a prefetch must not be sunk behind the loop's exit branch.
-template <int VOL, bool PIN = false>
-__device__ __forceinline__ CellBits<VOL> load_cell(__amdgpu_buffer_rsrc_t rs, uint32_t off) {
-    constexpr int aux = PIN ? (int)0x80000000u : 0;
-    CellBits<VOL> c;
-    if constexpr (VOL == VOL_P8) c.v = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)off, 0, aux);
-    else c.v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, aux);
-    return c;
-}
-
-template <int VOL>
-__device__ __forceinline__ void xlerp_cell(const CellBits<VOL> &cb, float fx, float &c00, float &c10, float &c01, float &c11) {
-    if constexpr (VOL == VOL_P8) {
-        const uint32_t lo = cb.v.x, hi = cb.v.y;
-        float t0_ = (float)(lo & 0xffu), t1_ = (float)((lo >> 8) & 0xffu), t2_ = (float)((lo >> 16) & 0xffu), t3_ = (float)(lo >> 24);
-        float t4_ = (float)(hi & 0xffu), t5_ = (float)((hi >> 8) & 0xffu), t6_ = (float)((hi >> 16) & 0xffu), t7_ = (float)(hi >> 24);
-        c00 = fmaf(fx, t1_ - t0_, t0_); c10 = fmaf(fx, t3_ - t2_, t2_);
-        c01 = fmaf(fx, t5_ - t4_, t4_); c11 = fmaf(fx, t7_ - t6_, t6_);
-    } else {
-        union { u32x4_t u; half2_t h[4]; } c;
-        c.u = cb.v;
-        if constexpr (VOL == VOL_P16) {
-            // (tap, delta) pairs: delta = t1 - t0 is exact in f16 for u8 data -> v_fma_mix_f32
-            c00 = fmaf(fx, (float)c.h[0].y, (float)c.h[0].x); c10 = fmaf(fx, (float)c.h[1].y, (float)c.h[1].x);
-            c01 = fmaf(fx, (float)c.h[2].y, (float)c.h[2].x); c11 = fmaf(fx, (float)c.h[3].y, (float)c.h[3].x);
-        } else {
-            float a0 = (float)c.h[0].x, a1 = (float)c.h[0].y, a2 = (float)c.h[1].x, a3 = (float)c.h[1].y;
-            float a4 = (float)c.h[2].x, a5 = (float)c.h[2].y, a6 = (float)c.h[3].x, a7 = (float)c.h[3].y;
-            c00 = fmaf(fx, a1 - a0, a0); c10 = fmaf(fx, a3 - a2, a2);
-            c01 = fmaf(fx, a5 - a4, a4); c11 = fmaf(fx, a7 - a6, a6);
-        }
-    }
-}
-
-// xlerp_cell that also returns the four x-differences t1 - t0, t3 - t2, t5 - t4, t7 - t6 (the lit kernels' gradient, vk_light.hpp); PACKED_PAIRS
-// returns its stored deltas, which are those differences exactly for u8 data
-template <int VOL>
-__device__ __forceinline__ void xlerp_cell_dx(const CellBits<VOL> &cb, float fx, float &c00, float &c10, float &c01, float &c11,
-                                              float &dx00, float &dx10, float &dx01, float &dx11) {
-    if constexpr (VOL == VOL_P8) {
-        const uint32_t lo = cb.v.x, hi = cb.v.y;
-        float t0_ = (float)(lo & 0xffu), t1_ = (float)((lo >> 8) & 0xffu), t2_ = (float)((lo >> 16) & 0xffu), t3_ = (float)(lo >> 24);
-        float t4_ = (float)(hi & 0xffu), t5_ = (float)((hi >> 8) & 0xffu), t6_ = (float)((hi >> 16) & 0xffu), t7_ = (float)(hi >> 24);
-        dx00 = t1_ - t0_; dx10 = t3_ - t2_; dx01 = t5_ - t4_; dx11 = t7_ - t6_;
-        c00 = fmaf(fx, dx00, t0_); c10 = fmaf(fx, dx10, t2_);
-        c01 = fmaf(fx, dx01, t4_); c11 = fmaf(fx, dx11, t6_);
-    } else {
-        union { u32x4_t u; half2_t h[4]; } c;
-        c.u = cb.v;
-        if constexpr (VOL == VOL_P16) {
-            dx00 = (float)c.h[0].y; dx10 = (float)c.h[1].y; dx01 = (float)c.h[2].y; dx11 = (float)c.h[3].y;
-            c00 = fmaf(fx, dx00, (float)c.h[0].x); c10 = fmaf(fx, dx10, (float)c.h[1].x);
-            c01 = fmaf(fx, dx01, (float)c.h[2].x); c11 = fmaf(fx, dx11, (float)c.h[3].x);
-        } else {
-            float a0 = (float)c.h[0].x, a1 = (float)c.h[0].y, a2 = (float)c.h[1].x, a3 = (float)c.h[1].y;
-            float a4 = (float)c.h[2].x, a5 = (float)c.h[2].y, a6 = (float)c.h[3].x, a7 = (float)c.h[3].y;
-            dx00 = a1 - a0; dx10 = a3 - a2; dx01 = a5 - a4; dx11 = a7 - a6;
-            c00 = fmaf(fx, dx00, a0); c10 = fmaf(fx, dx10, a2);
-            c01 = fmaf(fx, dx01, a4); c11 = fmaf(fx, dx11, a6);
-        }
-    }
 }
 
 // -k for a walk of k = ceil(r) steps, 1 <= k <= iterations left (nleft = -left < 0): floor(-r) in one conversion (it saturates), clamped in one v_med3
@@ -180,28 +115,7 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
     uint32_t &n_iter = cs.n_iter, &n_samp = cs.n_samp, &w_outer = cs.w_outer, &w_inner = cs.w_inner, &w_sample = cs.w_sample, &n_look = cs.n_look;
     const int mx = (int)V.nx - 1, my = (int)V.ny - 1, mz = (int)V.nz - 1;
 
-    // per-ray constants of the skip bound (see below)
-    // Skip bound per axis: room_i / |du_i| with room_i = d - f_i (moving up) or f_i + d - 1 (moving
-    // down), minus a 0.02-cell margin that covers the rounding of the accumulated position
-    // (<= 1e-3 cells); folded into two fmas: r_i = f_i * ska_i + (d * idu_i + skb_i).
-    float idux = 0.f, iduy = 0.f, iduz = 0.f, skax = 0.f, skay = 0.f, skaz = 0.f, skbx = 0.f, skby = 0.f, skbz = 0.f;
-    if (SKIP) {
-        // rcp (1 ulp) is enough: these constants only bound a skip length, with the margins below.
-        const float dux = fabsf(sx) * fnx, duy = fabsf(sy) * fny, duz = fabsf(sz) * fnz;  // cells per step
-        idux = __builtin_amdgcn_rcpf(dux); iduy = __builtin_amdgcn_rcpf(duy); iduz = __builtin_amdgcn_rcpf(duz);
-        // Position margin, in cells: a walk crosses at most kDistRadius + 1 cells of its fastest axis,
-        // i.e. n <= 25 / max(du) steps, each adding <= 2^-25 of rounding to a coordinate in [0, 1]
-        // (x n_i cells); doubled, plus 0.01 for the rounding of u itself.
-        const float n_walk = (float)(kDistRadius + 1) * __builtin_amdgcn_rcpf(fmaxf(dux, fmaxf(duy, duz)));
-        const float mg = fmaf(n_walk * 0x1p-24f, fmaxf(fnx, fmaxf(fny, fnz)), 0.01f);
-        // (the walk counts its steps: no margin for a drifting loop variable; 2^-12 covers rcp and the fmas, 0.01 of a step on top)
-        constexpr float sc = 1.0f - 0x1p-12f, cst = -0.01f;
-        skax = (sx >= 0.0f ? -idux : idux) * sc; skay = (sy >= 0.0f ? -iduy : iduy) * sc; skaz = (sz >= 0.0f ? -iduz : iduz) * sc;
-        skbx = fmaf((sx >= 0.0f ? -mg : -1.0f - mg) * idux, sc, cst);
-        skby = fmaf((sy >= 0.0f ? -mg : -1.0f - mg) * iduy, sc, cst);
-        skbz = fmaf((sz >= 0.0f ? -mg : -1.0f - mg) * iduz, sc, cst);
-        idux *= sc; iduy *= sc; iduz *= sc;
-    }
+    const SkipBound sb = skip_bound<SKIP>(sx, sy, sz, fnx, fny, fnz);  // per-ray constants of the skip bound
     // this ray's octant selects its distance map (bit i: moving up on axis i, as in ska/skb above)
     const uint32_t doff = SKIP ? ((sx >= 0.0f ? 1u : 0u) | (sy >= 0.0f ? 2u : 0u) | (sz >= 0.0f ? 4u : 0u)) * V.dist_oct_stride : 0u;
     const uint32_t *luty = lut + (V.nx + 3), *lutz = lut + (V.nx + V.ny + 6);
@@ -239,13 +153,10 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
         float dx00 = 0.0f, dx10 = 0.0f, dx01 = 0.0f, dx11 = 0.0f;  // LIT: the x-differences of the taps
         if (PACKED) {
             if (SAFE) { ix = med3_i32(ix, -1, mx); iy = med3_i32(iy, -1, my); iz = med3_i32(iz, -1, mz); }
-            const int bx = ix >> 2, by = iy >> 2, bz = iz >> 2;
             const char *cptr = nullptr;
             uint32_t d = 0, coff = 0;
             if (SAFE) {
-                int64_t off = (int64_t)bz * (int64_t)V.kz + (int64_t)(by * (int)V.ky + bx * (int)V.kx) +
-                              (int64_t)((iz << V.sh_z) + (iy << V.sh_y) + (ix << V.sh_x)) + (int64_t)V.c0;
-                off = off < 0 ? 0 : (off > (int64_t)V.max_off ? (int64_t)V.max_off : off);
+                const int64_t off = safe_cell_offset(V, ix, iy, iz);
                 cptr = reinterpret_cast<const char *>(V.data) + off;
                 if (SKIP) d = V.dist[(uint64_t)(off >> V.sh_x) + doff];
             } else if (AHEAD) {
@@ -268,19 +179,11 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
             asm("s_cmp_lg_u64 %1, 0\n\ts_cselect_b32 %0, %2, %3" : "=s"(cap_now) : "s"(samplers), "s"(__builtin_amdgcn_readfirstlane(__float_as_uint(walk_cap))), "s"(__builtin_amdgcn_readfirstlane(__float_as_uint(walk_cap_all))) : "scc");
             if (SKIP && d != 0) {
                 if (BOUNDED) cs.skips++;
-                // Every cell within Chebyshev distance d-1 of this one is empty.  Sample j sits at
-                // u + j*du; it is skipped iff its cell provably stays in that range on every axis:
-                // j*|du| < d - f (moving up) or j*|du| <= f + d - 1 (moving down), minus the margins:
-                // j < r = min_i r_i, r_i = f_i * ska_i + (d * idu_i + skb_i).
-                const float fd = (float)d;
-                const float rx = fmaf(fx, skax, fmaf(fd, idux, skbx));
-                const float ry = fmaf(fy, skay, fmaf(fd, iduy, skby));
-                const float rz = fmaf(fz, skaz, fmaf(fd, iduz, skbz));
                 // Samples j = 0 .. k - 1 are skipped, k = ceil(r) (j < r keeps a sample inside the empty range; the current sample, j = 0,
                 // sits in an empty cell: k >= 1), at most the trip's cap and at most the iterations the loop has left -- every skipped
                 // iteration is one the reference makes (it passes `t < t1` on the reference's own t: that is what `left` counts).
                 // The walk advances the reference's position, p += s, k times: the same f32 additions in the same order.
-                float rmin = fminf(fminf(rx, ry), rz);
+                float rmin = sb.steps(fx, fy, fz, (float)d);
                 if constexpr (WALK == WALK_FMA) {
                     // one real addition, the other k - 1 as one fma with that addition's rounded increment (tolerance: see WalkKind)
                     const float x_1 = px + sx, y_1 = py + sy, z_1 = pz + sz;
@@ -324,12 +227,8 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
                 continue;
             }
             CellBits<VOL> cb;
-            if (SAFE) {
-                if constexpr (VOL == VOL_P8) { const uint2 c = *reinterpret_cast<const uint2 *>(cptr); cb.v.x = c.x; cb.v.y = c.y; }
-                else { const uint4 c = *reinterpret_cast<const uint4 *>(cptr); cb.v.x = c.x; cb.v.y = c.y; cb.v.z = c.z; cb.v.w = c.w; }
-            } else {
-                cb = load_cell<VOL>(cells, coff);
-            }
+            if (SAFE) cb = load_cell<VOL>(cptr);
+            else cb = load_cell<VOL>(cells, coff);
             if (AHEAD) {
                 // :118 and :101's increment (one iteration fewer left) now -- neither depends on the sample -- then the next position's distance byte is requested
                 // under this sample's arithmetic (fx, fy, fz keep THIS position's weights)
@@ -340,49 +239,14 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
             if constexpr (LIT) xlerp_cell_dx<VOL>(cb, fx, c00, c10, c01, c11, dx00, dx10, dx01, dx11);
             else xlerp_cell<VOL>(cb, fx, c00, c10, c01, c11);
         } else if (BRICK9) {
-            // cell coords c = i + 1 in [0, n]; brick c >> 3, local c & 7; the taps sit at local
-            // (l, l+1) per axis of the 9^3 brick: offsets {0,1} + {0,9} + {0,81} from one base
-            const int cx = med3_i32(ix, -1, mx) + 1, cy = med3_i32(iy, -1, my) + 1, cz = med3_i32(iz, -1, mz) + 1;
-            const uint32_t brick = (uint32_t)(((cz >> 3) * (int)V.nby + (cy >> 3)) * (int)V.nbx + (cx >> 3));
-            const uint32_t local = (uint32_t)((cz & 7) * 81 + (cy & 7) * 9 + (cx & 7));
-            typedef uint16_t u16_unaligned __attribute__((aligned(1)));
-            typedef uint32_t u32_unaligned __attribute__((aligned(2)));
             float tp[8];
-            if (VOL == VOL_B9U8) {
-                const uint8_t *b = reinterpret_cast<const uint8_t *>(V.data) + ((uint64_t)brick * 729u + local);
-                const uint32_t p00 = *reinterpret_cast<const u16_unaligned *>(b), p10 = *reinterpret_cast<const u16_unaligned *>(b + 9);
-                const uint32_t p01 = *reinterpret_cast<const u16_unaligned *>(b + 81), p11 = *reinterpret_cast<const u16_unaligned *>(b + 90);
-                tp[0] = (float)(p00 & 0xffu); tp[1] = (float)(p00 >> 8); tp[2] = (float)(p10 & 0xffu); tp[3] = (float)(p10 >> 8);
-                tp[4] = (float)(p01 & 0xffu); tp[5] = (float)(p01 >> 8); tp[6] = (float)(p11 & 0xffu); tp[7] = (float)(p11 >> 8);
-            } else {
-                const uint16_t *b = reinterpret_cast<const uint16_t *>(V.data) + ((uint64_t)brick * 729u + local);
-                const uint32_t p00 = *reinterpret_cast<const u32_unaligned *>(b), p10 = *reinterpret_cast<const u32_unaligned *>(b + 9);
-                const uint32_t p01 = *reinterpret_cast<const u32_unaligned *>(b + 81), p11 = *reinterpret_cast<const u32_unaligned *>(b + 90);
-                tp[0] = h2f(p00 & 0xffffu); tp[1] = h2f(p00 >> 16); tp[2] = h2f(p10 & 0xffffu); tp[3] = h2f(p10 >> 16);
-                tp[4] = h2f(p01 & 0xffffu); tp[5] = h2f(p01 >> 16); tp[6] = h2f(p11 & 0xffffu); tp[7] = h2f(p11 >> 16);
-            }
-            c00 = fmaf(fx, tp[1] - tp[0], tp[0]); c10 = fmaf(fx, tp[3] - tp[2], tp[2]);
-            c01 = fmaf(fx, tp[5] - tp[4], tp[4]); c11 = fmaf(fx, tp[7] - tp[6], tp[6]);
+            b9_decode<VOL>(b9_request<VOL>(V, ix, iy, iz), tp);
+            xlerp_taps(tp, fx, c00, c10, c01, c11);
         } else {
-            int x0 = clampi(ix, 0, mx), x1 = clampi(ix + (ix < 0x7fffffff), 0, mx);
-            int y0 = clampi(iy, 0, my), y1 = clampi(iy + (iy < 0x7fffffff), 0, my);
-            int z0 = clampi(iz, 0, mz), z1 = clampi(iz + (iz < 0x7fffffff), 0, mz);
-            size_t sy_ = V.nx, sz_ = (size_t)V.nx * V.ny;
-            size_t r00 = y0 * sy_ + z0 * sz_, r10 = y1 * sy_ + z0 * sz_;
-            size_t r01 = y0 * sy_ + z1 * sz_, r11 = y1 * sy_ + z1 * sz_;
             float tp[8];
-            if (VOL == VOL_LINEAR_U8) {
-                const uint8_t *v = reinterpret_cast<const uint8_t *>(V.data);
-                tp[0] = (float)v[r00 + x0]; tp[1] = (float)v[r00 + x1]; tp[2] = (float)v[r10 + x0]; tp[3] = (float)v[r10 + x1];
-                tp[4] = (float)v[r01 + x0]; tp[5] = (float)v[r01 + x1]; tp[6] = (float)v[r11 + x0]; tp[7] = (float)v[r11 + x1];
-            } else {
-                const uint16_t *v = reinterpret_cast<const uint16_t *>(V.data);
-                tp[0] = h2f(v[r00 + x0]); tp[1] = h2f(v[r00 + x1]); tp[2] = h2f(v[r10 + x0]); tp[3] = h2f(v[r10 + x1]);
-                tp[4] = h2f(v[r01 + x0]); tp[5] = h2f(v[r01 + x1]); tp[6] = h2f(v[r11 + x0]); tp[7] = h2f(v[r11 + x1]);
-            }
+            linear_taps<VOL>(V, ix, iy, iz, tp);
             if constexpr (LIT) { dx00 = tp[1] - tp[0]; dx10 = tp[3] - tp[2]; dx01 = tp[5] - tp[4]; dx11 = tp[7] - tp[6]; }
-            c00 = fmaf(fx, tp[1] - tp[0], tp[0]); c10 = fmaf(fx, tp[3] - tp[2], tp[2]);
-            c01 = fmaf(fx, tp[5] - tp[4], tp[4]); c11 = fmaf(fx, tp[7] - tp[6], tp[6]);
+            xlerp_taps(tp, fx, c00, c10, c01, c11);
         }
         float c0 = fmaf(fy, c10 - c00, c00), c1 = fmaf(fy, c11 - c01, c01);
         float r = fmaf(fz, c1 - c0, c0);
@@ -412,7 +276,7 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
                 lit_gradient(dx00, dx10, dx01, dx11, c00, c10, c01, c11, c0, c1, fy, fz, fnx, fny, fnz, gx, gy, gz);
                 lit_shade(*ld, *lr, gx, gy, gz, tr, tg, tb);
             }
-            const float w = (1.0f - A) * a;
+            const float w = (1.0f - A) * a;  // (composite(), written out: the ISA decided -- through the call two COUNT table kernels take two more registers)
             Gr = fmaf(w, tr, Gr); Gg = fmaf(w, tg, Gg); Gb = fmaf(w, tb, Gb);
             A = A + w;
             if (!AHEAD) {
@@ -421,17 +285,10 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
             }
             continue;
         }
-        // vertigo(): cos(6.28318*(c*a + d)); v_cos_f32 takes revolutions
-        constexpr double kk = 6.28318 / 6.283185307179586476925;
-        constexpr float pc0 = (float)(1.0 * kk), pc1 = (float)(1.7 * kk), pc2 = (float)(0.4 * kk);
-        constexpr float pd1 = (float)(0.15 * kk), pd2 = (float)(0.20 * kk);
-        const float cr = __builtin_amdgcn_cosf(a * pc0);
-        const float cg = __builtin_amdgcn_cosf(fmaf(a, pc1, pd1));
-        const float cb = __builtin_amdgcn_cosf(fmaf(a, pc2, pd2));
-        if (COUNT) { n_iter++; n_samp++; if (wave_leader()) w_sample++; }
-        const float w = (1.0f - A) * a;  // :112-114
-        Gr = fmaf(w, cr, Gr); Gg = fmaf(w, cg, Gg); Gb = fmaf(w, cb, Gb);
-        A = A + w;
+        float cr, cg, cb;
+        palette_cos(a, cr, cg, cb);
+        if (COUNT) { n_iter++; n_samp++; if (wave_leader()) w_sample++; }  // (between the cosines and the compositing: the COUNT kernels' registers follow it)
+        composite(a, cr, cg, cb, A, Gr, Gg, Gb);  // :112-114
         if (!AHEAD) {
             px = px + sx; py = py + sy; pz = pz + sz;  // :118
             nleft += 1;
@@ -489,20 +346,9 @@ __device__ __forceinline__ bool march_stream(const VolumeDesc &V, RayState &r, C
                 lit_gradient(dx00, dx10, dx01, dx11, c00, c10, c01, c11, l0, l1, fy, fz, fnx, fny, fnz, gx, gy, gz);
                 lit_shade(*ld, *lr, gx, gy, gz, cr, cg, cb);
             }
-            const float w = (1.0f - A) * a;
-            Gr = fmaf(w, cr, Gr); Gg = fmaf(w, cg, Gg); Gb = fmaf(w, cb, Gb);
-            A = A + w;
+            composite(a, cr, cg, cb, A, Gr, Gg, Gb);
         } else {
-        const float a = transfer_alpha<(VOL == VOL_P8 || VOL == VOL_P16) ? 1 : 0>(v);
-        constexpr double kk = 6.28318 / 6.283185307179586476925;
-        constexpr float pc0 = (float)(1.0 * kk), pc1 = (float)(1.7 * kk), pc2 = (float)(0.4 * kk);
-        constexpr float pd1 = (float)(0.15 * kk), pd2 = (float)(0.20 * kk);
-        const float cr = __builtin_amdgcn_cosf(a * pc0);
-        const float cg = __builtin_amdgcn_cosf(fmaf(a, pc1, pd1));
-        const float cb = __builtin_amdgcn_cosf(fmaf(a, pc2, pd2));
-        const float w = (1.0f - A) * a;  // :112-114
-        Gr = fmaf(w, cr, Gr); Gg = fmaf(w, cg, Gg); Gb = fmaf(w, cb, Gb);
-        A = A + w;
+            palette_composite(transfer_alpha<(VOL == VOL_P8 || VOL == VOL_P16) ? 1 : 0>(v), A, Gr, Gg, Gb);
         }
         left -= 1u;  // :101
         fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);
@@ -522,145 +368,41 @@ __device__ __forceinline__ bool march_stream(const VolumeDesc &V, RayState &r, C
     return alive;
 }
 
-// The dense 9^3-brick layouts, software-pipelined the same way: these serve volumes far larger than
-// the caches, where every step's four x-pair loads are HBM/fabric latency.  The next trip's loads are
+// The dense 9^3-brick and quad layouts, software-pipelined the same way: these serve volumes far larger than the caches, where
+// every step's loads (four x pairs of a 9^3 brick, one load of a quad) are HBM/fabric latency.  The next trip's loads are
 // requested (clamped indices, so always inside the array) before this trip's sample is evaluated.
 template <int VOL, bool COUNT>
-__device__ __forceinline__ void march_b9_stream(const VolumeDesc &V, RayState &r, Census &cs) {
-    static_assert(VOL == VOL_B9U8 || VOL == VOL_B9F16, "9^3 brick layouts");
+__device__ __forceinline__ void march_dense_stream(const VolumeDesc &V, RayState &r, Census &cs) {
+    static_assert(is_b9(VOL) || is_quads(VOL), "9^3 brick and quad layouts");
+    constexpr bool U8 = (VOL == VOL_B9U8 || VOL == VOL_Q8);
     float px = r.px, py = r.py, pz = r.pz, A = r.A, Gr = r.Gr, Gg = r.Gg, Gb = r.Gb;
     uint32_t left = r.left;
     const float sx = r.sx, sy = r.sy, sz = r.sz;
     const float fnx = (float)V.nx, fny = (float)V.ny, fnz = (float)V.nz;
-    const int mx = (int)V.nx - 1, my = (int)V.ny - 1, mz = (int)V.nz - 1;
     if (!(left != 0u && A < 0.95f)) return;
-    typedef uint16_t u16_unaligned __attribute__((aligned(1)));
-    typedef uint32_t u32_unaligned __attribute__((aligned(2)));
-    struct Taps { uint32_t p00, p10, p01, p11; };  // x pairs at (y, z) = (0,0) (1,0) (0,1) (1,1)
-    auto request = [&](float ux, float uy, float uz) -> Taps {
-        const int cx = med3_i32(cvt_floor_i32(ux), -1, mx) + 1, cy = med3_i32(cvt_floor_i32(uy), -1, my) + 1, cz = med3_i32(cvt_floor_i32(uz), -1, mz) + 1;
-        const uint32_t brick = (uint32_t)(((cz >> 3) * (int)V.nby + (cy >> 3)) * (int)V.nbx + (cx >> 3));
-        const uint32_t local = (uint32_t)((cz & 7) * 81 + (cy & 7) * 9 + (cx & 7));
-        Taps q;
-        if (VOL == VOL_B9U8) {
-            const uint8_t *b = reinterpret_cast<const uint8_t *>(V.data) + ((uint64_t)brick * 729u + local);
-            q.p00 = *reinterpret_cast<const u16_unaligned *>(b); q.p10 = *reinterpret_cast<const u16_unaligned *>(b + 9);
-            q.p01 = *reinterpret_cast<const u16_unaligned *>(b + 81); q.p11 = *reinterpret_cast<const u16_unaligned *>(b + 90);
-        } else {
-            const uint16_t *b = reinterpret_cast<const uint16_t *>(V.data) + ((uint64_t)brick * 729u + local);
-            q.p00 = *reinterpret_cast<const u32_unaligned *>(b); q.p10 = *reinterpret_cast<const u32_unaligned *>(b + 9);
-            q.p01 = *reinterpret_cast<const u32_unaligned *>(b + 81); q.p11 = *reinterpret_cast<const u32_unaligned *>(b + 90);
-        }
-        return q;
+    auto request = [&](float ux, float uy, float uz) -> DenseWords {
+        if constexpr (is_b9(VOL)) return b9_request<VOL>(V, cvt_floor_i32(ux), cvt_floor_i32(uy), cvt_floor_i32(uz));
+        else return quad_request<VOL>(V, cvt_floor_i32(ux), cvt_floor_i32(uy), cvt_floor_i32(uz));
     };
     float fx, fy, fz;
-    Taps c0, c1;
+    DenseWords c0, c1;
     {
         const float ux = fmaf(px, fnx, -0.5f), uy = fmaf(py, fny, -0.5f), uz = fmaf(pz, fnz, -0.5f);
         fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);
         c0 = request(ux, uy, uz);
     }
-    auto trip = [&](const Taps &cur, Taps &nxt) -> bool {
+    auto trip = [&](const DenseWords &cur, DenseWords &nxt) -> bool {
         if (COUNT) { cs.n_look++; cs.n_iter++; cs.n_samp++; if (wave_leader()) { cs.w_outer++; cs.w_sample++; } }
         px = px + sx; py = py + sy; pz = pz + sz;  // :118
         const float ux = fmaf(px, fnx, -0.5f), uy = fmaf(py, fny, -0.5f), uz = fmaf(pz, fnz, -0.5f);
         nxt = request(ux, uy, uz);
-        float tp[8];
-        if (VOL == VOL_B9U8) {
-            tp[0] = (float)(cur.p00 & 0xffu); tp[1] = (float)(cur.p00 >> 8); tp[2] = (float)(cur.p10 & 0xffu); tp[3] = (float)(cur.p10 >> 8);
-            tp[4] = (float)(cur.p01 & 0xffu); tp[5] = (float)(cur.p01 >> 8); tp[6] = (float)(cur.p11 & 0xffu); tp[7] = (float)(cur.p11 >> 8);
-        } else {
-            tp[0] = h2f(cur.p00 & 0xffffu); tp[1] = h2f(cur.p00 >> 16); tp[2] = h2f(cur.p10 & 0xffffu); tp[3] = h2f(cur.p10 >> 16);
-            tp[4] = h2f(cur.p01 & 0xffffu); tp[5] = h2f(cur.p01 >> 16); tp[6] = h2f(cur.p11 & 0xffffu); tp[7] = h2f(cur.p11 >> 16);
-        }
-        const float c00 = fmaf(fx, tp[1] - tp[0], tp[0]), c10 = fmaf(fx, tp[3] - tp[2], tp[2]);
-        const float c01 = fmaf(fx, tp[5] - tp[4], tp[4]), c11 = fmaf(fx, tp[7] - tp[6], tp[6]);
+        float tp[8], c00, c10, c01, c11;  // tap index dx + 2*dy + 4*dz
+        if constexpr (is_b9(VOL)) b9_decode<VOL>(cur, tp);
+        else quad_decode<VOL>(cur, tp);
+        xlerp_taps(tp, fx, c00, c10, c01, c11);
         const float l0 = fmaf(fy, c10 - c00, c00), l1 = fmaf(fy, c11 - c01, c01);
         float v = fmaf(fz, l1 - l0, l0);
-        const float a = transfer_alpha<VOL == VOL_B9U8 ? 1 : 0>(v);
-        constexpr double kk = 6.28318 / 6.283185307179586476925;
-        constexpr float pc0 = (float)(1.0 * kk), pc1 = (float)(1.7 * kk), pc2 = (float)(0.4 * kk);
-        constexpr float pd1 = (float)(0.15 * kk), pd2 = (float)(0.20 * kk);
-        const float cr = __builtin_amdgcn_cosf(a * pc0);
-        const float cg = __builtin_amdgcn_cosf(fmaf(a, pc1, pd1));
-        const float cb = __builtin_amdgcn_cosf(fmaf(a, pc2, pd2));
-        const float w = (1.0f - A) * a;  // :112-114
-        Gr = fmaf(w, cr, Gr); Gg = fmaf(w, cg, Gg); Gb = fmaf(w, cb, Gb);
-        A = A + w;
-        left -= 1u;  // :101
-        fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);
-        return left != 0u && A < 0.95f;
-    };
-    for (;;) {
-        if (!trip(c0, c1)) break;
-        if (!trip(c1, c0)) break;
-    }
-    asm volatile("" ::"v"(c0.p00), "v"(c0.p10), "v"(c0.p01), "v"(c0.p11), "v"(c1.p00), "v"(c1.p10), "v"(c1.p01), "v"(c1.p11));
-    r.left = left; r.px = px; r.py = py; r.pz = pz; r.A = A; r.Gr = Gr; r.Gg = Gg; r.Gb = Gb;
-}
-
-// The quad layouts: one load per sample (two consecutive elements), software-pipelined like the others.
-template <int VOL, bool COUNT>
-__device__ __forceinline__ void march_quads_stream(const VolumeDesc &V, RayState &r, Census &cs) {
-    static_assert(VOL == VOL_Q8 || VOL == VOL_QF16, "quad layouts");
-    float px = r.px, py = r.py, pz = r.pz, A = r.A, Gr = r.Gr, Gg = r.Gg, Gb = r.Gb;
-    uint32_t left = r.left;
-    const float sx = r.sx, sy = r.sy, sz = r.sz;
-    const float fnx = (float)V.nx, fny = (float)V.ny, fnz = (float)V.nz;
-    const int mx = (int)V.nx - 1, my = (int)V.ny - 1, mz = (int)V.nz - 1;
-    if (!(left != 0u && A < 0.95f)) return;
-    typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));  // elements are 4 / 8 bytes: the pair is under-aligned
-    typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
-    struct Taps { uint32_t a, b, c, d; };  // u8: a = element(x), b = element(x+1); f16: (a, b) = element(x), (c, d) = element(x+1)
-    auto request = [&](float ux, float uy, float uz) -> Taps {
-        const int cx = med3_i32(cvt_floor_i32(ux), -1, mx) + 1, cy = med3_i32(cvt_floor_i32(uy), -1, my) + 1, cz = med3_i32(cvt_floor_i32(uz), -1, mz) + 1;
-        const uint32_t brick = (uint32_t)(((cz >> 3) * (int)V.nby + (cy >> 3)) * (int)V.nbx + (cx >> 3));
-        const uint32_t local = (uint32_t)(((cz & 7) * 8 + (cy & 7)) * 9 + (cx & 7));
-        const uint64_t e = (uint64_t)brick * 576u + local;
-        Taps q;
-        if (VOL == VOL_Q8) {
-            const u32x2_a4 v = *reinterpret_cast<const u32x2_a4 *>(reinterpret_cast<const uint32_t *>(V.data) + e);
-            q.a = v.x; q.b = v.y; q.c = 0; q.d = 0;
-        } else {
-            const u32x4_a8 v = *reinterpret_cast<const u32x4_a8 *>(reinterpret_cast<const uint2 *>(V.data) + e);
-            q.a = v.x; q.b = v.y; q.c = v.z; q.d = v.w;
-        }
-        return q;
-    };
-    float fx, fy, fz;
-    Taps c0, c1;
-    {
-        const float ux = fmaf(px, fnx, -0.5f), uy = fmaf(py, fny, -0.5f), uz = fmaf(pz, fnz, -0.5f);
-        fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);
-        c0 = request(ux, uy, uz);
-    }
-    auto trip = [&](const Taps &cur, Taps &nxt) -> bool {
-        if (COUNT) { cs.n_look++; cs.n_iter++; cs.n_samp++; if (wave_leader()) { cs.w_outer++; cs.w_sample++; } }
-        px = px + sx; py = py + sy; pz = pz + sz;  // :118
-        const float ux = fmaf(px, fnx, -0.5f), uy = fmaf(py, fny, -0.5f), uz = fmaf(pz, fnz, -0.5f);
-        nxt = request(ux, uy, uz);
-        float tp[8];  // tap index dx + 2*dy + 4*dz
-        if (VOL == VOL_Q8) {
-            tp[0] = (float)(cur.a & 0xffu); tp[2] = (float)((cur.a >> 8) & 0xffu); tp[4] = (float)((cur.a >> 16) & 0xffu); tp[6] = (float)(cur.a >> 24);
-            tp[1] = (float)(cur.b & 0xffu); tp[3] = (float)((cur.b >> 8) & 0xffu); tp[5] = (float)((cur.b >> 16) & 0xffu); tp[7] = (float)(cur.b >> 24);
-        } else {
-            tp[0] = h2f(cur.a & 0xffffu); tp[2] = h2f(cur.a >> 16); tp[4] = h2f(cur.b & 0xffffu); tp[6] = h2f(cur.b >> 16);
-            tp[1] = h2f(cur.c & 0xffffu); tp[3] = h2f(cur.c >> 16); tp[5] = h2f(cur.d & 0xffffu); tp[7] = h2f(cur.d >> 16);
-        }
-        const float c00 = fmaf(fx, tp[1] - tp[0], tp[0]), c10 = fmaf(fx, tp[3] - tp[2], tp[2]);
-        const float c01 = fmaf(fx, tp[5] - tp[4], tp[4]), c11 = fmaf(fx, tp[7] - tp[6], tp[6]);
-        const float l0 = fmaf(fy, c10 - c00, c00), l1 = fmaf(fy, c11 - c01, c01);
-        float v = fmaf(fz, l1 - l0, l0);
-        const float a = transfer_alpha<VOL == VOL_Q8 ? 1 : 0>(v);
-        constexpr double kk = 6.28318 / 6.283185307179586476925;
-        constexpr float pc0 = (float)(1.0 * kk), pc1 = (float)(1.7 * kk), pc2 = (float)(0.4 * kk);
-        constexpr float pd1 = (float)(0.15 * kk), pd2 = (float)(0.20 * kk);
-        const float cr = __builtin_amdgcn_cosf(a * pc0);
-        const float cg = __builtin_amdgcn_cosf(fmaf(a, pc1, pd1));
-        const float cb = __builtin_amdgcn_cosf(fmaf(a, pc2, pd2));
-        const float w = (1.0f - A) * a;  // :112-114
-        Gr = fmaf(w, cr, Gr); Gg = fmaf(w, cg, Gg); Gb = fmaf(w, cb, Gb);
-        A = A + w;
+        palette_composite(transfer_alpha<U8 ? 1 : 0>(v), A, Gr, Gg, Gb);
         left -= 1u;  // :101
         fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);
         return left != 0u && A < 0.95f;

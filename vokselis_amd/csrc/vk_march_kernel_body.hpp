@@ -117,8 +117,7 @@
                 march<VOL, SKIP, SAFE, COUNT, false, WALK, AHEAD, TF, LIT>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd, ldp, &lr);
             }
         }
-        else if constexpr (VOL == VOL_B9U8 || VOL == VOL_B9F16) march_b9_stream<VOL, COUNT>(V, r, cs);
-        else if constexpr (VOL == VOL_Q8 || VOL == VOL_QF16) march_quads_stream<VOL, COUNT>(V, r, cs);
+        else if constexpr (is_b9(VOL) || is_quads(VOL)) march_dense_stream<VOL, COUNT>(V, r, cs);
         else if constexpr (MIP) march_mip<VOL, false, SAFE, COUNT, false>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, __builtin_inff(), __builtin_inff(), tfd->k1, tfd->k2, tfd->umax);
         else march<VOL, SKIP, SAFE, COUNT, false, WALK_LOOP, false, TF, LIT>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, __builtin_inff(), __builtin_inff(), tfd, ldp, &lr);
         A = r.A; Gr = r.Gr; Gg = r.Gg; Gb = r.Gb;

@@ -1,7 +1,9 @@
 // vk_march_mip.hpp -- the loops of the cell march under the maximum-intensity projection (vk_set_projection(VK_PROJ_MAX); DESIGN.md
 // section 12): march() and march_stream() of vk_march.hpp with another operator on the filtered sample, U = mip_update(U, x) (vk_tf.hpp),
-// the running maximum in table coordinates.  Loops of their own: the compositing loops do not carry the operator.  Included by
-// vk_march.hpp, after the definitions they share with its loops; called from vk_march_kernel_body.hpp under MIP.
+// the running maximum in table coordinates.  Loops of their own: the compositing loops do not carry the operator; the statement
+// groups they are built from are the same (vk_march_parts.hpp).  Included by vk_march.hpp, after the definitions it shares with
+// that file's loops, and so part of every unit that includes vk_march.hpp; instantiated by raymarch_mip_kernel (vk_launch_mip.hip) alone,
+// through vk_march_kernel_body.hpp under MIP.
 #pragma once
 
 namespace vk {
@@ -22,20 +24,7 @@ __device__ __forceinline__ bool march_mip(const VolumeDesc &V, RayState &r, cons
     const float fnx = (float)V.nx, fny = (float)V.ny, fnz = (float)V.nz;
     const int mx = (int)V.nx - 1, my = (int)V.ny - 1, mz = (int)V.nz - 1;
 
-    // per-ray constants of the skip bound: march()'s, with its margins
-    float idux = 0.f, iduy = 0.f, iduz = 0.f, skax = 0.f, skay = 0.f, skaz = 0.f, skbx = 0.f, skby = 0.f, skbz = 0.f;
-    if (SKIP) {
-        const float dux = fabsf(sx) * fnx, duy = fabsf(sy) * fny, duz = fabsf(sz) * fnz;  // cells per step
-        idux = __builtin_amdgcn_rcpf(dux); iduy = __builtin_amdgcn_rcpf(duy); iduz = __builtin_amdgcn_rcpf(duz);
-        const float n_walk = (float)(kDistRadius + 1) * __builtin_amdgcn_rcpf(fmaxf(dux, fmaxf(duy, duz)));
-        const float mg = fmaf(n_walk * 0x1p-24f, fmaxf(fnx, fmaxf(fny, fnz)), 0.01f);
-        constexpr float sc = 1.0f - 0x1p-12f, cst = -0.01f;
-        skax = (sx >= 0.0f ? -idux : idux) * sc; skay = (sy >= 0.0f ? -iduy : iduy) * sc; skaz = (sz >= 0.0f ? -iduz : iduz) * sc;
-        skbx = fmaf((sx >= 0.0f ? -mg : -1.0f - mg) * idux, sc, cst);
-        skby = fmaf((sy >= 0.0f ? -mg : -1.0f - mg) * iduy, sc, cst);
-        skbz = fmaf((sz >= 0.0f ? -mg : -1.0f - mg) * iduz, sc, cst);
-        idux *= sc; iduy *= sc; iduz *= sc;
-    }
+    const SkipBound sb = skip_bound<SKIP>(sx, sy, sz, fnx, fny, fnz);  // per-ray constants of the skip bound
     const uint32_t doff = SKIP ? ((sx >= 0.0f ? 1u : 0u) | (sy >= 0.0f ? 2u : 0u) | (sz >= 0.0f ? 4u : 0u)) * V.dist_oct_stride : 0u;
     const uint32_t *luty = lut + (V.nx + 3), *lutz = lut + (V.nx + V.ny + 6);
     const __amdgpu_buffer_rsrc_t cells = cell_buffer(V.data, SAFE ? 0u : (uint32_t)V.max_off + (1u << V.sh_x));
@@ -50,13 +39,10 @@ __device__ __forceinline__ bool march_mip(const VolumeDesc &V, RayState &r, cons
         float c00, c10, c01, c11;  // x-lerped corners
         if (PACKED) {
             if (SAFE) { ix = med3_i32(ix, -1, mx); iy = med3_i32(iy, -1, my); iz = med3_i32(iz, -1, mz); }
-            const int bx = ix >> 2, by = iy >> 2, bz = iz >> 2;
             const char *cptr = nullptr;
             uint32_t d = 0, coff = 0;
             if (SAFE) {
-                int64_t off = (int64_t)bz * (int64_t)V.kz + (int64_t)(by * (int)V.ky + bx * (int)V.kx) +
-                              (int64_t)((iz << V.sh_z) + (iy << V.sh_y) + (ix << V.sh_x)) + (int64_t)V.c0;
-                off = off < 0 ? 0 : (off > (int64_t)V.max_off ? (int64_t)V.max_off : off);
+                const int64_t off = safe_cell_offset(V, ix, iy, iz);
                 cptr = reinterpret_cast<const char *>(V.data) + off;
                 if (SKIP) d = V.dist[(uint64_t)(off >> V.sh_x) + doff];
             } else {
@@ -69,12 +55,8 @@ __device__ __forceinline__ bool march_mip(const VolumeDesc &V, RayState &r, cons
                 if (BOUNDED) cs.skips++;
                 // walks are capped in a trip in which other lanes sample (march(): the samplers pace the trip); any stop is exact
                 const float cap_now = __ballot(d == 0) != 0ull ? walk_cap : walk_cap_all;
-                const float fd = (float)d;
-                const float rx = fmaf(fx, skax, fmaf(fd, idux, skbx));
-                const float ry = fmaf(fy, skay, fmaf(fd, iduy, skby));
-                const float rz = fmaf(fz, skaz, fmaf(fd, iduz, skbz));
                 // samples j = 0 .. k - 1 are skipped, k = ceil(min r_i) clamped to [1, iterations left]: p += s, k times, the reference's additions
-                const float rmin = fminf(fminf(fminf(rx, ry), rz), cap_now);
+                const float rmin = fminf(sb.steps(fx, fy, fz, (float)d), cap_now);
                 const int kneg = walk_steps_neg(rmin, nleft);  // -k
                 nleft -= kneg;
                 if (COUNT) { cs.n_iter += (uint32_t)(-kneg); if (wave_leader()) cs.w_inner++; }
@@ -89,32 +71,13 @@ __device__ __forceinline__ bool march_mip(const VolumeDesc &V, RayState &r, cons
                 continue;
             }
             CellBits<VOL> cb;
-            if (SAFE) {
-                if constexpr (VOL == VOL_P8) { const uint2 c = *reinterpret_cast<const uint2 *>(cptr); cb.v.x = c.x; cb.v.y = c.y; }
-                else { const uint4 c = *reinterpret_cast<const uint4 *>(cptr); cb.v.x = c.x; cb.v.y = c.y; cb.v.z = c.z; cb.v.w = c.w; }
-            } else {
-                cb = load_cell<VOL>(cells, coff);
-            }
+            if (SAFE) cb = load_cell<VOL>(cptr);
+            else cb = load_cell<VOL>(cells, coff);
             xlerp_cell<VOL>(cb, fx, c00, c10, c01, c11);
         } else {
-            const int x0 = clampi(ix, 0, mx), x1 = clampi(ix + (ix < 0x7fffffff), 0, mx);
-            const int y0 = clampi(iy, 0, my), y1 = clampi(iy + (iy < 0x7fffffff), 0, my);
-            const int z0 = clampi(iz, 0, mz), z1 = clampi(iz + (iz < 0x7fffffff), 0, mz);
-            const size_t sy_ = V.nx, sz_ = (size_t)V.nx * V.ny;
-            const size_t r00 = y0 * sy_ + z0 * sz_, r10 = y1 * sy_ + z0 * sz_;
-            const size_t r01 = y0 * sy_ + z1 * sz_, r11 = y1 * sy_ + z1 * sz_;
             float tp[8];
-            if (VOL == VOL_LINEAR_U8) {
-                const uint8_t *v = reinterpret_cast<const uint8_t *>(V.data);
-                tp[0] = (float)v[r00 + x0]; tp[1] = (float)v[r00 + x1]; tp[2] = (float)v[r10 + x0]; tp[3] = (float)v[r10 + x1];
-                tp[4] = (float)v[r01 + x0]; tp[5] = (float)v[r01 + x1]; tp[6] = (float)v[r11 + x0]; tp[7] = (float)v[r11 + x1];
-            } else {
-                const uint16_t *v = reinterpret_cast<const uint16_t *>(V.data);
-                tp[0] = h2f(v[r00 + x0]); tp[1] = h2f(v[r00 + x1]); tp[2] = h2f(v[r10 + x0]); tp[3] = h2f(v[r10 + x1]);
-                tp[4] = h2f(v[r01 + x0]); tp[5] = h2f(v[r01 + x1]); tp[6] = h2f(v[r11 + x0]); tp[7] = h2f(v[r11 + x1]);
-            }
-            c00 = fmaf(fx, tp[1] - tp[0], tp[0]); c10 = fmaf(fx, tp[3] - tp[2], tp[2]);
-            c01 = fmaf(fx, tp[5] - tp[4], tp[4]); c11 = fmaf(fx, tp[7] - tp[6], tp[6]);
+            linear_taps<VOL>(V, ix, iy, iz, tp);
+            xlerp_taps(tp, fx, c00, c10, c01, c11);
         }
         const float c0 = fmaf(fy, c10 - c00, c00), c1 = fmaf(fy, c11 - c01, c01);
         const float x = fmaf(fz, c1 - c0, c0);

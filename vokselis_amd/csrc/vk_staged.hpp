@@ -130,16 +130,7 @@ __device__ __forceinline__ int mad_i24(int a, int b, int c) {
 // One sample's transfer function, colour and compositing: the statements of march() after the filter.
 template <int SCALE>
 __device__ __forceinline__ void composite_step(float v, float &A, float &Gr, float &Gg, float &Gb) {
-    const float a = transfer_alpha<SCALE>(v);
-    constexpr double kk = 6.28318 / 6.283185307179586476925;
-    constexpr float pc0 = (float)(1.0 * kk), pc1 = (float)(1.7 * kk), pc2 = (float)(0.4 * kk);
-    constexpr float pd1 = (float)(0.15 * kk), pd2 = (float)(0.20 * kk);
-    const float cr = __builtin_amdgcn_cosf(a * pc0);
-    const float cg = __builtin_amdgcn_cosf(fmaf(a, pc1, pd1));
-    const float cb = __builtin_amdgcn_cosf(fmaf(a, pc2, pd2));
-    const float w = (1.0f - A) * a;  // :112-114
-    Gr = fmaf(w, cr, Gr); Gg = fmaf(w, cg, Gg); Gb = fmaf(w, cb, Gb);
-    A = A + w;
+    palette_composite(transfer_alpha<SCALE>(v), A, Gr, Gg, Gb);
 }
 
 // The filter on four pairs along the copy's FAST axis: pair k = (lo[k], hi[k]) sits at MID offset k & 1, SLOW
