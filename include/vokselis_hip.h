@@ -445,6 +445,10 @@ int vk_step_counts_reset(vk_ctx *ctx);
  * out[0] wave-level march-loop iterations, out[1] wave-level skipped-step iterations,
  * out[2] wave-level sample executions, out[3] per-lane march-loop iterations (lookups). */
 int vk_simt_census(vk_ctx *ctx, uint64_t out[4]);
+/* Lone-speckle census of the built-in skip kernels, same launches: out[0] wave-level sample executions in which every sampling
+ * lane's alpha was 0 (the palette and the compositing were left out), out[1] lane-steps that a cell's speckle code proved
+ * transparent without a sample (they count in S_ref and in S_sampled like the samples they replace). */
+int vk_speckle_census(vk_ctx *ctx, uint64_t out[2]);
 /* Debug: override the tile order table of the last launch's partition (experiments on launch order): `order` is a permutation of
  * the n tiles (position -> row-major tile id) that keeps the active tiles -- the leading vk_partition_active positions of the
  * current order, the only ones a launch marches -- in front; anything else is VK_ERR_INVALID.  It stays until the partition's

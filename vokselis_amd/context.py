@@ -376,6 +376,11 @@ class Context:
         N.check(self._h, N.lib().vk_simt_census(self._h, out))
         return {"wave_loop_iters": out[0], "wave_skip_iters": out[1], "wave_sample_execs": out[2], "lane_loop_iters": out[3]}
 
+    def speckle_census(self) -> dict:
+        out = (C.c_uint64 * 2)()
+        N.check(self._h, N.lib().vk_speckle_census(self._h, out))
+        return {"wave_zero_alpha_execs": out[0], "lane_proven_steps": out[1]}
+
     def reset_step_counts(self):
         N.check(self._h, N.lib().vk_step_counts_reset(self._h))
 

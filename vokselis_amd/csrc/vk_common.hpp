@@ -426,6 +426,9 @@ __device__ __forceinline__ bool wave_leader() {
 // entries to byte offsets when no per-cell side table is read.
 __host__ __device__ __forceinline__ uint32_t cell_lut_entries(uint32_t nx, uint32_t ny, uint32_t nz) { return (nx + ny + nz + 9u + 3u) & ~3u; }  // padded to whole uint4
 __host__ __device__ __forceinline__ uint32_t cell_lut_bytes(uint32_t nx, uint32_t ny, uint32_t nz) { return cell_lut_entries(nx, ny, nz) * 4u; }
+// behind the tables in LDS, in the built-in skip kernels that decode lone-speckle codes (vk_march.hpp): 8 corners x (o_y, o_z, o_x, 0) f32, o_i = 1 - (corner bit i);
+// a code's bits 6..4 are the corner, so `code & 0x70` is the entry's byte offset
+constexpr uint32_t kSpeckleLutBytes = 128u;
 // Bounds-checked view of the cell array for the fast path (< 4 GiB): a raw buffer resource, so an
 // offset outside the array reads zeros instead of faulting (memory-safety net; never hit by a valid ray).
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));

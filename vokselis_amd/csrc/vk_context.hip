@@ -121,8 +121,8 @@ int vk_ctx_create(int device_ordinal, vk_ctx **out) {
     ctx->stream = ctx->own_stream;
     if ((e = hipEventCreate(&ctx->ev0)) != hipSuccess) return bail(e, "hipEventCreate");
     if ((e = hipEventCreate(&ctx->ev1)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipMalloc(&ctx->counters, 8 * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc(counters)");
-    if ((e = hipMemset(ctx->counters, 0, 8 * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMemset(counters)");
+    if ((e = hipMalloc(&ctx->counters, kCounters * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc(counters)");
+    if ((e = hipMemset(ctx->counters, 0, kCounters * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMemset(counters)");
     *out = ctx;
     return VK_OK;
 }
@@ -426,6 +426,16 @@ int vk_simt_census(vk_ctx *ctx, uint64_t out[4]) {
     return VK_OK;
 }
 
+int vk_speckle_census(vk_ctx *ctx, uint64_t out[2]) {
+    if (!ctx || !out) return fail(ctx, VK_ERR_INVALID, "vk_speckle_census: NULL argument");
+    unsigned long long h[2] = {0, 0};
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(h, ctx->counters + 8, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    out[0] = h[0]; out[1] = h[1];
+    return VK_OK;
+}
+
 int vk_debug_wave_trace(vk_ctx *ctx, int enable, uint64_t *out, size_t n_blocks) {
     if (!ctx) return VK_ERR_INVALID;
     ctx->want_trace = enable != 0;
@@ -455,6 +465,7 @@ int vk_debug_set_param(vk_ctx *ctx, const char *name, double value) {
     else if (n == "render_tile") ctx->render_tile = ((uint32_t)value & ~7u);
     else if (n == "pair_ring") ctx->pair_ring = (uint32_t)value;
     else if (n == "probe_ahead") ctx->probe_ahead = (uint32_t)value;
+    else if (n == "speckle_codes") ctx->speckle_codes = (uint32_t)value;        // census before / after: maps built from now on carry no lone-speckle codes (0) or carry them (1)
     else if (n == "pair_walk_min") ctx->pair_walk_min = (uint32_t)std::min(std::max(2.0, value), 1e6);
     else if (n == "order_rays") { ctx->order_rays = ctx->order_rays_batch = (uint32_t)std::min<double>(std::max<double>(value, 1), 8); ctx->batch_key.clear(); ctx->order_key.clear(); }
     else if (n == "naive_lds_pad") ctx->naive_lds_pad = (uint32_t)value;          // experiments: caps the cell kernels' waves per SIMD
@@ -466,7 +477,7 @@ int vk_debug_set_param(vk_ctx *ctx, const char *name, double value) {
 int vk_step_counts_reset(vk_ctx *ctx) {
     if (!ctx) return VK_ERR_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->counters, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters, 0, kCounters * sizeof(unsigned long long), ctx->stream));
     return VK_OK;
 }
 

@@ -28,6 +28,8 @@
 #include <utility>
 #include <vector>
 
+constexpr size_t kCounters = 10;  // vk_ctx::counters
+
 struct vk_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -73,7 +75,7 @@ struct vk_ctx {
     uint32_t width = 0, height = 0;
     int out_format = VK_OUT_RGBA32F;
     uint32_t *steps = nullptr;
-    unsigned long long *counters = nullptr;
+    unsigned long long *counters = nullptr;  // kCounters of them: 0-5 the march's steps and census, 7 the upload's empty cells, 8-9 the lone-speckle census
 
     // heaviest-first tile order (launch-order heuristic; see tile_order_update)
     std::vector<uint32_t> order, order_pos;
@@ -128,6 +130,7 @@ struct vk_ctx {
     uint32_t pair_ring = 0;      // compute twin: request buffers in the SHADE ring (4, 6; 42: 4 buffers, two revolutions per loop iteration; 0: by launch shape)
     uint32_t pair_walk_min = 4;  // compute twin: shortest run of empty records worth a walk (a walk restarts the request ring; docs/archive/tools/compute_mode.py)
     uint32_t probe_ahead = 2;    // skip kernels: request the next position's distance byte under the sample (0 never, 1 always, 2 single-frame launches)
+    uint32_t speckle_codes = 1;  // the built-in skip maps carry lone-speckle codes (vk_tf.hpp); 0 (debug, next map build): plain distances, every such cell is sampled
     uint32_t order_rays = 3;     // estimate rays per tile edge of the heaviest-first order (single-frame launches)
     uint32_t order_rays_batch = 1;  // ... of launches spanning >= 4 frames
     uint32_t order_never_inline = 0;  // debug / A-B: single-frame launches read the tile order from the device table as before round 6

@@ -50,11 +50,13 @@ void with_table_layout(const vk_ctx *ctx, bool skip, bool safe, F &&f) {
 
 // Dynamic LDS of a cell kernel (vk_march_kernel_body.hpp) -- the fast path of the cell layouts keeps its per-axis index tables there
 // (vk_march.hpp: load_cell_luts) -- and, for the variants without skipping, V.lut moved on to the byte-offset copy of the tables.
-template <int VOL, bool SKIP, bool SAFE>
+// SPECKLE: the kernel decodes lone-speckle codes (the built-in skip kernels of the u8 cell layouts, but for probe-ahead) and keeps the corners' table behind them.
+template <int VOL, bool SKIP, bool SAFE, bool SPECKLE = false>
 uint32_t cell_kernel_lds(const vk_ctx *ctx, VolumeDesc &V) {
     if (!SKIP && V.lut) V.lut += cell_lut_entries(V.nx, V.ny, V.nz);
     constexpr bool lut = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16) && !SAFE;
-    return (lut ? cell_lut_bytes(V.nx, V.ny, V.nz) : 0u) + ctx->naive_lds_pad;  // (pad: occupancy experiments, vk_debug_set_param)
+    constexpr bool corners = lut && SKIP && SPECKLE && (VOL == VOL_P8 || VOL == VOL_P16);
+    return (lut ? cell_lut_bytes(V.nx, V.ny, V.nz) : 0u) + (corners ? kSpeckleLutBytes : 0u) + ctx->naive_lds_pad;  // (pad: occupancy experiments, vk_debug_set_param)
 }
 
 }  // namespace vk

@@ -6,7 +6,7 @@ using namespace vk;
 
 template <int VOL, bool SKIP, bool SAFE, int WALK = WALK_LOOP, bool AHEAD = false>
 static void launch_naive(vk_ctx *ctx, const LaunchDesc &L, VolumeDesc V, uint32_t grid, bool count) {
-    const uint32_t lds = cell_kernel_lds<VOL, SKIP, SAFE>(ctx, V);
+    const uint32_t lds = cell_kernel_lds<VOL, SKIP, SAFE, !AHEAD>(ctx, V);
     with_out_count(ctx, count, [&](auto OUT, auto COUNT) {
         hipLaunchKernelGGL((raymarch_naive_kernel<VOL, SKIP, SAFE, WALK, AHEAD, OUT(), COUNT()>), dim3(grid), dim3(64), lds, ctx->stream, L, V);
     });

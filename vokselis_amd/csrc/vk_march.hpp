@@ -59,6 +59,9 @@ static_assert(sizeof(RayState) == 64, "RayState is one 64-byte record");
 struct Census {  // SIMT execution census + step counters (COUNT builds only)
     uint32_t n_iter = 0, n_samp = 0, w_outer = 0, w_inner = 0, w_sample = 0, n_look = 0, n_fb = 0;
     uint32_t skips = 0;  // trips that skipped (every build: drives the adaptive probing policy)
+    // the built-in skip kernels (COUNT builds): wave-level sample executions in which every sampling lane's alpha came out 0 (the upper bound on what
+    // the lone-speckle codes can take away), and lane-steps those codes proved transparent without a sample
+    uint32_t w_zero = 0, n_proven = 0;
     // per-trip log of the wave (COUNT builds, debug bit 6; docs/archive/tools/repack_census.py): entry = live lanes | samplers << 7 | samplers whose alpha is
     // not 0 << 14 | wave-level walk iterations << 21
     uint32_t *log = nullptr;
@@ -98,9 +101,11 @@ enum WalkKind : int { WALK_LOOP = 0, WALK_FMA = 2 };
 // Per ray the same operations in the same order on every variable.
 //
 // TF (the table kernels of vk_launch_tf.hip): the runtime transfer function replaces transfer_alpha and the palette (tf_lookup).
+// DECODES: false for the bounded loop compiled into the probe-ahead kernel (its launches never take it): that kernel keeps no corner table
+// (kSpeckleLutBytes) and reads a lone-speckle code as a cell to sample wherever it meets one.
 // LIT (vk_launch_lit.hip; needs TF): the table colour is shaded by the sample's gradient (vk_light.hpp: lit_gradient, lit_shade) before it is
 // composited; alpha, and with it every trip, walk and exit, is the table's.
-template <int VOL, bool SKIP, bool SAFE, bool COUNT, bool BOUNDED = false, int WALK = WALK_LOOP, bool AHEAD = false, bool TF = false, bool LIT = false>
+template <int VOL, bool SKIP, bool SAFE, bool COUNT, bool BOUNDED = false, int WALK = WALK_LOOP, bool AHEAD = false, bool TF = false, bool LIT = false, bool DECODES = true>
 __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const uint32_t budget, Census &cs,
                                       const uint32_t *lut = nullptr, const float walk_cap = __builtin_inff(), const float walk_cap_all = __builtin_inff(),
                                       const TfDesc *tfd = nullptr, const LightDesc *ld = nullptr, const LitRay *lr = nullptr) {
@@ -108,6 +113,11 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
     constexpr bool PACKED = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16);
     constexpr bool BRICK9 = (VOL == VOL_B9U8 || VOL == VOL_B9F16);
     static_assert(!AHEAD || (PACKED && SKIP && !SAFE && !BOUNDED), "probe-ahead: the skip kernels' fast path, unbounded");
+    constexpr bool CODED = SKIP && !TF && (VOL == VOL_P8 || VOL == VOL_P16);  // the maps this instantiation reads carry lone-speckle codes (see the trip)
+    // ... and it decodes them.  The probe-ahead trip does not: its lone waves pay for every instruction of a trip, and a sample costs them one fetch as a
+    // proven step would.  There a coded cell is what it was, a cell to sample: the byte read as a signed one makes that the same two compares as
+    // before (at its use: a conversion where the byte is requested would wait for it there, and undo the probe-ahead).
+    constexpr bool DECODE = CODED && !AHEAD && DECODES;
     float px = r.px, py = r.py, pz = r.pz, A = r.A, Gr = r.Gr, Gg = r.Gg, Gb = r.Gb;
     int nleft = -(int)r.left;  // minus the iterations left (counts up to 0: a walk's -k = floor(-r) comes out of one conversion)
     const float sx = r.sx, sy = r.sy, sz = r.sz;
@@ -127,6 +137,9 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
     // AHEAD: where the ray stands, carried from trip to trip: lerp weights, cell index, and the cell's distance byte (possibly still in flight)
     float a_fx = 0.0f, a_fy = 0.0f, a_fz = 0.0f;
     uint32_t a_idx = 0, a_d = 0;
+    // a cell's distance byte; where lone-speckle codes are decoded sign-extended (the load does it), so that a code (>= 128) is a negative word: the
+    // one compare a trip among plain cells pays for them
+    auto dist_at = [&](uint64_t i) -> uint32_t { return DECODE ? (uint32_t)(int32_t)(int8_t)V.dist[i] : (uint32_t)V.dist[i]; };
     auto locate = [&](float qx, float qy, float qz) {
         const float ux = fmaf(qx, fnx, -0.5f), uy = fmaf(qy, fny, -0.5f), uz = fmaf(qz, fnz, -0.5f);
         a_fx = __builtin_amdgcn_fractf(ux); a_fy = __builtin_amdgcn_fractf(uy); a_fz = __builtin_amdgcn_fractf(uz);
@@ -135,7 +148,7 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
         // one clamped entry beyond i = -1 and i = n - 1, which covers 1.5 cells; the host sets LF_PROBE_AHEAD only for dt_scale <= 1.25
         // (vk_render.hip), so the index is always a real cell's and the map is read inside its allocation.  (No branch around the request, and a
         // plain global load: an exec-masked region, or a bounds-checked buffer load, gives most of the gain back.)
-        a_d = V.dist[a_idx + doff];
+        a_d = dist_at(a_idx + doff);
     };
     if (AHEAD) locate(px, py, pz);
     while (nleft != 0 && A < 0.95f && (!BOUNDED || trip < budget)) {
@@ -158,7 +171,7 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
             if (SAFE) {
                 const int64_t off = safe_cell_offset(V, ix, iy, iz);
                 cptr = reinterpret_cast<const char *>(V.data) + off;
-                if (SKIP) d = V.dist[(uint64_t)(off >> V.sh_x) + doff];
+                if (SKIP) d = dist_at((uint64_t)(off >> V.sh_x) + doff);
             } else if (AHEAD) {
                 coff = (uint32_t)(a_idx << V.sh_x);
                 d = a_d;
@@ -166,7 +179,23 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
                 // cell index (SKIP) / cell byte offset (!SKIP) from the per-axis tables; entry i + 2 is voxel i
                 const uint32_t idx = lut[ix + 2] + luty[iy + 2] + lutz[iz + 2];
                 coff = SKIP ? (uint32_t)(idx << V.sh_x) : idx;
-                if (SKIP) d = V.dist[idx + doff];
+                if (SKIP) d = dist_at(idx + doff);
+            }
+            // Lone-speckle cells (built-in transfer, u8 cells; vk_tf.hpp: speckle_code, speckle_proven, with the proof): a distance byte >= 128 is no
+            // distance.  The cell is not empty -- one tap is above the threshold -- but the byte says how much weight the hot corner may get before a
+            // sample's alpha can leave +0.  A lane proven below it walks exactly this one step (the word 256: non-zero, so a walker, and its low byte,
+            // which is all the walk's length reads, is 0: no room on any axis, k = 1; the next position is probed afresh, in the same cell or not).
+            // A lane not proven samples the cell, as every lane in such a cell did before.  A wave among plain cells pays one compare and the branch
+            // over the region.  Before `samplers`: a trip whose only non-empty cells were proven transparent walks under walk_cap_all.
+            if constexpr (DECODE) {
+                if ((int32_t)d < 0) {
+                    asm volatile("" : "+v"(d));  // (keeps this an exec-masked region, skipped by the wave when no lane is in it: if-converted, every trip pays the decode)
+                    if constexpr (SAFE) d = speckle_proven(d, fx, fy, fz) ? 256u : 0u;
+                    else {  // the corner's o_i from the table behind the index tables (vk_common.hpp: kSpeckleLutBytes): one LDS read for the bit work
+                        const float4 o = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(lut + cell_lut_entries(V.nx, V.ny, V.nz)) + (d & 0x70u));
+                        d = speckle_below(d, o.z, o.x, o.y, fx, fy, fz) ? 256u : 0u;  // (stored y, z, x: the pair the packed subtraction takes comes first)
+                    }
+                }
             }
             // A trip in which some lanes sample is paced by them: whatever a walker covers beyond a few steps it covers while
             // the samplers -- and every walker with a shorter walk -- wait for the longest walk of the wave (the walk loop ran
@@ -174,16 +203,18 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
             // probes again next trip, which the wave makes anyway.  Any stop is exact: what is not skipped now is probed again.
             // (One compare serves the branch and the wave-level test; the cap is a scalar.)
             // (one compare serves the branch and the wave-level test; the cap is chosen on the scalar unit, as bits)
-            const unsigned long long samplers = SKIP ? __ballot(d == 0) : 0ull;
+            const bool walker = SKIP && (DECODE ? (int32_t)d > 0 : (CODED ? (int8_t)d > 0 : d != 0));  // (a code left undecoded is negative: a cell to sample)
+            const unsigned long long samplers = SKIP ? __ballot(!walker) : 0ull;
             uint32_t cap_now;  // (s_cmp + s_cselect: written as a ternary the compiler builds two branches and five moves around it; C2 batches -0.6 %)
             asm("s_cmp_lg_u64 %1, 0\n\ts_cselect_b32 %0, %2, %3" : "=s"(cap_now) : "s"(samplers), "s"(__builtin_amdgcn_readfirstlane(__float_as_uint(walk_cap))), "s"(__builtin_amdgcn_readfirstlane(__float_as_uint(walk_cap_all))) : "scc");
-            if (SKIP && d != 0) {
-                if (BOUNDED) cs.skips++;
+            if (walker) {
+                if (BOUNDED) cs.skips++;  // (a proven speckle step votes with the skips: it was not sampled)
                 // Samples j = 0 .. k - 1 are skipped, k = ceil(r) (j < r keeps a sample inside the empty range; the current sample, j = 0,
                 // sits in an empty cell: k >= 1), at most the trip's cap and at most the iterations the loop has left -- every skipped
                 // iteration is one the reference makes (it passes `t < t1` on the reference's own t: that is what `left` counts).
                 // The walk advances the reference's position, p += s, k times: the same f32 additions in the same order.
-                float rmin = sb.steps(fx, fy, fz, (float)d);
+                float rmin = sb.steps(fx, fy, fz, CODED ? (float)(d & 0xffu) : (float)d);  // (v_cvt_f32_ubyte0 either way)
+                if (COUNT && CODED && d == 256u) { n_samp++; cs.n_proven++; }  // a step in a non-empty cell, as before: S_sampled keeps its meaning
                 if constexpr (WALK == WALK_FMA) {
                     // one real addition, the other k - 1 as one fma with that addition's rounded increment (tolerance: see WalkKind)
                     const float x_1 = px + sx, y_1 = py + sy, z_1 = pz + sz;
@@ -261,7 +292,7 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
             // the executions that serve one or two lanes -- the palette and the compositing are left out: 17 of the 45
             // instructions, no bit changes.
             if (__ballot(a != 0.0f) == 0ull) {
-                if (COUNT) { n_iter++; n_samp++; if (wave_leader()) w_sample++; }
+                if (COUNT) { n_iter++; n_samp++; if (wave_leader()) { w_sample++; if constexpr (!TF) cs.w_zero++; } }
                 if (!AHEAD) {
                     px = px + sx; py = py + sy; pz = pz + sz;  // :118
                     nleft += 1;

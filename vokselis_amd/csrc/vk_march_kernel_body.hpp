@@ -40,6 +40,8 @@
     extern __shared__ uint32_t cell_lut[];
     if (USE_LUT) {  // all 64 lanes are still here
         load_cell_luts(V, cell_lut, lane);
+        if constexpr (SKIP && !TF && !MIP && !AHEAD && (VOL == VOL_P8 || VOL == VOL_P16))  // the corners of the lone-speckle codes (kSpeckleLutBytes; march() decodes with them)
+            if (lane < 8u) reinterpret_cast<float4 *>(cell_lut + cell_lut_entries(V.nx, V.ny, V.nz))[lane] = make_float4((lane & 2u) ? 0.0f : 1.0f, (lane & 4u) ? 0.0f : 1.0f, (lane & 1u) ? 0.0f : 1.0f, 0.0f);
         __syncthreads();
     }
     if (!pm.valid) return;
@@ -100,7 +102,7 @@
                     cs.skips = 0;
                     bool alive;
                     if constexpr (MIP) alive = march_mip<VOL, true, SAFE, COUNT, true>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd->k1, tfd->k2, tfd->umax);
-                    else alive = march<VOL, true, SAFE, COUNT, true, WALK, false, TF, LIT>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd, ldp, &lr);
+                    else alive = march<VOL, true, SAFE, COUNT, true, WALK, false, TF, LIT, !AHEAD>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd, ldp, &lr);
                     const unsigned long long live = __ballot(alive);
                     if (live == 0ull) break;
                     if (__popcll(__ballot(alive && cs.skips != 0u)) * 8 >= __popcll(live)) { stretch = stretch0; continue; }
@@ -152,6 +154,10 @@
             atomicAdd(&L.counters[3], (unsigned long long)cs.w_inner);
             atomicAdd(&L.counters[4], (unsigned long long)cs.w_sample);
             atomicAdd(&L.counters[5], (unsigned long long)cs.n_look);
+            if constexpr (SKIP && !TF && !MIP) {  // the lone-speckle census of the built-in skip kernels (vk_speckle_census)
+                atomicAdd(&L.counters[8], (unsigned long long)cs.w_zero);
+                atomicAdd(&L.counters[9], (unsigned long long)cs.n_proven);
+            }
         }
         if (L.trace && !trip_log) {  // stamps leave only through this debug buffer
             unsigned long long t_end = __builtin_amdgcn_s_memrealtime();

@@ -95,6 +95,56 @@ VK_TF_HD bool builtin_cell_empty(const float t[8], bool f16) {
     return empty;
 }
 
+// ---- lone-speckle cells of the built-in transfer (u8 cells: P8 and P16) ----
+// A cell with exactly one tap above the threshold (v > 25 at corner dx | dy << 1 | dz << 2, every other tap <= m <= 25) is not empty,
+// yet most samples inside it filter to a value that transfer_alpha<1> clamps to +0.  Its distance byte says how close a sample may
+// come to the hot corner for that to be certain:
+//   speckle_code:    0x80 | corner << 4 | q,  q = floor(16 (25 - m) / (v - m)) in 1 .. 15  (v > 25 >= m: the quotient is below 16);
+//                    0 for any other cell -- no tap or several taps above 25, q = 0, a tap that is no u8 value.  For u8 taps the f32
+//                    division is exact: numerator and denominator are integers <= 400, and a quotient that is no integer is at
+//                    least 1/255 away from one.  f16 cells are never coded, so no tap here is NaN or infinite.  A border cell's
+//                    clamped taps repeat a hot voxel: two or more hot taps, not coded.
+//   speckle_proven:  w < q / 16, w = (wx wy) wz the trilinear weight of the hot corner, w_i = f_i toward the corner's upper side and
+//                    1 - f_i toward its lower side -- written |f_i - o_i| with o_i = 1 - (corner bit i), which is the same f32 value
+//                    (a subtraction, its sign dropped) and needs no select.
+// Proof that a proven sample's alpha is +0, with the margin.  In exact arithmetic the filter is sum_i w_i t_i over the eight corners,
+// the weights >= 0 with sum 1, so it is at most w v + (1 - w) m = m + w (v - m).
+//   (a) the decoder's w.  1 - f rounds once (<= 2^-25 absolute; f, and with it every w_i, is in [0, 1]), each product once (2^-24
+//       relative): the exact weight is below the computed one plus 2^-22.  q / 16 is exact.  So computed w < q / 16 gives an exact
+//       filter value below m + (q / 16)(v - m) + 255 * 2^-22 <= 25 + 6.1e-5, by the definition of q.
+//   (b) the f32 chain, for both layouts: x-lerps fma(fx, t1 - t0, t0) on exact differences (P8: of integers; P16: the stored f16
+//       delta, exact for u8 data -- xlerp_cell), then c0 = fma(fy, c10 - c00, c00), c1 likewise, r = fma(fz, c1 - c0, c0).  Every
+//       intermediate lies between its operands (the argument at the top of this file), so in [0, 255], where one rounding is at most
+//       2^-17.  An x-lerp is off by <= 2^-17; each later level adds the rounding of its difference and its own: <= 3 * 2^-17 after y,
+//       <= 5 * 2^-17 = 3.9e-5 after z.
+//   (c) so r < 25 + 1.1e-4.  transfer_alpha<1> computes s = fma(min(r, 229.5), k1, k2) with k1 = f32(1 / 280.5), k2 = f32(-1 / 11):
+//       s <= 0 exactly when r k1 <= -k2 up to one rounding, i.e. for every r <= 25.4 (25.4 k1 = 0.09055 against 0.09091: a relative gap
+//       of 4e-3, thousands of roundings wide); fmaxf(s, 0) is then +0 and alpha = (0 * 0) * 3 = +0.  The margin between what (a)
+//       and (b) allow, 25.0001, and what (c) needs, 25.4, is why q carries no margin of its own.
+// A NaN weight (the position of a ray that left the finite range) compares false: not proven, the sample is evaluated as before.
+VK_TF_HD uint32_t speckle_code(const float t[8]) {
+    int hot = 0, n_hot = 0;
+    float m = 0.0f;
+    for (int b = 0; b < 8; b++) {
+        if (!(t[b] >= 0.0f && t[b] <= 255.0f)) return 0;
+        if (t[b] > 25.0f) { hot = b; n_hot++; }
+        else m = fmaxf(m, t[b]);
+    }
+    if (n_hot != 1) return 0;
+    const float q = floorf(16.0f * (25.0f - m) / (t[hot] - m));
+    if (!(q >= 1.0f)) return 0;
+    return 0x80u | ((uint32_t)hot << 4) | (uint32_t)q;
+}
+
+// the decoder with the corner's o_i in hand (the march keeps the eight corners' in LDS, kSpeckleLutBytes: one read instead of the bit work)
+VK_TF_HD bool speckle_below(uint32_t code, float ox, float oy, float oz, float fx, float fy, float fz) {
+    return (fabsf(fx - ox) * fabsf(fy - oy)) * fabsf(fz - oz) < (float)(code & 15u) * 0.0625f;
+}
+VK_TF_HD bool speckle_proven(uint32_t code, float fx, float fy, float fz) {
+    const uint32_t lower = ~code;  // bit 4 + i set: the hot corner is on the lower side of axis i, its weight there 1 - f
+    return speckle_below(code, (float)((lower >> 4) & 1u), (float)((lower >> 5) & 1u), (float)((lower >> 6) & 1u), fx, fy, fz);
+}
+
 // ---- maximum-intensity projection (vk_set_projection(VK_PROJ_MAX)) ----
 // One step of the running maximum in table coordinates: U' = fmaxf(U, tf_u(x)) with the rule that a U comparing equal to zero is +0.
 // Written as a select: with 0 <= U <= umax (U starts at +0), u = fma(x, k1, k2) replaces U only when u > U, which is never the case

@@ -82,14 +82,15 @@ static int commit_volume(vk_ctx *ctx, VolBuild &nb) {
 }
 
 // ---- skip maps of the cell layouts -----------------------------------------------------------------
-// scratch of a map build: occupancy seed (0: the cell can contribute, 255: empty) + two pass buffers, one byte per cell each
+// scratch of a map build: occupancy seed (0: the cell can contribute, 255: empty) + two pass buffers + the lone-speckle codes
+// (vk_tf.hpp: speckle_code; 0: none), one byte per cell each
 struct CellScratch {
-    uint8_t *occ = nullptr, *tx = nullptr, *txy = nullptr;
-    ~CellScratch() { (void)hipFree(occ); (void)hipFree(tx); (void)hipFree(txy); }
+    uint8_t *occ = nullptr, *tx = nullptr, *txy = nullptr, *code = nullptr;
+    ~CellScratch() { (void)hipFree(occ); (void)hipFree(tx); (void)hipFree(txy); (void)hipFree(code); }
 };
 
 static int alloc_scratch(vk_ctx *ctx, CellScratch &sc, uint64_t n_cells) {
-    for (uint8_t **p : {&sc.occ, &sc.tx, &sc.txy}) {
+    for (uint8_t **p : {&sc.occ, &sc.tx, &sc.txy, &sc.code}) {
         hipError_t e = hipMalloc((void **)p, n_cells);
         if (e != hipSuccess) { *p = nullptr; return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("re-layout scratch allocation failed: ") + hipGetErrorString(e)); }
     }
@@ -100,7 +101,7 @@ static int alloc_scratch(vk_ctx *ctx, CellScratch &sc, uint64_t n_cells) {
 // census counter (ctx->counters[7]) pack_cells_kernel left.  prefix == nullptr: the built-in threshold.
 // mip (VK_PROJ_MAX): the predicate of the maximum projection over the table's window (mip_cell_empty; its alphas, and with them prefix, are
 // not read), n == 0: over the implicit grey ramp's, two entries on [0, 1].
-static int launch_cell_occ(vk_ctx *ctx, int kind, const void *cells, uint8_t *occ, uint64_t n_cells, uint32_t blocks, const uint32_t *prefix,
+static int launch_cell_occ(vk_ctx *ctx, int kind, const void *cells, uint8_t *occ, uint8_t *code, uint64_t n_cells, uint32_t blocks, const uint32_t *prefix,
                            uint32_t n, float lo, float hi, bool mip) {
     float k1 = 0.0f, k2 = 0.0f;
     if (mip && n == 0) { n = 2; lo = 0.0f; hi = 1.0f; }
@@ -108,11 +109,11 @@ static int launch_cell_occ(vk_ctx *ctx, int kind, const void *cells, uint8_t *oc
     if (prefix || mip) tf_constants(n, lo, hi, kind != VOL_PF16, k1, k2);
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters + 7, 0, sizeof(unsigned long long), ctx->stream));
     if (kind == VOL_PF16)
-        hipLaunchKernelGGL(cell_occ_kernel<VOL_PF16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, n_cells, prefix, (int)n, k1, k2, mip ? 1 : 0, ctx->counters + 7);
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_PF16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, code, n_cells, prefix, (int)n, k1, k2, mip ? 1 : 0, ctx->counters + 7);
     else if (kind == VOL_P16)
-        hipLaunchKernelGGL(cell_occ_kernel<VOL_P16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, n_cells, prefix, (int)n, k1, k2, mip ? 1 : 0, ctx->counters + 7);
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_P16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, code, n_cells, prefix, (int)n, k1, k2, mip ? 1 : 0, ctx->counters + 7);
     else
-        hipLaunchKernelGGL(cell_occ_kernel<VOL_P8>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, n_cells, prefix, (int)n, k1, k2, mip ? 1 : 0, ctx->counters + 7);
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_P8>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, code, n_cells, prefix, (int)n, k1, k2, mip ? 1 : 0, ctx->counters + 7);
     return VK_OK;  // (launch errors: read_census)
 }
 
@@ -130,8 +131,10 @@ static int read_census(vk_ctx *ctx, uint64_t n_cells, double *empty_fraction) {
 
 // Distance maps from the seed in sc.occ.  Eight one-sided maps (one per ray octant) when skipping will be on by default
 // or may well be forced on (>= 30 % empty cells) and they stay <= 2 GiB; otherwise one isotropic map serves every octant.
+// coded: the seed is the built-in transfer's and sc.code holds its cells' lone-speckle codes, which the last pass of every map puts in
+// place of their 0; maps under a table or the maximum projection carry none.
 // On success *dist (the caller's from then on), *oct_stride and *dist_bytes are set; on failure nothing is left allocated.
-static int build_skip_maps(vk_ctx *ctx, CellScratch &sc, uint32_t nbx, uint32_t nby, uint32_t nbz, uint64_t n_cells, double empty_fraction,
+static int build_skip_maps(vk_ctx *ctx, CellScratch &sc, bool coded, uint32_t nbx, uint32_t nby, uint32_t nbz, uint64_t n_cells, double empty_fraction,
                            uint8_t **dist, uint32_t *oct_stride, uint64_t *dist_bytes) {
     const uint32_t blocks = (uint32_t)((n_cells + 255) / 256);
     const bool octants = empty_fraction >= 0.30 && n_cells <= (1ull << 28);  // (the default policy skips from 45 %)
@@ -140,7 +143,8 @@ static int build_skip_maps(vk_ctx *ctx, CellScratch &sc, uint32_t nbx, uint32_t 
     hipError_t e = hipMalloc((void **)&d, bytes);
     if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("distance map allocation failed: ") + hipGetErrorString(e));
     auto pass = [&](const uint8_t *in, uint8_t *out, int axis, int dir, int last) {
-        hipLaunchKernelGGL(dist_pass_kernel, dim3(blocks), dim3(256), 0, ctx->stream, in, out, nbx, nby, nbz, axis, dir, last);
+        hipLaunchKernelGGL(dist_pass_kernel, dim3(blocks), dim3(256), 0, ctx->stream, in, out, nbx, nby, nbz, axis, dir, last, (int)kDistRadius,
+                           last && coded ? (const uint8_t *)sc.code : (const uint8_t *)nullptr);
     };
     if (octants) {
         for (int ux = 0; ux < 2; ux++) {
@@ -178,13 +182,14 @@ int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float l
     CellScratch sc;
     int rc = alloc_scratch(ctx, sc, n_cells);
     if (rc) return rc;
-    if ((rc = launch_cell_occ(ctx, kind, ctx->vol, sc.occ, n_cells, (uint32_t)((n_cells + 255) / 256), d_prefix, n, lo, hi, projection == VK_PROJ_MAX))) return rc;
+    const bool builtin = !d_prefix && projection != VK_PROJ_MAX && ctx->speckle_codes;  // clearing the table brings the built-in seed back, and its codes with it
+    if ((rc = launch_cell_occ(ctx, kind, ctx->vol, sc.occ, sc.code, n_cells, (uint32_t)((n_cells + 255) / 256), d_prefix, n, lo, hi, projection == VK_PROJ_MAX))) return rc;
     double ef = 0.0;
     if ((rc = read_census(ctx, n_cells, &ef))) return rc;
     uint8_t *dist = nullptr;
     uint32_t stride = 0;
     uint64_t dist_bytes = 0;
-    if ((rc = build_skip_maps(ctx, sc, ctx->nbx, ctx->nby, ctx->nbz, n_cells, ef, &dist, &stride, &dist_bytes))) return rc;
+    if ((rc = build_skip_maps(ctx, sc, builtin, ctx->nbx, ctx->nby, ctx->nbz, n_cells, ef, &dist, &stride, &dist_bytes))) return rc;
     (void)hipFree(ctx->dist);
     ctx->dist = dist;
     ctx->vdesc.dist_oct_stride = stride;
@@ -379,19 +384,20 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
     nb.vol_kind = kind;
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters + 7, 0, sizeof(unsigned long long), ctx->stream));
     if (kind == VOL_PF16)
-        hipLaunchKernelGGL(pack_cells_kernel<VOL_PF16>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
+        hipLaunchKernelGGL(pack_cells_kernel<VOL_PF16>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, sc.code, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
     else if (kind == VOL_P16)
-        hipLaunchKernelGGL(pack_cells_kernel<VOL_P16>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
+        hipLaunchKernelGGL(pack_cells_kernel<VOL_P16>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, sc.code, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
     else
-        hipLaunchKernelGGL(pack_cells_kernel<VOL_P8>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
+        hipLaunchKernelGGL(pack_cells_kernel<VOL_P8>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, sc.code, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
     // under a runtime transfer function the seed and the census follow its table (vk_set_transfer_function), under the maximum projection its predicate (vk_set_projection)
-    if ((ctx->d_tf || ctx->proj == VK_PROJ_MAX) &&
-        (rc = launch_cell_occ(ctx, kind, nb.vol, sc.occ, n_cells, pack_blocks, ctx->d_tf ? reinterpret_cast<const uint32_t *>(ctx->d_tf + 4 * ctx->tf_n) : nullptr,
+    const bool builtin = !ctx->d_tf && ctx->proj != VK_PROJ_MAX;
+    if (!builtin &&
+        (rc = launch_cell_occ(ctx, kind, nb.vol, sc.occ, nullptr, n_cells, pack_blocks, ctx->d_tf ? reinterpret_cast<const uint32_t *>(ctx->d_tf + 4 * ctx->tf_n) : nullptr,
                               ctx->d_tf ? ctx->tf_n : 0u, ctx->tf_lo, ctx->tf_hi, ctx->proj == VK_PROJ_MAX)))
         return rc;
     if ((rc = read_census(ctx, n_cells, &nb.empty_fraction))) return rc;
     uint64_t dist_bytes = 0;
-    if ((rc = build_skip_maps(ctx, sc, nb.nbx, nb.nby, nb.nbz, n_cells, nb.empty_fraction, &nb.dist, &nb.vdesc.dist_oct_stride, &dist_bytes))) return rc;
+    if ((rc = build_skip_maps(ctx, sc, builtin && ctx->speckle_codes, nb.nbx, nb.nby, nb.nbz, n_cells, nb.empty_fraction, &nb.dist, &nb.vdesc.dist_oct_stride, &dist_bytes))) return rc;
     nb.vol_bytes = n_cells * cell_bytes + dist_bytes;
     {
         // per-axis cell-index tables of the fast path, two copies: cell units, byte offsets

@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void embed_pair_dist_kernel(uint4 *__restrict_
 // brick B = (i >> 2) + 1 and in-brick w = i & 3 per axis, i = low-corner voxel index in [-1, n-1].
 template <int VOL>
 __global__ __launch_bounds__(256) void pack_cells_kernel(const void *__restrict__ src, void *__restrict__ dst,
-                                                          uint8_t *__restrict__ occ, uint32_t nx, uint32_t ny,
+                                                          uint8_t *__restrict__ occ, uint8_t *__restrict__ code, uint32_t nx, uint32_t ny,
                                                           uint32_t nz, uint32_t nbx, uint32_t nby, uint64_t n_cells,
                                                           unsigned long long *__restrict__ n_empty) {
     uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -113,6 +113,8 @@ __global__ __launch_bounds__(256) void pack_cells_kernel(const void *__restrict_
     for (int b = 0; b < 8; b++) tv[b] = (VOL == VOL_PF16) ? h2f(t[b]) : (float)t[b];
     const bool nonempty = !builtin_cell_empty(tv, VOL == VOL_PF16);
     occ[id] = nonempty ? 0 : 255;
+    // the lone-speckle code of a u8 cell (vk_tf.hpp: speckle_code; 0: none), which replaces the cell's distance 0 in the finished maps
+    code[id] = (VOL == VOL_PF16) ? (uint8_t)0 : (uint8_t)speckle_code(tv);
     {   // census of exactly-transparent cells (one atomic per wave): decides whether skipping can pay
         const unsigned long long m = __ballot(!nonempty);
         if ((threadIdx.x & 63u) == 0 && m) atomicAdd(n_empty, (unsigned long long)__popcll(m));
@@ -138,9 +140,10 @@ __global__ __launch_bounds__(256) void pack_cells_kernel(const void *__restrict_
 // (P8: u8 taps; P16: (tap, delta) pairs, tap + delta exact; PF16: f16 taps), tested by the runtime transfer function's emptiness
 // predicate (vk_tf.hpp; prefix: the table's prefix counts of non-zero alphas), or with prefix == nullptr by the built-in threshold
 // of pack_cells_kernel -- whose occ and census it then reproduces byte for byte.  mip != 0 (vk_set_projection(VK_PROJ_MAX)): the predicate
-// of the maximum projection over the window behind k1, k2 and its n entries (vk_tf.hpp: mip_cell_empty).
+// of the maximum projection over the window behind k1, k2 and its n entries (vk_tf.hpp: mip_cell_empty).  code (nullptr: not wanted): the
+// cells' lone-speckle codes, as pack_cells_kernel writes them; they exist under the built-in transfer only.
 template <int VOL>
-__global__ __launch_bounds__(256) void cell_occ_kernel(const void *__restrict__ cells, uint8_t *__restrict__ occ, uint64_t n_cells,
+__global__ __launch_bounds__(256) void cell_occ_kernel(const void *__restrict__ cells, uint8_t *__restrict__ occ, uint8_t *__restrict__ code, uint64_t n_cells,
                                                        const uint32_t *__restrict__ prefix, int n, float k1, float k2, int mip,
                                                        unsigned long long *__restrict__ n_empty) {
     const uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -161,6 +164,7 @@ __global__ __launch_bounds__(256) void cell_occ_kernel(const void *__restrict__ 
     }
     const bool nonempty = mip ? !mip_cell_empty(t, k1, k2, (float)(n - 1)) : prefix ? !tf_cell_empty(t, prefix, n, k1, k2) : !builtin_cell_empty(t, VOL == VOL_PF16);  // (pack_cells_kernel's predicate)
     occ[id] = nonempty ? 0 : 255;
+    if (code) code[id] = (VOL == VOL_PF16 || mip || prefix) ? (uint8_t)0 : (uint8_t)speckle_code(t);
     const unsigned long long m = __ballot(!nonempty);
     if ((threadIdx.x & 63u) == 0 && m) atomicAdd(n_empty, (unsigned long long)__popcll(m));
 }
@@ -220,13 +224,16 @@ __global__ __launch_bounds__(256) void pack_quads_kernel(const void *__restrict_
 // out(c) = min_j max(in(c + j*axis), |j|), |j| <= kDistRadius, j restricted to j >= 0 (dir > 0),
 // j <= 0 (dir < 0) or unrestricted (dir == 0).  Outside the grid counts as empty.
 // Cells are addressed in their bricked storage order.
+// code (last pass of a cell map only; nullptr: none): a cell with a lone-speckle code is non-empty, seeded 0 like any other, and so still 0
+// here; its code (>= 128, above every distance) takes the place of that 0.  No other byte of the map changes.
 __device__ __forceinline__ uint64_t cell_index(uint32_t x, uint32_t y, uint32_t z, uint32_t nbx, uint32_t nby) {
     uint64_t brick = ((uint64_t)(z >> 2) * nby + (y >> 2)) * nbx + (x >> 2);
     return brick * 64 + (((z & 3u) << 4) | ((y & 3u) << 2) | (x & 3u));
 }
 
 __global__ __launch_bounds__(256) void dist_pass_kernel(const uint8_t *__restrict__ in, uint8_t *__restrict__ out,
-                                                        uint32_t nbx, uint32_t nby, uint32_t nbz, int axis, int dir, int last, int radius = kDistRadius) {
+                                                        uint32_t nbx, uint32_t nby, uint32_t nbz, int axis, int dir, int last, int radius = kDistRadius,
+                                                        const uint8_t *__restrict__ code = nullptr) {
     uint64_t id = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint64_t n = (uint64_t)nbx * nby * nbz * 64;
     if (id >= n) return;
@@ -249,6 +256,7 @@ __global__ __launch_bounds__(256) void dist_pass_kernel(const uint8_t *__restric
         best = min(best, max(v, aj));
     }
     if (last) best = min(best, radius + 1);
+    if (last && code && code[id]) best = code[id];
     out[id] = (uint8_t)best;
 }
 
