@@ -347,7 +347,9 @@ int vk_untile(vk_ctx *ctx, const void *gathered, uint32_t tile_size, uint32_t nr
 int vk_render_batch(vk_ctx *ctx, int mode, uint32_t n_frames, const void *cameras, uint32_t tile_size, uint32_t rank,
                     uint32_t nranks, float dt_scale, uint32_t flags, void *out, int compact, uint32_t slot_capacity,
                     uint32_t *batch_id, uint32_t *n_active_slots);
-/* Root side of a batch: gathered [nranks][n_slots][frame][ts][ts] -> out_frames [n_frames][height][width]. */
+/* Root side of a batch: gathered [nranks][n_slots][frame][ts][ts] -> out_frames [n_frames][height][width].
+ * A batch in which no frame has an active tile (*n_active_slots == 0) still has every frame cleared by this call, and `gathered` is
+ * still checked: NULL is VK_ERR_INVALID even though nothing is read through it -- pass any device pointer with n_slots = 0. */
 int vk_untile_batch(vk_ctx *ctx, uint32_t batch_id, const void *gathered, uint32_t n_slots, void *out_frames);
 /* The same when out_frames still holds, untouched, what un-tiling `prev_batch_id` (one of the last 4 batches, same frame count
  * and shape) wrote there -- a driver that alternates two frame buffers passes the batch before last: tiles that were inactive
