@@ -219,6 +219,54 @@ enum vk_projection { VK_PROJ_COMPOSITE = 0, VK_PROJ_MAX = 1 };
 int vk_set_projection(vk_ctx *ctx, int projection);
 int vk_get_projection(vk_ctx *ctx, int *projection);
 
+/* First-hit isosurface rendering of VK_MODE_NAIVE_TRILINEAR: an opaque surface where the filtered volume
+ * first reaches a threshold, the crossing refined by bisection, shaded from the gradient.  While an isosurface is set,
+ * NAIVE_TRILINEAR renders are isosurface renders: the transfer table and the projection are ignored (they stay stored --
+ * vk_get_projection still reports the stored projection -- and are in force again after vk_set_isosurface(ctx, NULL)); lighting
+ * (vk_set_lighting) is honoured, with or without a table.  COMPUTE_NEAREST and PROCEDURAL ignore it.
+ * iso_k is the threshold on the kernel's scale, rounded once to f32: R8: iso * 255.0f; R16F: iso.  For a pixel whose ray hits the
+ * box, ray, box, t0 = max(t0, 0), dt, p = eye + t0 dir and s = dir * dt are as without an isosurface, and
+ *     hit = false; j = 0
+ *     for (t = t0; t < t1; t = t + dt) {           the reference's loop
+ *         x = trilinear(V, p)                      the filter of every other render, bit for bit
+ *         if (x >= iso_k) { hit = true; break; }   a NaN sample is no hit; the break comes before p is advanced
+ *         p = p + s;  j = j + 1
+ *     }
+ *     if (!hit) out = (0, 0, 0, 1)                 as a miss
+ *     else {
+ *         a = 0                                    how far back towards the eye the surface lies, in steps: a dyadic in [0, 1)
+ *         if (j >= 1)                              a hit in the ray's first iteration is not refined (the cut face of the box)
+ *             for (i = 1; i <= refine; i++) {
+ *                 m = a + 2^-i
+ *                 q = (fma(-m, s.x, p.x), fma(-m, s.y, p.y), fma(-m, s.z, p.z))
+ *                 if (trilinear(V, q) >= iso_k) a = m
+ *             }
+ *         q = fma(-a, s, p) per component
+ *         g = the gradient of the sample at q, as under vk_set_lighting
+ *         c = rgb;  with lighting set: c = c (ambient + diffuse diff) + specular spec   (two-sided; no gradient: diff = 1, spec = 0)
+ *         out = (srgb(c.r), srgb(c.g), srgb(c.b), 1)
+ *     }
+ * The texel indices of a refinement sample are clamped to the edge like any sample's.  The per-pixel step count (VK_RENDER_COUNT) is
+ * the number of loop iterations executed, the hitting one included; S_sampled counts the iterations that fetched taps; the
+ * refinement and shading samples count in neither.  The skip maps and vk_volume_empty_fraction follow the isosurface: a cell is
+ * empty iff its 8 taps are finite and its largest tap lies below iso_k.
+ * The call drains every frame slot (as vk_ctx_sync), stores the value and rebuilds the skip maps of the current volume under the
+ * predicate now in force: the isosurface's when one is set, otherwise that of the (projection, table) pair.  The order of
+ * vk_set_isosurface, vk_set_projection and vk_set_transfer_function does not matter.  iso == NULL turns the isosurface off.
+ * VK_ERR_INVALID (the previous state stays in force): a non-finite iso, a colour that is not finite or beyond +-VK_TF_MAX_COLOUR,
+ * refine > VK_ISO_MAX_REFINE, or a call between vk_frame_begin and vk_frame_end.  The state stays in force across vk_volume_upload /
+ * _upload_device / vk_volume_generate.  Layouts: LINEAR, PACKED, PACKED_PAIRS; NAIVE renders of BRICKED / QUADS / STAGED volumes,
+ * and VK_RENDER_FAST_WALK, are VK_ERR_UNSUPPORTED while an isosurface is set.
+ * vk_get_isosurface: *enabled (may be NULL) says whether one is set; *out (may be NULL) receives it when one is. */
+#define VK_ISO_MAX_REFINE 16
+typedef struct vk_isosurface {
+    float iso;       /* threshold in sample values, the units of vk_set_transfer_function's lo / hi (R8: the normalised value; R16F: the value) */
+    float rgb[3];    /* linear surface colour, not premultiplied; finite, |c| <= VK_TF_MAX_COLOUR */
+    uint32_t refine; /* bisection steps R at the hit, 0 .. VK_ISO_MAX_REFINE */
+} vk_isosurface;     /* 20 bytes */
+int vk_set_isosurface(vk_ctx *ctx, const vk_isosurface *iso);
+int vk_get_isosurface(vk_ctx *ctx, vk_isosurface *out, int *enabled);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

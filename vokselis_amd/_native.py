@@ -25,6 +25,7 @@ MAX_FRAMES_IN_FLIGHT = 4
 GEN_FOG, GEN_BONSAI_STANDIN, GEN_FOG_DENSE_CORE = 0, 1, 2
 TF_MAX_ENTRIES = 256
 PROJ_COMPOSITE, PROJ_MAX = 0, 1
+ISO_MAX_REFINE = 16
 
 
 class VkLighting(C.Structure):
@@ -34,6 +35,14 @@ class VkLighting(C.Structure):
 
 
 assert C.sizeof(VkLighting) == 32
+
+
+class VkIsosurface(C.Structure):
+    """vk_isosurface (20 bytes): the threshold in sample values, the linear surface colour, the bisection steps at the hit."""
+    _fields_ = [("iso", C.c_float), ("rgb", C.c_float * 3), ("refine", C.c_uint32)]
+
+
+assert C.sizeof(VkIsosurface) == 20
 
 # every symbol include/vokselis_hip.h declares: name -> (restype, argtypes)
 _u32, _i32, _f32, _vp, _sz = C.c_uint32, C.c_int32, C.c_float, C.c_void_p, C.c_size_t
@@ -54,6 +63,8 @@ SYMBOLS = {
     "vk_set_lighting": (C.c_int, [_vp, _vp]),  # const vk_lighting * (VkLighting below), NULL: off
     "vk_set_projection": (C.c_int, [_vp, C.c_int]),
     "vk_get_projection": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "vk_set_isosurface": (C.c_int, [_vp, _vp]),  # const vk_isosurface * (VkIsosurface above), NULL: off
+    "vk_get_isosurface": (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),
     "vk_set_uniform": (C.c_int, [_vp, _vp]),
     "vk_set_camera": (C.c_int, [_vp, _vp]),

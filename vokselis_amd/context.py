@@ -229,6 +229,34 @@ class Context:
         N.check(self._h, N.lib().vk_get_projection(self._h, C.byref(v)))
         return "max" if v.value == N.PROJ_MAX else None
 
+    def set_isosurface(self, iso, colour=(1.0, 1.0, 1.0), refine=4):
+        """First-hit isosurface rendering of MODE_NAIVE_TRILINEAR (vk_set_isosurface): a ray stops at its first sample at or above
+        `iso` (in sample values: normalised for R8 volumes, values for R16F), the crossing is refined by `refine` bisection steps
+        (0 .. 16) and the surface of linear colour `colour` is shaded by set_lighting's light, if one is set.  While set, the transfer
+        table and the projection are ignored (they stay stored); None turns it off and brings them back.  Drains the frames in flight
+        and rebuilds the skip maps of the current volume."""
+        L = N.lib()
+        if iso is None:
+            N.check(self._h, L.vk_set_isosurface(self._h, None))
+            return
+        c = tuple(float(v) for v in colour)
+        if len(c) != 3:
+            raise ValueError("set_isosurface: colour needs three components")
+        if int(refine) != refine or not 0 <= int(refine) <= N.ISO_MAX_REFINE:
+            raise ValueError("set_isosurface: refine is an integer in [0, %d]" % N.ISO_MAX_REFINE)
+        s = N.VkIsosurface()
+        s.iso = float(iso)
+        s.rgb[0], s.rgb[1], s.rgb[2] = c
+        s.refine = int(refine)
+        N.check(self._h, L.vk_set_isosurface(self._h, C.byref(s)))
+
+    @property
+    def isosurface(self):
+        """The isosurface in force as (iso, (r, g, b), refine), or None (vk_get_isosurface)."""
+        s, on = N.VkIsosurface(), C.c_int(0)
+        N.check(self._h, N.lib().vk_get_isosurface(self._h, C.byref(s), C.byref(on)))
+        return (s.iso, (s.rgb[0], s.rgb[1], s.rgb[2]), int(s.refine)) if on.value else None
+
     def set_lighting(self, direction=None, ambient=0.3, diffuse=0.7, specular=0.2, shininess=32.0):
         """Gradient lighting of the table march (vk_set_lighting): each sample's table colour is shaded by the gradient of the trilinear
         interpolant, two-sided Blinn-Phong, rgb' = c.rgb (ambient + diffuse |N.L|) + specular |N.H|^shininess; alpha is untouched.

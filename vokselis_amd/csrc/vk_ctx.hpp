@@ -10,6 +10,7 @@
 //   vk_launch_tf.hip       instantiates the cell march under a transfer table (vk_march.hpp)
 //   vk_launch_lit.hip      instantiates the table march with gradient lighting (vk_march.hpp, vk_light.hpp)
 //   vk_launch_mip.hip      instantiates the cell march under the maximum-intensity projection (vk_march.hpp, vk_march_mip.hpp)
+//   vk_launch_iso.hip      instantiates the cell march under a first-hit isosurface (vk_march.hpp, vk_march_iso.hpp, vk_iso.hpp)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)
@@ -18,6 +19,7 @@
 
 #include "../../include/vokselis_hip.h"
 #include "vk_common.hpp"
+#include "vk_iso.hpp"
 #include "vk_light.hpp"
 #include "vk_tf.hpp"
 
@@ -61,6 +63,9 @@ struct vk_ctx {
     float tf_lo = 0.0f, tf_hi = 1.0f;
     // projection of NAIVE_TRILINEAR (vk_set_projection): compositing, or the maximum over the table's window (vk_launch_mip.hip)
     int proj = VK_PROJ_COMPOSITE;
+    // first-hit isosurface of NAIVE_TRILINEAR (vk_set_isosurface; vk_launch_iso.hip): while set, it replaces table and projection, which stay stored
+    bool iso_on = false;
+    vk_isosurface iso{};
     // gradient lighting of the table march (vk_set_lighting): host state, passed by value to the lit kernels
     bool lit = false;
     vk::LightDesc light{};
@@ -199,7 +204,7 @@ inline size_t px_bytes(int fmt) { return fmt == VK_OUT_RGBA16F ? 8 : 16; }
 inline size_t wire_px_bytes(int fmt, int wire) { return wire == VK_WIRE_RGB ? px_bytes(fmt) / 4 * 3 : px_bytes(fmt); }
 
 // ---- shared between translation units --------------------------------------------------------------------
-int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float lo, float hi, int projection);  // vk_volume.hip: the current volume's maps under a table (nullptr: built-in) and a projection
+int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float lo, float hi, int projection, const float *iso = nullptr);  // vk_volume.hip: the current volume's maps under a table (nullptr: built-in) and a projection, or under an isosurface (iso: its threshold in sample values; nullptr: none)
 int frames_drain(vk_ctx *ctx);   // vk_context.hip: wait for the work of every frame slot (one stream when fif_k == 1)
 void free_volume(vk_ctx *ctx);   // vk_volume.hip
 void comm_release(vk_ctx *ctx);  // vk_comm.hip
@@ -226,6 +231,7 @@ void launch_cells_tf(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc 
 void launch_cells_lit(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::LightDesc &Lt, uint32_t grid, bool count, bool skip,
                       bool safe);  // vk_launch_lit.hip
 void launch_cells_mip(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_mip.hip (T.rgba == nullptr: the grey ramp)
+void launch_cells_iso(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::IsoDesc &I, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_iso.hip
 void launch_staged(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, const float *cam);
 void launch_compute(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, bool records, bool skip);
 void launch_procedural(vk_ctx *ctx, const vk::LaunchDesc &L, uint32_t grid, bool count, float time, bool device_sine);

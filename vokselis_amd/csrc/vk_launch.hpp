@@ -10,6 +10,16 @@
 
 namespace vk {
 
+// The by-value arguments of a march kernel -- LaunchDesc, VolumeDesc and the family's own descriptors -- share the 4 KiB kernel-argument
+// segment with the hidden arguments the runtime appends (at most 256 bytes): the sum is held here, not each struct on its own.
+template <class... D>
+constexpr bool kernargs_fit = sizeof(LaunchDesc) + sizeof(VolumeDesc) + (sizeof(D) + ... + 0) + 256 <= 4096;
+static_assert(kernargs_fit<>, "raymarch_naive_kernel, the compute kernels: LaunchDesc + VolumeDesc");
+static_assert(kernargs_fit<StagedDesc>, "the staged kernels: LaunchDesc + VolumeDesc + StagedDesc");
+static_assert(kernargs_fit<TfDesc>, "raymarch_tf_kernel, raymarch_mip_kernel: LaunchDesc + VolumeDesc + TfDesc");
+static_assert(kernargs_fit<TfDesc, LightDesc>, "raymarch_lit_kernel: LaunchDesc + VolumeDesc + TfDesc + LightDesc");
+static_assert(kernargs_fit<IsoDesc>, "raymarch_iso_kernel: LaunchDesc + VolumeDesc + IsoDesc");
+
 template <int I>
 using int_tag = std::integral_constant<int, I>;
 template <bool B>

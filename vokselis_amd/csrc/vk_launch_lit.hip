@@ -11,9 +11,10 @@ template <int VOL, bool SKIP, bool SAFE, int OUT, bool COUNT>
 __global__ __launch_bounds__(64) void raymarch_lit_kernel(const LaunchDesc L, const VolumeDesc V, const TfDesc T, const LightDesc Lt) {
     constexpr int WALK = WALK_LOOP;
     constexpr bool AHEAD = false;
-    constexpr bool TF = true, LIT = true, MIP = false;
+    constexpr bool TF = true, LIT = true, MIP = false, ISO = false;
     const TfDesc *tfd = &T;
     const LightDesc *ldp = &Lt;
+    const IsoDesc *isd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

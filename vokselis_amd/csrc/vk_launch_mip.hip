@@ -15,9 +15,10 @@ template <int VOL, bool SKIP, bool SAFE, int OUT, bool COUNT>
 __global__ __launch_bounds__(64) void raymarch_mip_kernel(const LaunchDesc L, const VolumeDesc V, const TfDesc T) {
     constexpr int WALK = WALK_LOOP;
     constexpr bool AHEAD = false;
-    constexpr bool TF = false, LIT = false, MIP = true;
+    constexpr bool TF = false, LIT = false, MIP = true, ISO = false;
     const TfDesc *tfd = &T;
     const LightDesc *ldp = nullptr;
+    const IsoDesc *isd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

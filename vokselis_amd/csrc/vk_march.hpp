@@ -8,6 +8,7 @@
 
 #include "vk_common.hpp"
 #include "vk_march_parts.hpp"
+#include "vk_iso.hpp"
 #include "vk_light.hpp"
 #include "vk_tf.hpp"
 #include "vk_trips.hpp"
@@ -476,15 +477,17 @@ __device__ __forceinline__ void clear_inactive_strip(const LaunchDesc &L, uint32
 }  // namespace vk
 
 #include "vk_march_mip.hpp"  // march_mip, march_mip_stream: the loops of the maximum projection, which the kernel body calls under MIP
+#include "vk_march_iso.hpp"  // march_iso, march_iso_stream, iso_sample: the loops and the sampler of the isosurface, which the kernel body calls under ISO
 
 namespace vk {
 
 // AHEAD: the probe-ahead trip (march<..., AHEAD>), an instantiation of its own -- it needs six more registers, and the launches that fill the machine keep the leaner kernel
 template <int VOL, bool SKIP, bool SAFE, int WALK, bool AHEAD, int OUT, bool COUNT>
 __global__ __launch_bounds__(64) void raymarch_naive_kernel(const LaunchDesc L, const VolumeDesc V) {
-    constexpr bool TF = false, LIT = false, MIP = false;  // (the table kernels: vk_launch_tf.hip; lit: vk_launch_lit.hip; the maximum projection: vk_launch_mip.hip)
+    constexpr bool TF = false, LIT = false, MIP = false, ISO = false;  // (the table kernels: vk_launch_tf.hip; lit: vk_launch_lit.hip; the maximum projection: vk_launch_mip.hip; the isosurface: vk_launch_iso.hip)
     const TfDesc *tfd = nullptr;
     const LightDesc *ldp = nullptr;
+    const IsoDesc *isd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

@@ -1,20 +1,25 @@
 // vk_march_kernel_body.hpp -- the body of the cell-march kernels, included inside them (no include guard): raymarch_naive_kernel
-// (vk_march.hpp), raymarch_tf_kernel (vk_launch_tf.hip), raymarch_lit_kernel (vk_launch_lit.hip) and raymarch_mip_kernel
-// (vk_launch_mip.hip).  The including kernel defines the template parameters VOL, SKIP, SAFE, WALK, AHEAD, OUT, COUNT, the constants TF
-// (a runtime transfer function: vk_set_transfer_function), LIT (gradient lighting: vk_set_lighting) and MIP (the maximum-intensity
-// projection: vk_set_projection), `tfd`, its table (nullptr without one; under MIP the window, whose rgba is nullptr for the grey ramp),
-// and `ldp`, its lighting (nullptr without), and takes its arguments L (LaunchDesc) and V (VolumeDesc) by value.  (Shared textually
-// rather than as an inlined function: that moved the register allocation of the existing kernels.)
-// Shared by all four families: the block and pixel mapping, the cull, the index tables in LDS, the ray set-up, the wave priority, the
+// (vk_march.hpp), raymarch_tf_kernel (vk_launch_tf.hip), raymarch_lit_kernel (vk_launch_lit.hip), raymarch_mip_kernel
+// (vk_launch_mip.hip) and raymarch_iso_kernel (vk_launch_iso.hip).  The including kernel defines the template parameters VOL, SKIP, SAFE,
+// WALK, AHEAD, OUT, COUNT, the constants TF (a runtime transfer function: vk_set_transfer_function), LIT (gradient lighting:
+// vk_set_lighting), MIP (the maximum-intensity projection: vk_set_projection) and ISO (a first-hit isosurface: vk_set_isosurface),
+// `tfd`, its table (nullptr without one; under MIP the window, whose rgba is nullptr for the grey ramp), `ldp`, its lighting (nullptr
+// without) and `isd`, its isosurface (nullptr without; it brings its own lighting, a runtime flag), and takes its arguments L
+// (LaunchDesc) and V (VolumeDesc) by value.  (Shared textually rather than as an inlined function: that moved the register allocation
+// of the existing kernels.)
+// Shared by all five families: the block and pixel mapping, the cull, the index tables in LDS, the ray set-up, the wave priority, the
 // adaptive-probing policy, the step image, the counters and the trace.  A family's own: its loops -- march / march_stream (vk_march.hpp), or under MIP
 // march_mip / march_mip_stream (vk_march_mip.hpp), which take the window's k1, k2 and umax from *tfd and carry the running maximum U in
+// RayState::A, or under ISO march_iso / march_iso_stream (vk_march_iso.hpp), which take iso_k from *isd and carry the last sample in
 // RayState::A; selected at each call site, since a forwarding wrapper moved registers in the COUNT kernels -- and what the epilogue
-// makes of the ray's sums.
+// makes of the ray's sums: under ISO the refinement of the crossing and the shade, once per ray, after the wave's loops have ended.
     static_assert(VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16 || (!SKIP && SAFE), "linear / bricked layouts: no skip map, clamped indices");
     static_assert(SKIP || WALK == WALK_LOOP, "the closed-form walks are variants of the skip kernels");
     static_assert(!AHEAD || (SKIP && !SAFE), "probe ahead: the skip kernels' fast path");
     static_assert(!MIP || (!TF && !LIT && WALK == WALK_LOOP && !AHEAD), "the maximum projection: loops of its own, walking with the loop; the table is looked up in the epilogue");
     static_assert(!MIP || (VOL != VOL_B9U8 && VOL != VOL_B9F16 && VOL != VOL_Q8 && VOL != VOL_QF16), "the maximum projection: LINEAR and cell layouts");
+    static_assert(!ISO || (!TF && !LIT && !MIP && WALK == WALK_LOOP && !AHEAD), "the isosurface: loops of its own, walking with the loop; refined and shaded in the epilogue");
+    static_assert(!ISO || (VOL != VOL_B9U8 && VOL != VOL_B9F16 && VOL != VOL_Q8 && VOL != VOL_QF16), "the isosurface: LINEAR and cell layouts");
     if (blockIdx.x >= L.grid_march) { clear_inactive_strip<OUT>(L, blockIdx.x - L.grid_march, threadIdx.x); return; }  // wave-uniform
     const uint32_t lb = logical_block(blockIdx.x);
     if (lb >= L.n_blocks) return;  // wave-uniform
@@ -40,7 +45,7 @@
     extern __shared__ uint32_t cell_lut[];
     if (USE_LUT) {  // all 64 lanes are still here
         load_cell_luts(V, cell_lut, lane);
-        if constexpr (SKIP && !TF && !MIP && !AHEAD && (VOL == VOL_P8 || VOL == VOL_P16))  // the corners of the lone-speckle codes (kSpeckleLutBytes; march() decodes with them)
+        if constexpr (SKIP && !TF && !MIP && !ISO && !AHEAD && (VOL == VOL_P8 || VOL == VOL_P16))  // the corners of the lone-speckle codes (kSpeckleLutBytes; march() decodes with them)
             if (lane < 8u) reinterpret_cast<float4 *>(cell_lut + cell_lut_entries(V.nx, V.ny, V.nz))[lane] = make_float4((lane & 2u) ? 0.0f : 1.0f, (lane & 4u) ? 0.0f : 1.0f, (lane & 1u) ? 0.0f : 1.0f, 0.0f);
         __syncthreads();
     }
@@ -78,15 +83,18 @@
         const float sx = dir[0] * dt, sy = dir[1] * dt, sz = dir[2] * dt;  // :118
         RayState r;
         r.left = min(count_trips(t0, t1, dt), 0x7fffffffu);  // :101
+        [[maybe_unused]] const uint32_t left0 = r.left;  // ISO: a hit leaves `left` alone, so a ray that hit with left == left0 hit in its first iteration
         r.px = px; r.py = py; r.pz = pz; r.sx = sx; r.sy = sy; r.sz = sz;
         r.A = 0.0f; r.Gr = 0.0f; r.Gg = 0.0f; r.Gb = 0.0f;  // colour sums: G = sum w*cos(phase); C = A/2 + G/2 (sum w == A); MIP: A is U, the running maximum
+        if constexpr (ISO) r.A = __builtin_nanf("");  // ISO: A is the last sample's value; none yet: a NaN meets no threshold (x >= k is false), whatever iso_k is, -inf included
         r.out = (uint32_t)pm.out_index;
         LitRay lr;  // LIT: the ray's light and half vectors (vk_light.hpp; left unset in the other kernels, which never read it)
         if constexpr (LIT) lr = lit_ray(*ldp, dir);
         // (not in the skip kernels: a ray's nominal length says little about its work there -- C2 at 64 orbit frames per launch 0.06509 -> 0.06467 ms without)
         if (!SKIP && (L.flags & LF_WAVE_PRIORITY)) set_wave_priority(true, r.left, fmaxf(fnx, fmaxf(fny, fnz)) / L.dt_scale);
         if constexpr (USE_LUT && !SKIP) {
-            if constexpr (MIP) march_mip_stream<VOL, COUNT, false>(V, r, cs, cell_lut, 0xffffffffu, tfd->k1, tfd->k2, tfd->umax);
+            if constexpr (ISO) march_iso_stream<VOL, COUNT, false>(V, r, cs, cell_lut, 0xffffffffu, isd->iso_k);
+            else if constexpr (MIP) march_mip_stream<VOL, COUNT, false>(V, r, cs, cell_lut, 0xffffffffu, tfd->k1, tfd->k2, tfd->umax);
             else march_stream<VOL, COUNT, false, TF, LIT>(V, r, cs, cell_lut, 0xffffffffu, tfd, ldp, &lr);
         }
         else if constexpr (SKIP) {
@@ -101,18 +109,23 @@
                 for (;;) {
                     cs.skips = 0;
                     bool alive;
-                    if constexpr (MIP) alive = march_mip<VOL, true, SAFE, COUNT, true>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd->k1, tfd->k2, tfd->umax);
+                    if constexpr (ISO) alive = march_iso<VOL, true, SAFE, COUNT, true>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, isd->iso_k);
+                    else if constexpr (MIP) alive = march_mip<VOL, true, SAFE, COUNT, true>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd->k1, tfd->k2, tfd->umax);
                     else alive = march<VOL, true, SAFE, COUNT, true, WALK, false, TF, LIT, !AHEAD>(V, r, 16u, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd, ldp, &lr);
                     const unsigned long long live = __ballot(alive);
                     if (live == 0ull) break;
                     if (__popcll(__ballot(alive && cs.skips != 0u)) * 8 >= __popcll(live)) { stretch = stretch0; continue; }
-                    if constexpr (MIP && USE_LUT) alive = march_mip_stream<VOL, COUNT, true>(V, r, cs, cell_lut, stretch, tfd->k1, tfd->k2, tfd->umax);
+                    if constexpr (ISO && USE_LUT) alive = march_iso_stream<VOL, COUNT, true>(V, r, cs, cell_lut, stretch, isd->iso_k);
+                    else if constexpr (ISO) alive = march_iso<VOL, false, SAFE, COUNT, true>(V, r, stretch, cs, nullptr, __builtin_inff(), __builtin_inff(), isd->iso_k);
+                    else if constexpr (MIP && USE_LUT) alive = march_mip_stream<VOL, COUNT, true>(V, r, cs, cell_lut, stretch, tfd->k1, tfd->k2, tfd->umax);
                     else if constexpr (MIP) alive = march_mip<VOL, false, SAFE, COUNT, true>(V, r, stretch, cs, nullptr, __builtin_inff(), __builtin_inff(), tfd->k1, tfd->k2, tfd->umax);
                     else if constexpr (USE_LUT) alive = march_stream<VOL, COUNT, true, TF, LIT>(V, r, cs, cell_lut, stretch, tfd, ldp, &lr);
                     else alive = march<VOL, false, SAFE, COUNT, true, WALK_LOOP, false, TF, LIT>(V, r, stretch, cs, nullptr, __builtin_inff(), __builtin_inff(), tfd, ldp, &lr);
                     if (__ballot(alive) == 0ull) break;
                     stretch = min(stretch * 2u, 512u);
                 }
+            } else if constexpr (ISO) {
+                march_iso<VOL, true, SAFE, COUNT, false>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, isd->iso_k);
             } else if constexpr (MIP) {
                 march_mip<VOL, true, SAFE, COUNT, false>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, L.walk_cap, L.walk_cap_all, tfd->k1, tfd->k2, tfd->umax);
             } else {
@@ -120,10 +133,29 @@
             }
         }
         else if constexpr (is_b9(VOL) || is_quads(VOL)) march_dense_stream<VOL, COUNT>(V, r, cs);
+        else if constexpr (ISO) march_iso<VOL, false, SAFE, COUNT, false>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, __builtin_inff(), __builtin_inff(), isd->iso_k);
         else if constexpr (MIP) march_mip<VOL, false, SAFE, COUNT, false>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, __builtin_inff(), __builtin_inff(), tfd->k1, tfd->k2, tfd->umax);
         else march<VOL, SKIP, SAFE, COUNT, false, WALK_LOOP, false, TF, LIT>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, __builtin_inff(), __builtin_inff(), tfd, ldp, &lr);
         A = r.A; Gr = r.Gr; Gg = r.Gg; Gb = r.Gb;
-        if constexpr (MIP) {
+        if constexpr (ISO) {
+            // A ray that hit: its colour is the surface's, shaded once.  Only the shade reads the crossing, so the refinement runs
+            // under lighting alone: here, after the loops, the wave's hit lanes make the R + 1 dependent fetches together.  The index
+            // tables in LDS are still valid (no barrier: nothing has written them since the loops read them).
+            if (iso_hit(r.A, isd->iso_k)) {
+                float cr = isd->r, cg = isd->g, cb = isd->b;
+                if (isd->lit) {
+                    const uint32_t *tl = USE_LUT ? cell_lut : nullptr;
+                    float a = 0.0f;
+                    if (r.left != left0)  // a hit in the ray's first iteration is not refined
+                        a = iso_refine(isd->refine, [&](float m) { return iso_hit(iso_sample<VOL, SKIP, SAFE>(V, tl, iso_back(m, sx, r.px), iso_back(m, sy, r.py), iso_back(m, sz, r.pz)).x, isd->iso_k); });
+                    const IsoSample h = iso_sample<VOL, SKIP, SAFE>(V, tl, iso_back(a, sx, r.px), iso_back(a, sy, r.py), iso_back(a, sz, r.pz));
+                    float gx, gy, gz;
+                    lit_gradient(h.dx00, h.dx10, h.dx01, h.dx11, h.c00, h.c10, h.c01, h.c11, h.l0, h.l1, h.fy, h.fz, fnx, fny, fnz, gx, gy, gz);
+                    lit_shade(isd->light, lit_ray(isd->light, dir), gx, gy, gz, cr, cg, cb);
+                }
+                Cr = linear_to_srgb(cr); Cg = linear_to_srgb(cg); Cb = linear_to_srgb(cb);
+            }
+        } else if constexpr (MIP) {
             // the table path's lookup at U, once per ray.  No table: the implicit two-entry grey ramp {(0,0,0), (1,1,1)}, whose lerp
             // fma(U, 1 - 0, 0) is U itself, bit for bit (U is +0 or positive)
             const float U = r.A;
@@ -154,7 +186,7 @@
             atomicAdd(&L.counters[3], (unsigned long long)cs.w_inner);
             atomicAdd(&L.counters[4], (unsigned long long)cs.w_sample);
             atomicAdd(&L.counters[5], (unsigned long long)cs.n_look);
-            if constexpr (SKIP && !TF && !MIP) {  // the lone-speckle census of the built-in skip kernels (vk_speckle_census)
+            if constexpr (SKIP && !TF && !MIP && !ISO) {  // the lone-speckle census of the built-in skip kernels (vk_speckle_census)
                 atomicAdd(&L.counters[8], (unsigned long long)cs.w_zero);
                 atomicAdd(&L.counters[9], (unsigned long long)cs.n_proven);
             }

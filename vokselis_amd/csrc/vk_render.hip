@@ -76,12 +76,25 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
     uint32_t grid = (uint32_t)((n_blocks + 511) / 512 * 512);
     L.grid_march = grid;
     // a runtime transfer function (vk_set_transfer_function) has kernels on the LINEAR / PACKED / PACKED_PAIRS layouts, walking with the loop
-    const bool tf = mode == VK_MODE_NAIVE_TRILINEAR && ctx->d_tf;
+    // a first-hit isosurface (vk_set_isosurface): kernels of its own with the table kernels' coverage; table and projection are ignored under it, lighting is honoured
+    const bool iso = mode == VK_MODE_NAIVE_TRILINEAR && ctx->iso_on;
+    const bool tf = mode == VK_MODE_NAIVE_TRILINEAR && ctx->d_tf && !iso;
     // the maximum-intensity projection (vk_set_projection): kernels of its own with the table kernels' coverage; lighting is ignored under it
-    const bool mip = mode == VK_MODE_NAIVE_TRILINEAR && ctx->proj == VK_PROJ_MAX;
+    const bool mip = mode == VK_MODE_NAIVE_TRILINEAR && ctx->proj == VK_PROJ_MAX && !iso;
     // gradient lighting (vk_set_lighting) shades the table's colour: it has no kernels without a table
-    if (mode == VK_MODE_NAIVE_TRILINEAR && ctx->lit && !tf && !mip)
+    if (mode == VK_MODE_NAIVE_TRILINEAR && ctx->lit && !tf && !mip && !iso)
         return fail(ctx, VK_ERR_UNSUPPORTED, "lighting: NAIVE_TRILINEAR renders with lighting need a transfer function (set a table with vk_set_transfer_function, or turn lighting off with vk_set_lighting(NULL))");
+    IsoDesc I{};
+    if (iso) {
+        const int k = ctx->vol_kind;
+        if (k != VOL_LINEAR_U8 && k != VOL_LINEAR_F16 && k != VOL_P8 && k != VOL_P16 && k != VOL_PF16)
+            return fail(ctx, VK_ERR_UNSUPPORTED, "isosurface: NAIVE_TRILINEAR renders under an isosurface need a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no isosurface kernels; vk_set_isosurface(NULL) resets)");
+        if (flags & VK_RENDER_FAST_WALK) return fail(ctx, VK_ERR_UNSUPPORTED, "isosurface: VK_RENDER_FAST_WALK has no isosurface kernels");
+        const char *bad = iso_desc(ctx->iso.iso, ctx->iso.rgb, ctx->iso.refine, ctx->format == VK_FMT_R8_UNORM, I);
+        if (bad) return fail(ctx, VK_ERR_INVALID, std::string("isosurface: ") + bad);  // (vk_set_isosurface has checked it)
+        I.lit = ctx->lit ? 1 : 0;
+        I.light = ctx->light;
+    }
     TfDesc T{};
     if (mip || tf) {
         const int k = ctx->vol_kind;
@@ -137,6 +150,7 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
             if (V.max_off + 16 < (1ll << 32) && cell_lut_bytes(ctx->nx, ctx->ny, ctx->nz) <= 16384u && 64.0f * ulp < 0.25f / nmax && !(flags & VK_RENDER_SAFE)) safe = false;
         }
         if (ctx->vol_kind == VOL_S8U8 || ctx->vol_kind == VOL_S8F16) launch_staged(ctx, L, V, grid, count, reach_cam);
+        else if (iso) launch_cells_iso(ctx, L, V, I, grid, count, skip, safe);
         else if (mip) launch_cells_mip(ctx, L, V, T, grid, count, skip, safe);
         else if (tf && ctx->lit) launch_cells_lit(ctx, L, V, T, ctx->light, grid, count, skip, safe);
         else if (tf) launch_cells_tf(ctx, L, V, T, grid, count, skip, safe);

@@ -101,19 +101,22 @@ static int alloc_scratch(vk_ctx *ctx, CellScratch &sc, uint64_t n_cells) {
 // census counter (ctx->counters[7]) pack_cells_kernel left.  prefix == nullptr: the built-in threshold.
 // mip (VK_PROJ_MAX): the predicate of the maximum projection over the table's window (mip_cell_empty; its alphas, and with them prefix, are
 // not read), n == 0: over the implicit grey ramp's, two entries on [0, 1].
+// iso (vk_set_isosurface; nullptr: none): the isosurface's threshold in sample values; its predicate (iso_cell_empty) replaces the others.
 static int launch_cell_occ(vk_ctx *ctx, int kind, const void *cells, uint8_t *occ, uint8_t *code, uint64_t n_cells, uint32_t blocks, const uint32_t *prefix,
-                           uint32_t n, float lo, float hi, bool mip) {
+                           uint32_t n, float lo, float hi, bool mip_on, const float *iso) {
     float k1 = 0.0f, k2 = 0.0f;
-    if (mip && n == 0) { n = 2; lo = 0.0f; hi = 1.0f; }
-    if (mip) prefix = nullptr;
-    if (prefix || mip) tf_constants(n, lo, hi, kind != VOL_PF16, k1, k2);
+    int mip = mip_on ? 1 : 0;  // cell_occ_kernel's predicate: 0 the table's or the built-in one, 1 the maximum projection's, 2 the isosurface's
+    if (iso) { mip = 2; prefix = nullptr; k1 = iso_k(*iso, kind != VOL_PF16); }
+    if (mip == 1 && n == 0) { n = 2; lo = 0.0f; hi = 1.0f; }
+    if (mip == 1) prefix = nullptr;
+    if (prefix || mip == 1) tf_constants(n, lo, hi, kind != VOL_PF16, k1, k2);
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters + 7, 0, sizeof(unsigned long long), ctx->stream));
     if (kind == VOL_PF16)
-        hipLaunchKernelGGL(cell_occ_kernel<VOL_PF16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, code, n_cells, prefix, (int)n, k1, k2, mip ? 1 : 0, ctx->counters + 7);
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_PF16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, code, n_cells, prefix, (int)n, k1, k2, mip, ctx->counters + 7);
     else if (kind == VOL_P16)
-        hipLaunchKernelGGL(cell_occ_kernel<VOL_P16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, code, n_cells, prefix, (int)n, k1, k2, mip ? 1 : 0, ctx->counters + 7);
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_P16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, code, n_cells, prefix, (int)n, k1, k2, mip, ctx->counters + 7);
     else
-        hipLaunchKernelGGL(cell_occ_kernel<VOL_P8>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, code, n_cells, prefix, (int)n, k1, k2, mip ? 1 : 0, ctx->counters + 7);
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_P8>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, code, n_cells, prefix, (int)n, k1, k2, mip, ctx->counters + 7);
     return VK_OK;  // (launch errors: read_census)
 }
 
@@ -173,8 +176,8 @@ static int build_skip_maps(vk_ctx *ctx, CellScratch &sc, bool coded, uint32_t nb
 
 // The current packed volume's seed, census and maps under the table (d_prefix: its prefix counts on the device; nullptr: the built-in
 // transfer) and the projection, swapped in only when all of it has been built.  The caller has drained the frame slots.  Other layouts
-// have no maps.
-int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float lo, float hi, int projection) {
+// have no maps.  iso (nullptr: none): the threshold of the isosurface in force, whose predicate then replaces the pair's.
+int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float lo, float hi, int projection, const float *iso) {
     const int kind = ctx->vol_kind;
     if (ctx->format < 0 || (kind != VOL_P8 && kind != VOL_P16 && kind != VOL_PF16)) return VK_OK;
     const uint64_t n_cells = (uint64_t)ctx->nbx * ctx->nby * ctx->nbz * kBrickCells;
@@ -182,8 +185,8 @@ int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float l
     CellScratch sc;
     int rc = alloc_scratch(ctx, sc, n_cells);
     if (rc) return rc;
-    const bool builtin = !d_prefix && projection != VK_PROJ_MAX && ctx->speckle_codes;  // clearing the table brings the built-in seed back, and its codes with it
-    if ((rc = launch_cell_occ(ctx, kind, ctx->vol, sc.occ, sc.code, n_cells, (uint32_t)((n_cells + 255) / 256), d_prefix, n, lo, hi, projection == VK_PROJ_MAX))) return rc;
+    const bool builtin = !d_prefix && projection != VK_PROJ_MAX && !iso && ctx->speckle_codes;  // clearing the table brings the built-in seed back, and its codes with it
+    if ((rc = launch_cell_occ(ctx, kind, ctx->vol, sc.occ, sc.code, n_cells, (uint32_t)((n_cells + 255) / 256), d_prefix, n, lo, hi, projection == VK_PROJ_MAX, iso))) return rc;
     double ef = 0.0;
     if ((rc = read_census(ctx, n_cells, &ef))) return rc;
     uint8_t *dist = nullptr;
@@ -390,10 +393,11 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
     else
         hipLaunchKernelGGL(pack_cells_kernel<VOL_P8>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, sc.code, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
     // under a runtime transfer function the seed and the census follow its table (vk_set_transfer_function), under the maximum projection its predicate (vk_set_projection)
-    const bool builtin = !ctx->d_tf && ctx->proj != VK_PROJ_MAX;
+    // ... and under an isosurface its predicate (vk_set_isosurface)
+    const bool builtin = !ctx->d_tf && ctx->proj != VK_PROJ_MAX && !ctx->iso_on;
     if (!builtin &&
         (rc = launch_cell_occ(ctx, kind, nb.vol, sc.occ, nullptr, n_cells, pack_blocks, ctx->d_tf ? reinterpret_cast<const uint32_t *>(ctx->d_tf + 4 * ctx->tf_n) : nullptr,
-                              ctx->d_tf ? ctx->tf_n : 0u, ctx->tf_lo, ctx->tf_hi, ctx->proj == VK_PROJ_MAX)))
+                              ctx->d_tf ? ctx->tf_n : 0u, ctx->tf_lo, ctx->tf_hi, ctx->proj == VK_PROJ_MAX, ctx->iso_on ? &ctx->iso.iso : nullptr)))
         return rc;
     if ((rc = read_census(ctx, n_cells, &nb.empty_fraction))) return rc;
     uint64_t dist_bytes = 0;
@@ -537,7 +541,8 @@ int vk_set_transfer_function(vk_ctx *ctx, const float *rgba, uint32_t n, float l
     if (rc) return rc;
     if (!rgba) {
         if (!ctx->d_tf) return VK_OK;
-        if ((rc = rebuild_skip_maps(ctx, nullptr, 0, 0.0f, 1.0f, ctx->proj))) return rc;
+        // (under an isosurface the maps are its own and stay: the stored table changes what vk_set_isosurface(NULL) will restore)
+        if (!ctx->iso_on && (rc = rebuild_skip_maps(ctx, nullptr, 0, 0.0f, 1.0f, ctx->proj))) return rc;
         (void)hipFree(ctx->d_tf);
         ctx->d_tf = nullptr;
         ctx->tf_n = 0;
@@ -553,7 +558,7 @@ int vk_set_transfer_function(vk_ctx *ctx, const float *rgba, uint32_t n, float l
     HIP_TRY(ctx, hipMalloc((void **)&d, blob.size()));
     hipError_t e = hipMemcpy(d, blob.data(), blob.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d); return fail(ctx, VK_ERR_HIP, std::string("vk_set_transfer_function: upload: ") + hipGetErrorString(e)); }
-    if ((rc = rebuild_skip_maps(ctx, reinterpret_cast<const uint32_t *>(d + 4 * n), n, lo, hi, ctx->proj))) { (void)hipFree(d); return rc; }
+    if (!ctx->iso_on && (rc = rebuild_skip_maps(ctx, reinterpret_cast<const uint32_t *>(d + 4 * n), n, lo, hi, ctx->proj))) { (void)hipFree(d); return rc; }
     (void)hipFree(ctx->d_tf);
     ctx->d_tf = d;
     ctx->tf_n = n; ctx->tf_lo = lo; ctx->tf_hi = hi;
@@ -569,8 +574,8 @@ int vk_set_projection(vk_ctx *ctx, int projection) {
     int rc = frames_drain(ctx);
     if (rc) return rc;
     if (projection == ctx->proj) return VK_OK;
-    // the maps of the (projection, table) pair now in force, whichever setter came first
-    if ((rc = rebuild_skip_maps(ctx, ctx->d_tf ? reinterpret_cast<const uint32_t *>(ctx->d_tf + 4 * ctx->tf_n) : nullptr, ctx->d_tf ? ctx->tf_n : 0u,
+    // the maps of the (projection, table) pair now in force, whichever setter came first (under an isosurface: its own maps stay)
+    if (!ctx->iso_on && (rc = rebuild_skip_maps(ctx, ctx->d_tf ? reinterpret_cast<const uint32_t *>(ctx->d_tf + 4 * ctx->tf_n) : nullptr, ctx->d_tf ? ctx->tf_n : 0u,
                                 ctx->d_tf ? ctx->tf_lo : 0.0f, ctx->d_tf ? ctx->tf_hi : 1.0f, projection)))
         return rc;
     ctx->proj = projection;
@@ -580,6 +585,38 @@ int vk_set_projection(vk_ctx *ctx, int projection) {
 int vk_get_projection(vk_ctx *ctx, int *projection) {
     if (!ctx || !projection) return VK_ERR_INVALID;
     *projection = ctx->proj;
+    return VK_OK;
+}
+
+int vk_set_isosurface(vk_ctx *ctx, const vk_isosurface *iso) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (iso) {
+        IsoDesc D{};
+        const char *bad = iso_desc(iso->iso, iso->rgb, iso->refine, true, D);
+        if (bad) return fail(ctx, VK_ERR_INVALID, std::string("vk_set_isosurface: ") + bad);
+    }
+    if (ctx->fif_open) return fail(ctx, VK_ERR_INVALID, "vk_set_isosurface: a frame is being recorded (call it outside vk_frame_begin / vk_frame_end)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // every frame recorded so far renders under the state it was recorded under, with that state's maps: drain them first
+    int rc = frames_drain(ctx);
+    if (rc) return rc;
+    if (!iso && !ctx->iso_on) return VK_OK;
+    // the maps change with the threshold alone: a new colour or refinement depth keeps them
+    if (!(iso && ctx->iso_on && iso->iso == ctx->iso.iso)) {
+        // the isosurface's predicate, or -- turned off -- that of the (projection, table) pair in force, byte for byte what it was
+        if ((rc = rebuild_skip_maps(ctx, ctx->d_tf ? reinterpret_cast<const uint32_t *>(ctx->d_tf + 4 * ctx->tf_n) : nullptr, ctx->d_tf ? ctx->tf_n : 0u,
+                                    ctx->d_tf ? ctx->tf_lo : 0.0f, ctx->d_tf ? ctx->tf_hi : 1.0f, ctx->proj, iso ? &iso->iso : nullptr)))
+            return rc;
+    }
+    ctx->iso_on = iso != nullptr;
+    if (iso) ctx->iso = *iso;
+    return VK_OK;
+}
+
+int vk_get_isosurface(vk_ctx *ctx, vk_isosurface *out, int *enabled) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (enabled) *enabled = ctx->iso_on ? 1 : 0;
+    if (out && ctx->iso_on) *out = ctx->iso;
     return VK_OK;
 }
 

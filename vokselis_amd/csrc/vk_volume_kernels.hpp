@@ -140,7 +140,8 @@ __global__ __launch_bounds__(256) void pack_cells_kernel(const void *__restrict_
 // (P8: u8 taps; P16: (tap, delta) pairs, tap + delta exact; PF16: f16 taps), tested by the runtime transfer function's emptiness
 // predicate (vk_tf.hpp; prefix: the table's prefix counts of non-zero alphas), or with prefix == nullptr by the built-in threshold
 // of pack_cells_kernel -- whose occ and census it then reproduces byte for byte.  mip != 0 (vk_set_projection(VK_PROJ_MAX)): the predicate
-// of the maximum projection over the window behind k1, k2 and its n entries (vk_tf.hpp: mip_cell_empty).  code (nullptr: not wanted): the
+// of the maximum projection over the window behind k1, k2 and its n entries (vk_tf.hpp: mip_cell_empty).  mip == 2 (vk_set_isosurface):
+// the predicate of the isosurface whose threshold on the kernel's scale is k1 (vk_iso.hpp: iso_cell_empty).  code (nullptr: not wanted): the
 // cells' lone-speckle codes, as pack_cells_kernel writes them; they exist under the built-in transfer only.
 template <int VOL>
 __global__ __launch_bounds__(256) void cell_occ_kernel(const void *__restrict__ cells, uint8_t *__restrict__ occ, uint8_t *__restrict__ code, uint64_t n_cells,
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(256) void cell_occ_kernel(const void *__restrict__ 
             else { t[2 * k] = (float)c.h[2 * k]; t[2 * k + 1] = (float)c.h[2 * k + 1]; }
         }
     }
-    const bool nonempty = mip ? !mip_cell_empty(t, k1, k2, (float)(n - 1)) : prefix ? !tf_cell_empty(t, prefix, n, k1, k2) : !builtin_cell_empty(t, VOL == VOL_PF16);  // (pack_cells_kernel's predicate)
+    const bool nonempty = mip == 2 ? !iso_cell_empty(t, k1) : mip ? !mip_cell_empty(t, k1, k2, (float)(n - 1)) : prefix ? !tf_cell_empty(t, prefix, n, k1, k2) : !builtin_cell_empty(t, VOL == VOL_PF16);  // (pack_cells_kernel's predicate)
     occ[id] = nonempty ? 0 : 255;
     if (code) code[id] = (VOL == VOL_PF16 || mip || prefix) ? (uint8_t)0 : (uint8_t)speckle_code(t);
     const unsigned long long m = __ballot(!nonempty);

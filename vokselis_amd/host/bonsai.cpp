@@ -12,6 +12,9 @@
 //                                                            towards (X, Y, Z) or at the eye; ambient, diffuse, specular, shininess (default 0.3 0.7 0.2 32)
 //          [--mip]                                            maximum-intensity projection (vk_set_projection(VK_PROJ_MAX)) over the table's window,
 //                                                            without --tf a grey ramp over [0, 1]
+//          [--iso V [--iso-colour R G B] [--iso-refine N]]    first-hit isosurface at sample value V (vk_set_isosurface): linear surface colour
+//                                                            (default 1 1 1), N bisection steps at the hit (default 4); shaded by --light /
+//                                                            --headlight (no --tf needed); refused together with --mip
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -29,6 +32,8 @@ static std::vector<float> g_tf;  // --tf: n x 4 floats (empty: the built-in tran
 static float g_tf_lo = 0.0f, g_tf_hi = 1.0f;
 static bool g_lit = false;  // --light / --headlight: gradient lighting (the library checks the parameters)
 static bool g_mip = false;  // --mip: maximum-intensity projection
+static bool g_iso_on = false;  // --iso: first-hit isosurface (the library checks the parameters)
+static vk_isosurface g_iso = {0.0f, {1.0f, 1.0f, 1.0f}, 4u};
 static vk_lighting g_light = {{0.0f, 0.0f, 0.0f}, 0, 0.3f, 0.7f, 0.2f, 32.0f};
 
 // --tf PATH: the whole file as little-endian f32 RGBA rows (the library checks n, finiteness and alpha)
@@ -52,6 +57,7 @@ struct Bonsai : Demo {
         if (!g_tf.empty()) ctx.set_transfer_function(g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi);
         if (g_lit) ctx.set_lighting(&g_light);
         if (g_mip) ctx.set_projection(VK_PROJ_MAX);
+        if (g_iso_on) ctx.set_isosurface(&g_iso);
         if (!g_raw.empty()) self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::from_raw(ctx, g_raw));
         else self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, 256, 256, 256));
         self->pipeline = RaycastPipeline{VK_MODE_NAIVE_TRILINEAR, g_dt, 0};
@@ -84,6 +90,7 @@ static int run_group(int n_gpus, uint32_t frames, uint32_t batch, uint32_t w, ui
             if (!g_tf.empty()) check(c, vk_set_transfer_function(c, g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi));
             if (g_lit) check(c, vk_set_lighting(c, &g_light));
             if (g_mip) check(c, vk_set_projection(c, VK_PROJ_MAX));
+            if (g_iso_on) check(c, vk_set_isosurface(c, &g_iso));
             if (!raw.empty()) check(c, vk_volume_upload(c, raw.data(), nullptr, 256, 256, 256, VK_FMT_R8_UNORM, VK_LAYOUT_AUTO));
             else check(c, vk_volume_generate(c, VK_GEN_BONSAI_STANDIN, 256, 256, 256, VK_FMT_R8_UNORM, 0x5EED0001u, 0, 1, VK_LAYOUT_AUTO));
         }
@@ -163,6 +170,9 @@ int main(int argc, char **argv) {
         }
         else if (a == "--tf-domain") { g_tf_lo = (float)std::atof(next()); g_tf_hi = (float)std::atof(next()); }
         else if (a == "--mip") g_mip = true;
+        else if (a == "--iso") { g_iso_on = true; g_iso.iso = (float)std::atof(next()); }
+        else if (a == "--iso-colour") { for (int k = 0; k < 3; k++) g_iso.rgb[k] = (float)std::atof(next()); }
+        else if (a == "--iso-refine") g_iso.refine = (uint32_t)std::max(0, std::atoi(next()));
         else if (a == "--light") { g_lit = true; g_light.headlight = 0; for (int k = 0; k < 3; k++) g_light.dir[k] = (float)std::atof(next()); }
         else if (a == "--headlight") { g_lit = true; g_light.headlight = 1; }
         else if (a == "--light-params") {
@@ -172,6 +182,7 @@ int main(int argc, char **argv) {
         else if (a == "--camera-blobs") { std::string in = next(); return dump_camera_blobs(in, next()); }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
+    if (g_iso_on && g_mip) { std::fprintf(stderr, "bonsai: --iso and --mip exclude each other (an isosurface ignores the projection)\n"); return 2; }
     if (gpus > 0) return run_group(gpus, frames, batch, w, h, peer_direct);
     try {
         // examples/bonsai/main.rs:64-74: 1280x720 window, Camera::new(1., 0.5, 1., (0.5,0.5,0.5), w/h)

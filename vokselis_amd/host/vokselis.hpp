@@ -170,6 +170,7 @@ struct Uniform {
     float _padding = 0.f;
 };
 static_assert(sizeof(Uniform) == 48, "Uniform is 48 bytes (src/context/global_ubo.rs:52-65)");
+static_assert(sizeof(vk_isosurface) == 20, "vk_isosurface is 20 bytes (vk_set_isosurface)");
 
 // src/context/hdr_backbuffer.rs:10-11
 struct HdrBackBuffer {
@@ -239,6 +240,9 @@ class Context {
     // Projection of NAIVE_TRILINEAR (vk_set_projection): VK_PROJ_MAX, a maximum-intensity projection over the table's window, or VK_PROJ_COMPOSITE.
     void set_projection(int projection) { check(ctx_, vk_set_projection(ctx_, projection)); }
     int projection() const { int p = VK_PROJ_COMPOSITE; check(ctx_, vk_get_projection(ctx_, &p)); return p; }
+    // First-hit isosurface rendering of NAIVE_TRILINEAR (vk_set_isosurface); nullptr turns it off.  While set, table and projection are ignored (and kept).
+    void set_isosurface(const vk_isosurface *iso) { check(ctx_, vk_set_isosurface(ctx_, iso)); }
+    bool isosurface(vk_isosurface *out = nullptr) const { int on = 0; check(ctx_, vk_get_isosurface(ctx_, out, &on)); return on != 0; }
     // Gradient lighting of the table march (vk_set_lighting); nullptr turns it off.
     void set_lighting(const vk_lighting *light) { check(ctx_, vk_set_lighting(ctx_, light)); }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
