@@ -1,5 +1,5 @@
-// vk_launch.hpp -- host side of the vk_launch_*.hip files (included by them only): the runtime choices that select a kernel instantiation,
-// each written once.  A helper turns its runtime values into compile-time tags and hands them to a generic lambda that names the kernel:
+// vk_launch.hpp -- host side of the vk_launch_*.hip files (included by them, and by vk_render.hip for has_table_layout): the runtime choices that
+// select a kernel instantiation, each written once.  A helper turns its runtime values into compile-time tags and hands them to a generic lambda that names the kernel:
 //     with_out_count(ctx, count, [&](auto OUT, auto COUNT) { hipLaunchKernelGGL((kernel<..., OUT(), COUNT()>), ...); });
 // A helper calls its lambda with exactly the combinations the ladder it replaces spelled out: the set of instantiated kernels is the same.
 #pragma once
@@ -44,7 +44,10 @@ void with_skip_safe(bool skip, bool safe, F &&f) {
     else { if (safe) f(bool_tag<false>(), bool_tag<true>()); else f(bool_tag<false>(), bool_tag<false>()); }
 }
 
-// f(VOL, SKIP, SAFE) over the layouts that have table kernels (dispatch_march has refused the others): the cell layouts in all four
+// the layouts that have table, maximum-projection and isosurface kernels: dispatch_march refuses the others under any of the three
+inline bool has_table_layout(int k) { return k == VOL_LINEAR_U8 || k == VOL_LINEAR_F16 || k == VOL_P8 || k == VOL_P16 || k == VOL_PF16; }
+
+// f(VOL, SKIP, SAFE) over the layouts that have table kernels (has_table_layout): the cell layouts in all four
 // variants, the LINEAR layouts without a skip map and with clamped indices only.
 template <class F>
 void with_table_layout(const vk_ctx *ctx, bool skip, bool safe, F &&f) {

@@ -1,9 +1,9 @@
 // vk_march.hpp -- NAIVE_TRILINEAR (raycast_naive.wgsl:83-125) on the cell layouts (and the LINEAR / 9^3 / quad comparison layouts).
-// The loops march / march_stream / march_dense_stream, RayState, Census, and raymarch_naive_kernel around the shared kernel body
+// The loops march / march_stream / march_dense_stream, RayState, and raymarch_naive_kernel around the shared kernel body
 // (vk_march_kernel_body.hpp).  Included by vk_launch_cells.hip for that kernel, by vk_launch_tf.hip and vk_launch_lit.hip, whose
-// kernels instantiate the same loops with TF / LIT, by vk_launch_mip.hip for the loops of vk_march_mip.hpp (included below), and by
-// vk_staged.hpp (vk_launch_staged.hip) for RayState, Census, clear_inactive_strip and the palette.  The statement groups the loops
-// share are vk_march_parts.hpp's.
+// kernels instantiate the same loops with TF / LIT, by vk_launch_mip.hip and vk_launch_iso.hip for the loops of vk_march_mip.hpp and
+// vk_march_iso.hpp (included below), and by vk_staged.hpp (vk_launch_staged.hip) for RayState, Census, clear_inactive_strip and the
+// palette.  The statement groups the loops share, and Census, which they count into, are vk_march_parts.hpp's.
 #pragma once
 
 #include "vk_common.hpp"
@@ -56,18 +56,6 @@ struct RayState {
     uint32_t pad[4];
 };
 static_assert(sizeof(RayState) == 64, "RayState is one 64-byte record");
-
-struct Census {  // SIMT execution census + step counters (COUNT builds only)
-    uint32_t n_iter = 0, n_samp = 0, w_outer = 0, w_inner = 0, w_sample = 0, n_look = 0, n_fb = 0;
-    uint32_t skips = 0;  // trips that skipped (every build: drives the adaptive probing policy)
-    // the built-in skip kernels (COUNT builds): wave-level sample executions in which every sampling lane's alpha came out 0 (the upper bound on what
-    // the lone-speckle codes can take away), and lane-steps those codes proved transparent without a sample
-    uint32_t w_zero = 0, n_proven = 0;
-    // per-trip log of the wave (COUNT builds, debug bit 6; docs/archive/tools/repack_census.py): entry = live lanes | samplers << 7 | samplers whose alpha is
-    // not 0 << 14 | wave-level walk iterations << 21
-    uint32_t *log = nullptr;
-    uint32_t log_cap = 0, trip_no = 0;
-};
 
 // Runs at most `budget` trips of the reference loop (raycast_naive.wgsl:101-119) on the state and
 // returns whether the ray is still alive.  State in, state out: a ray marched in several pieces
@@ -169,6 +157,7 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
             if (SAFE) { ix = med3_i32(ix, -1, mx); iy = med3_i32(iy, -1, my); iz = med3_i32(iz, -1, mz); }
             const char *cptr = nullptr;
             uint32_t d = 0, coff = 0;
+            // (cell_at's block in this loop's own text, with dist_at and AHEAD: through cell_at 16 COUNT kernels changed -- DESIGN.md section 13)
             if (SAFE) {
                 const int64_t off = safe_cell_offset(V, ix, iy, iz);
                 cptr = reinterpret_cast<const char *>(V.data) + off;
@@ -258,9 +247,7 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
                 if (AHEAD) locate(px, py, pz);
                 continue;
             }
-            CellBits<VOL> cb;
-            if (SAFE) cb = load_cell<VOL>(cptr);
-            else cb = load_cell<VOL>(cells, coff);
+            const CellBits<VOL> cb = load_cell<VOL, SAFE>(cells, cptr, coff);
             if (AHEAD) {
                 // :118 and :101's increment (one iteration fewer left) now -- neither depends on the sample -- then the next position's distance byte is requested
                 // under this sample's arithmetic (fx, fy, fz keep THIS position's weights)
@@ -356,14 +343,14 @@ __device__ __forceinline__ bool march_stream(const VolumeDesc &V, RayState &r, C
     {
         const float ux = fmaf(px, fnx, -0.5f), uy = fmaf(py, fny, -0.5f), uz = fmaf(pz, fnz, -0.5f);
         fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);
-        c0 = load_cell<VOL>(cells, (lut[cvt_floor_i32(ux) + 2] + luty[cvt_floor_i32(uy) + 2] + lutz[cvt_floor_i32(uz) + 2]) << lsh);
+        c0 = request_cell<VOL>(cells, lut, luty, lutz, lsh, ux, uy, uz);
     }
     // one trip: request `nxt` for the advanced position, evaluate `cur`; returns whether the ray goes on
     auto trip = [&](const CellBits<VOL> &cur, CellBits<VOL> &nxt) -> bool {
         if (COUNT) { cs.n_look++; cs.n_iter++; cs.n_samp++; if (wave_leader()) { cs.w_outer++; cs.w_sample++; } }
         px = px + sx; py = py + sy; pz = pz + sz;  // :118
         const float ux = fmaf(px, fnx, -0.5f), uy = fmaf(py, fny, -0.5f), uz = fmaf(pz, fnz, -0.5f);
-        nxt = load_cell<VOL>(cells, (lut[cvt_floor_i32(ux) + 2] + luty[cvt_floor_i32(uy) + 2] + lutz[cvt_floor_i32(uz) + 2]) << lsh);
+        nxt = request_cell<VOL>(cells, lut, luty, lutz, lsh, ux, uy, uz);
         float c00, c10, c01, c11;
         float dx00, dx10, dx01, dx11;
         if constexpr (LIT) xlerp_cell_dx<VOL>(cur, fx, c00, c10, c01, c11, dx00, dx10, dx01, dx11);
@@ -432,9 +419,7 @@ __device__ __forceinline__ void march_dense_stream(const VolumeDesc &V, RayState
         if constexpr (is_b9(VOL)) b9_decode<VOL>(cur, tp);
         else quad_decode<VOL>(cur, tp);
         xlerp_taps(tp, fx, c00, c10, c01, c11);
-        const float l0 = fmaf(fy, c10 - c00, c00), l1 = fmaf(fy, c11 - c01, c01);
-        float v = fmaf(fz, l1 - l0, l0);
-        palette_composite(transfer_alpha<U8 ? 1 : 0>(v), A, Gr, Gg, Gb);
+        palette_composite(transfer_alpha<U8 ? 1 : 0>(lerp_yz(fy, fz, c00, c10, c01, c11)), A, Gr, Gg, Gb);
         left -= 1u;  // :101
         fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);
         return left != 0u && A < 0.95f;

@@ -1,7 +1,8 @@
 // vk_march_iso.hpp -- the loops of the cell march under first-hit isosurface rendering (vk_set_isosurface):
 // march_mip() and march_mip_stream() of vk_march_mip.hpp with another operator on the filtered sample, one compare, x >= iso_k
-// (vk_iso.hpp: iso_hit), and another exit: the hit sample's position stays in p.  Built from the same statement groups
-// (vk_march_parts.hpp).  Included by vk_march.hpp after vk_march_mip.hpp, and so part of every unit that includes vk_march.hpp;
+// (vk_iso.hpp: iso_hit), and another exit: the hit sample's position stays in p.  The family's own: each loop's frame, condition, skip
+// decision, operator and advance; the rest are the parts the MAX loops call (vk_march_parts.hpp; one loop for both: DESIGN.md section 13).
+// Included by vk_march.hpp after vk_march_mip.hpp, and so part of every unit that includes vk_march.hpp;
 // instantiated by raymarch_iso_kernel (vk_launch_iso.hip) alone, through vk_march_kernel_body.hpp under ISO.  The refinement and the
 // shade are the kernel body's epilogue, once per ray; iso_sample() below is what both fetch with.
 #pragma once
@@ -40,48 +41,25 @@ __device__ __forceinline__ bool march_iso(const VolumeDesc &V, RayState &r, cons
         float c00, c10, c01, c11;  // x-lerped corners
         if (PACKED) {
             if (SAFE) { ix = med3_i32(ix, -1, mx); iy = med3_i32(iy, -1, my); iz = med3_i32(iz, -1, mz); }
-            const char *cptr = nullptr;
-            uint32_t d = 0, coff = 0;
-            if (SAFE) {
-                const int64_t off = safe_cell_offset(V, ix, iy, iz);
-                cptr = reinterpret_cast<const char *>(V.data) + off;
-                if (SKIP) d = V.dist[(uint64_t)(off >> V.sh_x) + doff];
-            } else {
-                // cell index (SKIP) / cell byte offset (!SKIP) from the per-axis tables in LDS; entry i + 2 is voxel i
-                const uint32_t idx = lut[ix + 2] + luty[iy + 2] + lutz[iz + 2];
-                coff = SKIP ? (uint32_t)(idx << V.sh_x) : idx;
-                if (SKIP) d = V.dist[idx + doff];
-            }
-            if (SKIP && d != 0) {
+            const CellAt ca = cell_at<SKIP, SAFE>(V, lut, luty, lutz, doff, ix, iy, iz);
+            if (SKIP && ca.d != 0) {
                 if (BOUNDED) cs.skips++;
-                // walks are capped in a trip in which other lanes sample (march(): the samplers pace the trip); any stop is exact
-                const float cap_now = __ballot(d == 0) != 0ull ? walk_cap : walk_cap_all;
-                // samples j = 0 .. k - 1 are skipped, k = ceil(min r_i) clamped to [1, iterations left]: p += s, k times, the reference's additions
-                const float rmin = fminf(sb.steps(fx, fy, fz, (float)d), cap_now);
+                // the skip decision of march_mip(), statement for statement; shared below it (as one function: DESIGN.md section 13)
+                const float cap_now = __ballot(ca.d == 0) != 0ull ? walk_cap : walk_cap_all;
+                const float rmin = fminf(sb.steps(fx, fy, fz, (float)ca.d), cap_now);
                 const int kneg = walk_steps_neg(rmin, nleft);  // -k
                 nleft -= kneg;
                 if (COUNT) { cs.n_iter += (uint32_t)(-kneg); if (wave_leader()) cs.w_inner++; }
-                px = px + sx; py = py + sy; pz = pz + sz;
-                uint32_t m = (uint32_t)(-1 - kneg);  // the steps after the first
-                for (uint32_t q = m >> 2; q != 0u; --q) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) { px = px + sx; py = py + sy; pz = pz + sz; }
-                    if (COUNT) { if (wave_leader()) cs.w_inner++; }
-                }
-                for (m &= 3u; m != 0u; --m) { px = px + sx; py = py + sy; pz = pz + sz; }
+                walk_exact<COUNT>(px, py, pz, sx, sy, sz, kneg, cs);
                 continue;
             }
-            CellBits<VOL> cb;
-            if (SAFE) cb = load_cell<VOL>(cptr);
-            else cb = load_cell<VOL>(cells, coff);
-            xlerp_cell<VOL>(cb, fx, c00, c10, c01, c11);
+            xlerp_cell<VOL>(load_cell<VOL, SAFE>(cells, ca.cptr, ca.coff), fx, c00, c10, c01, c11);
         } else {
             float tp[8];
             linear_taps<VOL>(V, ix, iy, iz, tp);
             xlerp_taps(tp, fx, c00, c10, c01, c11);
         }
-        const float c0 = fmaf(fy, c10 - c00, c00), c1 = fmaf(fy, c11 - c01, c01);
-        X = fmaf(fz, c1 - c0, c0);
+        X = lerp_yz(fy, fz, c00, c10, c01, c11);
         if (COUNT) { cs.n_iter++; cs.n_samp++; if (wave_leader()) cs.w_sample++; }
         if (!iso_hit(X, iso_k)) {  // the hit sample keeps its position and its iteration
             px = px + sx; py = py + sy; pz = pz + sz;
@@ -112,20 +90,18 @@ __device__ __forceinline__ bool march_iso_stream(const VolumeDesc &V, RayState &
     {
         const float ux = fmaf(ax, fnx, -0.5f), uy = fmaf(ay, fny, -0.5f), uz = fmaf(az, fnz, -0.5f);
         fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);
-        c0 = load_cell<VOL>(cells, (lut[cvt_floor_i32(ux) + 2] + luty[cvt_floor_i32(uy) + 2] + lutz[cvt_floor_i32(uz) + 2]) << lsh);
+        c0 = request_cell<VOL>(cells, lut, luty, lutz, lsh, ux, uy, uz);
     }
-    // one trip: `cur` is the cell of position (cx, cy, cz); request `nxt` for the advanced position (nx, ny, nz) (a clamped table
-    // entry, a bounds-checked buffer load: inside the cell array also one step past the ray's end), evaluate `cur`; returns whether
-    // the ray goes on.  A hit leaves `left` as it is.
+    // one trip: `cur` is the cell of position (cx, cy, cz); request `nxt` for the advanced position (nx, ny, nz) (request_cell: safe one
+    // step past the ray's end too), evaluate `cur`; returns whether the ray goes on.  A hit leaves `left` as it is.
     auto trip = [&](const CellBits<VOL> &cur, CellBits<VOL> &nxt, const float cx, const float cy, const float cz, float &nx, float &ny, float &nz) -> bool {
         if (COUNT) { cs.n_look++; cs.n_iter++; cs.n_samp++; if (wave_leader()) { cs.w_outer++; cs.w_sample++; } }
         nx = cx + sx; ny = cy + sy; nz = cz + sz;
         const float ux = fmaf(nx, fnx, -0.5f), uy = fmaf(ny, fny, -0.5f), uz = fmaf(nz, fnz, -0.5f);
-        nxt = load_cell<VOL>(cells, (lut[cvt_floor_i32(ux) + 2] + luty[cvt_floor_i32(uy) + 2] + lutz[cvt_floor_i32(uz) + 2]) << lsh);
+        nxt = request_cell<VOL>(cells, lut, luty, lutz, lsh, ux, uy, uz);
         float c00, c10, c01, c11;
         xlerp_cell<VOL>(cur, fx, c00, c10, c01, c11);
-        const float l0 = fmaf(fy, c10 - c00, c00), l1 = fmaf(fy, c11 - c01, c01);
-        X = fmaf(fz, l1 - l0, l0);
+        X = lerp_yz(fy, fz, c00, c10, c01, c11);
         if (iso_hit(X, iso_k)) return false;
         left -= 1u;
         fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);
@@ -145,7 +121,7 @@ __device__ __forceinline__ bool march_iso_stream(const VolumeDesc &V, RayState &
 
 // The sample at (qx, qy, qz) with what the shade needs of it (vk_light.hpp: lit_gradient's arguments), fetched through the family's
 // own address path: the index tables in LDS on the fast path, the clamped 64-bit offset under SAFE, linear_taps on the LINEAR layouts.
-// Never consults a skip map.  The filter is the loops', bit for bit.
+// Never consults a skip map (cell_at without DIST).  The filter is the loops', bit for bit; y/z written out: lit_gradient takes l0, l1.
 struct IsoSample {
     float x, dx00, dx10, dx01, dx11, c00, c10, c01, c11, l0, l1, fy, fz;
 };
@@ -159,17 +135,10 @@ __device__ __forceinline__ IsoSample iso_sample(const VolumeDesc &V, const uint3
     IsoSample o;
     o.fy = __builtin_amdgcn_fractf(uy); o.fz = __builtin_amdgcn_fractf(uz);
     if constexpr (PACKED) {
-        CellBits<VOL> cb;
-        if constexpr (SAFE) {
-            ix = med3_i32(ix, -1, (int)V.nx - 1); iy = med3_i32(iy, -1, (int)V.ny - 1); iz = med3_i32(iz, -1, (int)V.nz - 1);
-            cb = load_cell<VOL>(reinterpret_cast<const char *>(V.data) + safe_cell_offset(V, ix, iy, iz));
-        } else {
-            // the loops' tables: cell indices in the skip kernels, byte offsets in the others (cell_kernel_lds)
-            const uint32_t *luty = lut + (V.nx + 3), *lutz = lut + (V.nx + V.ny + 6);
-            const uint32_t idx = lut[ix + 2] + luty[iy + 2] + lutz[iz + 2];
-            cb = load_cell<VOL>(cell_buffer(V.data, (uint32_t)V.max_off + (1u << V.sh_x)), SKIP ? (uint32_t)(idx << V.sh_x) : idx);
-        }
-        xlerp_cell_dx<VOL>(cb, fx, o.c00, o.c10, o.c01, o.c11, o.dx00, o.dx10, o.dx01, o.dx11);
+        if constexpr (SAFE) { ix = med3_i32(ix, -1, (int)V.nx - 1); iy = med3_i32(iy, -1, (int)V.ny - 1); iz = med3_i32(iz, -1, (int)V.nz - 1); }
+        // the loops' tables: cell indices in the skip kernels, byte offsets in the others (cell_kernel_lds)
+        const CellAt ca = cell_at<SKIP, SAFE, false>(V, lut, lut + (V.nx + 3), lut + (V.nx + V.ny + 6), 0u, ix, iy, iz);
+        xlerp_cell_dx<VOL>(load_cell<VOL, SAFE>(cell_buffer(V.data, (uint32_t)V.max_off + (1u << V.sh_x)), ca.cptr, ca.coff), fx, o.c00, o.c10, o.c01, o.c11, o.dx00, o.dx10, o.dx01, o.dx11);
     } else {
         float tp[8];
         linear_taps<VOL>(V, ix, iy, iz, tp);

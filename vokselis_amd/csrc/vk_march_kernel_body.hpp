@@ -11,8 +11,9 @@
 // adaptive-probing policy, the step image, the counters and the trace.  A family's own: its loops -- march / march_stream (vk_march.hpp), or under MIP
 // march_mip / march_mip_stream (vk_march_mip.hpp), which take the window's k1, k2 and umax from *tfd and carry the running maximum U in
 // RayState::A, or under ISO march_iso / march_iso_stream (vk_march_iso.hpp), which take iso_k from *isd and carry the last sample in
-// RayState::A; selected at each call site, since a forwarding wrapper moved registers in the COUNT kernels -- and what the epilogue
-// makes of the ray's sums: under ISO the refinement of the crossing and the shade, once per ray, after the wave's loops have ended.
+// RayState::A, each a frame of its own around the shared parts of vk_march_parts.hpp; selected at each call site, since a forwarding wrapper
+// moved registers -- and what the epilogue makes of the ray's sums: under ISO the refinement of the crossing and
+// the shade, once per ray, after the wave's loops have ended.
     static_assert(VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16 || (!SKIP && SAFE), "linear / bricked layouts: no skip map, clamped indices");
     static_assert(SKIP || WALK == WALK_LOOP, "the closed-form walks are variants of the skip kernels");
     static_assert(!AHEAD || (SKIP && !SAFE), "probe ahead: the skip kernels' fast path");

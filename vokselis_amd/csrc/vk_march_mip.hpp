@@ -1,9 +1,9 @@
 // vk_march_mip.hpp -- the loops of the cell march under the maximum-intensity projection (vk_set_projection(VK_PROJ_MAX); DESIGN.md
 // section 12): march() and march_stream() of vk_march.hpp with another operator on the filtered sample, U = mip_update(U, x) (vk_tf.hpp),
-// the running maximum in table coordinates.  Loops of their own: the compositing loops do not carry the operator; the statement
-// groups they are built from are the same (vk_march_parts.hpp).  Included by vk_march.hpp, after the definitions it shares with
-// that file's loops, and so part of every unit that includes vk_march.hpp; instantiated by raymarch_mip_kernel (vk_launch_mip.hip) alone,
-// through vk_march_kernel_body.hpp under MIP.
+// the running maximum in table coordinates.  The family's own: each loop's frame, condition, skip decision, operator and advance.
+// vk_march_parts.hpp's, and so the isosurface loops' too: the skip bound, cell_at, walk_exact, load_cell / request_cell, the taps and
+// the lerps.  Included by vk_march.hpp, after the definitions it shares with that file's loops, and so part of every unit that
+// includes vk_march.hpp; instantiated by raymarch_mip_kernel (vk_launch_mip.hip) alone, through vk_march_kernel_body.hpp under MIP.
 #pragma once
 
 namespace vk {
@@ -39,49 +39,26 @@ __device__ __forceinline__ bool march_mip(const VolumeDesc &V, RayState &r, cons
         float c00, c10, c01, c11;  // x-lerped corners
         if (PACKED) {
             if (SAFE) { ix = med3_i32(ix, -1, mx); iy = med3_i32(iy, -1, my); iz = med3_i32(iz, -1, mz); }
-            const char *cptr = nullptr;
-            uint32_t d = 0, coff = 0;
-            if (SAFE) {
-                const int64_t off = safe_cell_offset(V, ix, iy, iz);
-                cptr = reinterpret_cast<const char *>(V.data) + off;
-                if (SKIP) d = V.dist[(uint64_t)(off >> V.sh_x) + doff];
-            } else {
-                // cell index (SKIP) / cell byte offset (!SKIP) from the per-axis tables in LDS; entry i + 2 is voxel i
-                const uint32_t idx = lut[ix + 2] + luty[iy + 2] + lutz[iz + 2];
-                coff = SKIP ? (uint32_t)(idx << V.sh_x) : idx;
-                if (SKIP) d = V.dist[idx + doff];
-            }
-            if (SKIP && d != 0) {
+            const CellAt ca = cell_at<SKIP, SAFE>(V, lut, luty, lutz, doff, ix, iy, iz);
+            if (SKIP && ca.d != 0) {
                 if (BOUNDED) cs.skips++;
                 // walks are capped in a trip in which other lanes sample (march(): the samplers pace the trip); any stop is exact
-                const float cap_now = __ballot(d == 0) != 0ull ? walk_cap : walk_cap_all;
+                const float cap_now = __ballot(ca.d == 0) != 0ull ? walk_cap : walk_cap_all;
                 // samples j = 0 .. k - 1 are skipped, k = ceil(min r_i) clamped to [1, iterations left]: p += s, k times, the reference's additions
-                const float rmin = fminf(sb.steps(fx, fy, fz, (float)d), cap_now);
+                const float rmin = fminf(sb.steps(fx, fy, fz, (float)ca.d), cap_now);
                 const int kneg = walk_steps_neg(rmin, nleft);  // -k
                 nleft -= kneg;
                 if (COUNT) { cs.n_iter += (uint32_t)(-kneg); if (wave_leader()) cs.w_inner++; }
-                px = px + sx; py = py + sy; pz = pz + sz;
-                uint32_t m = (uint32_t)(-1 - kneg);  // the steps after the first
-                for (uint32_t q = m >> 2; q != 0u; --q) {
-#pragma unroll
-                    for (int j = 0; j < 4; j++) { px = px + sx; py = py + sy; pz = pz + sz; }
-                    if (COUNT) { if (wave_leader()) cs.w_inner++; }
-                }
-                for (m &= 3u; m != 0u; --m) { px = px + sx; py = py + sy; pz = pz + sz; }
+                walk_exact<COUNT>(px, py, pz, sx, sy, sz, kneg, cs);
                 continue;
             }
-            CellBits<VOL> cb;
-            if (SAFE) cb = load_cell<VOL>(cptr);
-            else cb = load_cell<VOL>(cells, coff);
-            xlerp_cell<VOL>(cb, fx, c00, c10, c01, c11);
+            xlerp_cell<VOL>(load_cell<VOL, SAFE>(cells, ca.cptr, ca.coff), fx, c00, c10, c01, c11);
         } else {
             float tp[8];
             linear_taps<VOL>(V, ix, iy, iz, tp);
             xlerp_taps(tp, fx, c00, c10, c01, c11);
         }
-        const float c0 = fmaf(fy, c10 - c00, c00), c1 = fmaf(fy, c11 - c01, c01);
-        const float x = fmaf(fz, c1 - c0, c0);
-        U = mip_update(U, x, k1, k2, umax);
+        U = mip_update(U, lerp_yz(fy, fz, c00, c10, c01, c11), k1, k2, umax);
         if (COUNT) { cs.n_iter++; cs.n_samp++; if (wave_leader()) cs.w_sample++; }
         px = px + sx; py = py + sy; pz = pz + sz;
         nleft += 1;
@@ -108,19 +85,17 @@ __device__ __forceinline__ bool march_mip_stream(const VolumeDesc &V, RayState &
     {
         const float ux = fmaf(px, fnx, -0.5f), uy = fmaf(py, fny, -0.5f), uz = fmaf(pz, fnz, -0.5f);
         fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);
-        c0 = load_cell<VOL>(cells, (lut[cvt_floor_i32(ux) + 2] + luty[cvt_floor_i32(uy) + 2] + lutz[cvt_floor_i32(uz) + 2]) << lsh);
+        c0 = request_cell<VOL>(cells, lut, luty, lutz, lsh, ux, uy, uz);
     }
-    // one trip: request `nxt` for the advanced position (a clamped table entry, a bounds-checked buffer load: inside the cell array
-    // also one step past the ray's end), evaluate `cur`; returns whether the ray goes on
+    // one trip: request `nxt` for the advanced position (request_cell: safe one step past the ray's end too), evaluate `cur`; returns whether the ray goes on
     auto trip = [&](const CellBits<VOL> &cur, CellBits<VOL> &nxt) -> bool {
         if (COUNT) { cs.n_look++; cs.n_iter++; cs.n_samp++; if (wave_leader()) { cs.w_outer++; cs.w_sample++; } }
         px = px + sx; py = py + sy; pz = pz + sz;
         const float ux = fmaf(px, fnx, -0.5f), uy = fmaf(py, fny, -0.5f), uz = fmaf(pz, fnz, -0.5f);
-        nxt = load_cell<VOL>(cells, (lut[cvt_floor_i32(ux) + 2] + luty[cvt_floor_i32(uy) + 2] + lutz[cvt_floor_i32(uz) + 2]) << lsh);
+        nxt = request_cell<VOL>(cells, lut, luty, lutz, lsh, ux, uy, uz);
         float c00, c10, c01, c11;
         xlerp_cell<VOL>(cur, fx, c00, c10, c01, c11);
-        const float l0 = fmaf(fy, c10 - c00, c00), l1 = fmaf(fy, c11 - c01, c01);
-        U = mip_update(U, fmaf(fz, l1 - l0, l0), k1, k2, umax);
+        U = mip_update(U, lerp_yz(fy, fz, c00, c10, c01, c11), k1, k2, umax);
         left -= 1u;
         fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);
         return left != 0u && U < umax;

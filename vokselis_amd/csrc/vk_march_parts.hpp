@@ -1,14 +1,28 @@
-// vk_march_parts.hpp -- the statement groups the march loops are built from, each written once: the built-in palette and the
-// compositing, the per-ray constants of the skip bound (with the proof of its margins), the cell fetch and x-lerp of the PACKED
-// layouts, the eight taps of the LINEAR layouts, and the fetch and decode of the dense 9^3-brick and quad layouts.
-// Included by vk_march.hpp, and through it by the loops of vk_march_mip.hpp and vk_staged.hpp.  Plain inlined functions that keep
-// the statement order of the sites they replaced: the loops' register allocation follows how their source is factored
-// (DESIGN.md section 12), and tools/isa_diff.py holds every change here to the parent's device code.
+// vk_march_parts.hpp -- the statement groups the march loops are built from, each written once: the loops' counters, the built-in
+// palette and the compositing, the per-ray constants of the skip bound (with the proof of its margins), the cell address, fetch,
+// pipelined request and x-lerp of the PACKED layouts, the exact skip walk, the y/z lerp, the eight taps of the LINEAR layouts, and the
+// fetch and decode of the dense 9^3-brick and quad layouts.  Included by vk_march.hpp, and through it by the loops of vk_march_mip.hpp,
+// vk_march_iso.hpp and vk_staged.hpp.  Plain inlined functions that keep the statement order of the sites they replaced: the loops'
+// register allocation follows how their source is factored (who uses what, and the sites that kept their own
+// text), and tools/isa_diff.py holds every change here to the parent's device code.
 #pragma once
 
 #include "vk_common.hpp"
 
 namespace vk {
+
+// ---- what the loops count -----------------------------------------------------------------------------------------------------
+struct Census {  // SIMT execution census + step counters (COUNT builds only)
+    uint32_t n_iter = 0, n_samp = 0, w_outer = 0, w_inner = 0, w_sample = 0, n_look = 0, n_fb = 0;
+    uint32_t skips = 0;  // trips that skipped (every build: drives the adaptive probing policy)
+    // the built-in skip kernels (COUNT builds): wave-level sample executions in which every sampling lane's alpha came out 0 (the upper bound on what
+    // the lone-speckle codes can take away), and lane-steps those codes proved transparent without a sample
+    uint32_t w_zero = 0, n_proven = 0;
+    // per-trip log of the wave (COUNT builds, debug bit 6; docs/archive/tools/repack_census.py): entry = live lanes | samplers << 7 | samplers whose alpha is
+    // not 0 << 14 | wave-level walk iterations << 21
+    uint32_t *log = nullptr;
+    uint32_t log_cap = 0, trip_no = 0;
+};
 
 // ---- the built-in palette and the compositing (raycast_naive.wgsl:70-81, :108-114) -------------------------------------------
 // vertigo(): 0.5 + 0.5*cos(6.28318*(c*a + d)).  v_cos_f32 takes its argument in revolutions, so the phase is a single fma with
@@ -104,6 +118,59 @@ __device__ __forceinline__ CellBits<VOL> load_cell(const char *cptr) {
     if constexpr (VOL == VOL_P8) { const uint2 c = *reinterpret_cast<const uint2 *>(cptr); cb.v.x = c.x; cb.v.y = c.y; }
     else { const uint4 c = *reinterpret_cast<const uint4 *>(cptr); cb.v.x = c.x; cb.v.y = c.y; cb.v.z = c.z; cb.v.w = c.w; }
     return cb;
+}
+
+// Where voxel (ix, iy, iz)'s cell is, and under DIST its distance byte in the ray's map (`doff`: the octant's offset).  SAFE: the clamped
+// offset as a pointer; otherwise the sum of the per-axis tables in LDS, entry i + 2 is voxel i -- a cell index in the skip kernels'
+// tables (SKIP), a cell byte offset in the others' -- as a byte offset.  (DIST = false: iso_sample, through either kind of table.)
+struct CellAt { const char *cptr = nullptr; uint32_t coff = 0, d = 0; };
+template <bool SKIP, bool SAFE, bool DIST = SKIP>
+__device__ __forceinline__ CellAt cell_at(const VolumeDesc &V, const uint32_t *lut, const uint32_t *luty, const uint32_t *lutz, uint32_t doff, int ix, int iy, int iz) {
+    CellAt c;
+    if (SAFE) {
+        const int64_t off = safe_cell_offset(V, ix, iy, iz);
+        c.cptr = reinterpret_cast<const char *>(V.data) + off;
+        if (DIST) c.d = V.dist[(uint64_t)(off >> V.sh_x) + doff];
+    } else {
+        const uint32_t idx = lut[ix + 2] + luty[iy + 2] + lutz[iz + 2];
+        c.coff = SKIP ? (uint32_t)(idx << V.sh_x) : idx;
+        if (DIST) c.d = V.dist[idx + doff];
+    }
+    return c;
+}
+// ... and the cell there: through the pointer under SAFE, else the bounds-checked buffer load
+template <int VOL, bool SAFE>
+__device__ __forceinline__ CellBits<VOL> load_cell(__amdgpu_buffer_rsrc_t cells, const char *cptr, uint32_t coff) {
+    if constexpr (SAFE) return load_cell<VOL>(cptr);
+    else return load_cell<VOL>(cells, coff);
+}
+
+// The pipelined loops' request: the cell at cell coordinates (ux, uy, uz) through the tables (`lsh`: V.sh_x where they hold cell indices,
+// 0 where byte offsets).  A clamped table entry and a bounds-checked buffer load: inside the cell array also one step past the ray's end.
+template <int VOL>
+__device__ __forceinline__ CellBits<VOL> request_cell(__amdgpu_buffer_rsrc_t cells, const uint32_t *lut, const uint32_t *luty, const uint32_t *lutz,
+                                                      uint32_t lsh, float ux, float uy, float uz) {
+    return load_cell<VOL>(cells, (lut[cvt_floor_i32(ux) + 2] + luty[cvt_floor_i32(uy) + 2] + lutz[cvt_floor_i32(uz) + 2]) << lsh);
+}
+
+// The exact walk over k = -kneg >= 1 skipped samples: p += s, k times, the reference's own additions -- the first, then four per loop
+// iteration (counted by the wave leader under COUNT), then the remainder.  (`cs` whole: a reference to the one counter moved 12 COUNT kernels to class C.)
+template <bool COUNT>
+__device__ __forceinline__ void walk_exact(float &px, float &py, float &pz, float sx, float sy, float sz, int kneg, Census &cs) {
+    px = px + sx; py = py + sy; pz = pz + sz;
+    uint32_t m = (uint32_t)(-1 - kneg);  // the steps after the first
+    for (uint32_t q = m >> 2; q != 0u; --q) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) { px = px + sx; py = py + sy; pz = pz + sz; }
+        if (COUNT) { if (wave_leader()) cs.w_inner++; }
+    }
+    for (m &= 3u; m != 0u; --m) { px = px + sx; py = py + sy; pz = pz + sz; }
+}
+
+// the y and z lerps of the four x-lerped corners: the filtered sample
+__device__ __forceinline__ float lerp_yz(float fy, float fz, float c00, float c10, float c01, float c11) {
+    const float c0 = fmaf(fy, c10 - c00, c00), c1 = fmaf(fy, c11 - c01, c01);
+    return fmaf(fz, c1 - c0, c0);
 }
 
 // x-lerps of one cell: c00, c10, c01, c11 (the four x edges of the footprint), and the four x-differences t1 - t0, t3 - t2,

@@ -1,6 +1,7 @@
 // vk_render.hip -- vk_render / vk_render_partition: one raycast pass into the backbuffer (the reference's
 // RaycastPipeline::record, examples/bonsai/raycast.rs / examples/xor/raycast.rs) -- argument checks, LaunchDesc, kernel choice.
 #include "vk_ctx.hpp"
+#include "vk_launch.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -86,8 +87,7 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
         return fail(ctx, VK_ERR_UNSUPPORTED, "lighting: NAIVE_TRILINEAR renders with lighting need a transfer function (set a table with vk_set_transfer_function, or turn lighting off with vk_set_lighting(NULL))");
     IsoDesc I{};
     if (iso) {
-        const int k = ctx->vol_kind;
-        if (k != VOL_LINEAR_U8 && k != VOL_LINEAR_F16 && k != VOL_P8 && k != VOL_P16 && k != VOL_PF16)
+        if (!has_table_layout(ctx->vol_kind))
             return fail(ctx, VK_ERR_UNSUPPORTED, "isosurface: NAIVE_TRILINEAR renders under an isosurface need a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no isosurface kernels; vk_set_isosurface(NULL) resets)");
         if (flags & VK_RENDER_FAST_WALK) return fail(ctx, VK_ERR_UNSUPPORTED, "isosurface: VK_RENDER_FAST_WALK has no isosurface kernels");
         const char *bad = iso_desc(ctx->iso.iso, ctx->iso.rgb, ctx->iso.refine, ctx->format == VK_FMT_R8_UNORM, I);
@@ -97,8 +97,7 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
     }
     TfDesc T{};
     if (mip || tf) {
-        const int k = ctx->vol_kind;
-        if (k != VOL_LINEAR_U8 && k != VOL_LINEAR_F16 && k != VOL_P8 && k != VOL_P16 && k != VOL_PF16)
+        if (!has_table_layout(ctx->vol_kind))
             return fail(ctx, VK_ERR_UNSUPPORTED, mip ? "projection: NAIVE_TRILINEAR renders under VK_PROJ_MAX need a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no maximum-projection kernels; vk_set_projection(VK_PROJ_COMPOSITE) resets)"
                                                      : "transfer function: NAIVE_TRILINEAR renders with a table need a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no table kernels; vk_set_transfer_function(NULL) resets)");
         if (flags & VK_RENDER_FAST_WALK)
