@@ -267,6 +267,36 @@ typedef struct vk_isosurface {
 int vk_set_isosurface(vk_ctx *ctx, const vk_isosurface *iso);
 int vk_get_isosurface(vk_ctx *ctx, vk_isosurface *out, int *enabled);
 
+/* A clip box (cut-away, region of interest) of the table, lit, MAX and isosurface marches: NAIVE_TRILINEAR rays of those renders march
+ * the box [lo, hi], given in unit-cube coordinates, instead of the unit cube.  intersect_box takes box_min = lo and box_max = hi per
+ * axis, in the same f32 operations:
+ *     inv = 1 / d[i];  a = (lo[i] - o[i]) * inv;  b = (hi[i] - o[i]) * inv;  tmin[i] = fmin(a, b);  tmax[i] = fmax(a, b)
+ *     t0 = max(tmin[0], tmin[1], tmin[2]);  t1 = min(tmax[0], tmax[1], tmax[2])
+ * and everything after it is as without a box: t0 > t1 is a miss, (0, 0, 0, 1); t0 = max(t0, 0); dt comes from the direction and the
+ * volume's dimensions alone; the loop runs for (t = t0; t < t1; t = t + dt) from p = eye + t0 dir; the family's loop and epilogue are
+ * unchanged.  Under an isosurface, "a hit in the ray's first iteration is not refined" now also means the cut face of the clip box.
+ * The box lo = (0, 0, 0), hi = (1, 1, 1) gives bit for bit the frame and the step counts of no box.
+ * box == NULL turns the box off.  VK_ERR_INVALID (the previous box stays in force): a component that is not finite, or
+ * 0 <= lo[i] < hi[i] <= 1 fails on an axis.
+ * The box is host state like lighting, taken into the kernel arguments -- and into the host's screen-space geometry: cull rectangle,
+ * active tiles and tile order follow the box's projected corners -- when a render is recorded: no drain, no map rebuild, it may be set
+ * at any time, between vk_frame_begin and vk_frame_end too (renders recorded before the call keep the old box), and it stays in force
+ * across vk_volume_upload / _upload_device / vk_volume_generate.  The skip maps and vk_volume_empty_fraction do not depend on it.
+ * NAIVE renders of the table, lit, MAX and isosurface kernels honour it (LINEAR, PACKED, PACKED_PAIRS).  A NAIVE render that would
+ * launch the built-in march -- no table, the compositing projection, no isosurface, on any layout -- is VK_ERR_UNSUPPORTED while a box
+ * is set.  COMPUTE_NEAREST and PROCEDURAL ignore it.  vk_partition_active, vk_partition_order, vk_render_partition, vk_render_batch,
+ * vk_untile* and vk_group_render follow the context's box: the ranks of a partition, and the members of a group, need the same box on
+ * every context (as for vk_partition_wire).  vk_tiles_active keeps the unit cube; vk_tiles_active_clip is vk_tiles_active under a box
+ * (NULL: the unit cube; VK_ERR_INVALID for a box vk_set_clip_box would refuse).
+ * vk_get_clip_box: *enabled (may be NULL) says whether one is set; *out (may be NULL) receives it when one is. */
+typedef struct vk_clip_box {
+    float lo[3], hi[3]; /* unit-cube coordinates, 0 <= lo[i] < hi[i] <= 1 */
+} vk_clip_box;          /* 24 bytes */
+int vk_set_clip_box(vk_ctx *ctx, const vk_clip_box *box);
+int vk_get_clip_box(vk_ctx *ctx, vk_clip_box *out, int *enabled);
+int vk_tiles_active_clip(const void *camera144, int mode, uint32_t width, uint32_t height, uint32_t tile_size,
+                         const vk_clip_box *box, unsigned char *active, uint32_t *n_active);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

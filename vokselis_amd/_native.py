@@ -44,6 +44,32 @@ class VkIsosurface(C.Structure):
 
 assert C.sizeof(VkIsosurface) == 20
 
+class VkClipBox(C.Structure):
+    """vk_clip_box (24 bytes): the clip box of the table, lit, MAX and isosurface marches, lo and hi per axis in unit-cube coordinates."""
+    _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
+assert C.sizeof(VkClipBox) == 24
+
+
+def clip_box(lo, hi) -> VkClipBox:
+    """A VkClipBox from two triples, held to vk_set_clip_box's rules before the library sees it: finite components (as f32) and
+    0 <= lo < hi <= 1 on every axis.  Raises ValueError."""
+    import math
+
+    lo, hi = tuple(float(v) for v in lo), tuple(float(v) for v in hi)
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("clip box: lo and hi need three components each")
+    b = VkClipBox()
+    for i in range(3):
+        if not (math.isfinite(lo[i]) and math.isfinite(hi[i])):
+            raise ValueError("clip box: a component is not finite")
+        b.lo[i], b.hi[i] = lo[i], hi[i]
+        if not 0.0 <= b.lo[i] < b.hi[i] <= 1.0:  # (as the library compares them: rounded to f32)
+            raise ValueError("clip box: needs 0 <= lo < hi <= 1 on every axis")
+    return b
+
+
 # every symbol include/vokselis_hip.h declares: name -> (restype, argtypes)
 _u32, _i32, _f32, _vp, _sz = C.c_uint32, C.c_int32, C.c_float, C.c_void_p, C.c_size_t
 SYMBOLS = {
@@ -65,6 +91,8 @@ SYMBOLS = {
     "vk_get_projection": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "vk_set_isosurface": (C.c_int, [_vp, _vp]),  # const vk_isosurface * (VkIsosurface above), NULL: off
     "vk_get_isosurface": (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
+    "vk_set_clip_box": (C.c_int, [_vp, _vp]),  # const vk_clip_box * (VkClipBox above), NULL: off
+    "vk_get_clip_box": (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),
     "vk_set_uniform": (C.c_int, [_vp, _vp]),
     "vk_set_camera": (C.c_int, [_vp, _vp]),
@@ -84,6 +112,7 @@ SYMBOLS = {
     "vk_partition_wire": (C.c_int, [_vp, C.c_int]),
     "vk_wire_pixel_bytes": (C.c_int, [_vp, C.POINTER(_u32)]),
     "vk_tiles_active": (C.c_int, [_vp, C.c_int, _u32, _u32, _u32, C.POINTER(C.c_ubyte), C.POINTER(_u32)]),
+    "vk_tiles_active_clip": (C.c_int, [_vp, C.c_int, _u32, _u32, _u32, _vp, C.POINTER(C.c_ubyte), C.POINTER(_u32)]),  # const vk_clip_box *, NULL: the unit cube
     "vk_partition_root_skip": (C.c_int, [_vp, _u32]),
     "vk_render_partition": (C.c_int, [_vp, C.c_int, _u32, _u32, _u32, _f32, _u32, _vp]),
     "vk_partition_order": (C.c_int, [_vp, C.c_int, _u32, C.POINTER(_u32), _u32]),

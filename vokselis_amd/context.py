@@ -279,6 +279,30 @@ class Context:
         li.ambient, li.diffuse, li.specular, li.shininess = float(ambient), float(diffuse), float(specular), float(shininess)
         N.check(self._h, L.vk_set_lighting(self._h, C.byref(li)))
 
+    def set_clip_box(self, lo, hi=None):
+        """A clip box (cut-away) of the table, lit, MAX and isosurface marches (vk_set_clip_box): NAIVE_TRILINEAR rays march the box
+        lo = (x0, y0, z0) .. hi = (x1, y1, z1), in unit-cube coordinates with 0 <= lo < hi <= 1 per axis, instead of the whole cube.
+        set_clip_box(None) turns it off.  Host state like lighting: it takes effect from the next recorded render and needs no drain; the
+        active tiles and the tile order follow it.  While it is set, NAIVE renders need a transfer function, the "max" projection or an
+        isosurface (the built-in march has no clip kernels); the compute and procedural modes ignore it."""
+        L = N.lib()
+        if lo is None:
+            if hi is not None:
+                raise ValueError("set_clip_box: (lo, hi) or None")
+            N.check(self._h, L.vk_set_clip_box(self._h, None))
+            return
+        if hi is None:
+            raise ValueError("set_clip_box: (lo, hi) or None")
+        b = N.clip_box(lo, hi)
+        N.check(self._h, L.vk_set_clip_box(self._h, C.byref(b)))
+
+    @property
+    def clip_box(self):
+        """The clip box in force as ((x0, y0, z0), (x1, y1, z1)), or None (vk_get_clip_box)."""
+        b, on = N.VkClipBox(), C.c_int(0)
+        N.check(self._h, N.lib().vk_get_clip_box(self._h, C.byref(b), C.byref(on)))
+        return (tuple(b.lo), tuple(b.hi)) if on.value else None
+
     # -- frames in flight: the queue running ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain (src/context.rs:118,252)
     def frames_in_flight(self, k: int):
         """vk_ctx_frames_in_flight: a ring of k frame surfaces, each on its own stream (1: one surface, the default)."""

@@ -80,8 +80,13 @@ int vk_render_batch(vk_ctx *ctx, int mode, uint32_t n_frames, const void *camera
     // at N = 8 (13.6 us of march per frame and rank) needs.
     const int G = n_frames >= 4 ? (int)ctx->order_rays_batch : (int)ctx->order_rays;
     const uint32_t kk[8] = {(uint32_t)geo_mode, ts, ctx->width, ctx->height, ctx->nx, ctx->ny, ctx->nz, (uint32_t)G};
-    std::vector<unsigned char> key(144 + 32);
+    std::vector<unsigned char> key(144 + 32 + 28);
     std::memcpy(key.data() + 144, kk, 32);
+    {   // (the clip box decides the active tiles and the estimate with the camera)
+        uint32_t ck[7];
+        clip_key(ctx, ck);
+        std::memcpy(key.data() + 176, ck, 28);
+    }
     std::vector<uint32_t> actives(n_frames, 0u);
     // Frames whose camera differs from the frame before them each need an order of their own: ~10 us of host arithmetic apiece (hull test of 510
     // tiles, estimate rays, sort).  One GPU hides that behind its 69 us per frame; a rank of 8 marches its share of a frame in ~9 us, and a

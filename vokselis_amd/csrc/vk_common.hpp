@@ -347,6 +347,27 @@ __device__ __forceinline__ void intersect_box(const float o[3], const float d[3]
     t1 = fminf(tmax[0], fminf(tmax[1], tmax[2]));
 }
 
+// The clip box of the table, lit, MAX and isosurface kernels (vk_set_clip_box): a ray marches [lo, hi] per axis instead of the unit cube.
+// By value in the kernel arguments of those families' _clip_ kernels, which the host launches while a box is set.
+struct ClipDesc {
+    float lo[3], hi[3];
+    uint32_t pad[2];
+};
+static_assert(sizeof(ClipDesc) == 32, "ClipDesc is read with scalar loads: 32 bytes");
+// ... and intersect_box with bounds per axis: the same f32 operations, lo[i] and hi[i] for lo and hi
+__device__ __forceinline__ void intersect_box(const float o[3], const float d[3], const float lo[3], const float hi[3], float &t0, float &t1) {
+    float tmin[3], tmax[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        float inv = 1.0f / d[i];
+        float a = (lo[i] - o[i]) * inv, b = (hi[i] - o[i]) * inv;
+        tmin[i] = fminf(a, b);
+        tmax[i] = fmaxf(a, b);
+    }
+    t0 = fmaxf(tmin[0], fmaxf(tmin[1], tmin[2]));
+    t1 = fminf(tmax[0], fminf(tmax[1], tmax[2]));
+}
+
 // raycast_naive.wgsl:63-68.  pow(x, 1/2.4) = exp2(log2(x)/2.4) on the transcendental unit;
 // colour only (never control flow), |err| ~ 1e-6.
 __device__ __forceinline__ float linear_to_srgb(float x) {

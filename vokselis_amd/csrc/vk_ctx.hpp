@@ -69,6 +69,10 @@ struct vk_ctx {
     // gradient lighting of the table march (vk_set_lighting): host state, passed by value to the lit kernels
     bool lit = false;
     vk::LightDesc light{};
+    // clip box of the table, lit, MAX and isosurface marches (vk_set_clip_box): host state like lighting, in unit-cube coordinates; it also
+    // tightens the host's screen-space geometry (vk_order.hip) and is part of the cached orders' keys
+    bool clip_on = false;
+    float clip_lo[3] = {0.0f, 0.0f, 0.0f}, clip_hi[3] = {1.0f, 1.0f, 1.0f};
 
     // uniforms (host copies; passed to kernels by value)
     unsigned char uniform[48] = {0};
@@ -210,7 +214,8 @@ void free_volume(vk_ctx *ctx);   // vk_volume.hip
 void comm_release(vk_ctx *ctx);  // vk_comm.hip
 
 // vk_order.hip: screen-space geometry of a camera, the tile order and its device ring
-void cull_rect_cam(const vk_ctx *ctx, const float *cam, int mode, int32_t r[4]);
+void cull_rect_cam(const vk_ctx *ctx, const float *cam, int mode, int32_t r[4]);  // (rectangle and order below: of the context's clip box, if one is set)
+void clip_key(const vk_ctx *ctx, uint32_t k[7]);  // the clip box as part of a cached order's key
 void compute_tile_order_raw(const vk_ctx *ctx, const float *cam, int mode, int32_t ox, int32_t oy, uint32_t rw, uint32_t rh, uint32_t ts,
                             uint32_t *order, uint32_t *order_pos, uint32_t &order_active, int G);
 int tile_order_update(vk_ctx *ctx, int mode, int32_t ox, int32_t oy, uint32_t rw, uint32_t rh, uint32_t ts, bool need_device);
@@ -227,11 +232,11 @@ uint32_t launch_flags(const vk_ctx *ctx, uint32_t render_flags, bool batch);
 
 // the kernel-instantiating TUs: each launches on ctx->stream and returns; the caller checks hipGetLastError
 void launch_cells(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, bool skip, bool safe, int walk /* vk_march.hpp: WalkKind */);
-void launch_cells_tf(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_tf.hip
-void launch_cells_lit(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::LightDesc &Lt, uint32_t grid, bool count, bool skip,
+void launch_cells_tf(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_tf.hip
+void launch_cells_lit(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::LightDesc &Lt, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool count, bool skip,
                       bool safe);  // vk_launch_lit.hip
-void launch_cells_mip(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_mip.hip (T.rgba == nullptr: the grey ramp)
-void launch_cells_iso(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::IsoDesc &I, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_iso.hip
+void launch_cells_mip(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_mip.hip (T.rgba == nullptr: the grey ramp)
+void launch_cells_iso(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::IsoDesc &I, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_iso.hip
 void launch_staged(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, const float *cam);
 void launch_compute(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, bool records, bool skip);
 void launch_procedural(vk_ctx *ctx, const vk::LaunchDesc &L, uint32_t grid, bool count, float time, bool device_sine);

@@ -130,16 +130,20 @@ VK_HD size_t batch_order_offset(uint32_t n_frames, size_t frame_desc_bytes) { re
 // ---- host-side geometry of a frame (plain host functions) ---------------------------------------------------------------
 constexpr int kModeNaive = 0;  // == VK_MODE_NAIVE_TRILINEAR (include/vokselis_hip.h); the other modes march the [-1, 1]^3 box from the near plane
 
-// Screen-space bounding rectangle of the unit cube (NAIVE mode): the 8 corners projected with
+// The box the NAIVE rays march, in unit-cube coordinates: the unit cube, or the context's clip box (vk_set_clip_box).  The bounds are the
+// kernels' f32 values, held in double.
+struct ClipBox { double lo[3] = {0.0, 0.0, 0.0}, hi[3] = {1.0, 1.0, 1.0}; };
+
+// Screen-space bounding rectangle of the box (NAIVE mode; the unit cube by default): the 8 corners projected with
 // proj_view in double; any corner at or behind the eye plane disables the cull.  Padded by 2 px.
 // Pixels outside [x0,x1) x [y0,y1) cannot hit the box.
-inline void cull_rect_wh(uint32_t W, uint32_t H, const float *cam, int mode, int32_t r[4]) {
+inline void cull_rect_wh(uint32_t W, uint32_t H, const float *cam, int mode, int32_t r[4], const ClipBox &box = ClipBox()) {
     r[0] = 0; r[1] = 0; r[2] = (int32_t)W; r[3] = (int32_t)H;
     if (mode != kModeNaive) return;
     const float *pv = cam + 4;
     double x0 = 1e300, y0 = 1e300, x1 = -1e300, y1 = -1e300;
     for (int c = 0; c < 8; c++) {
-        const double X = c & 1, Y = (c >> 1) & 1, Z = (c >> 2) & 1;
+        const double X = (c & 1) ? box.hi[0] : box.lo[0], Y = (c & 2) ? box.hi[1] : box.lo[1], Z = (c & 4) ? box.hi[2] : box.lo[2];
         const double cx = pv[0] * X + pv[4] * Y + pv[8] * Z + pv[12], cy = pv[1] * X + pv[5] * Y + pv[9] * Z + pv[13];
         const double cw = pv[3] * X + pv[7] * Y + pv[11] * Z + pv[15];
         if (!(cw > 1e-6)) return;
@@ -154,19 +158,19 @@ inline void cull_rect_wh(uint32_t W, uint32_t H, const float *cam, int mode, int
     r[3] = (int32_t)std::max(0.0, std::min((double)H, std::ceil(y1) + 2.0));
 }
 
-// The cube's silhouette on the screen: the convex hull of its 8 projected corners (counter-clockwise in screen
+// The box's silhouette on the screen (the unit cube's by default): the convex hull of its 8 projected corners (counter-clockwise in screen
 // coordinates, y down), in double.  A pixel's ray hits the box only if the pixel centre lies inside it, so a tile that a
 // hull edge separates from it by more than 2 px holds only clear-colour pixels.  The bounding rectangle alone keeps
 // 288 of C2's 510 tiles; the hull keeps the ones a ray can actually hit.  n = 0: no hull (a corner behind the eye
 // plane, or another mode) -- the rectangle decides alone.
 struct CullHull { int n = 0; double x[16], y[16]; };
-inline void cull_hull_wh(uint32_t W, uint32_t H, const float *cam, int mode, CullHull &h) {
+inline void cull_hull_wh(uint32_t W, uint32_t H, const float *cam, int mode, CullHull &h, const ClipBox &box = ClipBox()) {
     h.n = 0;
     if (mode != kModeNaive) return;
     const float *pv = cam + 4;
     std::pair<double, double> p[8];
     for (int c = 0; c < 8; c++) {
-        const double X = c & 1, Y = (c >> 1) & 1, Z = (c >> 2) & 1;
+        const double X = (c & 1) ? box.hi[0] : box.lo[0], Y = (c & 2) ? box.hi[1] : box.lo[1], Z = (c & 4) ? box.hi[2] : box.lo[2];
         const double cx = pv[0] * X + pv[4] * Y + pv[8] * Z + pv[12], cy = pv[1] * X + pv[5] * Y + pv[9] * Z + pv[13];
         const double cw = pv[3] * X + pv[7] * Y + pv[11] * Z + pv[15];
         if (!(cw > 1e-6)) return;
@@ -209,24 +213,45 @@ inline bool tile_is_inactive(const int32_t cr[4], const CullHull &hull, int64_t 
            (hull.n && hull_separates(hull, (double)x0, (double)y0, (double)(x0 + ts), (double)(y0 + ts), 2.0));
 }
 
+// ... under a box: rectangle and hull of the box, and -- when the box is not the unit cube -- of the cube too.  A ray that hits the box hits
+// the cube, so either pair may rule a tile out.  The hull test looks along the hull's own edges only; with both pairs a tile the cube's
+// silhouette rules out stays ruled out under every box: a clip box never activates a tile.
+struct TileCull {
+    int32_t cr[4], cube_cr[4];
+    CullHull hull, cube_hull;
+    bool boxed = false;
+};
+inline void tile_cull_wh(uint32_t W, uint32_t H, const float *cam, int mode, const ClipBox &box, TileCull &c) {
+    cull_rect_wh(W, H, cam, mode, c.cr, box);
+    cull_hull_wh(W, H, cam, mode, c.hull, box);
+    c.boxed = false;
+    for (int k = 0; k < 3; k++) c.boxed = c.boxed || box.lo[k] != 0.0 || box.hi[k] != 1.0;
+    if (c.boxed) {
+        cull_rect_wh(W, H, cam, mode, c.cube_cr);
+        cull_hull_wh(W, H, cam, mode, c.cube_hull);
+    }
+}
+inline bool tile_is_inactive(const TileCull &c, int64_t x0, int64_t y0, uint32_t ts) {
+    return tile_is_inactive(c.cr, c.hull, x0, y0, ts) || (c.boxed && tile_is_inactive(c.cube_cr, c.cube_hull, x0, y0, ts));
+}
+
 // Tiles are dealt to the launch (and, at N > 1, to the ranks) heaviest first.  The frame is ~70 %
 // empty and a dense ray ends after 2 steps while a grazing one takes 513, so with ~10 working waves
 // per SIMD the kernel's tail is set by whichever heavy tiles start last; starting them first (and
 // round-robining them over ranks) shortens it.  The cost estimate is the nominal step count of a
 // G x G grid of rays per tile, from the same camera maths as the kernel, in double precision on the
 // host.  It is only a launch order: every tile is rendered by the same kernel whatever its rank.
-// (W, H): the frame; (ox, oy, rw, rh): the region the launch covers; dims: the volume's.
+// (W, H): the frame; (ox, oy, rw, rh): the region the launch covers; dims: the volume's; box: what the NAIVE rays march (a clip box
+// shortens the estimate's rays and tightens rectangle and hull).
 inline void tile_order(uint32_t W_, uint32_t H_, const uint32_t dims_[3], const float *cam, int mode, int32_t ox, int32_t oy, uint32_t rw, uint32_t rh, uint32_t ts,
-                       uint32_t *order, uint32_t *order_pos, uint32_t &order_active, int G) {
+                       uint32_t *order, uint32_t *order_pos, uint32_t &order_active, int G, const ClipBox &box = ClipBox()) {
     const uint32_t tx = (rw + ts - 1) / ts, ty = (rh + ts - 1) / ts;
     const size_t n = (size_t)tx * ty;
     const double W = W_, H = H_;
     // tiles that do not touch the cube's screen rectangle hold only clear-colour pixels: they sort last (in index
     // order) and are "inactive" -- never marched, never gathered (the root clears them in vk_untile); no rays for them
-    int32_t cr[4];
-    cull_rect_wh(W_, H_, cam, mode, cr);
-    CullHull hull;
-    cull_hull_wh(W_, H_, cam, mode, hull);
+    TileCull cull;
+    tile_cull_wh(W_, H_, cam, mode, box, cull);
     struct Key { double cost; uint32_t tile; };
     std::vector<Key> act;
     act.reserve(n);
@@ -237,18 +262,18 @@ inline void tile_order(uint32_t W_, uint32_t H_, const uint32_t dims_[3], const 
         for (uint32_t i = 0; i < tx; i++) {
             const int64_t x0 = (int64_t)ox + (int64_t)i * ts, y0 = (int64_t)oy + (int64_t)j * ts;
             const uint32_t tile = j * tx + i;
-            if (tile_is_inactive(cr, hull, x0, y0, ts)) { order[n - 1 - n_inactive++] = tile; continue; }  // (reversed below)
+            if (tile_is_inactive(cull, x0, y0, ts)) { order[n - 1 - n_inactive++] = tile; continue; }  // (reversed below)
             double c = 0.0;
             for (int sy = 0; sy < G; sy++)
                 for (int sx = 0; sx < G; sx++) {
                     const double px = (double)x0 + (2 * sx + 1) * ts / (2.0 * G), py = (double)y0 + (2 * sy + 1) * ts / (2.0 * G);
                     if (px < 0 || py < 0 || px >= W || py >= H) continue;
-                    double e[3], d[3], lo, hi;
+                    double e[3], d[3], lo[3], hi[3];
                     if (mode == kModeNaive) {
                         const double X = 2.0 * px / W - 1.0, Y = 1.0 - 2.0 * py / H;
                         const double qw = 1.0 / (m[3] * X + m[7] * Y + m[11] + m[15]);
                         for (int k = 0; k < 3; k++) { e[k] = cam[k]; d[k] = (m[k] * X + m[4 + k] * Y + m[8 + k] + m[12 + k]) * qw - e[k]; }
-                        lo = 0.0; hi = 1.0;
+                        for (int k = 0; k < 3; k++) { lo[k] = box.lo[k]; hi[k] = box.hi[k]; }
                     } else {
                         const double X = 2.0 * px / W - 1.0, Y = (2.0 * py / H - 1.0) * -(H / W);
                         const double aw = 1.0 / (m[3] * X + m[7] * Y + m[15]), bw = 1.0 / (m[3] * X + m[7] * Y + m[11] + m[15]);
@@ -256,14 +281,14 @@ inline void tile_order(uint32_t W_, uint32_t H_, const uint32_t dims_[3], const 
                             e[k] = (m[k] * X + m[4 + k] * Y + m[12 + k]) * aw;
                             d[k] = (m[k] * X + m[4 + k] * Y + m[8 + k] + m[12 + k]) * bw - e[k];
                         }
-                        lo = -1.0; hi = 1.0;
+                        for (int k = 0; k < 3; k++) { lo[k] = -1.0; hi[k] = 1.0; }
                     }
                     const double len2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
                     if (!(len2 > 0)) continue;
                     // steps = (t1 - t0) / dt with t in units of |d| (the normalisation cancels): dt = min_k 1 / (dims_k |d_k|)
                     double t0 = -1e300, t1 = 1e300, inv_dt = 0.0;
                     for (int k = 0; k < 3; k++) {
-                        const double inv = 1.0 / d[k], ta = (lo - e[k]) * inv, tb = (hi - e[k]) * inv;
+                        const double inv = 1.0 / d[k], ta = (lo[k] - e[k]) * inv, tb = (hi[k] - e[k]) * inv;
                         t0 = std::max(t0, std::min(ta, tb));
                         t1 = std::min(t1, std::max(ta, tb));
                         inv_dt = std::max(inv_dt, dims[k] * std::fabs(d[k]));

@@ -16,9 +16,9 @@ template <class... D>
 constexpr bool kernargs_fit = sizeof(LaunchDesc) + sizeof(VolumeDesc) + (sizeof(D) + ... + 0) + 256 <= 4096;
 static_assert(kernargs_fit<>, "raymarch_naive_kernel, the compute kernels: LaunchDesc + VolumeDesc");
 static_assert(kernargs_fit<StagedDesc>, "the staged kernels: LaunchDesc + VolumeDesc + StagedDesc");
-static_assert(kernargs_fit<TfDesc>, "raymarch_tf_kernel, raymarch_mip_kernel: LaunchDesc + VolumeDesc + TfDesc");
-static_assert(kernargs_fit<TfDesc, LightDesc>, "raymarch_lit_kernel: LaunchDesc + VolumeDesc + TfDesc + LightDesc");
-static_assert(kernargs_fit<IsoDesc>, "raymarch_iso_kernel: LaunchDesc + VolumeDesc + IsoDesc");
+static_assert(kernargs_fit<TfDesc, ClipDesc>, "raymarch_tf_kernel, raymarch_mip_kernel and their _clip_ kernels: LaunchDesc + VolumeDesc + TfDesc (+ ClipDesc)");
+static_assert(kernargs_fit<TfDesc, LightDesc, ClipDesc>, "raymarch_lit_kernel, raymarch_lit_clip_kernel: LaunchDesc + VolumeDesc + TfDesc + LightDesc (+ ClipDesc)");
+static_assert(kernargs_fit<IsoDesc, ClipDesc>, "raymarch_iso_kernel, raymarch_iso_clip_kernel: LaunchDesc + VolumeDesc + IsoDesc (+ ClipDesc)");
 
 template <int I>
 using int_tag = std::integral_constant<int, I>;

@@ -473,6 +473,8 @@ __global__ __launch_bounds__(64) void raymarch_naive_kernel(const LaunchDesc L, 
     const TfDesc *tfd = nullptr;
     const LightDesc *ldp = nullptr;
     const IsoDesc *isd = nullptr;
+    constexpr bool CLIP = false;  // (no clip box in this family: vk_render.hip refuses the render)
+    const ClipDesc *clp = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

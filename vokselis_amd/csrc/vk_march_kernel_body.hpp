@@ -4,7 +4,9 @@
 // WALK, AHEAD, OUT, COUNT, the constants TF (a runtime transfer function: vk_set_transfer_function), LIT (gradient lighting:
 // vk_set_lighting), MIP (the maximum-intensity projection: vk_set_projection) and ISO (a first-hit isosurface: vk_set_isosurface),
 // `tfd`, its table (nullptr without one; under MIP the window, whose rgba is nullptr for the grey ramp), `ldp`, its lighting (nullptr
-// without) and `isd`, its isosurface (nullptr without; it brings its own lighting, a runtime flag), and takes its arguments L
+// without), `isd`, its isosurface (nullptr without; it brings its own lighting, a runtime flag), the constant CLIP and `clp`, the clip box
+// (vk_set_clip_box: the _clip_ kernels of the table, lit, MAX and isosurface families; nullptr in the others, whose rays march the unit
+// cube), and takes its arguments L
 // (LaunchDesc) and V (VolumeDesc) by value.  (Shared textually rather than as an inlined function: that moved the register allocation
 // of the existing kernels.)
 // Shared by all five families: the block and pixel mapping, the cull, the index tables in LDS, the ray set-up, the wave priority, the
@@ -20,6 +22,7 @@
     static_assert(!MIP || (!TF && !LIT && WALK == WALK_LOOP && !AHEAD), "the maximum projection: loops of its own, walking with the loop; the table is looked up in the epilogue");
     static_assert(!MIP || (VOL != VOL_B9U8 && VOL != VOL_B9F16 && VOL != VOL_Q8 && VOL != VOL_QF16), "the maximum projection: LINEAR and cell layouts");
     static_assert(!ISO || (!TF && !LIT && !MIP && WALK == WALK_LOOP && !AHEAD), "the isosurface: loops of its own, walking with the loop; refined and shaded in the epilogue");
+    static_assert(!CLIP || TF || MIP || ISO, "the clip box: the table, lit, MAX and isosurface families");
     static_assert(!ISO || (VOL != VOL_B9U8 && VOL != VOL_B9F16 && VOL != VOL_Q8 && VOL != VOL_QF16), "the isosurface: LINEAR and cell layouts");
     if (blockIdx.x >= L.grid_march) { clear_inactive_strip<OUT>(L, blockIdx.x - L.grid_march, threadIdx.x); return; }  // wave-uniform
     const uint32_t lb = logical_block(blockIdx.x);
@@ -63,7 +66,8 @@
     normalize3(dir[0], dir[1], dir[2]);
 
     float t0, t1;
-    intersect_box(eye, dir, 0.0f, 1.0f, t0, t1);
+    if constexpr (CLIP) intersect_box(eye, dir, clp->lo, clp->hi, t0, t1);  // the clip box (vk_set_clip_box): the family's kernels of their own
+    else intersect_box(eye, dir, 0.0f, 1.0f, t0, t1);
     Census cs;
     const bool trip_log = COUNT && L.trace && (L.flags & LF_TRIP_LOG);
     if (trip_log) {  // (the loops of the maximum projection keep no log: such a launch writes neither a log nor stamps)

@@ -17,12 +17,25 @@ using namespace vk;
 // The geometry itself -- cull rectangle, silhouette hull, tile_is_inactive, the heaviest-first order -- lives in vk_hostmath.hpp (pure C++:
 // tests/hostmath_fuzz.cpp runs it under -fsanitize=address,undefined); these are the context-shaped entry points the other TUs call.
 static_assert(vk::kModeNaive == VK_MODE_NAIVE_TRILINEAR, "vk_hostmath.hpp's mode constant");
-void cull_rect_cam(const vk_ctx *ctx, const float *cam, int mode, int32_t r[4]) { vk::cull_rect_wh(ctx->width, ctx->height, cam, mode, r); }
+// what the context's NAIVE rays march: its clip box (vk_set_clip_box), or the unit cube
+static ClipBox ctx_box(const vk_ctx *ctx) {
+    ClipBox b;
+    if (ctx->clip_on)
+        for (int i = 0; i < 3; i++) { b.lo[i] = ctx->clip_lo[i]; b.hi[i] = ctx->clip_hi[i]; }
+    return b;
+}
+void clip_key(const vk_ctx *ctx, uint32_t k[7]) {
+    k[0] = ctx->clip_on ? 1u : 0u;
+    std::memcpy(k + 1, ctx->clip_lo, 12);
+    std::memcpy(k + 4, ctx->clip_hi, 12);
+    if (!ctx->clip_on) std::memset(k + 1, 0, 24);
+}
+void cull_rect_cam(const vk_ctx *ctx, const float *cam, int mode, int32_t r[4]) { vk::cull_rect_wh(ctx->width, ctx->height, cam, mode, r, ctx_box(ctx)); }
 
 void compute_tile_order_raw(const vk_ctx *ctx, const float *cam, int mode, int32_t ox, int32_t oy, uint32_t rw, uint32_t rh, uint32_t ts,
                             uint32_t *order, uint32_t *order_pos, uint32_t &order_active, int G) {
     const uint32_t dims[3] = {ctx->nx, ctx->ny, ctx->nz};
-    vk::tile_order(ctx->width, ctx->height, dims, cam, mode, ox, oy, rw, rh, ts, order, order_pos, order_active, G);
+    vk::tile_order(ctx->width, ctx->height, dims, cam, mode, ox, oy, rw, rh, ts, order, order_pos, order_active, G, ctx_box(ctx));
 }
 
 static void compute_tile_order(const vk_ctx *ctx, const float *cam, int mode, int32_t ox, int32_t oy, uint32_t rw, uint32_t rh, uint32_t ts,
@@ -40,17 +53,20 @@ static void order_note_use(vk_ctx *ctx) {
     ctx->ring_use_frame[ctx->ring_slot] = ctx->fif_open ? ctx->fif[ctx->fif_cur].id : 0;
 }
 
-// The order of the context's camera for a region: computed on the host when the key (camera, region, frame and volume shape) changes, and
+// The order of the context's camera for a region: computed on the host when the key (camera, region, frame and volume shape, clip box) changes, and
 // -- need_device -- uploaded to the next slot of the device ring.  A whole-pixel single-frame launch of up to kOrderInline tiles carries the
 // order in its kernel arguments instead (LaunchDesc::order_inline) and asks for no upload: the copy was a blit kernel of ~10 us in the
 // frame's own stream, on a frame of 140.
 int tile_order_update(vk_ctx *ctx, int mode, int32_t ox, int32_t oy, uint32_t rw, uint32_t rh, uint32_t ts, bool need_device) {
     const uint32_t tx = (rw + ts - 1) / ts, ty = (rh + ts - 1) / ts;
     const size_t n = (size_t)tx * ty;
-    std::vector<unsigned char> key(144 + 40);
+    std::vector<unsigned char> key(144 + 40 + 28);
     std::memcpy(key.data(), ctx->camera, 144);
     const uint32_t kk[10] = {(uint32_t)mode, (uint32_t)ox, (uint32_t)oy, rw, rh, ts, ctx->width, ctx->height, ctx->nx ^ (ctx->ny << 10) ^ (ctx->nz << 20), 0};
     std::memcpy(key.data() + 144, kk, 40);
+    uint32_t ck[7];
+    clip_key(ctx, ck);
+    std::memcpy(key.data() + 184, ck, 28);
     if (!(key == ctx->order_key && ctx->order.size() == n)) {
         compute_tile_order(ctx, ctx->camera, mode, ox, oy, rw, rh, ts, ctx->order, ctx->order_pos, ctx->order_active);
         ctx->order_key = key;
@@ -161,27 +177,41 @@ int vk_partition_slots_weighted(uint32_t width, uint32_t height, uint32_t tile_s
 // Which tiles of a width x height frame can hold a pixel whose ray hits the volume's box under this camera: the decision
 // every partition makes (inactive tiles are never marched nor gathered; the root clears them).  Pure host arithmetic, no
 // context: active[tile] (row-major, tiles_x * tiles_y bytes) is 1 or 0.
-int vk_tiles_active(const void *camera144, int mode, uint32_t width, uint32_t height, uint32_t tile_size, unsigned char *active, uint32_t *n_active) {
+static int tiles_active(const void *camera144, int mode, uint32_t width, uint32_t height, uint32_t tile_size, const ClipBox &box, unsigned char *active, uint32_t *n_active) {
     if (!camera144 || !active || tile_size == 0 || (tile_size & 7u) || width == 0 || height == 0) return VK_ERR_INVALID;
     if (mode != VK_MODE_NAIVE_TRILINEAR && mode != VK_MODE_COMPUTE_NEAREST && mode != VK_MODE_PROCEDURAL) return VK_ERR_INVALID;
     float cam[36];
     std::memcpy(cam, camera144, 144);
     for (float v : cam) if (!std::isfinite(v)) return VK_ERR_INVALID;
     const int geo_mode = mode == VK_MODE_PROCEDURAL ? VK_MODE_COMPUTE_NEAREST : mode;
-    int32_t cr[4];
-    cull_rect_wh(width, height, cam, geo_mode, cr);
-    CullHull hull;
-    cull_hull_wh(width, height, cam, geo_mode, hull);
+    TileCull cull;
+    tile_cull_wh(width, height, cam, geo_mode, box, cull);
     const uint32_t tx = (width + tile_size - 1) / tile_size, ty = (height + tile_size - 1) / tile_size;
     uint32_t n = 0;
     for (uint32_t j = 0; j < ty; j++)
         for (uint32_t i = 0; i < tx; i++) {
-            const bool on = !tile_is_inactive(cr, hull, (int64_t)i * tile_size, (int64_t)j * tile_size, tile_size);
+            const bool on = !tile_is_inactive(cull, (int64_t)i * tile_size, (int64_t)j * tile_size, tile_size);
             active[(size_t)j * tx + i] = on ? 1 : 0;
             n += on;
         }
     if (n_active) *n_active = n;
     return VK_OK;
+}
+
+int vk_tiles_active(const void *camera144, int mode, uint32_t width, uint32_t height, uint32_t tile_size, unsigned char *active, uint32_t *n_active) {
+    return tiles_active(camera144, mode, width, height, tile_size, ClipBox(), active, n_active);
+}
+
+// ... under a clip box (vk_set_clip_box's rules; NULL: the unit cube, i.e. vk_tiles_active): what a partition of a context with that box decides
+int vk_tiles_active_clip(const void *camera144, int mode, uint32_t width, uint32_t height, uint32_t tile_size, const vk_clip_box *box, unsigned char *active,
+                         uint32_t *n_active) {
+    ClipBox b;
+    if (box)
+        for (int i = 0; i < 3; i++) {
+            if (!std::isfinite(box->lo[i]) || !std::isfinite(box->hi[i]) || !(0.0f <= box->lo[i] && box->lo[i] < box->hi[i] && box->hi[i] <= 1.0f)) return VK_ERR_INVALID;
+            b.lo[i] = box->lo[i] + 0.0f; b.hi[i] = box->hi[i];
+        }
+    return tiles_active(camera144, mode, width, height, tile_size, b, active, n_active);
 }
 
 int vk_partition_root_skip(vk_ctx *ctx, uint32_t root_skip) {

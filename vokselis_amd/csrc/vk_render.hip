@@ -85,6 +85,12 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
     // gradient lighting (vk_set_lighting) shades the table's colour: it has no kernels without a table
     if (mode == VK_MODE_NAIVE_TRILINEAR && ctx->lit && !tf && !mip && !iso)
         return fail(ctx, VK_ERR_UNSUPPORTED, "lighting: NAIVE_TRILINEAR renders with lighting need a transfer function (set a table with vk_set_transfer_function, or turn lighting off with vk_set_lighting(NULL))");
+    // a clip box (vk_set_clip_box) is an argument of the table, lit, MAX and isosurface kernels: the built-in family has none
+    if (mode == VK_MODE_NAIVE_TRILINEAR && ctx->clip_on && !tf && !mip && !iso)
+        return fail(ctx, VK_ERR_UNSUPPORTED, "clip box: NAIVE_TRILINEAR renders under a clip box need a transfer function, VK_PROJ_MAX or an isosurface (the built-in march has no clip kernels; vk_set_clip_box(NULL) resets)");
+    ClipDesc Cb{};
+    for (int i = 0; i < 3; i++) { Cb.lo[i] = ctx->clip_lo[i]; Cb.hi[i] = ctx->clip_hi[i]; }
+    const ClipDesc *Cl = mode == VK_MODE_NAIVE_TRILINEAR && ctx->clip_on ? &Cb : nullptr;  // nullptr: the kernels without a box
     IsoDesc I{};
     if (iso) {
         if (!has_table_layout(ctx->vol_kind))
@@ -149,10 +155,10 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
             if (V.max_off + 16 < (1ll << 32) && cell_lut_bytes(ctx->nx, ctx->ny, ctx->nz) <= 16384u && 64.0f * ulp < 0.25f / nmax && !(flags & VK_RENDER_SAFE)) safe = false;
         }
         if (ctx->vol_kind == VOL_S8U8 || ctx->vol_kind == VOL_S8F16) launch_staged(ctx, L, V, grid, count, reach_cam);
-        else if (iso) launch_cells_iso(ctx, L, V, I, grid, count, skip, safe);
-        else if (mip) launch_cells_mip(ctx, L, V, T, grid, count, skip, safe);
-        else if (tf && ctx->lit) launch_cells_lit(ctx, L, V, T, ctx->light, grid, count, skip, safe);
-        else if (tf) launch_cells_tf(ctx, L, V, T, grid, count, skip, safe);
+        else if (iso) launch_cells_iso(ctx, L, V, I, Cl, grid, count, skip, safe);
+        else if (mip) launch_cells_mip(ctx, L, V, T, Cl, grid, count, skip, safe);
+        else if (tf && ctx->lit) launch_cells_lit(ctx, L, V, T, ctx->light, Cl, grid, count, skip, safe);
+        else if (tf) launch_cells_tf(ctx, L, V, T, Cl, grid, count, skip, safe);
         else launch_cells(ctx, L, V, grid, count, skip, safe, (flags & VK_RENDER_FAST_WALK) ? 2 : 0);  // (vk_march.hpp: WalkKind)
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -270,6 +276,32 @@ int vk_set_lighting(vk_ctx *ctx, const vk_lighting *light) {
         return fail(ctx, VK_ERR_INVALID, std::string("vk_set_lighting: ") + why);
     ctx->light = D;
     ctx->lit = true;
+    return VK_OK;
+}
+
+// The clip box is host state like lighting: dispatch_march takes it into the kernel arguments and vk_order.hip into the frame's screen-space
+// geometry when a render is recorded.  No drain, no map rebuild; the cached tile orders carry it in their keys.
+int vk_set_clip_box(vk_ctx *ctx, const vk_clip_box *box) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (!box) {
+        ctx->clip_on = false;
+        return VK_OK;
+    }
+    for (int i = 0; i < 3; i++) {
+        if (!std::isfinite(box->lo[i]) || !std::isfinite(box->hi[i])) return fail(ctx, VK_ERR_INVALID, "vk_set_clip_box: a component is not finite");
+        if (!(0.0f <= box->lo[i] && box->lo[i] < box->hi[i] && box->hi[i] <= 1.0f))
+            return fail(ctx, VK_ERR_INVALID, "vk_set_clip_box: needs 0 <= lo < hi <= 1 on every axis");
+    }
+    for (int i = 0; i < 3; i++) { ctx->clip_lo[i] = box->lo[i] + 0.0f; ctx->clip_hi[i] = box->hi[i]; }  // (+ 0: a -0 bound is stored as +0)
+    ctx->clip_on = true;
+    return VK_OK;
+}
+
+int vk_get_clip_box(vk_ctx *ctx, vk_clip_box *out, int *enabled) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (enabled) *enabled = ctx->clip_on ? 1 : 0;
+    if (out && ctx->clip_on)
+        for (int i = 0; i < 3; i++) { out->lo[i] = ctx->clip_lo[i]; out->hi[i] = ctx->clip_hi[i]; }
     return VK_OK;
 }
 

@@ -171,6 +171,7 @@ struct Uniform {
 };
 static_assert(sizeof(Uniform) == 48, "Uniform is 48 bytes (src/context/global_ubo.rs:52-65)");
 static_assert(sizeof(vk_isosurface) == 20, "vk_isosurface is 20 bytes (vk_set_isosurface)");
+static_assert(sizeof(vk_clip_box) == 24, "vk_clip_box is 24 bytes (vk_set_clip_box)");
 
 // src/context/hdr_backbuffer.rs:10-11
 struct HdrBackBuffer {
@@ -245,6 +246,9 @@ class Context {
     bool isosurface(vk_isosurface *out = nullptr) const { int on = 0; check(ctx_, vk_get_isosurface(ctx_, out, &on)); return on != 0; }
     // Gradient lighting of the table march (vk_set_lighting); nullptr turns it off.
     void set_lighting(const vk_lighting *light) { check(ctx_, vk_set_lighting(ctx_, light)); }
+    // Clip box (cut-away) of the table, lit, MAX and isosurface marches, in unit-cube coordinates (vk_set_clip_box); nullptr turns it off.
+    void set_clip_box(const vk_clip_box *box) { check(ctx_, vk_set_clip_box(ctx_, box)); }
+    bool clip_box(vk_clip_box *out = nullptr) const { int on = 0; check(ctx_, vk_get_clip_box(ctx_, out, &on)); return on != 0; }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
     void frames_in_flight(uint32_t k) { check(ctx_, vk_ctx_frames_in_flight(ctx_, k)); }
