@@ -36,8 +36,14 @@ enum vk_status {
 };
 
 /* src/context/volume_texture.rs:39-47 (R8Unorm), SURVEY C4 (R16Float),
- * examples/xor/xor_compute.rs:94-118 (two rgba16float storage textures). */
-enum vk_volume_format { VK_FMT_R8_UNORM = 0, VK_FMT_R16_FLOAT = 1, VK_FMT_RGBA16F_PAIR = 2 };
+ * examples/xor/xor_compute.rs:94-118 (two rgba16float storage textures).
+ * R16_UNORM (wgpu's R16Unorm): `host` is the dense x-fastest array of native-endian uint16_t, the shader-side value
+ * of a tap t is t / 65535, and the kernels filter the integer taps (S = 65535; every u16 is exact in f32) -- the 12- and 16-bit data
+ * of CT / MR scans, which R8 requantises and R16F holds exactly only up to 2048.  NAIVE_TRILINEAR only, every family (built-in, table,
+ * lit, MAX, isosurface, clip box); layouts LINEAR and PACKED (AUTO: PACKED wherever an R16F volume of the dimensions gets PACKED,
+ * LINEAR where that volume would be STAGED); PACKED_PAIRS / BRICKED / QUADS / STAGED, vk_volume_generate and VK_RENDER_FAST_WALK are
+ * VK_ERR_UNSUPPORTED with it. */
+enum vk_volume_format { VK_FMT_R8_UNORM = 0, VK_FMT_R16_FLOAT = 1, VK_FMT_RGBA16F_PAIR = 2, VK_FMT_R16_UNORM = 3 };
 
 /* raycast_naive.wgsl fs_main vs raycast_compute.wgsl render()/get_col2 */
 enum vk_mode {
@@ -151,15 +157,15 @@ int vk_volume_generate(vk_ctx *ctx, int kind, uint32_t nx, uint32_t ny, uint32_t
  * filling the two rgba16float storage textures (density, normals) the compute raycast reads. */
 int vk_volume_generate_xor(vk_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, float time);
 /* Share of the cells that are exactly transparent under the transfer function (packed layouts).  Built-in transfer: a cell
- * is empty iff each of its 8 taps is (R8: <= 25; R16F: finite and <= 0.1 -- a NaN or infinite tap is never empty). */
+ * is empty iff each of its 8 taps is (R8: <= 25; R16_UNORM: <= 6553; R16F: finite and <= 0.1 -- a NaN or infinite tap is never empty). */
 int vk_volume_empty_fraction(vk_ctx *ctx, double *fraction);
 int vk_volume_info(vk_ctx *ctx, uint32_t dims[3], int *format, int *layout, size_t *device_bytes);
 
 /* Runtime transfer function of VK_MODE_NAIVE_TRILINEAR: a context-wide RGBA table that replaces the built-in transfer and
  * palette (min(0.9, v), smoothstep, the cosine "vertigo" palette: raycast_naive.wgsl:104-110) until it is reset.
  * rgba: n entries of 4 floats (r, g, b, a), not premultiplied, alpha in [0, 1], spread evenly over the sample values
- * [lo, hi] (R8 volumes: the normalised value, as the shader sees it; R16F: the value).  Per step, with x the filtered sample
- * on the kernel's scale (R8: 0..255, S = 255; R16F: the value, S = 1) and k1 = (n-1) / ((hi-lo) S), k2 = -lo (n-1) / (hi-lo)
+ * [lo, hi] (R8 and R16_UNORM volumes: the normalised value, as the shader sees it; R16F: the value).  Per step, with x the filtered sample
+ * on the kernel's scale (R8: 0..255, S = 255; R16_UNORM: 0..65535, S = 65535; R16F: the value, S = 1) and k1 = (n-1) / ((hi-lo) S), k2 = -lo (n-1) / (hi-lo)
  * rounded once to f32:  u = min(max(fma(x, k1, k2), 0), n-1);  i = min(floor(u), n-2);  c = lerp(T[i], T[i+1], u - i);
  * w = (1 - A) c.a;  C += w c.rgb;  A += w  -- the early-out, the sRGB step and the miss colour as without a table.
  * The skip maps and vk_volume_empty_fraction follow the table: a cell is empty iff its taps are finite and every entry
@@ -224,7 +230,7 @@ int vk_get_projection(vk_ctx *ctx, int *projection);
  * NAIVE_TRILINEAR renders are isosurface renders: the transfer table and the projection are ignored (they stay stored --
  * vk_get_projection still reports the stored projection -- and are in force again after vk_set_isosurface(ctx, NULL)); lighting
  * (vk_set_lighting) is honoured, with or without a table.  COMPUTE_NEAREST and PROCEDURAL ignore it.
- * iso_k is the threshold on the kernel's scale, rounded once to f32: R8: iso * 255.0f; R16F: iso.  For a pixel whose ray hits the
+ * iso_k is the threshold on the kernel's scale, rounded once to f32: R8: iso * 255.0f; R16_UNORM: iso * 65535.0f; R16F: iso.  For a pixel whose ray hits the
  * box, ray, box, t0 = max(t0, 0), dt, p = eye + t0 dir and s = dir * dt are as without an isosurface, and
  *     hit = false; j = 0
  *     for (t = t0; t < t1; t = t + dt) {           the reference's loop
@@ -260,7 +266,7 @@ int vk_get_projection(vk_ctx *ctx, int *projection);
  * vk_get_isosurface: *enabled (may be NULL) says whether one is set; *out (may be NULL) receives it when one is. */
 #define VK_ISO_MAX_REFINE 16
 typedef struct vk_isosurface {
-    float iso;       /* threshold in sample values, the units of vk_set_transfer_function's lo / hi (R8: the normalised value; R16F: the value) */
+    float iso;       /* threshold in sample values, the units of vk_set_transfer_function's lo / hi (R8, R16_UNORM: the normalised value; R16F: the value) */
     float rgb[3];    /* linear surface colour, not premultiplied; finite, |c| <= VK_TF_MAX_COLOUR */
     uint32_t refine; /* bisection steps R at the hit, 0 .. VK_ISO_MAX_REFINE */
 } vk_isosurface;     /* 20 bytes */

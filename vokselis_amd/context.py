@@ -198,7 +198,7 @@ class Context:
     def set_transfer_function(self, table, domain=(0.0, 1.0)):
         """Runtime transfer function of MODE_NAIVE_TRILINEAR (vk_set_transfer_function): `table` is an (n, 4) float32 array of RGBA
         entries (not premultiplied, alpha in [0, 1], 2 <= n <= 256) spread evenly over the sample values `domain` = (lo, hi) -- normalised
-        values for R8 volumes, values for R16F.  It replaces the built-in transfer and palette (raycast_naive.wgsl:104-110) until
+        values for R8 and R16_UNORM volumes, values for R16F.  It replaces the built-in transfer and palette (raycast_naive.wgsl:104-110) until
         `table` is None, which resets.  Drains the frames in flight and rebuilds the skip maps of the current volume."""
         L = N.lib()
         if table is None:
@@ -231,7 +231,7 @@ class Context:
 
     def set_isosurface(self, iso, colour=(1.0, 1.0, 1.0), refine=4):
         """First-hit isosurface rendering of MODE_NAIVE_TRILINEAR (vk_set_isosurface): a ray stops at its first sample at or above
-        `iso` (in sample values: normalised for R8 volumes, values for R16F), the crossing is refined by `refine` bisection steps
+        `iso` (in sample values: normalised for R8 and R16_UNORM volumes, values for R16F), the crossing is refined by `refine` bisection steps
         (0 .. 16) and the surface of linear colour `colour` is shaded by set_lighting's light, if one is set.  While set, the transfer
         table and the projection are ignored (they stay stored); None turns it off and brings them back.  Drains the frames in flight
         and rebuilds the skip maps of the current volume."""
@@ -468,18 +468,29 @@ def transfer_table(points, n: int = 256) -> np.ndarray:
 
 
 class VolumeTexture:
-    """src/context/volume_texture.rs:32-89: uploads the dense x-fastest volume ([nz,ny,nx])."""
+    """src/context/volume_texture.rs:32-89: uploads the dense x-fastest volume ([nz,ny,nx]).
 
-    def __init__(self, ctx: Context, data: np.ndarray, data2: np.ndarray | None = None, layout: int = N.LAYOUT_AUTO):
+    fmt=None infers the format from the array: u8 -> R8_UNORM, f16 -> R16_FLOAT, and a uint16 array is taken as f16 BIT PATTERNS
+    (R16_FLOAT), as it always was.  16-bit integer data (CT / MR scans) is uploaded with fmt=FMT_R16_UNORM, which takes a 3-D
+    np.uint16 array and nothing else; any other explicit fmt must be the one the array would infer."""
+
+    def __init__(self, ctx: Context, data: np.ndarray, data2: np.ndarray | None = None, layout: int = N.LAYOUT_AUTO, fmt: int | None = None):
         vol = np.ascontiguousarray(data)
         if vol.dtype == np.uint8 and vol.ndim == 3:
-            fmt = N.FMT_R8_UNORM
+            inferred = N.FMT_R8_UNORM
         elif vol.dtype in (np.float16, np.uint16) and vol.ndim == 3:
-            fmt = N.FMT_R16_FLOAT
+            inferred = N.FMT_R16_FLOAT
         elif vol.dtype in (np.float16, np.uint16) and vol.ndim == 4 and vol.shape[3] == 4 and data2 is not None:
-            fmt = N.FMT_RGBA16F_PAIR
+            inferred = N.FMT_RGBA16F_PAIR
         else:
             raise ValueError("volume must be u8[nz,ny,nx], f16[nz,ny,nx] or a pair of f16[nz,ny,nx,4]")
+        if fmt == N.FMT_R16_UNORM:
+            if vol.dtype != np.uint16 or vol.ndim != 3 or data2 is not None:
+                raise ValueError("fmt=FMT_R16_UNORM takes one np.uint16 array [nz,ny,nx]")
+        elif fmt is not None and fmt != inferred:
+            raise ValueError("fmt=%r does not match the array (dtype %s, %d-D): pass fmt=None, or FMT_R16_UNORM with a uint16 array" % (fmt, vol.dtype, vol.ndim))
+        else:
+            fmt = inferred
         nz, ny, nx = vol.shape[:3]
         v2 = None
         if data2 is not None:
@@ -492,13 +503,17 @@ class VolumeTexture:
         self.format = fmt
 
     @classmethod
-    def from_raw(cls, ctx: Context, path: str, dims=(256, 256, 256), layout: int = N.LAYOUT_AUTO) -> "VolumeTexture":
-        """Drop-in for the reference's `bonsai_256x256x256_uint8.raw` (absent from the checkout, F3)."""
+    def from_raw(cls, ctx: Context, path: str, dims=(256, 256, 256), layout: int = N.LAYOUT_AUTO, dtype=np.uint8) -> "VolumeTexture":
+        """Drop-in for the reference's `bonsai_256x256x256_uint8.raw` (absent from the checkout, F3).  dtype=np.uint16: a raw file of
+        native-endian 16-bit integers, uploaded as R16_UNORM."""
         nx, ny, nz = dims
-        raw = np.fromfile(path, dtype=np.uint8)
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+            raise ValueError("from_raw: dtype is np.uint8 or np.uint16")
+        raw = np.fromfile(path, dtype=dtype)
         if raw.size != nx * ny * nz:
-            raise ValueError(f"{path}: expected {nx * ny * nz} bytes, found {raw.size}")
-        return cls(ctx, raw.reshape(nz, ny, nx), layout=layout)
+            raise ValueError(f"{path}: expected {nx * ny * nz * dtype.itemsize} bytes, found {raw.size * dtype.itemsize}")
+        return cls(ctx, raw.reshape(nz, ny, nx), layout=layout, fmt=N.FMT_R16_UNORM if dtype == np.uint16 else None)
 
     @classmethod
     def generate(cls, ctx: Context, kind: int, dims, fmt=N.FMT_R8_UNORM, seed=0x5EED0001, lo=20, span=12,

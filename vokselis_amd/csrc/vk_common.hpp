@@ -36,7 +36,7 @@ constexpr int kBrickCells = 64;
 constexpr int kDistRadius = 24;  // distance map saturates at kDistRadius + 1
 
 // P8: 8 u8 taps (8 B).  P16: u8 volume as 4 x (tap, delta = next_x_tap - tap) f16 pairs (16 B).
-// PF16: f16 volume, 8 f16 taps (16 B).
+// PF16: f16 volume, 8 f16 taps (16 B).  PU16: R16_UNORM volume, 8 u16 taps (16 B) in PF16's tap order.
 // B9U8 / B9F16: dense voxels in 8^3 bricks stored with a one-voxel apron on the low side (9^3 = 729
 // voxels, clamp-to-edge baked in): brick b holds voxels [8b-1, 8b+7] per axis, so the 8 taps of any
 // sample come from ONE brick at fixed local offsets (+1, +9, +81).  1.42x the dense bytes instead
@@ -50,7 +50,10 @@ constexpr int kDistRadius = 24;  // distance map saturates at kDistRadius + 1
 // PAIRB: the two rgba16f volumes of the compute mode interleaved as 16-byte (density, normals) records in
 // 4^3 bricks: one nearest-neighbour step is ONE aligned 16-byte load.
 // S8U8 / S8F16: dense 8^3 bricks without apron, staged through LDS by the wave (vk_staged.hpp).
-enum VolKind : int { VOL_LINEAR_U8 = 0, VOL_LINEAR_F16 = 1, VOL_P8 = 2, VOL_P16 = 3, VOL_PF16 = 4, VOL_B9U8 = 5, VOL_B9F16 = 6, VOL_PAIRB = 7, VOL_Q8 = 8, VOL_QF16 = 9, VOL_S8U8 = 10, VOL_S8F16 = 11 };
+enum VolKind : int { VOL_LINEAR_U8 = 0, VOL_LINEAR_F16 = 1, VOL_P8 = 2, VOL_P16 = 3, VOL_PF16 = 4, VOL_B9U8 = 5, VOL_B9F16 = 6, VOL_PAIRB = 7, VOL_Q8 = 8, VOL_QF16 = 9, VOL_S8U8 = 10, VOL_S8F16 = 11, VOL_LINEAR_U16 = 12, VOL_PU16 = 13 };
+// the cell layouts (PACKED, PACKED_PAIRS): one aligned load per sample, skip maps, index tables; and the kinds of an R16_UNORM volume
+constexpr bool is_cell_layout(int VOL) { return VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16 || VOL == VOL_PU16; }
+constexpr bool is_u16_kind(int VOL) { return VOL == VOL_LINEAR_U16 || VOL == VOL_PU16; }
 enum OutKind : int { OUT_RGBA32F = 0, OUT_RGBA16F = 1 };
 
 struct VolumeDesc {
@@ -379,16 +382,20 @@ __device__ __forceinline__ float linear_to_srgb(float x) {
 // raycast_naive.wgsl:106-107 -- bit-exact with vo_transfer_alpha: min(x, c), then smoothstep's affine map as ONE
 // fused op whose constants carry the scale of x, then t*t*(3 - 2t).  SCALE 0: x is a value (f16 volumes); 1: filtered
 // R8Unorm taps on their 0..255 scale; 2: the same times 2^-24 (the staged kernel's u8 taps enter the filter as f16
-// subnormals; a power of two folds into c and k1 exactly).  5 VALU (min, fma+clamp, mul, fma, mul).
+// subnormals; a power of two folds into c and k1 exactly); 3: filtered R16Unorm taps on their 0..65535 scale (0.9 * 65535 = 58981.5
+// is exact in f32).  5 VALU (min, fma+clamp, mul, fma, mul).
 template <int SCALE>
 __device__ __forceinline__ float transfer_alpha(float x) {
     constexpr float k2 = (float)(-0.1 / 1.1);
-    constexpr float c = SCALE == 0 ? 0.9f : (SCALE == 1 ? 229.5f : 229.5f * 0x1p-24f);
-    constexpr float k1 = SCALE == 0 ? (float)(1.0 / 1.1) : (SCALE == 1 ? (float)(1.0 / (255.0 * 1.1)) : (float)(1.0 / (255.0 * 1.1)) * 16777216.0f);
+    constexpr float c = SCALE == 0 ? 0.9f : (SCALE == 1 ? 229.5f : (SCALE == 3 ? 58981.5f : 229.5f * 0x1p-24f));
+    constexpr float k1 = SCALE == 0 ? (float)(1.0 / 1.1) : (SCALE == 1 ? (float)(1.0 / (255.0 * 1.1)) : (SCALE == 3 ? (float)(1.0 / (65535.0 * 1.1)) : (float)(1.0 / (255.0 * 1.1)) * 16777216.0f));
     float s = fmaf(fminf(x, c), k1, k2);
     s = fminf(fmaxf(s, 0.0f), 1.0f);
     return (s * s) * fmaf(-2.0f, s, 3.0f);
 }
+
+// the SCALE of a layout's filtered samples
+constexpr int transfer_scale(int VOL) { return is_u16_kind(VOL) ? 3 : ((VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_LINEAR_U8 || VOL == VOL_B9U8) ? 1 : 0); }
 
 __device__ __forceinline__ float h2f(uint32_t bits16) {
     union { uint16_t u; _Float16 h; } c;

@@ -203,6 +203,9 @@ inline int fail(vk_ctx *ctx, int code, const std::string &msg) {
 inline uint32_t frames_concurrent(const vk_ctx *ctx) { return ctx->fif_concurrent ? ctx->fif_concurrent : (ctx->fif_k >= 3u ? ctx->fif_k - 1u : ctx->fif_k); }
 inline bool frames_crowded(const vk_ctx *ctx) { return ctx->fif_open && ctx->fif_k > 1u && frames_concurrent(ctx) >= 3u; }
 
+// the kernel's scale of a scalar volume format (vk_tf.hpp)
+inline vk::SampleScale format_scale(int format) { return format == VK_FMT_R8_UNORM ? vk::SCALE_R8 : (format == VK_FMT_R16_UNORM ? vk::SCALE_U16 : vk::SCALE_VALUE); }
+
 inline size_t px_bytes(int fmt) { return fmt == VK_OUT_RGBA16F ? 8 : 16; }
 // a pixel of a partition's compact tiles: the backbuffer's pixel, or its three colour channels (VK_WIRE_RGB)
 inline size_t wire_px_bytes(int fmt, int wire) { return wire == VK_WIRE_RGB ? px_bytes(fmt) / 4 * 3 : px_bytes(fmt); }
@@ -237,6 +240,14 @@ void launch_cells_lit(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc
                       bool safe);  // vk_launch_lit.hip
 void launch_cells_mip(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_mip.hip (T.rgba == nullptr: the grey ramp)
 void launch_cells_iso(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::IsoDesc &I, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_iso.hip
+// vk_launch_u16_*.hip: the same five families on an R16_UNORM volume (vk_march_u16.hpp); a family reads its own descriptors, Cl == nullptr: no box
+#define VK_U16_LAUNCH(name) void name(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::LightDesc &Li, const vk::IsoDesc &I, const vk::ClipDesc *Cl, uint32_t grid, bool count, bool skip, bool safe)
+VK_U16_LAUNCH(launch_u16_cells);
+VK_U16_LAUNCH(launch_u16_tf);
+VK_U16_LAUNCH(launch_u16_lit);
+VK_U16_LAUNCH(launch_u16_mip);
+VK_U16_LAUNCH(launch_u16_iso);
+#undef VK_U16_LAUNCH
 void launch_staged(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, const float *cam);
 void launch_compute(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, uint32_t grid, bool count, bool records, bool skip);
 void launch_procedural(vk_ctx *ctx, const vk::LaunchDesc &L, uint32_t grid, bool count, float time, bool device_sine);

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "vk_light.hpp"
+#include "vk_tf.hpp"  // SampleScale
 
 #if defined(__HIPCC__)
 #define VK_ISO_HD __host__ __device__ __forceinline__
@@ -41,8 +42,10 @@ struct IsoDesc {
 };
 static_assert(sizeof(IsoDesc) == 56, "IsoDesc: six words and a LightDesc");
 
-// The threshold on the kernel's scale, rounded once to f32: R8 volumes filter their taps on 0..255, R16F volumes their values.
-VK_ISO_HD float iso_k(float iso, bool r8) { return r8 ? iso * 255.0f : iso; }
+// The threshold on the kernel's scale, rounded once to f32: R8 volumes filter their taps on 0..255, R16_UNORM volumes on 0..65535, R16F
+// volumes their values.
+VK_ISO_HD float iso_k(float iso, SampleScale s) { return s == SCALE_R8 ? iso * 255.0f : (s == SCALE_U16 ? iso * 65535.0f : iso); }
+VK_ISO_HD float iso_k(float iso, bool r8) { return iso_k(iso, r8 ? SCALE_R8 : SCALE_VALUE); }
 
 // The hit test: one compare; a NaN sample is no hit, +inf is one.
 VK_ISO_HD bool iso_hit(float x, float k) { return x >= k; }
@@ -60,16 +63,17 @@ VK_ISO_HD bool iso_cell_empty(const float t[8], float k) {
 
 // Host validation of the public parameters (vk_isosurface's fields); fills the descriptor but for its lighting and returns nullptr,
 // or returns what is wrong.
-inline const char *iso_desc(float iso, const float rgb[3], uint32_t refine, bool r8, IsoDesc &D) {
+inline const char *iso_desc(float iso, const float rgb[3], uint32_t refine, SampleScale s, IsoDesc &D) {
     if (!isfinite(iso)) return "iso is not finite";
     for (int c = 0; c < 3; c++)
         if (!(fabsf(rgb[c]) <= kIsoMaxColour)) return "a colour is not finite or beyond +-VK_TF_MAX_COLOUR";
     if (refine > kIsoMaxRefine) return "refine is above VK_ISO_MAX_REFINE";
-    D.iso_k = iso_k(iso, r8);
+    D.iso_k = iso_k(iso, s);
     D.r = rgb[0]; D.g = rgb[1]; D.b = rgb[2];
     D.refine = refine;
     return nullptr;
 }
+inline const char *iso_desc(float iso, const float rgb[3], uint32_t refine, bool r8, IsoDesc &D) { return iso_desc(iso, rgb, refine, r8 ? SCALE_R8 : SCALE_VALUE, D); }
 
 // One component of a refinement position: m steps back from the hit sample.
 VK_ISO_HD float iso_back(float m, float s, float p) { return fmaf(-m, s, p); }

@@ -45,7 +45,7 @@ void with_skip_safe(bool skip, bool safe, F &&f) {
 }
 
 // the layouts that have table, maximum-projection and isosurface kernels: dispatch_march refuses the others under any of the three
-inline bool has_table_layout(int k) { return k == VOL_LINEAR_U8 || k == VOL_LINEAR_F16 || k == VOL_P8 || k == VOL_P16 || k == VOL_PF16; }
+inline bool has_table_layout(int k) { return k == VOL_LINEAR_U8 || k == VOL_LINEAR_F16 || k == VOL_P8 || k == VOL_P16 || k == VOL_PF16 || is_u16_kind(k); }
 
 // f(VOL, SKIP, SAFE) over the layouts that have table kernels (has_table_layout): the cell layouts in all four
 // variants, the LINEAR layouts without a skip map and with clamped indices only.
@@ -67,7 +67,7 @@ void with_table_layout(const vk_ctx *ctx, bool skip, bool safe, F &&f) {
 template <int VOL, bool SKIP, bool SAFE, bool SPECKLE = false>
 uint32_t cell_kernel_lds(const vk_ctx *ctx, VolumeDesc &V) {
     if (!SKIP && V.lut) V.lut += cell_lut_entries(V.nx, V.ny, V.nz);
-    constexpr bool lut = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16) && !SAFE;
+    constexpr bool lut = is_cell_layout(VOL) && !SAFE;
     constexpr bool corners = lut && SKIP && SPECKLE && (VOL == VOL_P8 || VOL == VOL_P16);
     return (lut ? cell_lut_bytes(V.nx, V.ny, V.nz) : 0u) + (corners ? kSpeckleLutBytes : 0u) + ctx->naive_lds_pad;  // (pad: occupancy experiments, vk_debug_set_param)
 }

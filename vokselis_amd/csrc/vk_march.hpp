@@ -99,7 +99,7 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
                                       const uint32_t *lut = nullptr, const float walk_cap = __builtin_inff(), const float walk_cap_all = __builtin_inff(),
                                       const TfDesc *tfd = nullptr, const LightDesc *ld = nullptr, const LitRay *lr = nullptr) {
     static_assert(!LIT || TF, "lighting shades the table's colour");
-    constexpr bool PACKED = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16);
+    constexpr bool PACKED = is_cell_layout(VOL);
     constexpr bool BRICK9 = (VOL == VOL_B9U8 || VOL == VOL_B9F16);
     static_assert(!AHEAD || (PACKED && SKIP && !SAFE && !BOUNDED), "probe-ahead: the skip kernels' fast path, unbounded");
     constexpr bool CODED = SKIP && !TF && (VOL == VOL_P8 || VOL == VOL_P16);  // the maps this instantiation reads carry lone-speckle codes (see the trip)
@@ -271,7 +271,7 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
         float r = fmaf(fz, c1 - c0, c0);
         float a, tr = 0.0f, tg = 0.0f, tb = 0.0f;
         if constexpr (TF) tf_lookup(*tfd, r, tr, tg, tb, a);
-        else a = transfer_alpha<(VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_LINEAR_U8 || VOL == VOL_B9U8) ? 1 : 0>(r);
+        else a = transfer_alpha<transfer_scale(VOL)>(r);
         if (COUNT && le) atomicAdd(le, (1u << 7) + (a != 0.0f ? 1u << 14 : 0u));
         if (SKIP) {
             // A cell is non-empty as soon as one of its 8 taps is above the threshold; the FILTERED value of a sample inside it
@@ -367,7 +367,7 @@ __device__ __forceinline__ bool march_stream(const VolumeDesc &V, RayState &r, C
             }
             composite(a, cr, cg, cb, A, Gr, Gg, Gb);
         } else {
-            palette_composite(transfer_alpha<(VOL == VOL_P8 || VOL == VOL_P16) ? 1 : 0>(v), A, Gr, Gg, Gb);
+            palette_composite(transfer_alpha<transfer_scale(VOL)>(v), A, Gr, Gg, Gb);
         }
         left -= 1u;  // :101
         fx = __builtin_amdgcn_fractf(ux); fy = __builtin_amdgcn_fractf(uy); fz = __builtin_amdgcn_fractf(uz);

@@ -19,7 +19,7 @@ namespace vk {
 template <int VOL, bool SKIP, bool SAFE, bool COUNT, bool BOUNDED>
 __device__ __forceinline__ bool march_iso(const VolumeDesc &V, RayState &r, const uint32_t budget, Census &cs, const uint32_t *lut,
                                           const float walk_cap, const float walk_cap_all, const float iso_k) {
-    constexpr bool PACKED = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16);
+    constexpr bool PACKED = is_cell_layout(VOL);
     float px = r.px, py = r.py, pz = r.pz, X = r.A;
     int nleft = -(int)r.left;  // minus the iterations left (as march())
     const float sx = r.sx, sy = r.sy, sz = r.sz;
@@ -127,7 +127,7 @@ struct IsoSample {
 };
 template <int VOL, bool SKIP, bool SAFE>
 __device__ __forceinline__ IsoSample iso_sample(const VolumeDesc &V, const uint32_t *lut, const float qx, const float qy, const float qz) {
-    constexpr bool PACKED = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16);
+    constexpr bool PACKED = is_cell_layout(VOL);
     const float fnx = (float)V.nx, fny = (float)V.ny, fnz = (float)V.nz;
     const float ux = fmaf(qx, fnx, -0.5f), uy = fmaf(qy, fny, -0.5f), uz = fmaf(qz, fnz, -0.5f);
     int ix = cvt_floor_i32(ux), iy = cvt_floor_i32(uy), iz = cvt_floor_i32(uz);

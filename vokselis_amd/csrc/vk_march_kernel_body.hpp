@@ -16,7 +16,7 @@
 // RayState::A, each a frame of its own around the shared parts of vk_march_parts.hpp; selected at each call site, since a forwarding wrapper
 // moved registers -- and what the epilogue makes of the ray's sums: under ISO the refinement of the crossing and
 // the shade, once per ray, after the wave's loops have ended.
-    static_assert(VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16 || (!SKIP && SAFE), "linear / bricked layouts: no skip map, clamped indices");
+    static_assert(is_cell_layout(VOL) || (!SKIP && SAFE), "linear / bricked layouts: no skip map, clamped indices");
     static_assert(SKIP || WALK == WALK_LOOP, "the closed-form walks are variants of the skip kernels");
     static_assert(!AHEAD || (SKIP && !SAFE), "probe ahead: the skip kernels' fast path");
     static_assert(!MIP || (!TF && !LIT && WALK == WALK_LOOP && !AHEAD), "the maximum projection: loops of its own, walking with the loop; the table is looked up in the epilogue");
@@ -45,7 +45,7 @@
             return;
         }
     }
-    constexpr bool USE_LUT = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16) && !SAFE;
+    constexpr bool USE_LUT = is_cell_layout(VOL) && !SAFE;
     extern __shared__ uint32_t cell_lut[];
     if (USE_LUT) {  // all 64 lanes are still here
         load_cell_luts(V, cell_lut, lane);

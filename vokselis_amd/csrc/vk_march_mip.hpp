@@ -17,7 +17,7 @@ namespace vk {
 template <int VOL, bool SKIP, bool SAFE, bool COUNT, bool BOUNDED>
 __device__ __forceinline__ bool march_mip(const VolumeDesc &V, RayState &r, const uint32_t budget, Census &cs, const uint32_t *lut,
                                           const float walk_cap, const float walk_cap_all, const float k1, const float k2, const float umax) {
-    constexpr bool PACKED = (VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16);
+    constexpr bool PACKED = is_cell_layout(VOL);
     float px = r.px, py = r.py, pz = r.pz, U = r.A;
     int nleft = -(int)r.left;  // minus the iterations left (as march())
     const float sx = r.sx, sy = r.sy, sz = r.sz;

@@ -189,7 +189,14 @@ __device__ __forceinline__ void xlerp_cell_dx(const CellBits<VOL> &cb, float fx,
     } else {
         union { u32x4_t u; half2_t h[4]; } c;
         c.u = cb.v;
-        if constexpr (VOL == VOL_P16) {
+        if constexpr (VOL == VOL_PU16) {
+            // u16 taps, two per word: one conversion each (v_cvt_f32_u32 with a word select), exact; the differences are exact too (integers below 2^16)
+            const uint32_t w0 = cb.v.x, w1 = cb.v.y, w2 = cb.v.z, w3 = cb.v.w;
+            float a0 = (float)(w0 & 0xffffu), a1 = (float)(w0 >> 16), a2 = (float)(w1 & 0xffffu), a3 = (float)(w1 >> 16);
+            float a4 = (float)(w2 & 0xffffu), a5 = (float)(w2 >> 16), a6 = (float)(w3 & 0xffffu), a7 = (float)(w3 >> 16);
+            dx00 = a1 - a0; c00 = fmaf(fx, dx00, a0); dx10 = a3 - a2; c10 = fmaf(fx, dx10, a2);
+            dx01 = a5 - a4; c01 = fmaf(fx, dx01, a4); dx11 = a7 - a6; c11 = fmaf(fx, dx11, a6);
+        } else if constexpr (VOL == VOL_P16) {
             // (tap, delta) pairs: delta = t1 - t0 is exact in f16 for u8 data -> v_fma_mix_f32
             dx00 = (float)c.h[0].y; dx10 = (float)c.h[1].y; dx01 = (float)c.h[2].y; dx11 = (float)c.h[3].y;
             c00 = fmaf(fx, dx00, (float)c.h[0].x); c10 = fmaf(fx, dx10, (float)c.h[1].x);
@@ -226,6 +233,10 @@ __device__ __forceinline__ void linear_taps(const VolumeDesc &V, int ix, int iy,
     size_t r01 = y0 * sy_ + z1 * sz_, r11 = y1 * sy_ + z1 * sz_;
     if (VOL == VOL_LINEAR_U8) {
         const uint8_t *v = reinterpret_cast<const uint8_t *>(V.data);
+        tp[0] = (float)v[r00 + x0]; tp[1] = (float)v[r00 + x1]; tp[2] = (float)v[r10 + x0]; tp[3] = (float)v[r10 + x1];
+        tp[4] = (float)v[r01 + x0]; tp[5] = (float)v[r01 + x1]; tp[6] = (float)v[r11 + x0]; tp[7] = (float)v[r11 + x1];
+    } else if (VOL == VOL_LINEAR_U16) {
+        const uint16_t *v = reinterpret_cast<const uint16_t *>(V.data);
         tp[0] = (float)v[r00 + x0]; tp[1] = (float)v[r00 + x1]; tp[2] = (float)v[r10 + x0]; tp[3] = (float)v[r10 + x1];
         tp[4] = (float)v[r01 + x0]; tp[5] = (float)v[r01 + x1]; tp[6] = (float)v[r11 + x0]; tp[7] = (float)v[r11 + x1];
     } else {

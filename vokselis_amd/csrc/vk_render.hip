@@ -40,7 +40,7 @@ int check_render(vk_ctx *ctx, int mode, const float *cam, float dt_scale, uint32
     // PROCEDURAL shares the compute twin's ray, box and step: geometry helpers treat it as that mode
     const int geo_mode = mode == VK_MODE_PROCEDURAL ? VK_MODE_COMPUTE_NEAREST : mode;
     if (mode == VK_MODE_NAIVE_TRILINEAR && ctx->format == VK_FMT_RGBA16F_PAIR)
-        return fail(ctx, VK_ERR_INVALID, "NAIVE_TRILINEAR needs a scalar volume (R8_UNORM / R16_FLOAT)");
+        return fail(ctx, VK_ERR_INVALID, "NAIVE_TRILINEAR needs a scalar volume (R8_UNORM / R16_FLOAT / R16_UNORM)");
     if (mode == VK_MODE_COMPUTE_NEAREST && ctx->format != VK_FMT_RGBA16F_PAIR)
         return fail(ctx, VK_ERR_INVALID, "COMPUTE_NEAREST needs an RGBA16F_PAIR volume");
     if (!(dt_scale > 0.0f) || !std::isfinite(dt_scale)) return fail(ctx, VK_ERR_INVALID, "dt_scale must be finite and > 0");
@@ -96,7 +96,7 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
         if (!has_table_layout(ctx->vol_kind))
             return fail(ctx, VK_ERR_UNSUPPORTED, "isosurface: NAIVE_TRILINEAR renders under an isosurface need a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no isosurface kernels; vk_set_isosurface(NULL) resets)");
         if (flags & VK_RENDER_FAST_WALK) return fail(ctx, VK_ERR_UNSUPPORTED, "isosurface: VK_RENDER_FAST_WALK has no isosurface kernels");
-        const char *bad = iso_desc(ctx->iso.iso, ctx->iso.rgb, ctx->iso.refine, ctx->format == VK_FMT_R8_UNORM, I);
+        const char *bad = iso_desc(ctx->iso.iso, ctx->iso.rgb, ctx->iso.refine, format_scale(ctx->format), I);
         if (bad) return fail(ctx, VK_ERR_INVALID, std::string("isosurface: ") + bad);  // (vk_set_isosurface has checked it)
         I.lit = ctx->lit ? 1 : 0;
         I.light = ctx->light;
@@ -110,7 +110,7 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
             return fail(ctx, VK_ERR_UNSUPPORTED, mip ? "projection: VK_RENDER_FAST_WALK has no maximum-projection kernels (VK_PROJ_MAX)" : "transfer function: VK_RENDER_FAST_WALK has no table kernels");
         // the window of the table in force; under VK_PROJ_MAX without one the implicit grey ramp, two entries over [0, 1] (T.rgba stays NULL)
         const uint32_t n = tf ? ctx->tf_n : 2u;
-        tf_constants(n, tf ? ctx->tf_lo : 0.0f, tf ? ctx->tf_hi : 1.0f, ctx->format == VK_FMT_R8_UNORM, T.k1, T.k2);
+        tf_constants(n, tf ? ctx->tf_lo : 0.0f, tf ? ctx->tf_hi : 1.0f, format_scale(ctx->format), T.k1, T.k2);
         T.rgba = tf ? ctx->d_tf : nullptr;
         T.umax = (float)(n - 1u);
         T.imax = (int32_t)n - 2;
@@ -155,6 +155,14 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
             if (V.max_off + 16 < (1ll << 32) && cell_lut_bytes(ctx->nx, ctx->ny, ctx->nz) <= 16384u && 64.0f * ulp < 0.25f / nmax && !(flags & VK_RENDER_SAFE)) safe = false;
         }
         if (ctx->vol_kind == VOL_S8U8 || ctx->vol_kind == VOL_S8F16) launch_staged(ctx, L, V, grid, count, reach_cam);
+        else if (is_u16_kind(ctx->vol_kind)) {  // an R16_UNORM volume: the same families, kernels of their own units (vk_march_u16.hpp)
+            if (flags & VK_RENDER_FAST_WALK) return fail(ctx, VK_ERR_UNSUPPORTED, "R16_UNORM: VK_RENDER_FAST_WALK has no u16 kernels (the walks take the loop)");
+            if (iso) launch_u16_iso(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
+            else if (mip) launch_u16_mip(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
+            else if (tf && ctx->lit) launch_u16_lit(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
+            else if (tf) launch_u16_tf(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
+            else launch_u16_cells(ctx, L, V, T, ctx->light, I, nullptr, grid, count, skip, safe);
+        }
         else if (iso) launch_cells_iso(ctx, L, V, I, Cl, grid, count, skip, safe);
         else if (mip) launch_cells_mip(ctx, L, V, T, Cl, grid, count, skip, safe);
         else if (tf && ctx->lit) launch_cells_lit(ctx, L, V, T, ctx->light, Cl, grid, count, skip, safe);

@@ -2,7 +2,7 @@
 // emptiness predicate of a cell under the table, shared by the march kernels, the skip-map rebuild (vk_volume.hip) and the host
 // fuzz (tests/tf_fuzz.cpp, plain g++ under ASan / UBSan).
 //
-// x is the filtered sample on the kernel's own scale (R8: the filtered taps on 0..255; R16F: the value).  With k1, k2 from
+// x is the filtered sample on the kernel's own scale (R8: the filtered taps on 0..255; R16_UNORM: on 0..65535; R16F: the value).  With k1, k2 from
 // tf_constants():  u = min(max(fma(x, k1, k2), 0), n - 1)  (a NaN sample reads entry 0),  i = min(floor(u), n - 2),  f = u - i,
 // c = fma(f, T[i+1] - T[i], T[i]) per channel.
 //
@@ -38,12 +38,18 @@ struct TfDesc {
     int32_t imax;
 };
 
-// k1 = (n-1) / ((hi-lo) S), k2 = -lo (n-1) / (hi-lo), each computed in double and rounded once to f32; S = 255 for R8 volumes, 1 for R16F
-inline void tf_constants(uint32_t n, float lo, float hi, bool r8, float &k1, float &k2) {
+// The kernel's scale S of a volume format: a filtered sample is S times the shader-side value.  R16F: the value itself; R8_UNORM: the
+// taps 0..255; R16_UNORM: the taps 0..65535 (every u16 is exact in f32).  The numbers are transfer_alpha<>'s SCALE (vk_common.hpp).
+enum SampleScale : int { SCALE_VALUE = 0, SCALE_R8 = 1, SCALE_U16 = 3 };
+inline double sample_scale(SampleScale s) { return s == SCALE_R8 ? 255.0 : (s == SCALE_U16 ? 65535.0 : 1.0); }
+
+// k1 = (n-1) / ((hi-lo) S), k2 = -lo (n-1) / (hi-lo), each computed in double and rounded once to f32; S = 255 for R8 volumes, 65535 for R16_UNORM, 1 for R16F
+inline void tf_constants(uint32_t n, float lo, float hi, SampleScale s, float &k1, float &k2) {
     const double span = (double)hi - (double)lo, nm1 = (double)n - 1.0;
-    k1 = (float)(nm1 / (span * (r8 ? 255.0 : 1.0)));
+    k1 = (float)(nm1 / (span * sample_scale(s)));
     k2 = (float)(-(double)lo * nm1 / span);
 }
+inline void tf_constants(uint32_t n, float lo, float hi, bool r8, float &k1, float &k2) { tf_constants(n, lo, hi, r8 ? SCALE_R8 : SCALE_VALUE, k1, k2); }
 
 // the table coordinate u in [0, n - 1] (umax = n - 1)
 VK_TF_HD float tf_u(float x, float k1, float k2, float umax) { return fminf(fmaxf(fmaf(x, k1, k2), 0.0f), umax); }
@@ -86,14 +92,21 @@ VK_TF_HD bool tf_cell_empty(const float t[8], const uint32_t *prefix, int n, flo
 // infinite tap is never empty: the filter's fma(f, b - a, a) turns an infinite tap into NaN (inf - inf, 0 * inf) and
 // transfer_alpha(NaN) = smoothstep of min(NaN, 0.9) = 0.9, alpha ~0.817 -- the same for -inf as for +inf.  Shared by pack_cells_kernel,
 // cell_occ_kernel's built-in branch and the host fuzz (tests/builtin_fuzz.cpp); the oracle and the numpy restatement state it again.
-VK_TF_HD bool builtin_tap_empty(float t, bool f16) { return f16 ? (isfinite(t) && t <= 0.1f) : (t <= 25.0f); }
+// u16 (the tap's value 0..65535): t <= 6553.  transfer_alpha<3> computes s = fma(min(t, 58981.5), k1, k2), k1 = f32(1 / (65535 * 1.1)),
+// k2 = f32(-0.1 / 1.1): fma(6553, k1, k2) = -6.94e-6, clamped to +0, and fma(6554, k1, k2) = +6.93e-6 (tests/u16_fuzz.cpp walks all 65536
+// values).  A sample that lerps taps <= 6553 stays <= 6553 (the argument at the top of this file) and the fma is monotone: its alpha is +0.
+VK_TF_HD bool builtin_tap_empty(float t, SampleScale s) {
+    return s == SCALE_VALUE ? (isfinite(t) && t <= 0.1f) : (s == SCALE_U16 ? t <= 6553.0f : t <= 25.0f);
+}
+VK_TF_HD bool builtin_tap_empty(float t, bool f16) { return builtin_tap_empty(t, f16 ? SCALE_VALUE : SCALE_R8); }
 
-// The same for a cell's eight taps (f32 values: u8 taps on 0..255, f16 taps as values): empty when every tap is.
-VK_TF_HD bool builtin_cell_empty(const float t[8], bool f16) {
+// The same for a cell's eight taps (f32 values: u8 taps on 0..255, u16 taps on 0..65535, f16 taps as values): empty when every tap is.
+VK_TF_HD bool builtin_cell_empty(const float t[8], SampleScale s) {
     bool empty = true;
-    for (int b = 0; b < 8; b++) empty = empty && builtin_tap_empty(t[b], f16);
+    for (int b = 0; b < 8; b++) empty = empty && builtin_tap_empty(t[b], s);
     return empty;
 }
+VK_TF_HD bool builtin_cell_empty(const float t[8], bool f16) { return builtin_cell_empty(t, f16 ? SCALE_VALUE : SCALE_R8); }
 
 // ---- lone-speckle cells of the built-in transfer (u8 cells: P8 and P16) ----
 // A cell with exactly one tap above the threshold (v > 25 at corner dx | dy << 1 | dz << 2, every other tap <= m <= 25) is not empty,

@@ -106,13 +106,16 @@ static int launch_cell_occ(vk_ctx *ctx, int kind, const void *cells, uint8_t *oc
                            uint32_t n, float lo, float hi, bool mip_on, const float *iso) {
     float k1 = 0.0f, k2 = 0.0f;
     int mip = mip_on ? 1 : 0;  // cell_occ_kernel's predicate: 0 the table's or the built-in one, 1 the maximum projection's, 2 the isosurface's
-    if (iso) { mip = 2; prefix = nullptr; k1 = iso_k(*iso, kind != VOL_PF16); }
+    const SampleScale scale = kind == VOL_PF16 ? SCALE_VALUE : (kind == VOL_PU16 ? SCALE_U16 : SCALE_R8);
+    if (iso) { mip = 2; prefix = nullptr; k1 = iso_k(*iso, scale); }
     if (mip == 1 && n == 0) { n = 2; lo = 0.0f; hi = 1.0f; }
     if (mip == 1) prefix = nullptr;
-    if (prefix || mip == 1) tf_constants(n, lo, hi, kind != VOL_PF16, k1, k2);
+    if (prefix || mip == 1) tf_constants(n, lo, hi, scale, k1, k2);
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters + 7, 0, sizeof(unsigned long long), ctx->stream));
     if (kind == VOL_PF16)
         hipLaunchKernelGGL(cell_occ_kernel<VOL_PF16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, code, n_cells, prefix, (int)n, k1, k2, mip, ctx->counters + 7);
+    else if (kind == VOL_PU16)
+        hipLaunchKernelGGL(cell_occ_kernel<VOL_PU16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, code, n_cells, prefix, (int)n, k1, k2, mip, ctx->counters + 7);
     else if (kind == VOL_P16)
         hipLaunchKernelGGL(cell_occ_kernel<VOL_P16>, dim3(blocks), dim3(256), 0, ctx->stream, cells, occ, code, n_cells, prefix, (int)n, k1, k2, mip, ctx->counters + 7);
     else
@@ -179,7 +182,7 @@ static int build_skip_maps(vk_ctx *ctx, CellScratch &sc, bool coded, uint32_t nb
 // have no maps.  iso (nullptr: none): the threshold of the isosurface in force, whose predicate then replaces the pair's.
 int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float lo, float hi, int projection, const float *iso) {
     const int kind = ctx->vol_kind;
-    if (ctx->format < 0 || (kind != VOL_P8 && kind != VOL_P16 && kind != VOL_PF16)) return VK_OK;
+    if (ctx->format < 0 || !is_cell_layout(kind)) return VK_OK;
     const uint64_t n_cells = (uint64_t)ctx->nbx * ctx->nby * ctx->nbz * kBrickCells;
     const uint64_t cell_bytes = kind == VOL_P8 ? 8 : 16;
     CellScratch sc;
@@ -207,7 +210,7 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
     DenseSource src;
     src.p = d_src; src.p2 = d_src2; src.owned = own_src;
     const size_t n_vox = (size_t)nx * ny * nz;
-    const size_t bpv = format == VK_FMT_R8_UNORM ? 1 : (format == VK_FMT_R16_FLOAT ? 2 : 8);
+    const size_t bpv = format == VK_FMT_R8_UNORM ? 1 : (format == VK_FMT_R16_FLOAT || format == VK_FMT_R16_UNORM ? 2 : 8);
     if (layout == VK_LAYOUT_AUTO) {
         const double cells = ((double)((nx - 1) / 4 + 2)) * ((ny - 1) / 4 + 2) * ((nz - 1) / 4 + 2) * 64.0;
         const double cell_bytes = cells * 16.0;
@@ -218,7 +221,8 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
         }
         // beyond ~4 GiB of cells the march stops being cache-resident and the 8-16x inflation of the cell layouts
         // turns into HBM traffic: dense 8^3 bricks staged through LDS win there
-        else if (cell_bytes > 4.0 * 1024 * 1024 * 1024) layout = VK_LAYOUT_STAGED;
+        // (R16_UNORM has no staged kernels: LINEAR where an R16F volume of these dimensions is staged)
+        else if (cell_bytes > 4.0 * 1024 * 1024 * 1024) layout = format == VK_FMT_R16_UNORM ? VK_LAYOUT_LINEAR : VK_LAYOUT_STAGED;
         // u8: the (tap, delta) pair cells cost 2x the bytes and ~20 % fewer VALU ops per sample
         else layout = format == VK_FMT_R8_UNORM ? VK_LAYOUT_PACKED_PAIRS : VK_LAYOUT_PACKED;
     }
@@ -229,6 +233,8 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
         if (rec_bytes > (double)kPairOob || pair_lut_entries(nx, ny, nz) * 4u > 16384u)
             return fail(ctx, VK_ERR_UNSUPPORTED, "RGBA16F_PAIR record layout holds <= 1.25 GiB of records: use VK_LAYOUT_LINEAR");
     }
+    if (format == VK_FMT_R16_UNORM && layout != VK_LAYOUT_LINEAR && layout != VK_LAYOUT_PACKED)
+        return fail(ctx, VK_ERR_UNSUPPORTED, "R16_UNORM volumes use VK_LAYOUT_LINEAR or VK_LAYOUT_PACKED (PACKED_PAIRS / BRICKED / QUADS / STAGED have no u16 kernels)");
     VolBuild nb;
     nb.nx = nx; nb.ny = ny; nb.nz = nz;
     nb.format = format;
@@ -260,7 +266,7 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
             }
         }
         nb.vol_bytes = n_vox * bpv * (d_src2 ? 2 : 1);
-        nb.vol_kind = format == VK_FMT_R16_FLOAT ? VOL_LINEAR_F16 : VOL_LINEAR_U8;
+        nb.vol_kind = format == VK_FMT_R16_FLOAT ? VOL_LINEAR_F16 : (format == VK_FMT_R16_UNORM ? VOL_LINEAR_U16 : VOL_LINEAR_U8);
         if ((rc = finish("dense copy"))) return rc;
         return commit_volume(ctx, nb);
     }
@@ -369,7 +375,7 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
     const bool f16 = format == VK_FMT_R16_FLOAT;
     if (f16 && layout == VK_LAYOUT_PACKED_PAIRS)
         return fail(ctx, VK_ERR_UNSUPPORTED, "PACKED_PAIRS stores exact u8 differences; f16 volumes use PACKED");
-    const int kind = f16 ? VOL_PF16 : (layout == VK_LAYOUT_PACKED_PAIRS ? VOL_P16 : VOL_P8);
+    const int kind = f16 ? VOL_PF16 : (format == VK_FMT_R16_UNORM ? VOL_PU16 : (layout == VK_LAYOUT_PACKED_PAIRS ? VOL_P16 : VOL_P8));
     nb.nbx = ((nx - 1) >> 2) + 2;
     nb.nby = ((ny - 1) >> 2) + 2;
     nb.nbz = ((nz - 1) >> 2) + 2;
@@ -388,6 +394,8 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
     HIP_TRY(ctx, hipMemsetAsync(ctx->counters + 7, 0, sizeof(unsigned long long), ctx->stream));
     if (kind == VOL_PF16)
         hipLaunchKernelGGL(pack_cells_kernel<VOL_PF16>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, sc.code, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
+    else if (kind == VOL_PU16)
+        hipLaunchKernelGGL(pack_cells_kernel<VOL_PU16>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, sc.code, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
     else if (kind == VOL_P16)
         hipLaunchKernelGGL(pack_cells_kernel<VOL_P16>, dim3(pack_blocks), dim3(256), 0, ctx->stream, d_src, nb.vol, sc.occ, sc.code, nx, ny, nz, nb.nbx, nb.nby, n_cells, ctx->counters + 7);
     else
@@ -431,7 +439,7 @@ static int check_volume_args(vk_ctx *ctx, const void *p, const void *p2, uint32_
     if (!p) return fail(ctx, VK_ERR_INVALID, "volume pointer is NULL");
     if (nx == 0 || ny == 0 || nz == 0 || nx > 8192 || ny > 8192 || nz > 8192)
         return fail(ctx, VK_ERR_INVALID, "volume dims must be in [1, 8192]");
-    if (format < VK_FMT_R8_UNORM || format > VK_FMT_RGBA16F_PAIR) return fail(ctx, VK_ERR_INVALID, "unknown volume format");
+    if (format < VK_FMT_R8_UNORM || format > VK_FMT_R16_UNORM) return fail(ctx, VK_ERR_INVALID, "unknown volume format");
     if (format == VK_FMT_RGBA16F_PAIR && !p2) return fail(ctx, VK_ERR_INVALID, "RGBA16F_PAIR needs the normals volume");
     if (layout < VK_LAYOUT_AUTO || layout > VK_LAYOUT_STAGED) return fail(ctx, VK_ERR_INVALID, "unknown layout");
     return VK_OK;
@@ -445,7 +453,7 @@ int vk_volume_upload(vk_ctx *ctx, const void *host, const void *host2, uint32_t 
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t n_vox = (size_t)nx * ny * nz;
-    const size_t bpv = format == VK_FMT_R8_UNORM ? 1 : (format == VK_FMT_R16_FLOAT ? 2 : 8);
+    const size_t bpv = format == VK_FMT_R8_UNORM ? 1 : (format == VK_FMT_R16_FLOAT || format == VK_FMT_R16_UNORM ? 2 : 8);
     void *d = nullptr, *d2 = nullptr;
     HIP_TRY(ctx, hipMalloc(&d, n_vox * bpv));
     hipError_t e = hipMemcpy(d, host, n_vox * bpv, hipMemcpyHostToDevice);
@@ -478,6 +486,7 @@ int vk_volume_generate(vk_ctx *ctx, int kind, uint32_t nx, uint32_t ny, uint32_t
     const uint32_t core = kind == VK_GEN_FOG_DENSE_CORE ? 1u : 0u;
     if (core) kind = VK_GEN_FOG;
     if (format == VK_FMT_RGBA16F_PAIR) return fail(ctx, VK_ERR_UNSUPPORTED, "generators make scalar volumes");
+    if (format == VK_FMT_R16_UNORM) return fail(ctx, VK_ERR_UNSUPPORTED, "generators make R8_UNORM and R16_FLOAT volumes (upload an R16_UNORM volume with vk_volume_upload)");
     if (kind == VK_GEN_BONSAI_STANDIN && format != VK_FMT_R8_UNORM) return fail(ctx, VK_ERR_UNSUPPORTED, "the bonsai stand-in is a u8 volume");
     if (kind == VK_GEN_FOG && format == VK_FMT_R8_UNORM && (span == 0 || lo + span > 256)) return fail(ctx, VK_ERR_INVALID, "fog range outside u8");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -592,7 +601,7 @@ int vk_set_isosurface(vk_ctx *ctx, const vk_isosurface *iso) {
     if (!ctx) return VK_ERR_INVALID;
     if (iso) {
         IsoDesc D{};
-        const char *bad = iso_desc(iso->iso, iso->rgb, iso->refine, true, D);
+        const char *bad = iso_desc(iso->iso, iso->rgb, iso->refine, SCALE_R8, D);  // (the checks do not depend on the scale)
         if (bad) return fail(ctx, VK_ERR_INVALID, std::string("vk_set_isosurface: ") + bad);
     }
     if (ctx->fif_open) return fail(ctx, VK_ERR_INVALID, "vk_set_isosurface: a frame is being recorded (call it outside vk_frame_begin / vk_frame_end)");

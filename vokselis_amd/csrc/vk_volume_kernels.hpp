@@ -103,18 +103,18 @@ __global__ __launch_bounds__(256) void pack_cells_kernel(const void *__restrict_
 #pragma unroll
     for (int b = 0; b < 8; b++) {
         size_t idx = (size_t)xs[b & 1] + (size_t)nx * ((size_t)ys[(b >> 1) & 1] + (size_t)ny * (size_t)zs[b >> 2]);
-        t[b] = (VOL == VOL_PF16) ? (uint32_t)reinterpret_cast<const uint16_t *>(src)[idx]
+        t[b] = (VOL == VOL_PF16 || VOL == VOL_PU16) ? (uint32_t)reinterpret_cast<const uint16_t *>(src)[idx]
                                  : (uint32_t)reinterpret_cast<const uint8_t *>(src)[idx];
     }
-    // occ = 0 unless every tap is empty under the built-in transfer (vk_tf.hpp: builtin_cell_empty -- u8 <= 25; f16 finite and
-    // <= 0.1f), else 255 ("no contributing cell seen yet")
+    // occ = 0 unless every tap is empty under the built-in transfer (vk_tf.hpp: builtin_cell_empty -- u8 <= 25; u16 <= 6553; f16 finite
+    // and <= 0.1f), else 255 ("no contributing cell seen yet")
     float tv[8];
 #pragma unroll
     for (int b = 0; b < 8; b++) tv[b] = (VOL == VOL_PF16) ? h2f(t[b]) : (float)t[b];
-    const bool nonempty = !builtin_cell_empty(tv, VOL == VOL_PF16);
+    const bool nonempty = !builtin_cell_empty(tv, (SampleScale)transfer_scale(VOL));
     occ[id] = nonempty ? 0 : 255;
     // the lone-speckle code of a u8 cell (vk_tf.hpp: speckle_code; 0: none), which replaces the cell's distance 0 in the finished maps
-    code[id] = (VOL == VOL_PF16) ? (uint8_t)0 : (uint8_t)speckle_code(tv);
+    code[id] = (VOL == VOL_PF16 || VOL == VOL_PU16) ? (uint8_t)0 : (uint8_t)speckle_code(tv);
     {   // census of exactly-transparent cells (one atomic per wave): decides whether skipping can pay
         const unsigned long long m = __ballot(!nonempty);
         if ((threadIdx.x & 63u) == 0 && m) atomicAdd(n_empty, (unsigned long long)__popcll(m));
@@ -131,13 +131,13 @@ __global__ __launch_bounds__(256) void pack_cells_kernel(const void *__restrict_
             c.h[2 * k + 1] = (_Float16)((float)t[2 * k + 1] - (float)t[2 * k]);      // delta, |.| <= 255: exact
         }
         reinterpret_cast<uint4 *>(dst)[id] = c.u;
-    } else {
+    } else {  // PF16, PU16: the eight 16-bit taps as they are
         reinterpret_cast<uint4 *>(dst)[id] = make_uint4(t[0] | (t[1] << 16), t[2] | (t[3] << 16), t[4] | (t[5] << 16), t[6] | (t[7] << 16));
     }
 }
 
 // The skip-map seed and census of a packed volume read back from its cells (the dense source is gone by then): each cell's 8 taps
-// (P8: u8 taps; P16: (tap, delta) pairs, tap + delta exact; PF16: f16 taps), tested by the runtime transfer function's emptiness
+// (P8: u8 taps; P16: (tap, delta) pairs, tap + delta exact; PF16: f16 taps; PU16: u16 taps), tested by the runtime transfer function's emptiness
 // predicate (vk_tf.hpp; prefix: the table's prefix counts of non-zero alphas), or with prefix == nullptr by the built-in threshold
 // of pack_cells_kernel -- whose occ and census it then reproduces byte for byte.  mip != 0 (vk_set_projection(VK_PROJ_MAX)): the predicate
 // of the maximum projection over the window behind k1, k2 and its n entries (vk_tf.hpp: mip_cell_empty).  mip == 2 (vk_set_isosurface):
@@ -154,6 +154,11 @@ __global__ __launch_bounds__(256) void cell_occ_kernel(const void *__restrict__ 
         const uint2 c = reinterpret_cast<const uint2 *>(cells)[id];
 #pragma unroll
         for (int b = 0; b < 4; b++) { t[b] = (float)((c.x >> (8 * b)) & 0xffu); t[4 + b] = (float)((c.y >> (8 * b)) & 0xffu); }
+    } else if (VOL == VOL_PU16) {
+        const uint4 c = reinterpret_cast<const uint4 *>(cells)[id];
+        const uint32_t w[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) { t[2 * k] = (float)(w[k] & 0xffffu); t[2 * k + 1] = (float)(w[k] >> 16); }
     } else {
         union { uint4 u; _Float16 h[8]; } c;
         c.u = reinterpret_cast<const uint4 *>(cells)[id];
@@ -163,9 +168,9 @@ __global__ __launch_bounds__(256) void cell_occ_kernel(const void *__restrict__ 
             else { t[2 * k] = (float)c.h[2 * k]; t[2 * k + 1] = (float)c.h[2 * k + 1]; }
         }
     }
-    const bool nonempty = mip == 2 ? !iso_cell_empty(t, k1) : mip ? !mip_cell_empty(t, k1, k2, (float)(n - 1)) : prefix ? !tf_cell_empty(t, prefix, n, k1, k2) : !builtin_cell_empty(t, VOL == VOL_PF16);  // (pack_cells_kernel's predicate)
+    const bool nonempty = mip == 2 ? !iso_cell_empty(t, k1) : mip ? !mip_cell_empty(t, k1, k2, (float)(n - 1)) : prefix ? !tf_cell_empty(t, prefix, n, k1, k2) : !builtin_cell_empty(t, (SampleScale)transfer_scale(VOL));  // (pack_cells_kernel's predicate)
     occ[id] = nonempty ? 0 : 255;
-    if (code) code[id] = (VOL == VOL_PF16 || mip || prefix) ? (uint8_t)0 : (uint8_t)speckle_code(t);
+    if (code) code[id] = (VOL == VOL_PF16 || VOL == VOL_PU16 || mip || prefix) ? (uint8_t)0 : (uint8_t)speckle_code(t);
     const unsigned long long m = __ballot(!nonempty);
     if ((threadIdx.x & 63u) == 0 && m) atomicAdd(n_empty, (unsigned long long)__popcll(m));
 }

@@ -1,6 +1,8 @@
 // bonsai.cpp -- headless counterpart of `cargo run --example bonsai` (examples/bonsai/main.rs):
 // the same Demo (volume + raycast pipeline), the same camera, rendered N frames into the backbuffer.
 //   bonsai [--frames N] [--size WxH] [--dt S] [--raw bonsai_256x256x256_uint8.raw] [--ppm out.ppm]
+//          [--raw-u16 FILE] [--dims NX NY NZ]                 a raw volume of native-endian 16-bit integers, uploaded as R16_UNORM (CT / MR data);
+//                                                            --dims: the voxel dims of --raw / --raw-u16 (default 256 256 256)
 //          [--f32] [--dump-rgba file] [--dump-steps file]   parity surface (rgba32f) + per-pixel trip counts, raw
 //          [--gpus N] [--batch B] [--peer-direct]            the frame's tiles over N GPUs of this node (vk_group_*); --peer-direct: the GPUs
 //                                                            store into GPU 0's frames themselves instead of gather + un-tile
@@ -28,6 +30,8 @@
 using namespace vokselis;
 
 static std::string g_raw;
+static int g_raw_fmt = VK_FMT_R8_UNORM;  // --raw-u16: VK_FMT_R16_UNORM
+static uint32_t g_dims[3] = {256, 256, 256};  // --dims
 static float g_dt = 1.0f;
 static bool g_orbit = false;
 static std::vector<float> g_tf;  // --tf: n x 4 floats (empty: the built-in transfer)
@@ -63,7 +67,7 @@ struct Bonsai : Demo {
         if (g_mip) ctx.set_projection(VK_PROJ_MAX);
         if (g_iso_on) ctx.set_isosurface(&g_iso);
         if (g_clip_on) ctx.set_clip_box(&g_clip);
-        if (!g_raw.empty()) self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::from_raw(ctx, g_raw));
+        if (!g_raw.empty()) self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt));
         else self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, 256, 256, 256));
         self->pipeline = RaycastPipeline{VK_MODE_NAIVE_TRILINEAR, g_dt, 0};
         return self;
@@ -82,13 +86,7 @@ static int run_group(int n_gpus, uint32_t frames, uint32_t batch, uint32_t w, ui
     int rc = 1;
     try {
         std::vector<char> raw;
-        if (!g_raw.empty()) {
-            std::ifstream f(g_raw, std::ios::binary);
-            if (!f) throw std::runtime_error("cannot open " + g_raw);
-            raw.resize((size_t)256 * 256 * 256);
-            f.read(raw.data(), (std::streamsize)raw.size());
-            if ((size_t)f.gcount() != raw.size()) throw std::runtime_error(g_raw + ": expected 16777216 bytes");
-        }
+        if (!g_raw.empty()) raw = VolumeTexture::read_raw(g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt);
         for (int i = 0; i < n_gpus; i++) {
             vk_ctx *c = vk_group_ctx(g, i);
             check(c, vk_backbuffer_resize(c, w, h, VK_OUT_RGBA16F));
@@ -97,7 +95,7 @@ static int run_group(int n_gpus, uint32_t frames, uint32_t batch, uint32_t w, ui
             if (g_mip) check(c, vk_set_projection(c, VK_PROJ_MAX));
             if (g_iso_on) check(c, vk_set_isosurface(c, &g_iso));
             if (g_clip_on) check(c, vk_set_clip_box(c, &g_clip));
-            if (!raw.empty()) check(c, vk_volume_upload(c, raw.data(), nullptr, 256, 256, 256, VK_FMT_R8_UNORM, VK_LAYOUT_AUTO));
+            if (!raw.empty()) check(c, vk_volume_upload(c, raw.data(), nullptr, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt, VK_LAYOUT_AUTO));
             else check(c, vk_volume_generate(c, VK_GEN_BONSAI_STANDIN, 256, 256, 256, VK_FMT_R8_UNORM, 0x5EED0001u, 0, 1, VK_LAYOUT_AUTO));
         }
         vk_ctx *root = vk_group_ctx(g, 0);
@@ -159,7 +157,9 @@ int main(int argc, char **argv) {
         if (a == "--frames") frames = (uint32_t)std::atoi(next());
         else if (a == "--size") { if (std::sscanf(next(), "%ux%u", &w, &h) != 2) { std::fprintf(stderr, "--size WxH\n"); return 2; } }
         else if (a == "--dt") g_dt = (float)std::atof(next());
-        else if (a == "--raw") g_raw = next();
+        else if (a == "--raw") { g_raw = next(); g_raw_fmt = VK_FMT_R8_UNORM; }
+        else if (a == "--raw-u16") { g_raw = next(); g_raw_fmt = VK_FMT_R16_UNORM; }
+        else if (a == "--dims") { for (int k = 0; k < 3; k++) g_dims[k] = (uint32_t)std::max(0, std::atoi(next())); }
         else if (a == "--ppm") ppm = next();
         else if (a == "--f32") f32 = true;
         else if (a == "--dump-rgba") dump_rgba = next();

@@ -326,14 +326,24 @@ class VolumeTexture {
                   int layout = VK_LAYOUT_AUTO, const void *data2 = nullptr) : nx(nx_), ny(ny_), nz(nz_), format(fmt) {
         check(ctx.handle(), vk_volume_upload(ctx.handle(), data, data2, nx, ny, nz, fmt, layout));
     }
-    // drop-in for the reference's include_bytes!("bonsai_256x256x256_uint8.raw") (absent from the checkout)
-    static VolumeTexture from_raw(Context &ctx, const std::string &path, uint32_t nx = 256, uint32_t ny = 256, uint32_t nz = 256) {
-        std::ifstream f(path, std::ios::binary);
+    // drop-in for the reference's include_bytes!("bonsai_256x256x256_uint8.raw") (absent from the checkout); fmt = VK_FMT_R16_UNORM: a raw
+    // file of native-endian 16-bit integers (CT / MR data)
+    static VolumeTexture from_raw(Context &ctx, const std::string &path, uint32_t nx = 256, uint32_t ny = 256, uint32_t nz = 256, int fmt = VK_FMT_R8_UNORM) {
+        std::vector<char> buf = read_raw(path, nx, ny, nz, fmt);
+        return VolumeTexture(ctx, buf.data(), nx, ny, nz, fmt);
+    }
+    // the bytes of such a file: nx * ny * nz voxels of 1 (R8_UNORM) or 2 (R16_UNORM) bytes.  An R16_UNORM file must have exactly that size (a
+    // wrong --dims would otherwise show a sheared volume); an R8_UNORM file may be longer, as it always could: its leading bytes are taken
+    static std::vector<char> read_raw(const std::string &path, uint32_t nx, uint32_t ny, uint32_t nz, int fmt) {
+        if (fmt != VK_FMT_R8_UNORM && fmt != VK_FMT_R16_UNORM) throw std::runtime_error("raw volumes are R8_UNORM or R16_UNORM");
+        std::ifstream f(path, std::ios::binary | std::ios::ate);
         if (!f) throw std::runtime_error("cannot open " + path);
-        std::vector<char> buf((size_t)nx * ny * nz);
+        std::vector<char> buf((size_t)nx * ny * nz * (fmt == VK_FMT_R16_UNORM ? 2 : 1));
+        if (fmt == VK_FMT_R16_UNORM && (size_t)f.tellg() != buf.size()) throw std::runtime_error(path + ": expected " + std::to_string(buf.size()) + " bytes");
+        f.seekg(0);
         f.read(buf.data(), (std::streamsize)buf.size());
         if ((size_t)f.gcount() != buf.size()) throw std::runtime_error(path + ": expected " + std::to_string(buf.size()) + " bytes");
-        return VolumeTexture(ctx, buf.data(), nx, ny, nz);
+        return buf;
     }
     static VolumeTexture generate(Context &ctx, int kind, uint32_t nx, uint32_t ny, uint32_t nz, int fmt = VK_FMT_R8_UNORM,
                                   uint32_t seed = 0x5EED0001u, uint32_t lo = 20, uint32_t span = 12, int layout = VK_LAYOUT_AUTO) {
