@@ -74,6 +74,9 @@ DEFINE_KERNEL(k_lshl_add, OP3("v_lshl_add_u32"))
 DEFINE_KERNEL(k_add3, OP3("v_add3_u32"))
 DEFINE_KERNEL(k_mad_i24, OP3("v_mad_i32_i24"))
 DEFINE_KERNEL(k_med3_i32, OP3("v_med3_i32"))
+// the 32-bit integer multiplies of an unsigned division by a launch constant (the block map before its reciprocals: profiles/block_map_scalar.txt)
+DEFINE_KERNEL(k_mul_lo_u32, OP2("v_mul_lo_u32"))
+DEFINE_KERNEL(k_mul_hi_u32, OP2("v_mul_hi_u32"))
 DEFINE_KERNEL(k_fma_mix, "v_fma_mix_f32 %0, %0, %8, %9 op_sel_hi:[0,1,1]\nv_fma_mix_f32 %1, %1, %8, %9 op_sel_hi:[0,1,1]\nv_fma_mix_f32 %2, %2, %8, %9 op_sel_hi:[0,1,1]\n"
                          "v_fma_mix_f32 %3, %3, %8, %9 op_sel_hi:[0,1,1]\nv_fma_mix_f32 %4, %4, %8, %9 op_sel_hi:[0,1,1]\nv_fma_mix_f32 %5, %5, %8, %9 op_sel_hi:[0,1,1]\n"
                          "v_fma_mix_f32 %6, %6, %8, %9 op_sel_hi:[0,1,1]\nv_fma_mix_f32 %7, %7, %8, %9 op_sel_hi:[0,1,1]\n")
@@ -224,7 +227,7 @@ int main(int argc, char **argv) {
         {"v_pk_fma_f32", k_pk_fma, 16}, {"v_fma_f64", k_fma_f64, 16}, {"v_fma_mix_f32", k_fma_mix, 16}, {"v_cos_f32", k_cos, 16}, {"v_exp_f32", k_exp, 16}, {"v_rcp_f32", k_rcp, 16},
         {"v_fract_f32", k_fract, 16}, {"v_cvt_flr_i32_f32", k_cvt_flr, 16}, {"v_cvt_f32_i32", k_cvt_f32_i32, 16}, {"v_cvt_f32_ubyte0", k_cvt_ub0, 16},
         {"v_min_i32", k_min_i32, 16}, {"v_add_u32", k_add_u32, 16}, {"v_lshlrev_b32", k_lshl, 16}, {"v_lshl_add_u32", k_lshl_add, 16}, {"v_add3_u32", k_add3, 16}, {"v_mad_i32_i24", k_mad_i24, 16},
-        {"v_med3_i32", k_med3_i32, 16}, {"v_fmac_f32 (VOP2)", k_fmac, 16}, {"v_add_f32_e64 (VOP3)", k_add_e64, 16}, {"v_max_f32", k_max, 16}, {"v_mov_b32", k_mov, 16}, {"v_and_b32", k_and, 16},
+        {"v_med3_i32", k_med3_i32, 16}, {"v_mul_lo_u32", k_mul_lo_u32, 16}, {"v_mul_hi_u32", k_mul_hi_u32, 16}, {"v_fmac_f32 (VOP2)", k_fmac, 16}, {"v_add_f32_e64 (VOP3)", k_add_e64, 16}, {"v_max_f32", k_max, 16}, {"v_mov_b32", k_mov, 16}, {"v_and_b32", k_and, 16},
         {"v_cvt_f32_f16", k_cvt_f32_f16, 16}, {"v_perm_b32", k_perm, 16}, {"v_cndmask_b32 (vcc never written)", k_cndmask, 16},
         {"v_cndmask_b32 (vcc from v_cmp, per 8+1)", k_cndmask_vcc_set, 2}, {"v_cmp + v_cndmask (per pair)", k_cmp_cndmask, 8}, {"v_cndmask_b32_e64 (SGPR pair)", k_cndmask_sgpr, 16},
         {"v_bfi_b32", k_bfi, 16}, {"v_xor_b32", k_xor, 16}, {"v_floor_f32", k_floor, 16}, {"v_rndne_f32", k_rndne, 16},

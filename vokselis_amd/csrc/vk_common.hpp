@@ -12,6 +12,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "vk_hostmath.hpp"  // deal_*, block / pixel / record index maps (shared with the host and with tests/hostmath_fuzz.cpp)
@@ -121,12 +122,17 @@ struct LaunchDesc {
     uint32_t *present_rgba8;       // nullptr: no fused present
     uint32_t *present_bgra8;       // optional surface copy
     uint32_t present_only;         // != 0: the HDR pixel itself is not stored
+    // the reciprocals of the block map's divisors -- ts / 8 and its square, n_frames, tiles_x, the deal's root_skip (vk_hostmath.hpp:
+    // block_map_make, called where the fields above are filled): a wave maps its block without a division
+    BlockMapDesc bm;
     // LF_ORDER_INLINE: the tile order rides in the kernel arguments (single-frame launches of up to kOrderInline tiles): no table upload
     // in the frame's stream.  Last member: launches that do not use it never touch these bytes.
     uint16_t order_inline[1024];
 };
 constexpr uint32_t kOrderInline = 1024;
-static_assert(sizeof(LaunchDesc) <= 2560, "LaunchDesc + VolumeDesc + StagedDesc travel as kernel arguments (4 KiB)");
+static_assert(offsetof(LaunchDesc, order_inline) % 4 == 0, "the inline order is read a dword at a time");
+// (its size is held where the kernels' arguments are summed -- LaunchDesc + VolumeDesc + the family's descriptors + the hidden arguments
+// against the 4 KiB segment: vk_launch.hpp, kernargs_fit)
 
 // LaunchDesc::flags.  Policy and instrumentation switches of one launch, set by the host (vk_render.hip) and read by the kernels.
 enum LaunchFlag : uint32_t {
@@ -170,36 +176,66 @@ struct PixelMap {
     uint32_t pos;      // position of the wave's tile in the heaviest-first order (wave-uniform)
 };
 
-// The frame a wave belongs to: camera, cull rectangle, order table.  Wave-uniform (scalar loads).
+// The frame a wave belongs to: camera, cull rectangle, order table, and the wave's place in it.  Wave-uniform, and kept so: every member
+// comes from kernel arguments or scalar loads.
 struct FrameView {
     float eye[4];
-    float inv_proj[16];
+    float inv_proj[16];  // column-major
     int32_t cull_x0, cull_y0, cull_x1, cull_y1;
     const uint32_t *order;
     uint32_t n_tiles_launch;
     uint32_t n_active;  // leading positions whose tiles the box's silhouette can reach; the tiles behind them hold only clear colour
     uint32_t frame;
-    uint32_t lb;  // the wave's logical block inside its frame
+    uint32_t slot, sub;  // the wave's tile slot in this launch and its 8x8 block inside the tile
 };
 
+// The batch's tables (FrameDesc, the order) are written before the launch and never by it, and a wave reads them at addresses that
+// depend on nothing of the lane: seen through the constant address space they arrive by scalar loads.
+typedef const __attribute__((address_space(4))) FrameDesc *ConstFrameDescPtr;
+typedef const __attribute__((address_space(4))) uint32_t *ConstU32Ptr;
+
+// The launch's constants the map reads, fetched in one block of scalar loads from the kernel arguments and waited for once: every value is
+// read first, then held in a scalar register by an empty asm (30 operands at most per statement).  Left to itself the compiler sinks each
+// scalar load of the map to its first use, and the map becomes a chain of a dozen dependent round trips to the scalar cache -- which a
+// single frame, bound by its waves' latency, pays in full (profiles/block_map_scalar.txt).
+__device__ __forceinline__ void fetch_launch_constants(const LaunchDesc &L) {
+    const uint32_t W = L.W, H = L.H, rw = L.rw, rh = L.rh, ts = L.ts, tiles_x = L.tiles_x, tiles_y = L.tiles_y, n_tiles_launch = L.n_tiles_launch;
+    const int32_t ox = L.ox, oy = L.oy, c0 = L.cull_x0, c1 = L.cull_y0, c2 = L.cull_x1, c3 = L.cull_y1;
+    const uint32_t rank = L.rank, nranks = L.nranks, root_skip = L.root_skip, n_blocks = L.n_blocks, compact = L.compact, flags = L.flags;
+    const uint32_t n_frames = L.n_frames, n_active_tiles = L.n_active_tiles;
+    const uint32_t *order = L.tile_order;
+    const FrameDesc *frames = L.frames;
+    const BlockMapDesc bm = L.bm;
+    asm volatile("" ::"s"(W), "s"(H), "s"(rw), "s"(rh), "s"(ts), "s"(tiles_x), "s"(tiles_y), "s"(n_tiles_launch), "s"(ox), "s"(oy), "s"(c0), "s"(c1), "s"(c2), "s"(c3),
+                 "s"(rank), "s"(nranks), "s"(root_skip), "s"(n_blocks), "s"(compact), "s"(flags), "s"(n_frames), "s"(n_active_tiles), "s"(order), "s"(frames),
+                 "s"(bm.per_tile.mul), "s"(bm.per_tile.shift), "s"(bm.n_frames.mul), "s"(bm.n_frames.shift), "s"(bm.tiles_x.mul), "s"(bm.tiles_x.shift));
+    asm volatile("" ::"s"(bm.sps.mul), "s"(bm.sps.shift), "s"(bm.skip.mul), "s"(bm.skip.shift), "s"(bm.skip_m1.mul), "s"(bm.skip_m1.shift));
+}
+
+// A batch's camera comes from its FrameDesc by scalar loads; a single frame's from the kernel arguments.
 __device__ __forceinline__ FrameView frame_view(const LaunchDesc &L, uint32_t lb) {
     FrameView f;
+    fetch_launch_constants(L);
+    const uint32_t sps = L.ts >> 3, per_tile = sps * sps;
+    // (slot, frame) pairs, frame fastest; with LF_FRAME_RUNS every XCD marches a run of CONSECUTIVE frames of a tile position: under a moving
+    // camera neighbouring frames share almost all of their cells, frames eight apart far fewer (vk_hostmath.hpp: batch_block_split)
+    const BlockSplit bs = batch_block_split(lb, per_tile, L.frames ? L.n_frames : 1u, L.frames && (L.flags & LF_FRAME_RUNS) != 0u, L.bm);
+    f.frame = bs.frame; f.slot = bs.slot; f.sub = bs.sub;
     if (L.frames) {
-        const uint32_t sps = L.ts >> 3, per_tile = sps * sps;
-        // (slot, frame) pairs, frame fastest; with LF_FRAME_RUNS every XCD marches a run of CONSECUTIVE frames of a tile position: under a moving
-        // camera neighbouring frames share almost all of their cells, frames eight apart far fewer (vk_hostmath.hpp: batch_block_split)
-        const BlockSplit bs = batch_block_split(lb, per_tile, L.n_frames, (L.flags & LF_FRAME_RUNS) != 0u);
-        f.frame = bs.frame;
-        f.lb = bs.slot * per_tile + bs.sub;
-        const FrameDesc &d = L.frames[f.frame];
+        ConstFrameDescPtr d = (ConstFrameDescPtr)L.frames + bs.frame;
+        {   // the record's tail in one block too (eye and inv_proj are whole-array loads already)
+            const int32_t c0 = d->cull_x0, c1 = d->cull_y0, c2 = d->cull_x1, c3 = d->cull_y1;
+            const uint32_t off = d->order_off, na = d->n_active, p0 = d->pad[0];
+            asm volatile("" ::"s"(c0), "s"(c1), "s"(c2), "s"(c3), "s"(off), "s"(na), "s"(p0));
+        }
 #pragma unroll
-        for (int i = 0; i < 4; i++) f.eye[i] = d.eye[i];
+        for (int i = 0; i < 4; i++) f.eye[i] = d->eye[i];
 #pragma unroll
-        for (int i = 0; i < 16; i++) f.inv_proj[i] = d.inv_proj[i];
-        f.cull_x0 = d.cull_x0; f.cull_y0 = d.cull_y0; f.cull_x1 = d.cull_x1; f.cull_y1 = d.cull_y1;
-        f.order = L.tile_order + d.order_off;
-        f.n_tiles_launch = d.n_active;
-        f.n_active = d.pad[0];
+        for (int i = 0; i < 16; i++) f.inv_proj[i] = d->inv_proj[i];
+        f.cull_x0 = d->cull_x0; f.cull_y0 = d->cull_y0; f.cull_x1 = d->cull_x1; f.cull_y1 = d->cull_y1;
+        f.order = L.tile_order + d->order_off;
+        f.n_tiles_launch = d->n_active;
+        f.n_active = d->pad[0];
     } else {
 #pragma unroll
         for (int i = 0; i < 4; i++) f.eye[i] = L.eye[i];
@@ -209,32 +245,38 @@ __device__ __forceinline__ FrameView frame_view(const LaunchDesc &L, uint32_t lb
         f.order = L.tile_order;
         f.n_tiles_launch = L.n_tiles_launch;
         f.n_active = L.n_active_tiles;
-        f.frame = 0;
-        f.lb = lb;
     }
     return f;
 }
 
+// entry `pos` of the order that rides in the kernel arguments: u16 entries, read as the dword that holds them (a scalar load)
+__device__ __forceinline__ uint32_t order_inline_at(const LaunchDesc &L, uint32_t pos) {
+    uint32_t w;
+    __builtin_memcpy(&w, reinterpret_cast<const char *>(L.order_inline) + (size_t)(pos >> 1) * 4u, 4);
+    return (w >> ((pos & 1u) * 16u)) & 0xffffu;
+}
+
+// Block -> pixels.  Everything up to the block's corner is wave-uniform and runs on the scalar unit; the lane adds (lane & 7, lane >> 3)
+// and its 32-bit part of the output index (vk_hostmath.hpp: tile_pixel, block_lane_part).
 __device__ __forceinline__ PixelMap map_pixel(const LaunchDesc &L, const FrameView &fv, uint32_t lane) {
     PixelMap m;
-    const uint32_t lb = fv.lb;
-    uint32_t sps = L.ts >> 3;              // 8x8 blocks per tile edge
-    uint32_t per_tile = sps * sps;
-    uint32_t slot = lb / per_tile, sub = lb - slot * per_tile;
-    uint32_t pos = deal_pos(L.rank, slot, L.nranks, L.root_skip);  // position in the heaviest-first order
+    const uint32_t pos = deal_pos(L.rank, fv.slot, L.nranks, L.root_skip, L.bm);  // position in the heaviest-first order
     const uint32_t n_tiles = L.tiles_x * L.tiles_y;
-    uint32_t tile = pos < fv.n_tiles_launch ? ((L.flags & LF_ORDER_INLINE) ? (uint32_t)L.order_inline[pos] : fv.order[pos]) : n_tiles;
-    const TilePixel tp = tile_pixel(L.ts, L.tiles_x, tile, sub, lane);  // (vk_hostmath.hpp)
-    const uint32_t lx = tp.lx, ly = tp.ly, rx = tp.rx, ry = tp.ry;
-    m.x = L.ox + (int32_t)rx;
-    m.y = L.oy + (int32_t)ry;
-    m.valid = (tile < n_tiles) && rx < L.rw && ry < L.rh && m.x >= 0 && m.y >= 0 &&
+    uint32_t tile = n_tiles;
+    if (pos < fv.n_tiles_launch) tile = (L.flags & LF_ORDER_INLINE) ? order_inline_at(L, pos) : ((ConstU32Ptr)fv.order)[pos];
+    const TilePixel c = tile_pixel(L.ts, L.tiles_x, tile, fv.sub, 0u, L.bm);  // the block's corner
+    const int32_t x0 = L.ox + (int32_t)c.rx, y0 = L.oy + (int32_t)c.ry;      // ... in the image
+    const uint32_t cx = lane & 7u, cy = lane >> 3;
+    m.x = x0 + (int32_t)cx;
+    m.y = y0 + (int32_t)cy;
+    m.valid = (tile < n_tiles) && c.rx + cx < L.rw && c.ry + cy < L.rh && m.x >= 0 && m.y >= 0 &&
               m.x < (int32_t)L.W && m.y < (int32_t)L.H;
     const uint32_t nf = L.frames ? L.n_frames : 1u;
     m.pos = pos;
-    m.rec = compact_record(slot, nf, fv.frame);
-    m.rec_px = ly * L.ts + lx;
-    m.out_index = L.compact ? compact_pixel_index(m.rec, L.ts, lx, ly) : frame_pixel_index(fv.frame, L.W, L.H, (uint32_t)m.x, (uint32_t)m.y);
+    m.rec = compact_record(fv.slot, nf, fv.frame);
+    m.rec_px = c.ly * L.ts + c.lx + block_lane_part(lane, L.ts);
+    m.out_index = L.compact ? compact_pixel_index(m.rec, L.ts, c.lx, c.ly) + block_lane_part(lane, L.ts)
+                            : (size_t)(frame_block_base(fv.frame, L.W, L.H, x0, y0) + (int64_t)block_lane_part(lane, L.W));
     return m;
 }
 

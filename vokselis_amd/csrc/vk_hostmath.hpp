@@ -5,6 +5,8 @@
 // No HIP in here: the kernels (vk_common.hpp, vk_post.hpp) and the host (vk_order.hip, vk_batch.hip) include it, and so does
 // tests/hostmath_fuzz.cpp, a plain g++ -fsanitize=address,undefined program that replays a whole partition -> gather -> un-tile on the CPU
 // with these very functions (tile sizes 8..1024, frame shapes that are not multiples of the tile, 1..8 ranks, weighted deals, 1..64 frames).
+// The kernels run the block map without a division (UDiv, block_map_make and the overloads that take a BlockMapDesc, below);
+// tests/block_map_fuzz.cpp holds those to the '/'-based functions here, which stay the definition.
 #pragma once
 
 #include <stdint.h>
@@ -99,6 +101,92 @@ VK_HD TilePixel tile_pixel(uint32_t ts, uint32_t tiles_x, uint32_t tile, uint32_
     p.rx = ttx * ts + p.lx; p.ry = tty * ts + p.ly;
     return p;
 }
+// ---- the same map without a division: what the kernels run (vk_common.hpp: frame_view, map_pixel) -------------------------------
+// Every divisor of the map above is a constant of the launch, so the host hands the kernel a reciprocal for each (LaunchDesc::bm)
+// and a wave maps its block with scalar multiplies.  The functions above stay the definition; tests/block_map_fuzz.cpp holds these
+// to them.
+//
+// UDiv: n / d == mulhi(2 n, mul) >> shift for EVERY n < 2^31, with s = ceil(log2 d), shift = s, mul = ceil(2^(31 + s) / d).
+// Proof: mul * d = 2^(31 + s) + e with 0 <= e < d <= 2^s, so n * mul / 2^(31 + s) = n / d + n * e / (d * 2^(31 + s)); the last term
+// is below 1 / d because n * e < 2^31 * 2^s, and the fractional part of n / d is at most (d - 1) / d: the floor does not move.
+// mul fits 32 bits: 2^(31 + s) / d < 2^32 (d > 2^(s - 1)), and is exactly 2^31 for a power of two, where the whole thing is a shift.
+// One form for every divisor, so the kernels carry no branch on the divisor's kind.  d in [1, 2^31]; a larger d divides every n < 2^31 to 0: mul = 0.
+struct UDiv { uint32_t mul, shift; };
+constexpr uint64_t kUDivBound = 1ull << 31;  // numerators stay below it
+inline bool udiv_make(uint32_t d, UDiv &u) {
+    u.mul = 0; u.shift = 0;
+    if (d == 0) return false;
+    if (d > (1u << 31)) return true;  // every n < 2^31 gives 0, and so does mul = 0 (a root_skip the deal never reaches)
+    uint32_t s = 0;
+    while ((1ull << s) < d) s++;
+    u.shift = s;
+    u.mul = (uint32_t)(((1ull << (31u + s)) + d - 1u) / d);
+    return true;
+}
+VK_HD uint32_t umulhi32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
+VK_HD uint32_t udiv(uint32_t n, UDiv u) { return umulhi32(n << 1, u.mul) >> u.shift; }
+
+// The reciprocals of one launch.  skip / skip_m1 are those of the deal's k and k - 1 (1 when the deal is the plain round robin).
+struct BlockMapDesc {
+    UDiv per_tile, n_frames, tiles_x, sps, skip, skip_m1;
+};
+// Filled where the host fills the launch (vk_render.hip, vk_batch.hip).  n_blocks: the launch's logical blocks -- every block index
+// the map sees is below it (the grid's padding returns first).  False when a divisor is 0 or a numerator could reach 2^31: the block
+// index itself, a tile id (tiles_x * tiles_y stands for "no tile"), or the deal's round slot + slot / (k - 1).
+inline bool block_map_make(uint32_t ts, uint32_t tiles_x, uint32_t tiles_y, uint32_t n_frames, uint32_t nranks, uint32_t root_skip, uint64_t n_blocks, BlockMapDesc &m) {
+    const uint32_t sps = ts >> 3;
+    const uint64_t per_tile = (uint64_t)sps * sps;
+    const uint32_t k = (nranks > 1 && root_skip >= 2u) ? root_skip : 0u;
+    bool ok = sps != 0 && (ts & 7u) == 0 && per_tile <= kUDivBound && nranks != 0;
+    ok = udiv_make((uint32_t)per_tile, m.per_tile) && ok;
+    ok = udiv_make(n_frames, m.n_frames) && ok;
+    ok = udiv_make(tiles_x, m.tiles_x) && ok;
+    ok = udiv_make(sps, m.sps) && ok;
+    ok = udiv_make(k ? k : 1u, m.skip) && ok;
+    ok = udiv_make(k ? k - 1u : 1u, m.skip_m1) && ok;
+    if (!ok) return false;
+    if (n_blocks > kUDivBound || (uint64_t)tiles_x * tiles_y >= kUDivBound) return false;
+    const uint64_t slot_max = n_blocks / per_tile / n_frames;  // the launch's slots: every slot is below it
+    if (k && slot_max + slot_max / (k - 1u) >= kUDivBound) return false;
+    return true;
+}
+
+// batch_block_split, deal_pos and tile_pixel with the launch's reciprocals: the same results (a single frame is a batch of one)
+VK_HD BlockSplit batch_block_split(uint32_t lb, uint32_t per_tile, uint32_t n_frames, bool frame_runs, const BlockMapDesc &m) {
+    BlockSplit s;
+    const uint32_t g = udiv(lb, m.per_tile);
+    s.sub = lb - g * per_tile;
+    s.slot = udiv(g, m.n_frames);
+    uint32_t fr = g - s.slot * n_frames;
+    if (frame_runs) {
+        const uint32_t x = fr & 7u, j = fr >> 3, q = n_frames >> 3, rem = n_frames & 7u;
+        fr = x * q + (x < rem ? x : rem) + j;
+    }
+    s.frame = fr;
+    return s;
+}
+VK_HD uint32_t deal_pos(uint32_t rank, uint32_t slot, uint32_t N, uint32_t k, const BlockMapDesc &m) {
+    if (k < 2u) return rank + slot * N;
+    const uint32_t round = rank ? slot : slot + udiv(slot, m.skip_m1);
+    const uint32_t rk = udiv(round, m.skip);
+    return round * N - rk + rank - ((round - rk * k) == k - 1u ? 1u : 0u);
+}
+// (lane 0 gives the 8x8 block's corner)
+VK_HD TilePixel tile_pixel(uint32_t ts, uint32_t tiles_x, uint32_t tile, uint32_t sub, uint32_t lane, const BlockMapDesc &m) {
+    TilePixel p;
+    const uint32_t sps = ts >> 3;
+    const uint32_t tty = udiv(tile, m.tiles_x), ttx = tile - tty * tiles_x;
+    const uint32_t sy = udiv(sub, m.sps), sx = sub - sy * sps;
+    p.lx = sx * 8u + (lane & 7u); p.ly = sy * 8u + (lane >> 3);
+    p.rx = ttx * ts + p.lx; p.ry = tty * ts + p.ly;
+    return p;
+}
+// The output index of a block's lane is the index of the block's corner -- wave-uniform, 64 bits -- plus the lane's 32-bit part
+// (l >> 3) * pitch + (l & 7), pitch = ts (compact records: compact_pixel_index of the corner) or W (whole frames).  A region origin off the
+// screen makes a corner (x0, y0) negative; the pixels such a block stores are on the screen, and for them base + part is frame_pixel_index.
+VK_HD int64_t frame_block_base(uint32_t frame, uint32_t W, uint32_t H, int32_t x0, int32_t y0) { return ((int64_t)frame * H + y0) * (int64_t)W + x0; }
+VK_HD uint32_t block_lane_part(uint32_t lane, uint32_t pitch) { return (lane >> 3) * pitch + (lane & 7u); }
+
 // compact output of a partition: the (slot, frame) record and the pixel inside it; whole frames: [frame][H][W]
 VK_HD uint32_t compact_record(uint32_t slot, uint32_t n_frames, uint32_t frame) { return slot * n_frames + frame; }
 VK_HD size_t compact_pixel_index(uint32_t rec, uint32_t ts, uint32_t lx, uint32_t ly) { return (size_t)rec * ((size_t)ts * ts) + (size_t)ly * ts + lx; }

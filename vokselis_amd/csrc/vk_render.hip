@@ -76,6 +76,9 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
     const uint64_t n_blocks = L.n_blocks;
     uint32_t grid = (uint32_t)((n_blocks + 511) / 512 * 512);
     L.grid_march = grid;
+    // the block map's reciprocals (vk_hostmath.hpp): exact for every block index below n_blocks, or the launch is refused
+    if (!block_map_make(L.ts, L.tiles_x, L.tiles_y, L.frames ? L.n_frames : 1u, L.nranks, L.root_skip, n_blocks, L.bm))
+        return fail(ctx, VK_ERR_UNSUPPORTED, "launch too large for the block map: a smaller image, larger tiles or fewer frames per batch");
     // a runtime transfer function (vk_set_transfer_function) has kernels on the LINEAR / PACKED / PACKED_PAIRS layouts, walking with the loop
     // a first-hit isosurface (vk_set_isosurface): kernels of its own with the table kernels' coverage; table and projection are ignored under it, lighting is honoured
     const bool iso = mode == VK_MODE_NAIVE_TRILINEAR && ctx->iso_on;
