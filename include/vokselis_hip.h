@@ -273,6 +273,47 @@ typedef struct vk_isosurface {
 int vk_set_isosurface(vk_ctx *ctx, const vk_isosurface *iso);
 int vk_get_isosurface(vk_ctx *ctx, vk_isosurface *out, int *enabled);
 
+/* Light-direction shadows of the first-hit isosurface: a ray that hit casts one more isosurface ray from its
+ * refined crossing towards the light, and a point whose shadow ray hits keeps 1 - strength of its diffuse and specular terms.
+ * They take effect on a NAIVE_TRILINEAR render only when an isosurface is set, lighting is set and the light is not a headlight (a
+ * headlight's shadow ray runs back along the primary ray, which was empty up to the hit).  In every other case -- unlit isosurface,
+ * headlight, table / lit / MAX / built-in renders, COMPUTE_NEAREST, PROCEDURAL -- the state is stored and ignored, and the render
+ * launches the kernels it launches without shadows, bit for bit.
+ * For a ray that hit, with q the refined crossing (a first-iteration hit: p itself), g the gradient, L = (lx, ly, lz) the unit light
+ * direction, iso_k the threshold and [lo, hi] the box the primary ray marched (the clip box when one is set, else the unit cube), every
+ * operation one f32 rounding:
+ *     dts = dt_scale * min(1 / (nx |L.x|), 1 / (ny |L.y|), 1 / (nz |L.z|))       the primary ray's dt formula with L for dir
+ *     intersect_box(q, L, lo, hi) -> tb0, tb1                                    the same function, the same operations
+ *     shadowed = false
+ *     if (!(tb0 > tb1)) {
+ *         ts0 = max(max(tb0, 0), bias * dts)
+ *         ps = (fma(ts0, L.x, q.x), fma(ts0, L.y, q.y), fma(ts0, L.z, q.z));  ss = L * dts
+ *         for (t = ts0; t < tb1; t = t + dts) {
+ *             if (trilinear(V, ps) >= iso_k) { shadowed = true; break; }         the filter of every other render; NaN is no hit
+ *             ps = ps + ss
+ *         }
+ *     }
+ *     k = shadowed ? 1 - strength : 1
+ *     rgb' = c.rgb * (ambient + (diffuse * diff) * k) + (specular * spec) * k    diff, spec as under vk_set_lighting; no gradient: diff = 1, spec = 0
+ * A point facing away from the light marches into its own material and is shadowed: with the two-sided |N.L| this is what keeps the
+ * far side of an object from lighting up.  bias = 0 samples q itself, which is at or above the threshold by the bisection's invariant:
+ * every hit pixel is then shadowed.  Shadow iterations count in neither the per-pixel step image nor S_ref / S_sampled.  The skip maps
+ * are the isosurface's and stay exact for the shadow ray (the same filter, the same compare, one map per octant).
+ * The state rules are lighting's: pure host state read when a render is recorded -- no drain, no map rebuild, settable at any time,
+ * between vk_frame_begin and vk_frame_end too (renders recorded before the call keep the old value) -- and it stays in force across
+ * vk_volume_upload / _upload_device / vk_volume_generate.  s == NULL turns shadows off.  VK_ERR_INVALID (the previous state stays in
+ * force): a non-finite field, strength outside [0, 1], bias outside [0, VK_SHADOW_MAX_BIAS].  Layouts and flags are the isosurface's.
+ * vk_render, vk_render_partition, vk_render_batch, frames in flight, the fused present and vk_group_render honour it; the ranks of a
+ * partition and the members of a group need the same value on every context (as for the clip box).
+ * vk_get_shadows: *enabled (may be NULL) says whether shadows are set; *out (may be NULL) receives them when they are. */
+#define VK_SHADOW_MAX_BIAS 1024
+typedef struct vk_shadows {
+    float strength; /* 0 .. 1: how much of the diffuse and specular terms a shadowed point loses */
+    float bias;     /* 0 .. VK_SHADOW_MAX_BIAS: distance of the first shadow sample from the surface, in shadow steps */
+} vk_shadows;       /* 8 bytes */
+int vk_set_shadows(vk_ctx *ctx, const vk_shadows *s);
+int vk_get_shadows(vk_ctx *ctx, vk_shadows *out, int *enabled);
+
 /* A clip box (cut-away, region of interest) of the table, lit, MAX and isosurface marches: NAIVE_TRILINEAR rays of those renders march
  * the box [lo, hi], given in unit-cube coordinates, instead of the unit cube.  intersect_box takes box_min = lo and box_max = hi per
  * axis, in the same f32 operations:

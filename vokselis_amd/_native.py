@@ -44,6 +44,14 @@ class VkIsosurface(C.Structure):
 
 assert C.sizeof(VkIsosurface) == 20
 
+
+class VkShadows(C.Structure):
+    """vk_shadows (8 bytes): how much of the diffuse and specular terms a shadowed point loses, and the first shadow sample's distance."""
+    _fields_ = [("strength", C.c_float), ("bias", C.c_float)]
+
+
+assert C.sizeof(VkShadows) == 8
+
 class VkClipBox(C.Structure):
     """vk_clip_box (24 bytes): the clip box of the table, lit, MAX and isosurface marches, lo and hi per axis in unit-cube coordinates."""
     _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3)]
@@ -91,6 +99,8 @@ SYMBOLS = {
     "vk_get_projection": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "vk_set_isosurface": (C.c_int, [_vp, _vp]),  # const vk_isosurface * (VkIsosurface above), NULL: off
     "vk_get_isosurface": (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
+    "vk_set_shadows": (C.c_int, [_vp, _vp]),  # const vk_shadows * (VkShadows above), NULL: off
+    "vk_get_shadows": (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
     "vk_set_clip_box": (C.c_int, [_vp, _vp]),  # const vk_clip_box * (VkClipBox above), NULL: off
     "vk_get_clip_box": (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),

@@ -279,6 +279,27 @@ class Context:
         li.ambient, li.diffuse, li.specular, li.shininess = float(ambient), float(diffuse), float(specular), float(shininess)
         N.check(self._h, L.vk_set_lighting(self._h, C.byref(li)))
 
+    def set_shadows(self, strength=0.7, bias=2.0):
+        """Light-direction shadows of the lit isosurface (vk_set_shadows): a ray that hit marches once more from the crossing towards
+        the light, and a point whose shadow ray meets the surface again keeps 1 - strength of its diffuse and specular terms.  `bias`:
+        the distance of the first shadow sample from the surface, in shadow steps (0 .. 1024; 0 shadows every hit).  set_shadows(None)
+        turns them off.  They take effect only under set_isosurface with set_lighting and a light that is not "headlight"; every other
+        render ignores them.  Host state like lighting: takes effect from the next recorded render, no drain."""
+        L = N.lib()
+        if strength is None:
+            N.check(self._h, L.vk_set_shadows(self._h, None))
+            return
+        s = N.VkShadows()
+        s.strength, s.bias = float(strength), float(bias)
+        N.check(self._h, L.vk_set_shadows(self._h, C.byref(s)))
+
+    @property
+    def shadows(self):
+        """The shadows in force as (strength, bias), or None (vk_get_shadows)."""
+        s, on = N.VkShadows(), C.c_int(0)
+        N.check(self._h, N.lib().vk_get_shadows(self._h, C.byref(s), C.byref(on)))
+        return (s.strength, s.bias) if on.value else None
+
     def set_clip_box(self, lo, hi=None):
         """A clip box (cut-away) of the table, lit, MAX and isosurface marches (vk_set_clip_box): NAIVE_TRILINEAR rays march the box
         lo = (x0, y0, z0) .. hi = (x1, y1, z1), in unit-cube coordinates with 0 <= lo < hi <= 1 per axis, instead of the whole cube.

@@ -11,6 +11,7 @@
 //   vk_launch_lit.hip      instantiates the table march with gradient lighting (vk_march.hpp, vk_light.hpp)
 //   vk_launch_mip.hip      instantiates the cell march under the maximum-intensity projection (vk_march.hpp, vk_march_mip.hpp)
 //   vk_launch_iso.hip      instantiates the cell march under a first-hit isosurface (vk_march.hpp, vk_march_iso.hpp, vk_iso.hpp)
+//   vk_launch_iso_shadow.hip  instantiates the isosurface march with light-direction shadows (vk_march_iso.hpp, vk_shadow.hpp)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)
@@ -21,6 +22,7 @@
 #include "vk_common.hpp"
 #include "vk_iso.hpp"
 #include "vk_light.hpp"
+#include "vk_shadow.hpp"
 #include "vk_tf.hpp"
 
 #include <hip/hip_runtime.h>
@@ -69,6 +71,9 @@ struct vk_ctx {
     // gradient lighting of the table march (vk_set_lighting): host state, passed by value to the lit kernels
     bool lit = false;
     vk::LightDesc light{};
+    // light-direction shadows of the lit isosurface (vk_set_shadows): host state like lighting, passed by value to the shadow kernels
+    bool shadows_on = false;
+    vk_shadows shadows{};
     // clip box of the table, lit, MAX and isosurface marches (vk_set_clip_box): host state like lighting, in unit-cube coordinates; it also
     // tightens the host's screen-space geometry (vk_order.hip) and is part of the cached orders' keys
     bool clip_on = false;
@@ -240,6 +245,10 @@ void launch_cells_lit(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc
                       bool safe);  // vk_launch_lit.hip
 void launch_cells_mip(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_mip.hip (T.rgba == nullptr: the grey ramp)
 void launch_cells_iso(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::IsoDesc &I, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool count, bool skip, bool safe);  // vk_launch_iso.hip
+void launch_cells_iso_shadow(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::IsoDesc &I, const vk::ShadowDesc &Sh, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool count,
+                             bool skip, bool safe);  // vk_launch_iso_shadow.hip
+void launch_u16_iso_shadow(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::IsoDesc &I, const vk::ShadowDesc &Sh, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool count,
+                           bool skip, bool safe);  // vk_launch_u16_iso_shadow.hip
 // vk_launch_u16_*.hip: the same five families on an R16_UNORM volume (vk_march_u16.hpp); a family reads its own descriptors, Cl == nullptr: no box
 #define VK_U16_LAUNCH(name) void name(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::LightDesc &Li, const vk::IsoDesc &I, const vk::ClipDesc *Cl, uint32_t grid, bool count, bool skip, bool safe)
 VK_U16_LAUNCH(launch_u16_cells);

@@ -21,6 +21,8 @@ __global__ __launch_bounds__(64) void raymarch_iso_kernel(const LaunchDesc L, co
     const IsoDesc *isd = &I;
     constexpr bool CLIP = false;
     const ClipDesc *clp = nullptr;
+    constexpr bool SHADOW = false;
+    const ShadowDesc *shd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 
@@ -36,6 +38,8 @@ __global__ __launch_bounds__(64) void raymarch_iso_clip_kernel(const LaunchDesc 
     const IsoDesc *isd = &I;
     constexpr bool CLIP = true;
     const ClipDesc *clp = &Cl;
+    constexpr bool SHADOW = false;
+    const ShadowDesc *shd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

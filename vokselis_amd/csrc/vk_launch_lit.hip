@@ -18,6 +18,8 @@ __global__ __launch_bounds__(64) void raymarch_lit_kernel(const LaunchDesc L, co
     const IsoDesc *isd = nullptr;
     constexpr bool CLIP = false;
     const ClipDesc *clp = nullptr;
+    constexpr bool SHADOW = false;
+    const ShadowDesc *shd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 
@@ -33,6 +35,8 @@ __global__ __launch_bounds__(64) void raymarch_lit_clip_kernel(const LaunchDesc 
     const IsoDesc *isd = nullptr;
     constexpr bool CLIP = true;
     const ClipDesc *clp = &Cl;
+    constexpr bool SHADOW = false;
+    const ShadowDesc *shd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

@@ -20,6 +20,8 @@ __global__ __launch_bounds__(64) void raymarch_tf_kernel(const LaunchDesc L, con
     const IsoDesc *isd = nullptr;
     constexpr bool CLIP = false;
     const ClipDesc *clp = nullptr;
+    constexpr bool SHADOW = false;
+    const ShadowDesc *shd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 
@@ -35,6 +37,8 @@ __global__ __launch_bounds__(64) void raymarch_tf_clip_kernel(const LaunchDesc L
     const IsoDesc *isd = nullptr;
     constexpr bool CLIP = true;
     const ClipDesc *clp = &Cl;
+    constexpr bool SHADOW = false;
+    const ShadowDesc *shd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

@@ -119,4 +119,27 @@ VK_LIGHT_HD void lit_shade(const LightDesc &D, const LitRay &R, float gx, float 
     cr = cr * f + sp; cg = cg * f + sp; cb = cb * f + sp;
 }
 
+// ... and with the shadow factor k on the diffuse and specular terms (vk_set_shadows; vk_shadow.hpp): rgb' = c.rgb * (ka + kd * diff * k) +
+// ks * spec * k, k = 1 - strength for a shadowed point and 1 otherwise.  A function of its own: the callers above keep their code.
+VK_LIGHT_HD void lit_shade(const LightDesc &D, const LitRay &R, float gx, float gy, float gz, float k, float &cr, float &cg, float &cb) {
+    const float q = fmaf(gz, gz, fmaf(gy, gy, gx * gx));
+    const bool has = q >= FLT_MIN && q <= FLT_MAX;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float s = __builtin_amdgcn_rsqf(has ? q : 1.0f);
+#else
+    const float s = 1.0f / sqrtf(has ? q : 1.0f);
+#endif
+    const float Nx = gx * s, Ny = gy * s, Nz = gz * s;
+    const float nl = fabsf(fmaf(Nz, R.lz, fmaf(Ny, R.ly, Nx * R.lx)));
+    const float nh = fabsf(fmaf(Nz, R.hz, fmaf(Ny, R.hy, Nx * R.hx)));
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float p = __builtin_amdgcn_exp2f(D.shininess * __builtin_amdgcn_logf(nh));
+#else
+    const float p = (float)pow((double)nh, (double)D.shininess);
+#endif
+    const float diff = has ? nl : 1.0f, spec = has ? p : 0.0f;
+    const float f = D.ka + (D.kd * diff) * k, sp = (D.ks * spec) * k;
+    cr = cr * f + sp; cg = cg * f + sp; cb = cb * f + sp;
+}
+
 }  // namespace vk

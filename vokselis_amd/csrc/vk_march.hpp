@@ -10,6 +10,7 @@
 #include "vk_march_parts.hpp"
 #include "vk_iso.hpp"
 #include "vk_light.hpp"
+#include "vk_shadow.hpp"
 #include "vk_tf.hpp"
 #include "vk_trips.hpp"
 
@@ -475,6 +476,8 @@ __global__ __launch_bounds__(64) void raymarch_naive_kernel(const LaunchDesc L, 
     const IsoDesc *isd = nullptr;
     constexpr bool CLIP = false;  // (no clip box in this family: vk_render.hip refuses the render)
     const ClipDesc *clp = nullptr;
+    constexpr bool SHADOW = false;
+    const ShadowDesc *shd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

@@ -3,8 +3,9 @@
 // (vk_iso.hpp: iso_hit), and another exit: the hit sample's position stays in p.  The family's own: each loop's frame, condition, skip
 // decision, operator and advance; the rest are the parts the MAX loops call (vk_march_parts.hpp; one loop for both: DESIGN.md section 13).
 // Included by vk_march.hpp after vk_march_mip.hpp, and so part of every unit that includes vk_march.hpp;
-// instantiated by raymarch_iso_kernel (vk_launch_iso.hip) alone, through vk_march_kernel_body.hpp under ISO.  The refinement and the
-// shade are the kernel body's epilogue, once per ray; iso_sample() below is what both fetch with.
+// instantiated by raymarch_iso_kernel (vk_launch_iso.hip), its shadowing twin raymarch_iso_shadow_kernel (vk_launch_iso_shadow.hip) and the
+// R16_UNORM units, through vk_march_kernel_body.hpp under ISO.  The refinement and the shade are the kernel body's epilogue, once per ray;
+// iso_sample() below is what both fetch with, and iso_shadowed() at the end is the shadow ray of the shadowing kernels: these loops again.
 #pragma once
 
 namespace vk {
@@ -148,6 +149,38 @@ __device__ __forceinline__ IsoSample iso_sample(const VolumeDesc &V, const uint3
     o.l0 = fmaf(o.fy, o.c10 - o.c00, o.c00); o.l1 = fmaf(o.fy, o.c11 - o.c01, o.c01);
     o.x = fmaf(o.fz, o.l1 - o.l0, o.l0);
     return o;
+}
+
+// The shadow ray of a surface point q (vk_set_shadows; vk_shadow.hpp): the loops above a second time, from q along
+// the unit light direction Ld through the box [lo, hi] the primary ray marched, with the primary ray's step formula for Ld.  Returns
+// whether a sample on it is at or above iso_k.  Called from the kernel body's epilogue by the wave's hit lanes together; Ld, lo, hi,
+// dt_scale and bias are kernel arguments, so the step, the octant offset of the skip maps and the constants of the skip bound are
+// wave-uniform and stay on the scalar unit.  Nothing is counted (COUNT = false, a Census of its own): the step image and the counters
+// are the primary ray's.  The skip kernels walk with the loop and the distance maps, the fast path without skipping takes the
+// pipelined loop, SAFE and LINEAR the plain one.  ts0 >= tb1 leaves no iteration: A stays NaN, no hit.
+template <int VOL, bool SKIP, bool SAFE>
+__device__ __forceinline__ bool iso_shadowed(const VolumeDesc &V, const uint32_t *lut, const float q[3], const float Ld[3], const float lo[3], const float hi[3],
+                                             const float dt_scale, const float bias, const float walk_cap, const float walk_cap_all, const float iso_k) {
+    constexpr bool USE_LUT = is_cell_layout(VOL) && !SAFE;
+    float tb0, tb1;
+    intersect_box(q, Ld, lo, hi, tb0, tb1);
+    if (tb0 > tb1) return false;
+    const float dtx = 1.0f / ((float)V.nx * fabsf(Ld[0]));
+    const float dty = 1.0f / ((float)V.ny * fabsf(Ld[1]));
+    const float dtz = 1.0f / ((float)V.nz * fabsf(Ld[2]));
+    const float dts = dt_scale * fminf(dtx, fminf(dty, dtz));
+    const float ts0 = shadow_ts0(tb0, bias, dts);
+    RayState s;
+    s.left = min(count_trips(ts0, tb1, dts), 0x7fffffffu);
+    s.px = fmaf(ts0, Ld[0], q[0]); s.py = fmaf(ts0, Ld[1], q[1]); s.pz = fmaf(ts0, Ld[2], q[2]);
+    s.sx = Ld[0] * dts; s.sy = Ld[1] * dts; s.sz = Ld[2] * dts;
+    s.A = __builtin_nanf(""); s.Gr = 0.0f; s.Gg = 0.0f; s.Gb = 0.0f;
+    s.out = 0u;
+    Census cs;
+    if constexpr (USE_LUT && !SKIP) march_iso_stream<VOL, false, false>(V, s, cs, lut, 0xffffffffu, iso_k);
+    else if constexpr (SKIP) march_iso<VOL, true, SAFE, false, false>(V, s, 0xffffffffu, cs, USE_LUT ? lut : nullptr, walk_cap, walk_cap_all, iso_k);
+    else march_iso<VOL, false, SAFE, false, false>(V, s, 0xffffffffu, cs, USE_LUT ? lut : nullptr, __builtin_inff(), __builtin_inff(), iso_k);
+    return iso_hit(s.A, iso_k);
 }
 
 }  // namespace vk

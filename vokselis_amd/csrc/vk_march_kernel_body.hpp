@@ -6,7 +6,8 @@
 // `tfd`, its table (nullptr without one; under MIP the window, whose rgba is nullptr for the grey ramp), `ldp`, its lighting (nullptr
 // without), `isd`, its isosurface (nullptr without; it brings its own lighting, a runtime flag), the constant CLIP and `clp`, the clip box
 // (vk_set_clip_box: the _clip_ kernels of the table, lit, MAX and isosurface families; nullptr in the others, whose rays march the unit
-// cube), and takes its arguments L
+// cube), the constant SHADOW and `shd`, the shadows of the lit isosurface (vk_set_shadows: raymarch_iso_shadow_kernel of
+// vk_launch_iso_shadow.hip and its R16_UNORM twin, under ISO alone; false and nullptr in every other kernel), and takes its arguments L
 // (LaunchDesc) and V (VolumeDesc) by value.  (Shared textually rather than as an inlined function: that moved the register allocation
 // of the existing kernels.)
 // Shared by all five families: the block and pixel mapping, the cull, the index tables in LDS, the ray set-up, the wave priority, the
@@ -23,6 +24,7 @@
     static_assert(!MIP || (VOL != VOL_B9U8 && VOL != VOL_B9F16 && VOL != VOL_Q8 && VOL != VOL_QF16), "the maximum projection: LINEAR and cell layouts");
     static_assert(!ISO || (!TF && !LIT && !MIP && WALK == WALK_LOOP && !AHEAD), "the isosurface: loops of its own, walking with the loop; refined and shaded in the epilogue");
     static_assert(!CLIP || TF || MIP || ISO, "the clip box: the table, lit, MAX and isosurface families");
+    static_assert(!SHADOW || ISO, "shadows (vk_set_shadows; `shd`, nullptr in the other kernels): the isosurface's epilogue, in kernels of their own (vk_launch_iso_shadow.hip)");
     static_assert(!ISO || (VOL != VOL_B9U8 && VOL != VOL_B9F16 && VOL != VOL_Q8 && VOL != VOL_QF16), "the isosurface: LINEAR and cell layouts");
     if (blockIdx.x >= L.grid_march) { clear_inactive_strip<OUT>(L, blockIdx.x - L.grid_march, threadIdx.x); return; }  // wave-uniform
     const uint32_t lb = logical_block(blockIdx.x);
@@ -156,7 +158,18 @@
                     const IsoSample h = iso_sample<VOL, SKIP, SAFE>(V, tl, iso_back(a, sx, r.px), iso_back(a, sy, r.py), iso_back(a, sz, r.pz));
                     float gx, gy, gz;
                     lit_gradient(h.dx00, h.dx10, h.dx01, h.dx11, h.c00, h.c10, h.c01, h.c11, h.l0, h.l1, h.fy, h.fz, fnx, fny, fnz, gx, gy, gz);
-                    lit_shade(isd->light, lit_ray(isd->light, dir), gx, gy, gz, cr, cg, cb);
+                    if constexpr (SHADOW) {
+                        // the shadow ray (vk_set_shadows): the wave's hit lanes march once more, from the crossing towards the light, through the box the
+                        // primary ray marched; a point whose ray hits keeps 1 - strength of its diffuse and specular terms
+                        const float qs[3] = {iso_back(a, sx, r.px), iso_back(a, sy, r.py), iso_back(a, sz, r.pz)};
+                        const float Ld[3] = {isd->light.lx, isd->light.ly, isd->light.lz};
+                        float blo[3] = {0.0f, 0.0f, 0.0f}, bhi[3] = {1.0f, 1.0f, 1.0f};
+                        if constexpr (CLIP) { for (int i = 0; i < 3; i++) { blo[i] = clp->lo[i]; bhi[i] = clp->hi[i]; } }
+                        const bool dark = iso_shadowed<VOL, SKIP, SAFE>(V, tl, qs, Ld, blo, bhi, L.dt_scale, shd->bias, L.walk_cap, L.walk_cap_all, isd->iso_k);
+                        lit_shade(isd->light, lit_ray(isd->light, dir), gx, gy, gz, dark ? shd->k : 1.0f, cr, cg, cb);
+                    } else {
+                        lit_shade(isd->light, lit_ray(isd->light, dir), gx, gy, gz, cr, cg, cb);
+                    }
                 }
                 Cr = linear_to_srgb(cr); Cg = linear_to_srgb(cg); Cb = linear_to_srgb(cb);
             }

@@ -30,6 +30,8 @@ __global__ __launch_bounds__(64) void raymarch_u16_kernel(const LaunchDesc L, co
     const IsoDesc *isd = &I;
     constexpr bool CLIP = CLIPPED;
     const ClipDesc *clp = &Cl;
+    constexpr bool SHADOW = false;
+    const ShadowDesc *shd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

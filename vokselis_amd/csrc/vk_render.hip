@@ -104,6 +104,14 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
         I.lit = ctx->lit ? 1 : 0;
         I.light = ctx->light;
     }
+    // light-direction shadows (vk_set_shadows) take effect under a lit isosurface whose light is not a headlight (a headlight's shadow ray runs back
+    // along the primary ray, which was empty up to the hit): kernels of their own; in every other case the state is ignored
+    const bool shadow = iso && ctx->shadows_on && ctx->lit && !ctx->light.headlight;
+    ShadowDesc Sh{};
+    if (shadow) {
+        const char *bad = shadow_desc(ctx->shadows.strength, ctx->shadows.bias, Sh);
+        if (bad) return fail(ctx, VK_ERR_INVALID, std::string("shadows: ") + bad);  // (vk_set_shadows has checked it)
+    }
     TfDesc T{};
     if (mip || tf) {
         if (!has_table_layout(ctx->vol_kind))
@@ -160,12 +168,14 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
         if (ctx->vol_kind == VOL_S8U8 || ctx->vol_kind == VOL_S8F16) launch_staged(ctx, L, V, grid, count, reach_cam);
         else if (is_u16_kind(ctx->vol_kind)) {  // an R16_UNORM volume: the same families, kernels of their own units (vk_march_u16.hpp)
             if (flags & VK_RENDER_FAST_WALK) return fail(ctx, VK_ERR_UNSUPPORTED, "R16_UNORM: VK_RENDER_FAST_WALK has no u16 kernels (the walks take the loop)");
-            if (iso) launch_u16_iso(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
+            if (shadow) launch_u16_iso_shadow(ctx, L, V, I, Sh, Cl, grid, count, skip, safe);
+            else if (iso) launch_u16_iso(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
             else if (mip) launch_u16_mip(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
             else if (tf && ctx->lit) launch_u16_lit(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
             else if (tf) launch_u16_tf(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
             else launch_u16_cells(ctx, L, V, T, ctx->light, I, nullptr, grid, count, skip, safe);
         }
+        else if (shadow) launch_cells_iso_shadow(ctx, L, V, I, Sh, Cl, grid, count, skip, safe);
         else if (iso) launch_cells_iso(ctx, L, V, I, Cl, grid, count, skip, safe);
         else if (mip) launch_cells_mip(ctx, L, V, T, Cl, grid, count, skip, safe);
         else if (tf && ctx->lit) launch_cells_lit(ctx, L, V, T, ctx->light, Cl, grid, count, skip, safe);
@@ -287,6 +297,29 @@ int vk_set_lighting(vk_ctx *ctx, const vk_lighting *light) {
         return fail(ctx, VK_ERR_INVALID, std::string("vk_set_lighting: ") + why);
     ctx->light = D;
     ctx->lit = true;
+    return VK_OK;
+}
+
+// Shadows are host state like lighting, read by dispatch_march when a render is recorded: no drain, no map rebuild (the skip maps are the
+// isosurface's), settable inside a frame; they stay in force across uploads.
+int vk_set_shadows(vk_ctx *ctx, const vk_shadows *s) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (!s) {
+        ctx->shadows_on = false;
+        return VK_OK;
+    }
+    ShadowDesc D{};
+    if (const char *why = shadow_desc(s->strength, s->bias, D)) return fail(ctx, VK_ERR_INVALID, std::string("vk_set_shadows: ") + why);
+    ctx->shadows.strength = s->strength + 0.0f;
+    ctx->shadows.bias = D.bias;
+    ctx->shadows_on = true;
+    return VK_OK;
+}
+
+int vk_get_shadows(vk_ctx *ctx, vk_shadows *out, int *enabled) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (enabled) *enabled = ctx->shadows_on ? 1 : 0;
+    if (out && ctx->shadows_on) *out = ctx->shadows;
     return VK_OK;
 }
 

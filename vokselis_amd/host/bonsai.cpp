@@ -17,6 +17,8 @@
 //          [--iso V [--iso-colour R G B] [--iso-refine N]]    first-hit isosurface at sample value V (vk_set_isosurface): linear surface colour
 //                                                            (default 1 1 1), N bisection steps at the hit (default 4); shaded by --light /
 //                                                            --headlight (no --tf needed); refused together with --mip
+//          [--shadows STRENGTH BIAS]                          light-direction shadows of the lit isosurface (vk_set_shadows; with --iso and --light): a shadowed
+//                                                            point loses STRENGTH (0 .. 1) of its diffuse and specular terms; BIAS: first shadow sample, in steps
 //          [--clip X0 Y0 Z0 X1 Y1 Z1]                         clip box (cut-away) in unit-cube coordinates (vk_set_clip_box): the rays march the box
 //                                                            only; needs --tf, --mip or --iso
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
@@ -40,6 +42,8 @@ static bool g_lit = false;  // --light / --headlight: gradient lighting (the lib
 static bool g_mip = false;  // --mip: maximum-intensity projection
 static bool g_iso_on = false;  // --iso: first-hit isosurface (the library checks the parameters)
 static vk_isosurface g_iso = {0.0f, {1.0f, 1.0f, 1.0f}, 4u};
+static bool g_shadows_on = false;  // --shadows: light-direction shadows (the library checks the parameters)
+static vk_shadows g_shadows = {0.7f, 2.0f};
 static bool g_clip_on = false;  // --clip: clip box (the library checks the bounds)
 static vk_clip_box g_clip = {{0.0f, 0.0f, 0.0f}, {1.0f, 1.0f, 1.0f}};
 static vk_lighting g_light = {{0.0f, 0.0f, 0.0f}, 0, 0.3f, 0.7f, 0.2f, 32.0f};
@@ -66,6 +70,7 @@ struct Bonsai : Demo {
         if (g_lit) ctx.set_lighting(&g_light);
         if (g_mip) ctx.set_projection(VK_PROJ_MAX);
         if (g_iso_on) ctx.set_isosurface(&g_iso);
+        if (g_shadows_on) ctx.set_shadows(&g_shadows);
         if (g_clip_on) ctx.set_clip_box(&g_clip);
         if (!g_raw.empty()) self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt));
         else self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, 256, 256, 256));
@@ -94,6 +99,7 @@ static int run_group(int n_gpus, uint32_t frames, uint32_t batch, uint32_t w, ui
             if (g_lit) check(c, vk_set_lighting(c, &g_light));
             if (g_mip) check(c, vk_set_projection(c, VK_PROJ_MAX));
             if (g_iso_on) check(c, vk_set_isosurface(c, &g_iso));
+            if (g_shadows_on) check(c, vk_set_shadows(c, &g_shadows));
             if (g_clip_on) check(c, vk_set_clip_box(c, &g_clip));
             if (!raw.empty()) check(c, vk_volume_upload(c, raw.data(), nullptr, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt, VK_LAYOUT_AUTO));
             else check(c, vk_volume_generate(c, VK_GEN_BONSAI_STANDIN, 256, 256, 256, VK_FMT_R8_UNORM, 0x5EED0001u, 0, 1, VK_LAYOUT_AUTO));
@@ -179,6 +185,7 @@ int main(int argc, char **argv) {
         else if (a == "--iso") { g_iso_on = true; g_iso.iso = (float)std::atof(next()); }
         else if (a == "--iso-colour") { for (int k = 0; k < 3; k++) g_iso.rgb[k] = (float)std::atof(next()); }
         else if (a == "--clip") { g_clip_on = true; for (int k = 0; k < 3; k++) g_clip.lo[k] = (float)std::atof(next()); for (int k = 0; k < 3; k++) g_clip.hi[k] = (float)std::atof(next()); }
+        else if (a == "--shadows") { g_shadows_on = true; g_shadows.strength = (float)std::atof(next()); g_shadows.bias = (float)std::atof(next()); }
         else if (a == "--iso-refine") g_iso.refine = (uint32_t)std::max(0, std::atoi(next()));
         else if (a == "--light") { g_lit = true; g_light.headlight = 0; for (int k = 0; k < 3; k++) g_light.dir[k] = (float)std::atof(next()); }
         else if (a == "--headlight") { g_lit = true; g_light.headlight = 1; }
@@ -190,6 +197,7 @@ int main(int argc, char **argv) {
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
     if (g_iso_on && g_mip) { std::fprintf(stderr, "bonsai: --iso and --mip exclude each other (an isosurface ignores the projection)\n"); return 2; }
+    if (g_shadows_on && !(g_iso_on && g_lit && !g_light.headlight)) { std::fprintf(stderr, "bonsai: --shadows needs --iso and --light (shadows are cast along a light direction, under an isosurface)\n"); return 2; }
     if (g_clip_on && g_tf.empty() && !g_mip && !g_iso_on) { std::fprintf(stderr, "bonsai: --clip needs --tf, --mip or --iso (the built-in march has no clip kernels)\n"); return 2; }
     if (gpus > 0) return run_group(gpus, frames, batch, w, h, peer_direct);
     try {

@@ -172,6 +172,7 @@ struct Uniform {
 static_assert(sizeof(Uniform) == 48, "Uniform is 48 bytes (src/context/global_ubo.rs:52-65)");
 static_assert(sizeof(vk_isosurface) == 20, "vk_isosurface is 20 bytes (vk_set_isosurface)");
 static_assert(sizeof(vk_clip_box) == 24, "vk_clip_box is 24 bytes (vk_set_clip_box)");
+static_assert(sizeof(vk_shadows) == 8, "vk_shadows is 8 bytes (vk_set_shadows)");
 
 // src/context/hdr_backbuffer.rs:10-11
 struct HdrBackBuffer {
@@ -246,6 +247,10 @@ class Context {
     bool isosurface(vk_isosurface *out = nullptr) const { int on = 0; check(ctx_, vk_get_isosurface(ctx_, out, &on)); return on != 0; }
     // Gradient lighting of the table march (vk_set_lighting); nullptr turns it off.
     void set_lighting(const vk_lighting *light) { check(ctx_, vk_set_lighting(ctx_, light)); }
+    // Light-direction shadows of the lit isosurface (vk_set_shadows); nullptr turns them off.  Ignored unless an isosurface and a light that is
+    // not a headlight are set.
+    void set_shadows(const vk_shadows *s) { check(ctx_, vk_set_shadows(ctx_, s)); }
+    bool shadows(vk_shadows *out = nullptr) const { int on = 0; check(ctx_, vk_get_shadows(ctx_, out, &on)); return on != 0; }
     // Clip box (cut-away) of the table, lit, MAX and isosurface marches, in unit-cube coordinates (vk_set_clip_box); nullptr turns it off.
     void set_clip_box(const vk_clip_box *box) { check(ctx_, vk_set_clip_box(ctx_, box)); }
     bool clip_box(vk_clip_box *out = nullptr) const { int on = 0; check(ctx_, vk_get_clip_box(ctx_, out, &on)); return on != 0; }
