@@ -344,6 +344,49 @@ int vk_get_clip_box(vk_ctx *ctx, vk_clip_box *out, int *enabled);
 int vk_tiles_active_clip(const void *camera144, int mode, uint32_t width, uint32_t height, uint32_t tile_size,
                          const vk_clip_box *box, unsigned char *active, uint32_t *n_active);
 
+/* The geometry pass of the first-hit isosurface: where the surface is.  It needs an isosurface set
+ * (vk_set_isosurface) and has VK_MODE_NAIVE_TRILINEAR's semantics.  For a pixel of the tile, the ray, intersect_box (the clip box when one
+ * is set), t0 = max(t0, 0), dt, p, s, the loop with its trip budget, the rule that a first-iteration hit is not refined and the
+ * bisection a (R = the stored refine) are exactly those of the isosurface colour render above.  The bisection runs ALWAYS, whether or not
+ * lighting is set; lighting, shadows, the surface colour, the table and the projection have no influence on the pass.
+ * Per pixel the pass writes a 32-byte record of two float4.  For a ray that hit, every operation one f32 rounding:
+ *     q = (fma(-a, s.x, p.x), fma(-a, s.y, p.y), fma(-a, s.z, p.z))                  a = 0: p itself
+ *     t = fma(q.z - eye.z, dir.z, fma(q.y - eye.y, dir.y, (q.x - eye.x) * dir.x))     the distance of q along the unit ray
+ *     g = the gradient of the sample at q, as under vk_set_lighting, in its operation order, on the kernel's scale (R8: taps 0..255,
+ *         R16_UNORM: 0..65535, R16F: values), times the volume's dimensions per axis -- NOT normalised
+ *     x = trilinear(V, q)                                                             the filtered sample, on the kernel's scale
+ *     record = { (q.x, q.y, q.z, t), (g.x, g.y, g.z, x) }
+ * A pixel whose ray misses the box or never hits, a pixel of a culled 8x8 block and a pixel of an inactive tile write the miss record
+ * { (0, 0, 0, +inf), (0, 0, 0, 0) }: isfinite(t) is the hit mask.  Pixels outside the tile are not written.
+ * The normal is left to the consumer: the outward normal of a surface entered from below the threshold is -g / |g|.  On the cut face of
+ * the box or the clip box (a first-iteration hit) g is still the data's gradient, not the face's normal.  The gradient is stored raw:
+ * its length serves edge detection and a "no gradient" test (g = 0).  The skip maps are the isosurface's and stay exact (the same operator
+ * and predicate); the pass triggers no map rebuild.
+ * The geometry surface, [height][width] records, belongs to the frame slot like the step image: it is allocated, and filled with the miss
+ * record, by the slot's first geometry pass at the backbuffer's size, and freed by vk_backbuffer_resize, vk_ctx_frames_in_flight and
+ * vk_ctx_destroy.  Between vk_frame_begin and vk_frame_end the pass goes to that frame's slot and stream.
+ * vk_render_geometry is asynchronous on the slot's stream and touches neither the backbuffer, the present targets, the step image nor
+ * the counters.  flags: VK_RENDER_NO_SKIP, VK_RENDER_SAFE, VK_RENDER_FORCE_SKIP, VK_RENDER_PROBE_ALWAYS -- the default skip policy is the
+ * colour render's, from the census -- and the records are identical under every combination of them.  VK_RENDER_FAST_WALK and a BRICKED /
+ * QUADS / STAGED volume are VK_ERR_UNSUPPORTED; any other flag, no isosurface set, no volume, no backbuffer, no camera: VK_ERR_INVALID.
+ * vk_geometry_info (does not synchronise) and vk_readback_geometry (blocking; row_pitch_bytes >= width * 32) are VK_ERR_INVALID before
+ * the slot's first geometry pass since the last resize; vk_frame_geometry reads a frame's surface under vk_frame_readback's rules.
+ * vk_pick (blocking) renders the 1 x 1 tile at (x, y) into the current slot's surface and downloads that record: bit for bit the
+ * full-frame pass's record of the pixel (the ray does not depend on the tile).  x >= width or y >= height: VK_ERR_INVALID.
+ * vk_render_partition, vk_render_batch, vk_group_render and the fused present have no geometry output. */
+typedef struct vk_hit {
+    int32_t hit;   /* 1: isfinite(t) */
+    float pos[3];  /* q, unit-cube coordinates */
+    float t;       /* distance along the unit ray; +inf for a miss */
+    float grad[3]; /* g, raw */
+    float value;   /* x */
+} vk_hit;          /* 36 bytes */
+int vk_render_geometry(vk_ctx *ctx, int32_t tile_x, int32_t tile_y, uint32_t tile_w, uint32_t tile_h, float dt_scale, uint32_t flags);
+int vk_geometry_info(vk_ctx *ctx, uint32_t *width, uint32_t *height, void **device_ptr);
+int vk_readback_geometry(vk_ctx *ctx, void *dst, size_t row_pitch_bytes);
+int vk_frame_geometry(vk_ctx *ctx, uint64_t frame_id, void *dst, size_t row_pitch_bytes);
+int vk_pick(vk_ctx *ctx, uint32_t x, uint32_t y, float dt_scale, vk_hit *out);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

@@ -60,6 +60,16 @@ class VkClipBox(C.Structure):
 assert C.sizeof(VkClipBox) == 24
 
 
+class VkHit(C.Structure):
+    """vk_hit (36 bytes): one pixel's record of the geometry pass (vk_pick) -- hit, the crossing, its distance along the ray, the raw
+    gradient and the sample value there."""
+    _fields_ = [("hit", C.c_int32), ("pos", C.c_float * 3), ("t", C.c_float), ("grad", C.c_float * 3), ("value", C.c_float)]
+
+
+assert C.sizeof(VkHit) == 36
+GEOM_RECORD_BYTES = 32  # a pixel of the geometry surface: two float4
+
+
 def clip_box(lo, hi) -> VkClipBox:
     """A VkClipBox from two triples, held to vk_set_clip_box's rules before the library sees it: finite components (as f32) and
     0 <= lo < hi <= 1 on every axis.  Raises ValueError."""
@@ -103,6 +113,11 @@ SYMBOLS = {
     "vk_get_shadows": (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
     "vk_set_clip_box": (C.c_int, [_vp, _vp]),  # const vk_clip_box * (VkClipBox above), NULL: off
     "vk_get_clip_box": (C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
+    "vk_render_geometry": (C.c_int, [_vp, _i32, _i32, _u32, _u32, _f32, _u32]),
+    "vk_geometry_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_vp)]),
+    "vk_readback_geometry": (C.c_int, [_vp, _vp, _sz]),
+    "vk_frame_geometry": (C.c_int, [_vp, C.c_uint64, _vp, _sz]),
+    "vk_pick": (C.c_int, [_vp, _u32, _u32, _f32, _vp]),  # vk_hit * (VkHit above)
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),
     "vk_set_uniform": (C.c_int, [_vp, _vp]),
     "vk_set_camera": (C.c_int, [_vp, _vp]),

@@ -94,6 +94,19 @@ class FrameCounter:
         return self._delta
 
 
+@dataclass
+class Hit:
+    """One pixel's surface point from the geometry pass (Context.pick): the refined crossing `pos` in unit-cube coordinates, its distance
+    `t` along the unit ray from the eye, the raw gradient `grad` (the kernel's scale, times the dimensions; not normalised), the filtered
+    sample `value` there, and `normal` = -grad / |grad| in float64 (outward for a surface entered from below the threshold), None
+    without a gradient (zero or non-finite)."""
+    pos: tuple
+    t: float
+    grad: tuple
+    value: float
+    normal: tuple | None
+
+
 class Context:
     """Device + per-frame uniform/camera upload + backbuffer (src/context.rs:38-67,225-249)."""
 
@@ -362,6 +375,53 @@ class Context:
         bb, r8, done = C.c_void_p(), C.c_void_p(), C.c_int()
         N.check(self._h, N.lib().vk_frame_info(self._h, frame_id, C.byref(bb), C.byref(r8), C.byref(done)))
         return {"backbuffer": bb.value, "rgba8": r8.value, "complete": bool(done.value)}
+
+    # -- the geometry pass of the first-hit isosurface (vk_render_geometry: where the surface is)
+    def render_geometry(self, dt_scale: float = 1.0, tile=None, flags: int = 0):
+        """vk_render_geometry: per pixel of the tile (None: the frame) the refined crossing, its distance along the ray, the gradient and the
+        sample there, into the current frame slot's geometry surface; asynchronous.  Needs an isosurface (set_isosurface); lighting,
+        shadows, table and projection have no influence.  flags: RENDER_NO_SKIP, RENDER_SAFE, RENDER_FORCE_SKIP, RENDER_PROBE_ALWAYS."""
+        bb = self.render_backbuffer
+        tx, ty, tw, th = (0, 0, bb.width, bb.height) if tile is None else tile
+        N.check(self._h, N.lib().vk_render_geometry(self._h, int(tx), int(ty), int(tw), int(th), float(dt_scale), int(flags)))
+
+    def _split_geometry(self, rec):
+        return rec[:, :, 0, :], rec[:, :, 1, :]
+
+    def read_geometry(self):
+        """vk_readback_geometry: (pos_t [H, W, 4] f32: the crossing and its distance t, +inf for a miss; grad_x [H, W, 4] f32: the raw
+        gradient and the sample value).  np.isfinite(pos_t[..., 3]) is the hit mask.  Blocks."""
+        bb = self.render_backbuffer
+        rec = np.empty((bb.height, bb.width, 2, 4), np.float32)
+        N.check(self._h, N.lib().vk_readback_geometry(self._h, rec.ctypes.data, rec.strides[0]))
+        return self._split_geometry(rec)
+
+    def frame_geometry(self, frame_id: int):
+        """vk_frame_geometry: read_geometry of that frame's slot (waits for that frame only), while its surface still holds it."""
+        bb = self.render_backbuffer
+        rec = np.empty((bb.height, bb.width, 2, 4), np.float32)
+        N.check(self._h, N.lib().vk_frame_geometry(self._h, frame_id, rec.ctypes.data, rec.strides[0]))
+        return self._split_geometry(rec)
+
+    def geometry_info(self) -> dict:
+        """vk_geometry_info: the current slot's geometry surface (does not synchronise)."""
+        w, h, p = C.c_uint32(), C.c_uint32(), C.c_void_p()
+        N.check(self._h, N.lib().vk_geometry_info(self._h, C.byref(w), C.byref(h), C.byref(p)))
+        return {"width": w.value, "height": h.value, "device_ptr": p.value}
+
+    def pick(self, x: int, y: int, dt_scale: float = 1.0):
+        """vk_pick: what the ray through pixel (x, y) hits -- a Hit, or None for a miss.  Blocks (one wave, one 32-byte download)."""
+        if x < 0 or y < 0:
+            raise ValueError("pick: negative pixel coordinates")
+        h = N.VkHit()
+        N.check(self._h, N.lib().vk_pick(self._h, int(x), int(y), float(dt_scale), C.byref(h)))
+        if not h.hit:
+            return None
+        g = np.array(h.grad[:], np.float64)
+        with np.errstate(over="ignore", invalid="ignore"):
+            n = float(np.sqrt((g * g).sum()))
+        normal = tuple(float(v) for v in -g / n) if np.isfinite(n) and n > 0.0 else None
+        return Hit(tuple(h.pos[:]), float(h.t), tuple(h.grad[:]), float(h.value), normal)
 
     def set_root_skip(self, k: int):
         """vk_partition_root_skip: rank 0 sits out every k-th round of the tile deal (0: never)."""

@@ -21,11 +21,11 @@ thread_local std::string g_create_err;
 static void frame_slot_switch(vk_ctx *ctx, uint32_t to) {
     if (to == ctx->fif_cur) return;
     vk_ctx::FrameSlot &a = ctx->fif[ctx->fif_cur], &b = ctx->fif[to];
-    a.backbuffer = ctx->backbuffer; a.steps = ctx->steps; a.rgba8 = ctx->rgba8; a.bgra8 = ctx->bgra8;
+    a.backbuffer = ctx->backbuffer; a.steps = ctx->steps; a.rgba8 = ctx->rgba8; a.bgra8 = ctx->bgra8; a.geom = ctx->geom;
     a.present_w = ctx->present_w; a.present_h = ctx->present_h;
-    ctx->backbuffer = b.backbuffer; ctx->steps = b.steps; ctx->rgba8 = b.rgba8; ctx->bgra8 = b.bgra8;
+    ctx->backbuffer = b.backbuffer; ctx->steps = b.steps; ctx->rgba8 = b.rgba8; ctx->bgra8 = b.bgra8; ctx->geom = b.geom;
     ctx->present_w = b.present_w; ctx->present_h = b.present_h;
-    b.backbuffer = nullptr; b.steps = nullptr; b.rgba8 = b.bgra8 = nullptr;
+    b.backbuffer = nullptr; b.steps = nullptr; b.rgba8 = b.bgra8 = nullptr; b.geom = nullptr;
     if (ctx->fif_k > 1) ctx->stream = b.stream;
     ctx->fif_cur = to;
 }
@@ -49,6 +49,7 @@ int frames_drain(vk_ctx *ctx) {
 static void frame_slot_release(vk_ctx::FrameSlot &s, bool keep_stream) {  // a parked slot's device memory, event and stream
     if (s.backbuffer) (void)hipFree(s.backbuffer);
     if (s.steps) (void)hipFree(s.steps);
+    if (s.geom) (void)hipFree(s.geom);
     if (s.rgba8) (void)hipFree(s.rgba8);
     if (s.bgra8) (void)hipFree(s.bgra8);
     if (s.done) (void)hipEventDestroy(s.done);
@@ -60,8 +61,10 @@ static void frame_slot_release(vk_ctx::FrameSlot &s, bool keep_stream) {  // a p
 static int surface_alloc_current(vk_ctx *ctx) {
     if (ctx->backbuffer) (void)hipFree(ctx->backbuffer);
     if (ctx->steps) (void)hipFree(ctx->steps);
+    if (ctx->geom) (void)hipFree(ctx->geom);  // the geometry surface goes with the shape: the next geometry pass allocates it again
     ctx->backbuffer = nullptr;
     ctx->steps = nullptr;
+    ctx->geom = nullptr;
     HIP_TRY(ctx, hipMalloc(&ctx->backbuffer, (size_t)ctx->width * ctx->height * px_bytes(ctx->out_format)));
     return vk_backbuffer_clear(ctx);
 }
@@ -140,6 +143,7 @@ int vk_ctx_destroy(vk_ctx *ctx) {
     if (ctx->d_tf) (void)hipFree(ctx->d_tf);
     if (ctx->backbuffer) (void)hipFree(ctx->backbuffer);
     if (ctx->steps) (void)hipFree(ctx->steps);
+    if (ctx->geom) (void)hipFree(ctx->geom);
     if (ctx->counters) (void)hipFree(ctx->counters);
     if (ctx->rgba8) (void)hipFree(ctx->rgba8);
     if (ctx->bgra8) (void)hipFree(ctx->bgra8);
@@ -240,6 +244,10 @@ int vk_ctx_frames_in_flight(vk_ctx *ctx, uint32_t k) {
     if (drc) return drc;
     frame_slot_switch(ctx, 0);
     for (uint32_t i = 0; i < VK_MAX_FRAMES_IN_FLIGHT; i++) { ctx->fif[i].id = 0; ctx->fif[i].ended = false; }
+    // a ring resize drops every slot's geometry surface (drained: no pass is writing one); the slots' next geometry passes allocate them again
+    if (ctx->geom) { (void)hipFree(ctx->geom); ctx->geom = nullptr; }
+    for (uint32_t i = 0; i < VK_MAX_FRAMES_IN_FLIGHT; i++)
+        if (ctx->fif[i].geom) { (void)hipFree(ctx->fif[i].geom); ctx->fif[i].geom = nullptr; }
     ctx->fif_seq = 0;
     for (int i = 0; i < 16; i++) { ctx->ring_use_stream[i] = nullptr; ctx->ring_use_frame[i] = 0; }  // (drained: no reader is left)
     for (uint32_t i = k; i < VK_MAX_FRAMES_IN_FLIGHT; i++) frame_slot_release(ctx->fif[i], false);  // a smaller ring
@@ -357,6 +365,10 @@ int vk_frame_info(vk_ctx *ctx, uint64_t frame_id, void **backbuffer, void **rgba
     });
 }
 
+int vk_frame_geometry(vk_ctx *ctx, uint64_t frame_id, void *dst, size_t row_pitch_bytes) {
+    return with_frame_slot(ctx, frame_id, "vk_frame_geometry", [&] { return vk_readback_geometry(ctx, dst, row_pitch_bytes); });
+}
+
 int vk_backbuffer_info(vk_ctx *ctx, uint32_t *width, uint32_t *height, int *out_format, void **device_ptr) {
     if (!ctx) return VK_ERR_INVALID;
     if (width) *width = ctx->width;
@@ -401,6 +413,27 @@ int vk_readback(vk_ctx *ctx, void *dst, size_t row_pitch_bytes) {
     if (row_pitch_bytes < row) return fail(ctx, VK_ERR_INVALID, "row pitch smaller than a row");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpy2DAsync(dst, row_pitch_bytes, ctx->backbuffer, row, row, ctx->height, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return VK_OK;
+}
+
+// The current slot's geometry surface (vk_render_geometry): [height][width] records of two float4 (vk_geom.hpp).
+int vk_geometry_info(vk_ctx *ctx, uint32_t *width, uint32_t *height, void **device_ptr) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (!ctx->geom) return fail(ctx, VK_ERR_INVALID, "no geometry pass (vk_render_geometry) since the last resize");
+    if (width) *width = ctx->width;
+    if (height) *height = ctx->height;
+    if (device_ptr) *device_ptr = ctx->geom;
+    return VK_OK;
+}
+
+int vk_readback_geometry(vk_ctx *ctx, void *dst, size_t row_pitch_bytes) {
+    if (!ctx || !dst) return fail(ctx, VK_ERR_INVALID, "vk_readback_geometry: NULL argument");
+    if (!ctx->geom) return fail(ctx, VK_ERR_INVALID, "no geometry pass (vk_render_geometry) since the last resize");
+    if (!geom_pitch_ok(ctx->width, row_pitch_bytes)) return fail(ctx, VK_ERR_INVALID, "row pitch smaller than a row of records (width * 32 bytes)");
+    const size_t row = geom_row_bytes(ctx->width);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpy2DAsync(dst, row_pitch_bytes, ctx->geom, row, row, ctx->height, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return VK_OK;
 }

@@ -12,6 +12,7 @@
 //   vk_launch_mip.hip      instantiates the cell march under the maximum-intensity projection (vk_march.hpp, vk_march_mip.hpp)
 //   vk_launch_iso.hip      instantiates the cell march under a first-hit isosurface (vk_march.hpp, vk_march_iso.hpp, vk_iso.hpp)
 //   vk_launch_iso_shadow.hip  instantiates the isosurface march with light-direction shadows (vk_march_iso.hpp, vk_shadow.hpp)
+//   vk_launch_geom.hip     instantiates the geometry pass of the isosurface march (vk_march_iso.hpp, vk_geom.hpp)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)
@@ -20,6 +21,7 @@
 
 #include "../../include/vokselis_hip.h"
 #include "vk_common.hpp"
+#include "vk_geom.hpp"
 #include "vk_iso.hpp"
 #include "vk_light.hpp"
 #include "vk_shadow.hpp"
@@ -89,6 +91,7 @@ struct vk_ctx {
     uint32_t width = 0, height = 0;
     int out_format = VK_OUT_RGBA32F;
     uint32_t *steps = nullptr;
+    void *geom = nullptr;  // the geometry surface of the current slot (vk_render_geometry): [height][width][2] float4, allocated by the slot's first geometry pass
     unsigned long long *counters = nullptr;  // kCounters of them: 0-5 the march's steps and census, 7 the upload's empty cells, 8-9 the lone-speckle census
 
     // heaviest-first tile order (launch-order heuristic; see tile_order_update)
@@ -164,6 +167,7 @@ struct vk_ctx {
     struct FrameSlot {
         void *backbuffer = nullptr;
         uint32_t *steps = nullptr, *rgba8 = nullptr, *bgra8 = nullptr;
+        void *geom = nullptr;
         uint32_t present_w = 0, present_h = 0;
         hipStream_t stream = nullptr;  // fif_k > 1: the slot's stream, created with the ring at the highest stream priority (vk_ctx_frames_in_flight)
         hipEvent_t done = nullptr;     // recorded by vk_frame_end
@@ -235,7 +239,7 @@ int present_targets(vk_ctx *ctx, uint32_t width, uint32_t height, bool also_bgra
 
 // vk_render.hip
 int check_render(vk_ctx *ctx, int mode, const float *cam, float dt_scale, uint32_t ts, uint32_t rank, uint32_t nranks);
-int dispatch_march(vk_ctx *ctx, int mode, const vk::LaunchDesc &L_in, uint32_t flags, const float *reach_cam);
+int dispatch_march(vk_ctx *ctx, int mode, const vk::LaunchDesc &L_in, uint32_t flags, const float *reach_cam, const vk::GeomDesc *geom = nullptr);  // geom: the geometry pass of the isosurface (vk_render_geometry)
 uint32_t launch_flags(const vk_ctx *ctx, uint32_t render_flags, bool batch);
 
 // the kernel-instantiating TUs: each launches on ctx->stream and returns; the caller checks hipGetLastError
@@ -249,6 +253,10 @@ void launch_cells_iso_shadow(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::Vol
                              bool skip, bool safe);  // vk_launch_iso_shadow.hip
 void launch_u16_iso_shadow(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::IsoDesc &I, const vk::ShadowDesc &Sh, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool count,
                            bool skip, bool safe);  // vk_launch_u16_iso_shadow.hip
+void launch_cells_geom(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::IsoDesc &I, const vk::GeomDesc &G, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool skip,
+                       bool safe);  // vk_launch_geom.hip
+void launch_u16_geom(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::IsoDesc &I, const vk::GeomDesc &G, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool skip,
+                     bool safe);  // vk_launch_u16_geom.hip
 // vk_launch_u16_*.hip: the same five families on an R16_UNORM volume (vk_march_u16.hpp); a family reads its own descriptors, Cl == nullptr: no box
 #define VK_U16_LAUNCH(name) void name(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::LightDesc &Li, const vk::IsoDesc &I, const vk::ClipDesc *Cl, uint32_t grid, bool count, bool skip, bool safe)
 VK_U16_LAUNCH(launch_u16_cells);

@@ -19,6 +19,7 @@ static_assert(kernargs_fit<StagedDesc>, "the staged kernels: LaunchDesc + Volume
 static_assert(kernargs_fit<TfDesc, ClipDesc>, "raymarch_tf_kernel, raymarch_mip_kernel and their _clip_ kernels: LaunchDesc + VolumeDesc + TfDesc (+ ClipDesc)");
 static_assert(kernargs_fit<TfDesc, LightDesc, ClipDesc>, "raymarch_lit_kernel, raymarch_lit_clip_kernel: LaunchDesc + VolumeDesc + TfDesc + LightDesc (+ ClipDesc)");
 static_assert(kernargs_fit<IsoDesc, ClipDesc>, "raymarch_iso_kernel, raymarch_iso_clip_kernel: LaunchDesc + VolumeDesc + IsoDesc (+ ClipDesc)");
+static_assert(kernargs_fit<IsoDesc, GeomDesc, ClipDesc>, "raymarch_geom_kernel, raymarch_u16_geom_kernel and their _clip_ kernels: LaunchDesc + VolumeDesc + IsoDesc + GeomDesc (+ ClipDesc)");
 
 template <int I>
 using int_tag = std::integral_constant<int, I>;

@@ -23,6 +23,8 @@ __global__ __launch_bounds__(64) void raymarch_iso_kernel(const LaunchDesc L, co
     const ClipDesc *clp = nullptr;
     constexpr bool SHADOW = false;
     const ShadowDesc *shd = nullptr;
+    constexpr bool GEOM = false;
+    const GeomDesc *gmd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 
@@ -40,6 +42,8 @@ __global__ __launch_bounds__(64) void raymarch_iso_clip_kernel(const LaunchDesc 
     const ClipDesc *clp = &Cl;
     constexpr bool SHADOW = false;
     const ShadowDesc *shd = nullptr;
+    constexpr bool GEOM = false;
+    const GeomDesc *gmd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

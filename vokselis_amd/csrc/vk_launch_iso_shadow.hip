@@ -24,6 +24,8 @@ __global__ __launch_bounds__(64) void raymarch_iso_shadow_kernel(const LaunchDes
     const ClipDesc *clp = nullptr;
     constexpr bool SHADOW = true;
     const ShadowDesc *shd = &Sh;
+    constexpr bool GEOM = false;
+    const GeomDesc *gmd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 
@@ -40,6 +42,8 @@ __global__ __launch_bounds__(64) void raymarch_iso_shadow_clip_kernel(const Laun
     const ClipDesc *clp = &Cl;
     constexpr bool SHADOW = true;
     const ShadowDesc *shd = &Sh;
+    constexpr bool GEOM = false;
+    const GeomDesc *gmd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

@@ -22,6 +22,8 @@ __global__ __launch_bounds__(64) void raymarch_tf_kernel(const LaunchDesc L, con
     const ClipDesc *clp = nullptr;
     constexpr bool SHADOW = false;
     const ShadowDesc *shd = nullptr;
+    constexpr bool GEOM = false;
+    const GeomDesc *gmd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 
@@ -39,6 +41,8 @@ __global__ __launch_bounds__(64) void raymarch_tf_clip_kernel(const LaunchDesc L
     const ClipDesc *clp = &Cl;
     constexpr bool SHADOW = false;
     const ShadowDesc *shd = nullptr;
+    constexpr bool GEOM = false;
+    const GeomDesc *gmd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

@@ -20,6 +20,8 @@ __global__ __launch_bounds__(64) void raymarch_u16_iso_shadow_kernel(const Launc
     const ClipDesc *clp = &Cl;
     constexpr bool SHADOW = true;
     const ShadowDesc *shd = &Sh;
+    constexpr bool GEOM = false;
+    const GeomDesc *gmd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

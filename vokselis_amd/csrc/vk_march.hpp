@@ -478,6 +478,8 @@ __global__ __launch_bounds__(64) void raymarch_naive_kernel(const LaunchDesc L, 
     const ClipDesc *clp = nullptr;
     constexpr bool SHADOW = false;
     const ShadowDesc *shd = nullptr;
+    constexpr bool GEOM = false;
+    const GeomDesc *gmd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

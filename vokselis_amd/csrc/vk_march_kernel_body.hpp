@@ -17,6 +17,10 @@
 // RayState::A, each a frame of its own around the shared parts of vk_march_parts.hpp; selected at each call site, since a forwarding wrapper
 // moved registers -- and what the epilogue makes of the ray's sums: under ISO the refinement of the crossing and
 // the shade, once per ray, after the wave's loops have ended.
+// The constant GEOM and `gmd` (GeomDesc; nullptr in every other kernel) make the geometry pass of the isosurface (vk_render_geometry; DESIGN.md
+// section 18; raymarch_geom_kernel of vk_launch_geom.hip and its R16_UNORM twin): under ISO without SHADOW, the same ray, loops and bisection, and
+// an epilogue that stores the crossing, its distance along the ray, the gradient and the sample there in place of a colour.  Every line
+// of it sits under `if constexpr (GEOM)`.
     static_assert(is_cell_layout(VOL) || (!SKIP && SAFE), "linear / bricked layouts: no skip map, clamped indices");
     static_assert(SKIP || WALK == WALK_LOOP, "the closed-form walks are variants of the skip kernels");
     static_assert(!AHEAD || (SKIP && !SAFE), "probe ahead: the skip kernels' fast path");
@@ -25,8 +29,12 @@
     static_assert(!ISO || (!TF && !LIT && !MIP && WALK == WALK_LOOP && !AHEAD), "the isosurface: loops of its own, walking with the loop; refined and shaded in the epilogue");
     static_assert(!CLIP || TF || MIP || ISO, "the clip box: the table, lit, MAX and isosurface families");
     static_assert(!SHADOW || ISO, "shadows (vk_set_shadows; `shd`, nullptr in the other kernels): the isosurface's epilogue, in kernels of their own (vk_launch_iso_shadow.hip)");
+    static_assert(!GEOM || (ISO && !SHADOW && !COUNT), "the geometry pass (vk_render_geometry; `gmd`, nullptr in the other kernels): the isosurface's ray without colour, shadows or counters");
     static_assert(!ISO || (VOL != VOL_B9U8 && VOL != VOL_B9F16 && VOL != VOL_Q8 && VOL != VOL_QF16), "the isosurface: LINEAR and cell layouts");
-    if (blockIdx.x >= L.grid_march) { clear_inactive_strip<OUT>(L, blockIdx.x - L.grid_march, threadIdx.x); return; }  // wave-uniform
+    if (blockIdx.x >= L.grid_march) {  // wave-uniform
+        if constexpr (!GEOM) clear_inactive_strip<OUT>(L, blockIdx.x - L.grid_march, threadIdx.x);  // (the geometry pass is never batched: no such blocks)
+        return;
+    }
     const uint32_t lb = logical_block(blockIdx.x);
     if (lb >= L.n_blocks) return;  // wave-uniform
     const uint32_t lane = threadIdx.x;
@@ -42,6 +50,7 @@
         // active positions: a whole-frame launch covers them too, a partition never launches them)
         if (pm.pos >= fv.n_active || bx0 + 8 <= fv.cull_x0 || bx0 >= fv.cull_x1 || by0 + 8 <= fv.cull_y0 || by0 >= fv.cull_y1) {
             if (!pm.valid) return;
+            if constexpr (GEOM) { geom_store(*gmd, L.W, pm.x, pm.y, geom_miss0(), geom_miss1()); return; }  // a culled block, an inactive tile: the miss record
             store_out<OUT>(L, pm, 0.0f, 0.0f, 0.0f);
             if (COUNT && L.steps) L.steps[(size_t)pm.y * L.W + (size_t)pm.x] = 0;
             return;
@@ -79,6 +88,8 @@
     // colour is accumulated as G = sum w*cos(phase); C = 0.5*A + 0.5*G at the end (sum w == A)
     float Gr = 0.0f, Gg = 0.0f, Gb = 0.0f, A = 0.0f;
     float Cr = 0.0f, Cg = 0.0f, Cb = 0.0f;
+    [[maybe_unused]] float4 geo0, geo1;  // GEOM: the pixel's record, the miss record until the ray hits
+    if constexpr (GEOM) { geo0 = geom_miss0(); geo1 = geom_miss1(); }
     if (!(t0 > t1)) {  // :91-93
         t0 = fmaxf(t0, 0.0f);  // :94
         const float fnx = (float)V.nx, fny = (float)V.ny, fnz = (float)V.nz;
@@ -144,7 +155,22 @@
         else if constexpr (MIP) march_mip<VOL, false, SAFE, COUNT, false>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, __builtin_inff(), __builtin_inff(), tfd->k1, tfd->k2, tfd->umax);
         else march<VOL, SKIP, SAFE, COUNT, false, WALK_LOOP, false, TF, LIT>(V, r, 0xffffffffu, cs, USE_LUT ? cell_lut : nullptr, __builtin_inff(), __builtin_inff(), tfd, ldp, &lr);
         A = r.A; Gr = r.Gr; Gg = r.Gg; Gb = r.Gb;
-        if constexpr (ISO) {
+        if constexpr (GEOM) {
+            // A ray that hit: the wave's hit lanes refine together, whether or not lighting is set (the crossing is what the pass is for), and
+            // take the sample at q with its gradient.  The index tables in LDS are still valid, as below.
+            if (iso_hit(r.A, isd->iso_k)) {
+                const uint32_t *tl = USE_LUT ? cell_lut : nullptr;
+                float a = 0.0f;
+                if (r.left != left0)  // a hit in the ray's first iteration is not refined
+                    a = iso_refine(isd->refine, [&](float m) { return iso_hit(iso_sample<VOL, SKIP, SAFE>(V, tl, iso_back(m, sx, r.px), iso_back(m, sy, r.py), iso_back(m, sz, r.pz)).x, isd->iso_k); });
+                const float qx = iso_back(a, sx, r.px), qy = iso_back(a, sy, r.py), qz = iso_back(a, sz, r.pz);
+                const IsoSample h = iso_sample<VOL, SKIP, SAFE>(V, tl, qx, qy, qz);
+                float gx, gy, gz;
+                lit_gradient(h.dx00, h.dx10, h.dx01, h.dx11, h.c00, h.c10, h.c01, h.c11, h.l0, h.l1, h.fy, h.fz, fnx, fny, fnz, gx, gy, gz);
+                geo0 = make_float4(qx, qy, qz, geom_distance(qx, qy, qz, eye, dir));
+                geo1 = make_float4(gx, gy, gz, h.x);
+            }
+        } else if constexpr (ISO) {
             // A ray that hit: its colour is the surface's, shaded once.  Only the shade reads the crossing, so the refinement runs
             // under lighting alone: here, after the loops, the wave's hit lanes make the R + 1 dependent fetches together.  The index
             // tables in LDS are still valid (no barrier: nothing has written them since the loops read them).
@@ -194,7 +220,8 @@
             Cb = linear_to_srgb(fmaf(0.5f, Gb, 0.5f * A));
         }
     }
-    store_out<OUT>(L, pm, Cr, Cg, Cb);
+    if constexpr (GEOM) geom_store(*gmd, L.W, pm.x, pm.y, geo0, geo1);  // no colour: the backbuffer is not touched
+    else store_out<OUT>(L, pm, Cr, Cg, Cb);
     if (COUNT) {
         if (L.steps) L.steps[(size_t)pm.y * L.W + (size_t)pm.x] = (L.flags & LF_STEPS_ARE_TRIPS) ? cs.n_look : cs.n_iter;
         if (L.counters) {

@@ -32,6 +32,8 @@ __global__ __launch_bounds__(64) void raymarch_u16_kernel(const LaunchDesc L, co
     const ClipDesc *clp = &Cl;
     constexpr bool SHADOW = false;
     const ShadowDesc *shd = nullptr;
+    constexpr bool GEOM = false;
+    const GeomDesc *gmd = nullptr;
 #include "vk_march_kernel_body.hpp"
 }
 

@@ -62,7 +62,8 @@ int check_render(vk_ctx *ctx, int mode, const float *cam, float dt_scale, uint32
 
 // Launch the march kernel of the context's volume for a filled LaunchDesc (one frame or a batch).
 // `reach_cam`: the camera whose distance decides whether the unclamped fast path is safe (the farthest of a batch).
-int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags, const float *reach_cam) {
+// `geom`: the geometry pass of the isosurface (vk_render_geometry) -- every choice below is the colour render's, but for the kernel family.
+int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags, const float *reach_cam, const GeomDesc *geom) {
     LaunchDesc L = L_in;
     // probe-ahead requests the distance byte of a position one step past a ray's end: inside the index tables' padding only while a step is
     // at most ~1.5 cells (vk_march.hpp: locate)
@@ -82,6 +83,7 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
     // a runtime transfer function (vk_set_transfer_function) has kernels on the LINEAR / PACKED / PACKED_PAIRS layouts, walking with the loop
     // a first-hit isosurface (vk_set_isosurface): kernels of its own with the table kernels' coverage; table and projection are ignored under it, lighting is honoured
     const bool iso = mode == VK_MODE_NAIVE_TRILINEAR && ctx->iso_on;
+    if (geom && !iso) return fail(ctx, VK_ERR_INVALID, "vk_render_geometry: no isosurface set (vk_set_isosurface)");
     const bool tf = mode == VK_MODE_NAIVE_TRILINEAR && ctx->d_tf && !iso;
     // the maximum-intensity projection (vk_set_projection): kernels of its own with the table kernels' coverage; lighting is ignored under it
     const bool mip = mode == VK_MODE_NAIVE_TRILINEAR && ctx->proj == VK_PROJ_MAX && !iso;
@@ -106,7 +108,7 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
     }
     // light-direction shadows (vk_set_shadows) take effect under a lit isosurface whose light is not a headlight (a headlight's shadow ray runs back
     // along the primary ray, which was empty up to the hit): kernels of their own; in every other case the state is ignored
-    const bool shadow = iso && ctx->shadows_on && ctx->lit && !ctx->light.headlight;
+    const bool shadow = !geom && iso && ctx->shadows_on && ctx->lit && !ctx->light.headlight;
     ShadowDesc Sh{};
     if (shadow) {
         const char *bad = shadow_desc(ctx->shadows.strength, ctx->shadows.bias, Sh);
@@ -168,13 +170,15 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
         if (ctx->vol_kind == VOL_S8U8 || ctx->vol_kind == VOL_S8F16) launch_staged(ctx, L, V, grid, count, reach_cam);
         else if (is_u16_kind(ctx->vol_kind)) {  // an R16_UNORM volume: the same families, kernels of their own units (vk_march_u16.hpp)
             if (flags & VK_RENDER_FAST_WALK) return fail(ctx, VK_ERR_UNSUPPORTED, "R16_UNORM: VK_RENDER_FAST_WALK has no u16 kernels (the walks take the loop)");
-            if (shadow) launch_u16_iso_shadow(ctx, L, V, I, Sh, Cl, grid, count, skip, safe);
+            if (geom) launch_u16_geom(ctx, L, V, I, *geom, Cl, grid, skip, safe);
+            else if (shadow) launch_u16_iso_shadow(ctx, L, V, I, Sh, Cl, grid, count, skip, safe);
             else if (iso) launch_u16_iso(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
             else if (mip) launch_u16_mip(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
             else if (tf && ctx->lit) launch_u16_lit(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
             else if (tf) launch_u16_tf(ctx, L, V, T, ctx->light, I, Cl, grid, count, skip, safe);
             else launch_u16_cells(ctx, L, V, T, ctx->light, I, nullptr, grid, count, skip, safe);
         }
+        else if (geom) launch_cells_geom(ctx, L, V, I, *geom, Cl, grid, skip, safe);
         else if (shadow) launch_cells_iso_shadow(ctx, L, V, I, Sh, Cl, grid, count, skip, safe);
         else if (iso) launch_cells_iso(ctx, L, V, I, Cl, grid, count, skip, safe);
         else if (mip) launch_cells_mip(ctx, L, V, T, Cl, grid, count, skip, safe);
@@ -187,7 +191,7 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
 }
 
 static int render_common(vk_ctx *ctx, int mode, int32_t ox, int32_t oy, uint32_t rw, uint32_t rh, uint32_t ts,
-                         uint32_t rank, uint32_t nranks, float dt_scale, uint32_t flags, void *compact_out) {
+                         uint32_t rank, uint32_t nranks, float dt_scale, uint32_t flags, void *compact_out, const GeomDesc *geom = nullptr) {
     if (!ctx) return VK_ERR_INVALID;
     int crc = check_render(ctx, mode, ctx->have_camera ? ctx->camera : nullptr, dt_scale, ts, rank, nranks);
     if (crc) return crc;
@@ -279,7 +283,15 @@ static int render_common(vk_ctx *ctx, int mode, int32_t ox, int32_t oy, uint32_t
         HIP_TRY(ctx, hipMemcpy(ctx->trace, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
         L.trace = ctx->trace;
     }
-    return dispatch_march(ctx, mode, L, flags, ctx->camera);
+    return dispatch_march(ctx, mode, L, flags, ctx->camera, geom);
+}
+
+// Fill of a freshly allocated geometry surface with the miss record (the record is not one repeated byte): one thread per pixel.
+__global__ __launch_bounds__(256) void geom_fill_kernel(float4 *surface, size_t n_pixels) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_pixels) return;
+    surface[2 * i] = geom_miss0();
+    surface[2 * i + 1] = geom_miss1();
 }
 
 extern "C" {
@@ -355,6 +367,50 @@ int vk_render(vk_ctx *ctx, int mode, int32_t tile_x, int32_t tile_y, uint32_t ti
     // C2 and the compute twin lose 0.5 - 4 % at 32)
     const bool staged = ctx && (ctx->vol_kind == vk::VOL_S8U8 || ctx->vol_kind == vk::VOL_S8F16) && mode == VK_MODE_NAIVE_TRILINEAR;
     return render_common(ctx, mode, tile_x, tile_y, tile_w, tile_h, ctx && ctx->render_tile ? ctx->render_tile : (staged ? 32u : 64u), 0, 1, dt_scale, flags, nullptr);
+}
+
+// The geometry pass of the first-hit isosurface: render_common's launch -- cull rectangle, active tiles, tile order,
+// fast-path condition and policy flags are the colour render's by construction -- with the geometry kernels, into the current slot's
+// geometry surface.  The surface is allocated, and filled with the miss record, by the slot's first pass since the last resize.
+int vk_render_geometry(vk_ctx *ctx, int32_t tile_x, int32_t tile_y, uint32_t tile_w, uint32_t tile_h, float dt_scale, uint32_t flags) {
+    if (!ctx) return VK_ERR_INVALID;
+    bool unsupported = false;
+    if (const char *why = geom_flags_check(flags, &unsupported)) return fail(ctx, unsupported ? VK_ERR_UNSUPPORTED : VK_ERR_INVALID, why);
+    const uint32_t ts = ctx->render_tile ? ctx->render_tile : 64u;
+    int crc = check_render(ctx, VK_MODE_NAIVE_TRILINEAR, ctx->have_camera ? ctx->camera : nullptr, dt_scale, ts, 0, 1);
+    if (crc) return crc;
+    if (!ctx->iso_on) return fail(ctx, VK_ERR_INVALID, "vk_render_geometry: no isosurface set (vk_set_isosurface)");
+    if (!has_table_layout(ctx->vol_kind))
+        return fail(ctx, VK_ERR_UNSUPPORTED, "isosurface: the geometry pass needs a LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED have no isosurface kernels)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!ctx->geom) {
+        const size_t n = (size_t)ctx->width * ctx->height;
+        HIP_TRY(ctx, hipMalloc(&ctx->geom, geom_surface_bytes(ctx->width, ctx->height)));
+        hipLaunchKernelGGL(geom_fill_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, ctx->stream, reinterpret_cast<float4 *>(ctx->geom), n);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    GeomDesc G{};
+    G.surface = ctx->geom;
+    return render_common(ctx, VK_MODE_NAIVE_TRILINEAR, tile_x, tile_y, tile_w, tile_h, ts, 0, 1, dt_scale, flags, nullptr, &G);
+}
+
+// One pixel's record: the 1 x 1 tile at (x, y) into the current slot's surface, then that record.  The ray does not depend on the tile,
+// so the record is the full-frame pass's, bit for bit.
+int vk_pick(vk_ctx *ctx, uint32_t x, uint32_t y, float dt_scale, vk_hit *out) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (!out) return fail(ctx, VK_ERR_INVALID, "vk_pick: out is NULL");
+    if (!ctx->backbuffer) return fail(ctx, VK_ERR_INVALID, "render: no backbuffer (vk_backbuffer_resize)");
+    if (x >= ctx->width || y >= ctx->height) return fail(ctx, VK_ERR_INVALID, "vk_pick: the pixel lies outside the backbuffer");
+    int rc = vk_render_geometry(ctx, (int32_t)x, (int32_t)y, 1, 1, dt_scale, 0);
+    if (rc) return rc;
+    float rec[8];
+    HIP_TRY(ctx, hipMemcpyAsync(rec, reinterpret_cast<const char *>(ctx->geom) + geom_record_offset(x, y, geom_row_bytes(ctx->width)), sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    out->hit = std::isfinite(rec[3]) ? 1 : 0;
+    for (int i = 0; i < 3; i++) { out->pos[i] = rec[i]; out->grad[i] = rec[4 + i]; }
+    out->t = rec[3];
+    out->value = rec[7];
+    return VK_OK;
 }
 
 int vk_render_partition(vk_ctx *ctx, int mode, uint32_t tile_size, uint32_t rank, uint32_t nranks, float dt_scale,

@@ -19,11 +19,16 @@
 //                                                            --headlight (no --tf needed); refused together with --mip
 //          [--shadows STRENGTH BIAS]                          light-direction shadows of the lit isosurface (vk_set_shadows; with --iso and --light): a shadowed
 //                                                            point loses STRENGTH (0 .. 1) of its diffuse and specular terms; BIAS: first shadow sample, in steps
+//          [--pick X Y]                                       what the ray through pixel (X, Y) of the last frame hits (vk_pick; needs --iso): the
+//                                                            crossing, its distance along the ray, the gradient, the outward normal -g / |g|, the value
+//          [--depth-ppm FILE]                                 the geometry pass of the last frame (vk_render_geometry; needs --iso) as a grey ramp of t between
+//                                                            the frame's smallest (white) and largest (dark grey) finite t, misses black
 //          [--clip X0 Y0 Z0 X1 Y1 Z1]                         clip box (cut-away) in unit-cube coordinates (vk_set_clip_box): the rays march the box
 //                                                            only; needs --tf, --mip or --iso
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <string>
 
@@ -156,7 +161,9 @@ int main(int argc, char **argv) {
     uint32_t frames = 100, w = 1280, h = 720, batch = 8, in_flight = 1;
     int gpus = 0;
     bool f32 = false, peer_direct = false, fuse_present = false, record = false;
-    std::string ppm, dump_rgba, dump_steps;
+    std::string ppm, dump_rgba, dump_steps, depth_ppm;
+    bool pick = false;
+    uint32_t pick_x = 0, pick_y = 0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -168,6 +175,8 @@ int main(int argc, char **argv) {
         else if (a == "--dims") { for (int k = 0; k < 3; k++) g_dims[k] = (uint32_t)std::max(0, std::atoi(next())); }
         else if (a == "--ppm") ppm = next();
         else if (a == "--f32") f32 = true;
+        else if (a == "--pick") { pick = true; pick_x = (uint32_t)std::max(0, std::atoi(next())); pick_y = (uint32_t)std::max(0, std::atoi(next())); }
+        else if (a == "--depth-ppm") depth_ppm = next();
         else if (a == "--dump-rgba") dump_rgba = next();
         else if (a == "--dump-steps") dump_steps = next();
         else if (a == "--gpus") gpus = std::atoi(next());
@@ -199,6 +208,7 @@ int main(int argc, char **argv) {
     if (g_iso_on && g_mip) { std::fprintf(stderr, "bonsai: --iso and --mip exclude each other (an isosurface ignores the projection)\n"); return 2; }
     if (g_shadows_on && !(g_iso_on && g_lit && !g_light.headlight)) { std::fprintf(stderr, "bonsai: --shadows needs --iso and --light (shadows are cast along a light direction, under an isosurface)\n"); return 2; }
     if (g_clip_on && g_tf.empty() && !g_mip && !g_iso_on) { std::fprintf(stderr, "bonsai: --clip needs --tf, --mip or --iso (the built-in march has no clip kernels)\n"); return 2; }
+    if ((pick || !depth_ppm.empty()) && !g_iso_on) { std::fprintf(stderr, "bonsai: --pick and --depth-ppm need --iso (the geometry pass is the isosurface's)\n"); return 2; }
     if (gpus > 0) return run_group(gpus, frames, batch, w, h, peer_direct);
     try {
         // examples/bonsai/main.rs:64-74: 1280x720 window, Camera::new(1., 0.5, 1., (0.5,0.5,0.5), w/h)
@@ -241,6 +251,37 @@ int main(int argc, char **argv) {
                 check(ctx.handle(), vk_readback_steps(ctx.handle(), st.data()));
                 std::ofstream(dump_steps, std::ios::binary).write(reinterpret_cast<const char *>(st.data()), (std::streamsize)(st.size() * 4));
             }
+        }
+        if (pick) {
+            const vk_hit hit = ctx.pick(pick_x, pick_y, g_dt);
+            if (!hit.hit) std::printf("pick (%u, %u): miss\n", pick_x, pick_y);
+            else {
+                const double g[3] = {hit.grad[0], hit.grad[1], hit.grad[2]}, len = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+                std::printf("pick (%u, %u): pos %.6f %.6f %.6f  t %.6f  value %g  grad %g %g %g", pick_x, pick_y, hit.pos[0], hit.pos[1], hit.pos[2], hit.t, hit.value,
+                            hit.grad[0], hit.grad[1], hit.grad[2]);
+                if (len > 0.0 && std::isfinite(len)) std::printf("  normal %.6f %.6f %.6f\n", -g[0] / len, -g[1] / len, -g[2] / len);
+                else std::printf("  normal none (no gradient)\n");
+            }
+        }
+        if (!depth_ppm.empty()) {
+            ctx.render_geometry(g_dt);
+            const std::vector<float> rec = ctx.read_geometry();
+            float t_min = INFINITY, t_max = -INFINITY;
+            size_t hits = 0;
+            for (size_t q = 0; q < (size_t)w * h; q++) {
+                const float t = rec[8 * q + 3];
+                if (std::isfinite(t)) { t_min = std::min(t_min, t); t_max = std::max(t_max, t); hits++; }
+            }
+            std::ofstream f(depth_ppm, std::ios::binary);
+            f << "P6\n" << w << " " << h << "\n255\n";
+            for (size_t q = 0; q < (size_t)w * h; q++) {
+                const float t = rec[8 * q + 3];
+                unsigned char v = 0;  // a miss
+                if (std::isfinite(t)) v = (unsigned char)(255.0f - 191.0f * (t_max > t_min ? (t - t_min) / (t_max - t_min) : 0.0f) + 0.5f);  // near 255 .. far 64
+                const char px[3] = {(char)v, (char)v, (char)v};
+                f.write(px, 3);
+            }
+            std::printf("depth: %zu hit pixels, t in [%g, %g] -> %s\n", hits, hits ? t_min : 0.0f, hits ? t_max : 0.0f, depth_ppm.c_str());
         }
         if (!ppm.empty()) {
             std::ofstream f(ppm, std::ios::binary);

@@ -173,6 +173,7 @@ static_assert(sizeof(Uniform) == 48, "Uniform is 48 bytes (src/context/global_ub
 static_assert(sizeof(vk_isosurface) == 20, "vk_isosurface is 20 bytes (vk_set_isosurface)");
 static_assert(sizeof(vk_clip_box) == 24, "vk_clip_box is 24 bytes (vk_set_clip_box)");
 static_assert(sizeof(vk_shadows) == 8, "vk_shadows is 8 bytes (vk_set_shadows)");
+static_assert(sizeof(vk_hit) == 36, "vk_hit is 36 bytes (vk_pick)");
 
 // src/context/hdr_backbuffer.rs:10-11
 struct HdrBackBuffer {
@@ -254,6 +255,26 @@ class Context {
     // Clip box (cut-away) of the table, lit, MAX and isosurface marches, in unit-cube coordinates (vk_set_clip_box); nullptr turns it off.
     void set_clip_box(const vk_clip_box *box) { check(ctx_, vk_set_clip_box(ctx_, box)); }
     bool clip_box(vk_clip_box *out = nullptr) const { int on = 0; check(ctx_, vk_get_clip_box(ctx_, out, &on)); return on != 0; }
+    // The geometry pass of the first-hit isosurface (vk_render_geometry): per pixel the refined crossing, its distance along the ray, the raw gradient
+    // and the sample there, into the current frame slot's geometry surface; asynchronous.  Needs an isosurface; lighting, shadows, table and
+    // projection have no influence.  flags: VK_RENDER_NO_SKIP, _SAFE, _FORCE_SKIP, _PROBE_ALWAYS.
+    void render_geometry(float dt_scale = 1.0f, uint32_t flags = 0) { check(ctx_, vk_render_geometry(ctx_, 0, 0, render_backbuffer.width, render_backbuffer.height, dt_scale, flags)); }
+    void render_geometry_tile(int32_t x, int32_t y, uint32_t w, uint32_t h, float dt_scale = 1.0f, uint32_t flags = 0) { check(ctx_, vk_render_geometry(ctx_, x, y, w, h, dt_scale, flags)); }
+    // [height][width][2][4] floats: (q.x, q.y, q.z, t), (g.x, g.y, g.z, x) per pixel; t = +inf: a miss.  Blocks.
+    std::vector<float> read_geometry() {
+        std::vector<float> out((size_t)render_backbuffer.width * render_backbuffer.height * 8);
+        check(ctx_, vk_readback_geometry(ctx_, out.data(), (size_t)render_backbuffer.width * 32));
+        return out;
+    }
+    std::vector<float> frame_geometry(uint64_t id) {  // ... of that frame's slot (vk_frame_readback's rules)
+        std::vector<float> out((size_t)render_backbuffer.width * render_backbuffer.height * 8);
+        check(ctx_, vk_frame_geometry(ctx_, id, out.data(), (size_t)render_backbuffer.width * 32));
+        return out;
+    }
+    void *geometry_device_ptr() const { void *p = nullptr; check(ctx_, vk_geometry_info(ctx_, nullptr, nullptr, &p)); return p; }  // (does not synchronise)
+    // What the ray through pixel (x, y) hits (vk_pick; blocks): hit.hit == 0 for a miss.  The outward normal of a surface entered from below the
+    // threshold is -grad / |grad|.
+    vk_hit pick(uint32_t x, uint32_t y, float dt_scale = 1.0f) { vk_hit h{}; check(ctx_, vk_pick(ctx_, x, y, dt_scale, &h)); return h; }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
     void frames_in_flight(uint32_t k) { check(ctx_, vk_ctx_frames_in_flight(ctx_, k)); }
