@@ -387,6 +387,66 @@ int vk_readback_geometry(vk_ctx *ctx, void *dst, size_t row_pitch_bytes);
 int vk_frame_geometry(vk_ctx *ctx, uint64_t frame_id, void *dst, size_t row_pitch_bytes);
 int vk_pick(vk_ctx *ctx, uint32_t x, uint32_t y, float dt_scale, vk_hit *out);
 
+/* The slice pass: a plane through the volume -- axial, coronal, sagittal or oblique -- windowed by the table in
+ * force, optionally a thick slab reduced by maximum, minimum or mean.  No ray: the pass needs no camera, and lighting, isosurface, shadows,
+ * projection and uniform have no influence.  Only the clip box is honoured.  The plane arrives per call, so three orthogonal views and a
+ * 3-D render can share one backbuffer, a tile each.
+ * For backbuffer pixel (px, py) of the tile, in absolute backbuffer coordinates (a pixel's result never depends on the tile), every
+ * operation one f32 rounding, fma fused:
+ *     P.c = fma((float)py, dv.c, fma((float)px, du.c, origin.c))                        c = x, y, z
+ *     inside = lo.c <= P.c && P.c <= hi.c on all three axes          [lo, hi]: the clip box when one is set, else [0, 1]^3; a NaN is outside
+ *     outside: out = (0, 0, 0, 1), value record (+0, 0)               the clear colour, like a miss
+ *     samples == 1:  x = trilinear(V, P)
+ *     otherwise, for k = 0 .. samples - 1:
+ *         w = (float)k - 0.5f * (float)(samples - 1);  Pk.c = fma(w, dn.c, P.c);  xk = trilinear(V, Pk)
+ *                                                      texel indices clamp to the edge like any sample's; no inside test per sample
+ *         VK_SLAB_MAX:  M starts at -inf;  M = (xk > M) ? xk : M;  x = M                a NaN sample is passed over; all NaN leaves -inf
+ *         VK_SLAB_MIN:  M starts at +inf;  M = (xk < M) ? xk : M;  x = M
+ *         VK_SLAB_MEAN: acc starts at +0;  acc = acc + xk in the order of k;  x = acc * rn,  rn = (float)(1.0 / (double)samples)
+ *     U = fmin(u > 0 ? u : +0, umax),  u = fma(x, k1, k2)             the running maximum of VK_PROJ_MAX after one sample: a NaN and
+ *                                                                     anything <= 0 read entry 0
+ *     i = min(floor(U), n - 2);  f = U - i;  c = fma(f, T[i+1] - T[i], T[i]) per channel;  no table: the grey ramp, c = U
+ *     out = (linear_to_srgb(c.r), linear_to_srgb(c.g), linear_to_srgb(c.b), 1);  value record (x, 1)
+ * trilinear is the filter of every other render, bit for bit, and x is on the kernel's scale (R8: 0..255, R16_UNORM: 0..65535, R16F: the
+ * value); k1, k2, umax are those of the table in force (vk_set_transfer_function) for the volume's format.
+ * vk_render_slice is asynchronous on the current slot's stream (between vk_frame_begin and vk_frame_end: that frame's), writes only the
+ * tile's pixels of the backbuffer -- tile pixels outside the backbuffer are dropped -- and touches no step image, counters, present
+ * targets or geometry surface.  flags: VK_SLICE_VALUES, under which it also writes the pixels' value records into the VALUE SURFACE,
+ * [height][width] records of two f32 (x, weight): what a viewer reads the number under the cursor from.  The value surface belongs to the
+ * frame slot like the geometry surface: allocated and zero-filled by the slot's first such pass, freed by vk_backbuffer_resize,
+ * vk_ctx_frames_in_flight and vk_ctx_destroy.
+ * VK_ERR_INVALID (the backbuffer is untouched): a NULL slice, a component that is not finite or beyond +-VK_SLICE_MAX_COORD (dn: when
+ * samples > 1), samples outside 1 .. VK_SLICE_MAX_SAMPLES, an unknown reduce with samples > 1, any flag other than VK_SLICE_VALUES, no
+ * volume, no backbuffer.  VK_ERR_UNSUPPORTED: a BRICKED / QUADS / STAGED or RGBA16F_PAIR volume (the pass has kernels for LINEAR, PACKED
+ * and PACKED_PAIRS).
+ * vk_slice_values_info (does not synchronise) and vk_readback_slice_values (blocking; row_pitch_bytes >= width * 8) are VK_ERR_INVALID
+ * before the slot's first pass with VK_SLICE_VALUES since the last resize; vk_frame_slice_values reads a frame's surface under
+ * vk_frame_readback's rules.  vk_slice_probe (blocking) renders the 1 x 1 tile at (x, y) with VK_SLICE_VALUES and downloads its record:
+ * bit for bit the full-frame pass's; x >= width or y >= height: VK_ERR_INVALID.
+ * vk_render_partition, vk_render_batch, vk_group_render and the fused present have no slice output. */
+#define VK_SLICE_MAX_SAMPLES 256
+#define VK_SLICE_MAX_COORD 1e6f
+enum { VK_SLAB_MAX = 0, VK_SLAB_MIN = 1, VK_SLAB_MEAN = 2 };
+enum { VK_SLICE_VALUES = 1 };
+typedef struct vk_slice {
+    float origin[3];   /* the position of the CENTRE of backbuffer pixel (0, 0), unit-cube coordinates */
+    float du[3];       /* position change per pixel in +x */
+    float dv[3];       /* position change per pixel in +y */
+    float dn[3];       /* position change per slab sample (ignored when samples == 1) */
+    uint32_t samples;  /* 1 .. VK_SLICE_MAX_SAMPLES */
+    int32_t reduce;    /* VK_SLAB_MAX / _MIN / _MEAN (ignored when samples == 1) */
+} vk_slice;            /* 56 bytes */
+typedef struct vk_slice_sample {
+    int32_t inside; /* 1: P lies in the box */
+    float pos[3];   /* P */
+    float value;    /* x; +0 outside */
+} vk_slice_sample;  /* 20 bytes */
+int vk_render_slice(vk_ctx *ctx, const vk_slice *slice, int32_t tile_x, int32_t tile_y, uint32_t tile_w, uint32_t tile_h, uint32_t flags);
+int vk_slice_values_info(vk_ctx *ctx, uint32_t *width, uint32_t *height, void **device_ptr);
+int vk_readback_slice_values(vk_ctx *ctx, void *dst, size_t row_pitch_bytes);
+int vk_frame_slice_values(vk_ctx *ctx, uint64_t frame_id, void *dst, size_t row_pitch_bytes);
+int vk_slice_probe(vk_ctx *ctx, const vk_slice *slice, uint32_t x, uint32_t y, vk_slice_sample *out);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

@@ -69,6 +69,30 @@ class VkHit(C.Structure):
 assert C.sizeof(VkHit) == 36
 GEOM_RECORD_BYTES = 32  # a pixel of the geometry surface: two float4
 
+SLAB_MAX, SLAB_MIN, SLAB_MEAN = 0, 1, 2
+SLICE_VALUES = 1
+SLICE_MAX_SAMPLES = 256
+SLICE_MAX_COORD = 1e6
+SLICE_RECORD_BYTES = 8  # a pixel of the slice pass's value surface: (x, weight) f32
+
+
+class VkSlice(C.Structure):
+    """vk_slice (56 bytes): the plane of a slice pass in unit-cube coordinates -- the position of the centre of backbuffer pixel (0, 0), the
+    change per pixel in +x and +y, the change per slab sample -- and the slab: its samples and their reduction."""
+    _fields_ = [("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3), ("dn", C.c_float * 3), ("samples", C.c_uint32),
+                ("reduce", C.c_int32)]
+
+
+assert C.sizeof(VkSlice) == 56
+
+
+class VkSliceSample(C.Structure):
+    """vk_slice_sample (20 bytes): one pixel of a slice (vk_slice_probe) -- whether its position lies in the box, the position, the value."""
+    _fields_ = [("inside", C.c_int32), ("pos", C.c_float * 3), ("value", C.c_float)]
+
+
+assert C.sizeof(VkSliceSample) == 20
+
 
 def clip_box(lo, hi) -> VkClipBox:
     """A VkClipBox from two triples, held to vk_set_clip_box's rules before the library sees it: finite components (as f32) and
@@ -118,6 +142,11 @@ SYMBOLS = {
     "vk_readback_geometry": (C.c_int, [_vp, _vp, _sz]),
     "vk_frame_geometry": (C.c_int, [_vp, C.c_uint64, _vp, _sz]),
     "vk_pick": (C.c_int, [_vp, _u32, _u32, _f32, _vp]),  # vk_hit * (VkHit above)
+    "vk_render_slice": (C.c_int, [_vp, _vp, _i32, _i32, _u32, _u32, _u32]),  # const vk_slice * (VkSlice above)
+    "vk_slice_values_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_vp)]),
+    "vk_readback_slice_values": (C.c_int, [_vp, _vp, _sz]),
+    "vk_frame_slice_values": (C.c_int, [_vp, C.c_uint64, _vp, _sz]),
+    "vk_slice_probe": (C.c_int, [_vp, _vp, _u32, _u32, _vp]),  # const vk_slice *, vk_slice_sample * (VkSliceSample above)
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),
     "vk_set_uniform": (C.c_int, [_vp, _vp]),
     "vk_set_camera": (C.c_int, [_vp, _vp]),

@@ -423,6 +423,46 @@ class Context:
         normal = tuple(float(v) for v in -g / n) if np.isfinite(n) and n > 0.0 else None
         return Hit(tuple(h.pos[:]), float(h.t), tuple(h.grad[:]), float(h.value), normal)
 
+    # -- the slice pass (vk_render_slice: a plane through the volume, thick slabs)
+    def render_slice(self, slice, tile=None, values: bool = False):
+        """vk_render_slice: the plane `slice` (a VkSlice: Slice.plane / axial / coronal / sagittal) into the tile (None: the frame) of the
+        backbuffer -- the volume filtered at each pixel's position, or a slab of samples reduced by max / min / mean, mapped through the
+        table in force like the maximum projection and stored as sRGB; asynchronous.  Needs no camera; of the context's state only the
+        table and the clip box have influence.  values: also write the (x, weight) records into the slot's value surface."""
+        bb = self.render_backbuffer
+        tx, ty, tw, th = (0, 0, bb.width, bb.height) if tile is None else tile
+        N.check(self._h, N.lib().vk_render_slice(self._h, C.byref(slice) if slice is not None else None, int(tx), int(ty), int(tw), int(th),
+                                                 N.SLICE_VALUES if values else 0))
+
+    def read_slice_values(self) -> np.ndarray:
+        """vk_readback_slice_values: [H, W, 2] f32 -- per pixel the value x on the kernel's scale (R8: 0..255, R16_UNORM: 0..65535, R16F: the
+        value) and the weight, 1 where the pixel's position lies in the box, 0 (with x = +0) elsewhere.  Blocks."""
+        bb = self.render_backbuffer
+        rec = np.empty((bb.height, bb.width, 2), np.float32)
+        N.check(self._h, N.lib().vk_readback_slice_values(self._h, rec.ctypes.data, rec.strides[0]))
+        return rec
+
+    def frame_slice_values(self, frame_id: int) -> np.ndarray:
+        """vk_frame_slice_values: read_slice_values of that frame's slot (waits for that frame only), while its surface still holds it."""
+        bb = self.render_backbuffer
+        rec = np.empty((bb.height, bb.width, 2), np.float32)
+        N.check(self._h, N.lib().vk_frame_slice_values(self._h, frame_id, rec.ctypes.data, rec.strides[0]))
+        return rec
+
+    def slice_values_info(self) -> dict:
+        """vk_slice_values_info: the current slot's value surface (does not synchronise)."""
+        w, h, p = C.c_uint32(), C.c_uint32(), C.c_void_p()
+        N.check(self._h, N.lib().vk_slice_values_info(self._h, C.byref(w), C.byref(h), C.byref(p)))
+        return {"width": w.value, "height": h.value, "device_ptr": p.value}
+
+    def slice_probe(self, slice, x: int, y: int) -> N.VkSliceSample:
+        """vk_slice_probe: the value under pixel (x, y) of the plane -- a VkSliceSample (inside, pos, value).  Blocks (one wave, 8 bytes down)."""
+        if x < 0 or y < 0:
+            raise ValueError("slice_probe: negative pixel coordinates")
+        out = N.VkSliceSample()
+        N.check(self._h, N.lib().vk_slice_probe(self._h, C.byref(slice) if slice is not None else None, int(x), int(y), C.byref(out)))
+        return out
+
     def set_root_skip(self, k: int):
         """vk_partition_root_skip: rank 0 sits out every k-th round of the tile deal (0: never)."""
         N.check(self._h, N.lib().vk_partition_root_skip(self._h, int(k)))

@@ -21,11 +21,11 @@ thread_local std::string g_create_err;
 static void frame_slot_switch(vk_ctx *ctx, uint32_t to) {
     if (to == ctx->fif_cur) return;
     vk_ctx::FrameSlot &a = ctx->fif[ctx->fif_cur], &b = ctx->fif[to];
-    a.backbuffer = ctx->backbuffer; a.steps = ctx->steps; a.rgba8 = ctx->rgba8; a.bgra8 = ctx->bgra8; a.geom = ctx->geom;
+    a.backbuffer = ctx->backbuffer; a.steps = ctx->steps; a.rgba8 = ctx->rgba8; a.bgra8 = ctx->bgra8; a.geom = ctx->geom; a.slice_values = ctx->slice_values;
     a.present_w = ctx->present_w; a.present_h = ctx->present_h;
-    ctx->backbuffer = b.backbuffer; ctx->steps = b.steps; ctx->rgba8 = b.rgba8; ctx->bgra8 = b.bgra8; ctx->geom = b.geom;
+    ctx->backbuffer = b.backbuffer; ctx->steps = b.steps; ctx->rgba8 = b.rgba8; ctx->bgra8 = b.bgra8; ctx->geom = b.geom; ctx->slice_values = b.slice_values;
     ctx->present_w = b.present_w; ctx->present_h = b.present_h;
-    b.backbuffer = nullptr; b.steps = nullptr; b.rgba8 = b.bgra8 = nullptr; b.geom = nullptr;
+    b.backbuffer = nullptr; b.steps = nullptr; b.rgba8 = b.bgra8 = nullptr; b.geom = nullptr; b.slice_values = nullptr;
     if (ctx->fif_k > 1) ctx->stream = b.stream;
     ctx->fif_cur = to;
 }
@@ -50,6 +50,7 @@ static void frame_slot_release(vk_ctx::FrameSlot &s, bool keep_stream) {  // a p
     if (s.backbuffer) (void)hipFree(s.backbuffer);
     if (s.steps) (void)hipFree(s.steps);
     if (s.geom) (void)hipFree(s.geom);
+    if (s.slice_values) (void)hipFree(s.slice_values);
     if (s.rgba8) (void)hipFree(s.rgba8);
     if (s.bgra8) (void)hipFree(s.bgra8);
     if (s.done) (void)hipEventDestroy(s.done);
@@ -65,6 +66,8 @@ static int surface_alloc_current(vk_ctx *ctx) {
     ctx->backbuffer = nullptr;
     ctx->steps = nullptr;
     ctx->geom = nullptr;
+    if (ctx->slice_values) (void)hipFree(ctx->slice_values);  // ... and so does the slice pass's value surface
+    ctx->slice_values = nullptr;
     HIP_TRY(ctx, hipMalloc(&ctx->backbuffer, (size_t)ctx->width * ctx->height * px_bytes(ctx->out_format)));
     return vk_backbuffer_clear(ctx);
 }
@@ -144,6 +147,7 @@ int vk_ctx_destroy(vk_ctx *ctx) {
     if (ctx->backbuffer) (void)hipFree(ctx->backbuffer);
     if (ctx->steps) (void)hipFree(ctx->steps);
     if (ctx->geom) (void)hipFree(ctx->geom);
+    if (ctx->slice_values) (void)hipFree(ctx->slice_values);
     if (ctx->counters) (void)hipFree(ctx->counters);
     if (ctx->rgba8) (void)hipFree(ctx->rgba8);
     if (ctx->bgra8) (void)hipFree(ctx->bgra8);
@@ -248,6 +252,10 @@ int vk_ctx_frames_in_flight(vk_ctx *ctx, uint32_t k) {
     if (ctx->geom) { (void)hipFree(ctx->geom); ctx->geom = nullptr; }
     for (uint32_t i = 0; i < VK_MAX_FRAMES_IN_FLIGHT; i++)
         if (ctx->fif[i].geom) { (void)hipFree(ctx->fif[i].geom); ctx->fif[i].geom = nullptr; }
+    // ... and every slot's value surface of the slice pass
+    if (ctx->slice_values) { (void)hipFree(ctx->slice_values); ctx->slice_values = nullptr; }
+    for (uint32_t i = 0; i < VK_MAX_FRAMES_IN_FLIGHT; i++)
+        if (ctx->fif[i].slice_values) { (void)hipFree(ctx->fif[i].slice_values); ctx->fif[i].slice_values = nullptr; }
     ctx->fif_seq = 0;
     for (int i = 0; i < 16; i++) { ctx->ring_use_stream[i] = nullptr; ctx->ring_use_frame[i] = 0; }  // (drained: no reader is left)
     for (uint32_t i = k; i < VK_MAX_FRAMES_IN_FLIGHT; i++) frame_slot_release(ctx->fif[i], false);  // a smaller ring
@@ -369,6 +377,10 @@ int vk_frame_geometry(vk_ctx *ctx, uint64_t frame_id, void *dst, size_t row_pitc
     return with_frame_slot(ctx, frame_id, "vk_frame_geometry", [&] { return vk_readback_geometry(ctx, dst, row_pitch_bytes); });
 }
 
+int vk_frame_slice_values(vk_ctx *ctx, uint64_t frame_id, void *dst, size_t row_pitch_bytes) {
+    return with_frame_slot(ctx, frame_id, "vk_frame_slice_values", [&] { return vk_readback_slice_values(ctx, dst, row_pitch_bytes); });
+}
+
 int vk_backbuffer_info(vk_ctx *ctx, uint32_t *width, uint32_t *height, int *out_format, void **device_ptr) {
     if (!ctx) return VK_ERR_INVALID;
     if (width) *width = ctx->width;
@@ -434,6 +446,27 @@ int vk_readback_geometry(vk_ctx *ctx, void *dst, size_t row_pitch_bytes) {
     const size_t row = geom_row_bytes(ctx->width);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemcpy2DAsync(dst, row_pitch_bytes, ctx->geom, row, row, ctx->height, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return VK_OK;
+}
+
+// The current slot's value surface of the slice pass (vk_render_slice under VK_SLICE_VALUES): [height][width] records of two f32 (vk_slice.hpp).
+int vk_slice_values_info(vk_ctx *ctx, uint32_t *width, uint32_t *height, void **device_ptr) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (!ctx->slice_values) return fail(ctx, VK_ERR_INVALID, "no slice pass with VK_SLICE_VALUES (vk_render_slice) since the last resize");
+    if (width) *width = ctx->width;
+    if (height) *height = ctx->height;
+    if (device_ptr) *device_ptr = ctx->slice_values;
+    return VK_OK;
+}
+
+int vk_readback_slice_values(vk_ctx *ctx, void *dst, size_t row_pitch_bytes) {
+    if (!ctx || !dst) return fail(ctx, VK_ERR_INVALID, "vk_readback_slice_values: NULL argument");
+    if (!ctx->slice_values) return fail(ctx, VK_ERR_INVALID, "no slice pass with VK_SLICE_VALUES (vk_render_slice) since the last resize");
+    if (!slice_pitch_ok(ctx->width, row_pitch_bytes)) return fail(ctx, VK_ERR_INVALID, "row pitch smaller than a row of records (width * 8 bytes)");
+    const size_t row = slice_row_bytes(ctx->width);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpy2DAsync(dst, row_pitch_bytes, ctx->slice_values, row, row, ctx->height, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return VK_OK;
 }

@@ -13,6 +13,7 @@
 //   vk_launch_iso.hip      instantiates the cell march under a first-hit isosurface (vk_march.hpp, vk_march_iso.hpp, vk_iso.hpp)
 //   vk_launch_iso_shadow.hip  instantiates the isosurface march with light-direction shadows (vk_march_iso.hpp, vk_shadow.hpp)
 //   vk_launch_geom.hip     instantiates the geometry pass of the isosurface march (vk_march_iso.hpp, vk_geom.hpp)
+//   vk_launch_slice.hip    the slice pass: a plane through the volume, thick slabs (vk_slice.hpp)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)
@@ -25,6 +26,7 @@
 #include "vk_iso.hpp"
 #include "vk_light.hpp"
 #include "vk_shadow.hpp"
+#include "vk_slice.hpp"
 #include "vk_tf.hpp"
 
 #include <hip/hip_runtime.h>
@@ -92,6 +94,7 @@ struct vk_ctx {
     int out_format = VK_OUT_RGBA32F;
     uint32_t *steps = nullptr;
     void *geom = nullptr;  // the geometry surface of the current slot (vk_render_geometry): [height][width][2] float4, allocated by the slot's first geometry pass
+    void *slice_values = nullptr;  // the value surface of the current slot (vk_render_slice under VK_SLICE_VALUES): [height][width] records of two f32, allocated and zero-filled by the slot's first such pass
     unsigned long long *counters = nullptr;  // kCounters of them: 0-5 the march's steps and census, 7 the upload's empty cells, 8-9 the lone-speckle census
 
     // heaviest-first tile order (launch-order heuristic; see tile_order_update)
@@ -168,6 +171,7 @@ struct vk_ctx {
         void *backbuffer = nullptr;
         uint32_t *steps = nullptr, *rgba8 = nullptr, *bgra8 = nullptr;
         void *geom = nullptr;
+        void *slice_values = nullptr;
         uint32_t present_w = 0, present_h = 0;
         hipStream_t stream = nullptr;  // fif_k > 1: the slot's stream, created with the ring at the highest stream priority (vk_ctx_frames_in_flight)
         hipEvent_t done = nullptr;     // recorded by vk_frame_end
@@ -257,6 +261,7 @@ void launch_cells_geom(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDes
                        bool safe);  // vk_launch_geom.hip
 void launch_u16_geom(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::IsoDesc &I, const vk::GeomDesc &G, const vk::ClipDesc *Cl /* nullptr: no box */, uint32_t grid, bool skip,
                      bool safe);  // vk_launch_u16_geom.hip
+void launch_slice(vk_ctx *ctx, const vk::VolumeDesc &V, const vk::SliceDesc &S);  // vk_launch_slice.hip
 // vk_launch_u16_*.hip: the same five families on an R16_UNORM volume (vk_march_u16.hpp); a family reads its own descriptors, Cl == nullptr: no box
 #define VK_U16_LAUNCH(name) void name(vk_ctx *ctx, const vk::LaunchDesc &L, const vk::VolumeDesc &V, const vk::TfDesc &T, const vk::LightDesc &Li, const vk::IsoDesc &I, const vk::ClipDesc *Cl, uint32_t grid, bool count, bool skip, bool safe)
 VK_U16_LAUNCH(launch_u16_cells);

@@ -413,6 +413,58 @@ int vk_pick(vk_ctx *ctx, uint32_t x, uint32_t y, float dt_scale, vk_hit *out) {
     return VK_OK;
 }
 
+// The slice pass: a kernel family of its own (vk_launch_slice.hip), no camera, no tile order, no cull.  The plane comes
+// with the call; table, clip box and format are the context's.  Every refusal comes before the first write: the backbuffer is untouched.
+int vk_render_slice(vk_ctx *ctx, const vk_slice *slice, int32_t tile_x, int32_t tile_y, uint32_t tile_w, uint32_t tile_h, uint32_t flags) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (flags & ~(uint32_t)VK_SLICE_VALUES) return fail(ctx, VK_ERR_INVALID, "vk_render_slice: takes VK_SLICE_VALUES only");
+    if (ctx->format < 0) return fail(ctx, VK_ERR_INVALID, "vk_render_slice: no volume uploaded");
+    if (!ctx->backbuffer) return fail(ctx, VK_ERR_INVALID, "vk_render_slice: no backbuffer (vk_backbuffer_resize)");
+    SliceDesc S{};
+    const bool tf = ctx->d_tf != nullptr;
+    if (const char *why = slice_validate(slice, tf ? ctx->tf_n : 0u, ctx->tf_lo, ctx->tf_hi, format_scale(ctx->format), S))
+        return fail(ctx, VK_ERR_INVALID, std::string("vk_render_slice: ") + why);
+    if (ctx->format == VK_FMT_RGBA16F_PAIR || !has_table_layout(ctx->vol_kind))
+        return fail(ctx, VK_ERR_UNSUPPORTED, "slice: the slice pass needs a scalar LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED and RGBA16F_PAIR have no slice kernels)");
+    if (!slice_tile_clip(tile_x, tile_y, tile_w, tile_h, ctx->width, ctx->height, S.x0, S.y0, S.x1, S.y1)) return VK_OK;  // no pixel of the tile on the backbuffer
+    if ((S.y1 - S.y0 + 7u) / 8u > 65535u) return fail(ctx, VK_ERR_UNSUPPORTED, "slice: tile too tall for one launch");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((flags & VK_SLICE_VALUES) && !ctx->slice_values) {
+        HIP_TRY(ctx, hipMalloc(&ctx->slice_values, slice_surface_bytes(ctx->width, ctx->height)));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->slice_values, 0, slice_surface_bytes(ctx->width, ctx->height), ctx->stream));
+    }
+    for (int i = 0; i < 3; i++) { S.lo[i] = ctx->clip_on ? ctx->clip_lo[i] : 0.0f; S.hi[i] = ctx->clip_on ? ctx->clip_hi[i] : 1.0f; }
+    S.rgba = tf ? ctx->d_tf : nullptr;
+    S.out = ctx->backbuffer;
+    S.values = (flags & VK_SLICE_VALUES) ? ctx->slice_values : nullptr;
+    S.W = ctx->width; S.H = ctx->height;
+    VolumeDesc V = ctx->vdesc;
+    V.data = ctx->vol; V.data2 = ctx->vol2; V.dist = ctx->dist; V.lut = ctx->lut;
+    V.nx = ctx->nx; V.ny = ctx->ny; V.nz = ctx->nz;
+    V.nbx = ctx->nbx; V.nby = ctx->nby; V.nbz = ctx->nbz;
+    launch_slice(ctx, V, S);
+    HIP_TRY(ctx, hipGetLastError());
+    return VK_OK;
+}
+
+// One pixel's sample: the 1 x 1 tile at (x, y) with VK_SLICE_VALUES into the current slot's surfaces, then that record.  The position does
+// not depend on the tile, so the record is the full-frame pass's, bit for bit; pos is slice_position() on the host, the kernel's function.
+int vk_slice_probe(vk_ctx *ctx, const vk_slice *slice, uint32_t x, uint32_t y, vk_slice_sample *out) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (!out) return fail(ctx, VK_ERR_INVALID, "vk_slice_probe: out is NULL");
+    if (!ctx->backbuffer) return fail(ctx, VK_ERR_INVALID, "vk_render_slice: no backbuffer (vk_backbuffer_resize)");
+    if (x >= ctx->width || y >= ctx->height) return fail(ctx, VK_ERR_INVALID, "vk_slice_probe: the pixel lies outside the backbuffer");
+    int rc = vk_render_slice(ctx, slice, (int32_t)x, (int32_t)y, 1, 1, VK_SLICE_VALUES);
+    if (rc) return rc;
+    float rec[2];
+    HIP_TRY(ctx, hipMemcpyAsync(rec, reinterpret_cast<const char *>(ctx->slice_values) + slice_record_offset(x, y, slice_row_bytes(ctx->width)), sizeof(rec), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    out->inside = rec[1] != 0.0f ? 1 : 0;
+    for (int i = 0; i < 3; i++) out->pos[i] = slice_position(slice->origin[i], slice->du[i], slice->dv[i], x, y);
+    out->value = rec[0];
+    return VK_OK;
+}
+
 int vk_render_partition(vk_ctx *ctx, int mode, uint32_t tile_size, uint32_t rank, uint32_t nranks, float dt_scale,
                         uint32_t flags, void *compact_out) {
     if (!ctx) return VK_ERR_INVALID;

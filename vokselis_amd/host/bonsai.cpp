@@ -25,6 +25,11 @@
 //                                                            the frame's smallest (white) and largest (dark grey) finite t, misses black
 //          [--clip X0 Y0 Z0 X1 Y1 Z1]                         clip box (cut-away) in unit-cube coordinates (vk_set_clip_box): the rays march the box
 //                                                            only; needs --tf, --mip or --iso
+//          [--slice AXIS POS | --slice-plane CX CY CZ NX NY NZ EXTENT]   the slice pass in place of the raycast (vk_render_slice): the plane AXIS = POS
+//                                                            (AXIS x | y | z, POS in 0 .. 1) fitted into the frame, or the plane through (CX, CY, CZ) with
+//                                                            normal (NX, NY, NZ) whose frame is EXTENT wide, in units of the volume's longest side; pixels
+//                                                            are square in voxel space.  With either: --ppm, --tf, --raw / --raw-u16, --dims, --clip, and
+//          [--slab SAMPLES THICKNESS max|min|mean]            a thick slab: SAMPLES (1 .. 256) planes over THICKNESS along the normal, reduced
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -144,6 +149,83 @@ static int run_group(int n_gpus, uint32_t frames, uint32_t batch, uint32_t w, ui
     return rc;
 }
 
+// --slice / --slice-plane: the plane's four vectors, formed in double and rounded once per component.  The volume's physical sides are its
+// dims (unit spacing) over the longest of them; a pixel is `px` of that on both screen axes.
+struct SliceArgs {
+    bool on = false, oblique = false;
+    int axis = 2;
+    double pos = 0.5, centre[3] = {0.5, 0.5, 0.5}, normal[3] = {0.0, 0.0, 1.0}, extent = 1.0, thickness = 0.0;
+    uint32_t samples = 1;
+    int reduce = VK_SLAB_MAX;
+};
+static vk_slice make_slice(const SliceArgs &a, uint32_t w, uint32_t h) {
+    const double longest = (double)std::max(g_dims[0], std::max(g_dims[1], g_dims[2]));
+    const double size[3] = {g_dims[0] / longest, g_dims[1] / longest, g_dims[2] / longest};
+    double n[3] = {0, 0, 0}, right[3] = {0, 0, 0}, down[3] = {0, 0, 0}, centre[3], px;  // unit directions in voxel space: the normal, +x and +y on screen
+    if (a.oblique) {
+        const double len = std::sqrt(a.normal[0] * a.normal[0] + a.normal[1] * a.normal[1] + a.normal[2] * a.normal[2]);
+        for (int k = 0; k < 3; k++) { n[k] = a.normal[k] / len; centre[k] = a.centre[k]; }
+        const int u = std::fabs(n[2]) < 0.9 ? 2 : 1;  // up: z, or y for a plane facing z; made perpendicular to the normal
+        double up[3], ul = 0.0;
+        for (int k = 0; k < 3; k++) { up[k] = (k == u ? 1.0 : 0.0) - n[u] * n[k]; ul += up[k] * up[k]; }
+        for (int k = 0; k < 3; k++) { up[k] /= std::sqrt(ul); down[k] = 0.0 - up[k]; }
+        right[0] = up[1] * n[2] - up[2] * n[1]; right[1] = up[2] * n[0] - up[0] * n[2]; right[2] = up[0] * n[1] - up[1] * n[0];  // up x normal
+        px = a.extent / w;
+    } else {
+        const int sa = a.axis == 0 ? 1 : 0, sb = a.axis == 2 ? 1 : 2;  // the screen's axes run up the volume's: (x, y), (x, z), (y, z)
+        n[a.axis] = 1.0; right[sa] = 1.0; down[sb] = 1.0;
+        for (int k = 0; k < 3; k++) centre[k] = 0.5;
+        centre[a.axis] = a.pos;
+        px = std::max(size[sa] / w, size[sb] / h);  // the face fits the frame
+    }
+    vk_slice s{};
+    const double step = a.samples > 1 ? a.thickness / (a.samples - 1) : 0.0;
+    for (int k = 0; k < 3; k++) {
+        const double du = right[k] * px / size[k], dv = down[k] * px / size[k];
+        s.du[k] = (float)du; s.dv[k] = (float)dv; s.dn[k] = (float)(n[k] * step / size[k]);
+        s.origin[k] = (float)(centre[k] - 0.5 * (w - 1) * du - 0.5 * (h - 1) * dv);
+    }
+    s.samples = a.samples;
+    s.reduce = a.reduce;
+    return s;
+}
+
+// The slice pass in place of the raycast: one pass with the value surface, the frame as a PPM (the stored sRGB, clamped to 0 .. 1).
+static int run_slice(const SliceArgs &a, uint32_t w, uint32_t h, const std::string &ppm) {
+    try {
+        HdrBackBuffer bb; bb.width = w; bb.height = h; bb.format = VK_OUT_RGBA32F;
+        Context ctx(w, h, nullptr, 0, bb);
+        if (!g_tf.empty()) ctx.set_transfer_function(g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi);
+        if (g_clip_on) ctx.set_clip_box(&g_clip);
+        if (!g_raw.empty()) VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt);
+        else VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, g_dims[0], g_dims[1], g_dims[2]);
+        const vk_slice s = make_slice(a, w, h);
+        ctx.render_slice(s, true);
+        const std::vector<float> val = ctx.read_slice_values();
+        const std::vector<float> px = ctx.read_backbuffer_f32();
+        size_t inside = 0;
+        float lo = INFINITY, hi = -INFINITY;
+        for (size_t q = 0; q < (size_t)w * h; q++)
+            if (val[2 * q + 1] != 0.0f) { inside++; lo = std::min(lo, val[2 * q]); hi = std::max(hi, val[2 * q]); }
+        const vk_slice_sample mid = ctx.slice_probe(s, w / 2, h / 2);
+        std::printf("slice: %ux%u, %u sample%s, %zu pixels inside, values in [%g, %g]; centre pixel at %.6f %.6f %.6f: %s %g\n", w, h, a.samples, a.samples == 1 ? "" : "s",
+                    inside, inside ? lo : 0.0f, inside ? hi : 0.0f, mid.pos[0], mid.pos[1], mid.pos[2], mid.inside ? "value" : "outside,", mid.value);
+        if (!ppm.empty()) {
+            std::ofstream f(ppm, std::ios::binary);
+            f << "P6\n" << w << " " << h << "\n255\n";
+            for (size_t q = 0; q < (size_t)w * h; q++) {
+                char c[3];
+                for (int k = 0; k < 3; k++) c[k] = (char)(unsigned char)(std::min(std::max(px[4 * q + k], 0.0f), 1.0f) * 255.0f + 0.5f);
+                f.write(c, 3);
+            }
+        }
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "bonsai: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 // `zoom pitch yaw tx ty tz aspect` per line -> 144 bytes per line (no GPU involved)
 static int dump_camera_blobs(const std::string &in, const std::string &out) {
     std::ifstream f(in);
@@ -164,6 +246,8 @@ int main(int argc, char **argv) {
     std::string ppm, dump_rgba, dump_steps, depth_ppm;
     bool pick = false;
     uint32_t pick_x = 0, pick_y = 0;
+    SliceArgs sl;
+    bool slab = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -202,13 +286,47 @@ int main(int argc, char **argv) {
             g_light.ambient = (float)std::atof(next()); g_light.diffuse = (float)std::atof(next());
             g_light.specular = (float)std::atof(next()); g_light.shininess = (float)std::atof(next());
         }
+        else if (a == "--slice") {
+            const std::string ax = next();
+            if (ax != "x" && ax != "y" && ax != "z") { std::fprintf(stderr, "bonsai: --slice AXIS POS: AXIS is x, y or z\n"); return 2; }
+            if (sl.on) { std::fprintf(stderr, "bonsai: --slice and --slice-plane exclude each other (one plane per run)\n"); return 2; }
+            sl.on = true; sl.oblique = false; sl.axis = ax[0] - 'x';
+            sl.pos = std::atof(next());
+            if (!(sl.pos >= 0.0 && sl.pos <= 1.0)) { std::fprintf(stderr, "bonsai: --slice AXIS POS: POS lies in 0 .. 1\n"); return 2; }
+        }
+        else if (a == "--slice-plane") {
+            if (sl.on) { std::fprintf(stderr, "bonsai: --slice and --slice-plane exclude each other (one plane per run)\n"); return 2; }
+            sl.on = true; sl.oblique = true;
+            for (int k = 0; k < 3; k++) sl.centre[k] = std::atof(next());
+            for (int k = 0; k < 3; k++) sl.normal[k] = std::atof(next());
+            sl.extent = std::atof(next());
+            const double len2 = sl.normal[0] * sl.normal[0] + sl.normal[1] * sl.normal[1] + sl.normal[2] * sl.normal[2];
+            if (!(len2 > 0.0) || !std::isfinite(len2)) { std::fprintf(stderr, "bonsai: --slice-plane: the normal has no direction\n"); return 2; }
+            if (!(sl.extent > 0.0) || !std::isfinite(sl.extent)) { std::fprintf(stderr, "bonsai: --slice-plane: EXTENT must be finite and > 0\n"); return 2; }
+            for (int k = 0; k < 3; k++) if (!std::isfinite(sl.centre[k])) { std::fprintf(stderr, "bonsai: --slice-plane: the centre is not finite\n"); return 2; }
+        }
+        else if (a == "--slab") {
+            slab = true;
+            const int n = std::atoi(next());
+            sl.thickness = std::atof(next());
+            const std::string red = next();
+            if (n < 1 || n > VK_SLICE_MAX_SAMPLES) { std::fprintf(stderr, "bonsai: --slab SAMPLES THICKNESS max|min|mean: SAMPLES lies in 1 .. %d\n", VK_SLICE_MAX_SAMPLES); return 2; }
+            if (!(sl.thickness >= 0.0) || !std::isfinite(sl.thickness)) { std::fprintf(stderr, "bonsai: --slab: THICKNESS must be finite and >= 0\n"); return 2; }
+            if (red != "max" && red != "min" && red != "mean") { std::fprintf(stderr, "bonsai: --slab: the reduction is max, min or mean\n"); return 2; }
+            sl.samples = (uint32_t)n;
+            sl.reduce = red == "max" ? VK_SLAB_MAX : (red == "min" ? VK_SLAB_MIN : VK_SLAB_MEAN);
+        }
         else if (a == "--camera-blobs") { std::string in = next(); return dump_camera_blobs(in, next()); }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
     if (g_iso_on && g_mip) { std::fprintf(stderr, "bonsai: --iso and --mip exclude each other (an isosurface ignores the projection)\n"); return 2; }
     if (g_shadows_on && !(g_iso_on && g_lit && !g_light.headlight)) { std::fprintf(stderr, "bonsai: --shadows needs --iso and --light (shadows are cast along a light direction, under an isosurface)\n"); return 2; }
-    if (g_clip_on && g_tf.empty() && !g_mip && !g_iso_on) { std::fprintf(stderr, "bonsai: --clip needs --tf, --mip or --iso (the built-in march has no clip kernels)\n"); return 2; }
+    if (g_clip_on && g_tf.empty() && !g_mip && !g_iso_on && !sl.on) { std::fprintf(stderr, "bonsai: --clip needs --tf, --mip or --iso (the built-in march has no clip kernels)\n"); return 2; }
     if ((pick || !depth_ppm.empty()) && !g_iso_on) { std::fprintf(stderr, "bonsai: --pick and --depth-ppm need --iso (the geometry pass is the isosurface's)\n"); return 2; }
+    if (slab && !sl.on) { std::fprintf(stderr, "bonsai: --slab needs --slice or --slice-plane (a slab is a thick slice)\n"); return 2; }
+    if (sl.on && gpus > 0) { std::fprintf(stderr, "bonsai: --slice and --slice-plane render on one GPU (groups have no slice output)\n"); return 2; }
+    if (sl.on && (pick || !depth_ppm.empty() || !dump_rgba.empty() || !dump_steps.empty())) { std::fprintf(stderr, "bonsai: --slice and --slice-plane replace the raycast: no --pick, --depth-ppm, --dump-rgba or --dump-steps\n"); return 2; }
+    if (sl.on) return run_slice(sl, w, h, ppm);
     if (gpus > 0) return run_group(gpus, frames, batch, w, h, peer_direct);
     try {
         // examples/bonsai/main.rs:64-74: 1280x720 window, Camera::new(1., 0.5, 1., (0.5,0.5,0.5), w/h)

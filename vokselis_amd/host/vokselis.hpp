@@ -174,6 +174,7 @@ static_assert(sizeof(vk_isosurface) == 20, "vk_isosurface is 20 bytes (vk_set_is
 static_assert(sizeof(vk_clip_box) == 24, "vk_clip_box is 24 bytes (vk_set_clip_box)");
 static_assert(sizeof(vk_shadows) == 8, "vk_shadows is 8 bytes (vk_set_shadows)");
 static_assert(sizeof(vk_hit) == 36, "vk_hit is 36 bytes (vk_pick)");
+static_assert(sizeof(vk_slice) == 56 && sizeof(vk_slice_sample) == 20, "vk_slice is 56 bytes, vk_slice_sample 20 (vk_render_slice, vk_slice_probe)");
 
 // src/context/hdr_backbuffer.rs:10-11
 struct HdrBackBuffer {
@@ -275,6 +276,25 @@ class Context {
     // What the ray through pixel (x, y) hits (vk_pick; blocks): hit.hit == 0 for a miss.  The outward normal of a surface entered from below the
     // threshold is -grad / |grad|.
     vk_hit pick(uint32_t x, uint32_t y, float dt_scale = 1.0f) { vk_hit h{}; check(ctx_, vk_pick(ctx_, x, y, dt_scale, &h)); return h; }
+    // The slice pass (vk_render_slice): the plane `s` into the backbuffer (or a tile of it) -- the volume filtered at each pixel's position, or a
+    // slab of samples reduced by max / min / mean, through the table in force, as sRGB; asynchronous.  No camera; only table and clip box have
+    // influence.  values: also write the (x, weight) records into the slot's value surface.
+    void render_slice(const vk_slice &s, bool values = false) { check(ctx_, vk_render_slice(ctx_, &s, 0, 0, render_backbuffer.width, render_backbuffer.height, values ? VK_SLICE_VALUES : 0u)); }
+    void render_slice_tile(const vk_slice &s, int32_t x, int32_t y, uint32_t w, uint32_t h, bool values = false) { check(ctx_, vk_render_slice(ctx_, &s, x, y, w, h, values ? VK_SLICE_VALUES : 0u)); }
+    // [height][width][2] floats: (x, weight) per pixel, weight 0 (and x = +0) outside the box.  Blocks.
+    std::vector<float> read_slice_values() {
+        std::vector<float> out((size_t)render_backbuffer.width * render_backbuffer.height * 2);
+        check(ctx_, vk_readback_slice_values(ctx_, out.data(), (size_t)render_backbuffer.width * 8));
+        return out;
+    }
+    std::vector<float> frame_slice_values(uint64_t id) {  // ... of that frame's slot (vk_frame_readback's rules)
+        std::vector<float> out((size_t)render_backbuffer.width * render_backbuffer.height * 2);
+        check(ctx_, vk_frame_slice_values(ctx_, id, out.data(), (size_t)render_backbuffer.width * 8));
+        return out;
+    }
+    void *slice_values_device_ptr() const { void *p = nullptr; check(ctx_, vk_slice_values_info(ctx_, nullptr, nullptr, &p)); return p; }  // (does not synchronise)
+    // The value under pixel (x, y) of the plane (vk_slice_probe; blocks): inside == 0 where the position lies outside the box.
+    vk_slice_sample slice_probe(const vk_slice &s, uint32_t x, uint32_t y) { vk_slice_sample o{}; check(ctx_, vk_slice_probe(ctx_, &s, x, y, &o)); return o; }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
     void frames_in_flight(uint32_t k) { check(ctx_, vk_ctx_frames_in_flight(ctx_, k)); }
