@@ -447,6 +447,60 @@ int vk_readback_slice_values(vk_ctx *ctx, void *dst, size_t row_pitch_bytes);
 int vk_frame_slice_values(vk_ctx *ctx, uint64_t frame_id, void *dst, size_t row_pitch_bytes);
 int vk_slice_probe(vk_ctx *ctx, const vk_slice *slice, uint32_t x, uint32_t y, vk_slice_sample *out);
 
+/* The histogram and region statistics of the volume: where the data lies -- what a caller needs to choose the
+ * domain of vk_set_transfer_function, an isovalue or a slice's window, and the mean and deviation of a region.  A reduction over the
+ * STORED texels (no filter, no ray, no plane) of the voxel box [x0, x1) x [y0, y1) x [z0, z1); the box must lie within the volume and
+ * may be empty; a NULL box is the whole volume.  Each voxel is counted once, whatever the layout duplicates.  For a voxel's texel t as
+ * f32 on the kernel's scale (R8: 0..255, R16_UNORM: 0..65535, R16F: the value -- the scale of vk_slice_sample.value):
+ *     S    = 255 / 65535 / 1
+ *     lo_k = (float)((double)lo * S),  hi_k = (float)((double)hi * S)
+ *     k1   = (float)(bins / (((double)hi - (double)lo) * S)),  k2 = (float)(-(double)lo * bins / ((double)hi - (double)lo))
+ *                                                     formed on the host in double, rounded once
+ *     t is a NaN   -> n_nan
+ *     t <  lo_k    -> n_below
+ *     t >  hi_k    -> n_above                         (+-inf land here; the top is closed, like numpy.histogram's)
+ *     otherwise    -> counts[min((int)floorf(fmaf(t, k1, k2)), bins - 1)], never below 0     (-0 at lo_k = 0 is bin 0)
+ *     min, max     over every texel that is not a NaN, in the order in which -0 lies below +0 (an empty box or all NaN: min = +inf,
+ *                  max = -inf)
+ *     sum, sum_sq  f64 sums of t and t * t (the product in f64) over the FINITE texels; n_finite their number
+ * So an R8 volume with bins = 256 over [0, 1] has counts == bincount(v), an R16_UNORM volume counts == bincount(v >> 8).
+ * Counts, categories, min and max are integers or selections: the same on every layout and every run, bit for bit.  The sums are exact
+ * for the integer formats while they stay below 2^53; for R16F they are f64 sums in an order that depends on the launch, the same from
+ * run to run on one device (no float atomics).
+ * vk_volume_histogram is blocking; it runs on the context's current stream behind whatever was recorded there and changes no context
+ * state: no surface, counter or frame slot is touched.  counts (bins entries) may be NULL: statistics only.  stats may be NULL.
+ * flags: VK_HIST_CLIP_BOX -- the voxel box is derived from the clip box in force (box must be NULL): a voxel belongs to it when its
+ * centre (i + 0.5) / n lies in the clip box's closed interval on every axis (the index range is formed on the host in double); no clip
+ * box set: the whole volume.
+ * VK_ERR_INVALID, decided before any launch, outputs untouched: a NULL request, bins outside 1 .. VK_HIST_MAX_BINS, lo or hi not
+ * finite or hi <= lo, an unknown flag, a box that is inverted or leaves the volume, a box together with VK_HIST_CLIP_BOX, no volume.
+ * VK_ERR_UNSUPPORTED ("histogram: ..."): a BRICKED / QUADS / STAGED or RGBA16F_PAIR volume -- the set the slice pass refuses.
+ * vk_histogram_window is host arithmetic and needs no context: the window [w_lo, w_hi] that holds the percentiles p_lo .. p_hi of a
+ * histogram over [lo, hi].  N = sum(counts); r_lo = floor(p_lo N), b_lo the first bin whose running total exceeds r_lo; r_hi =
+ * ceil(p_hi N), b_hi the first bin whose running total reaches r_hi, not less than b_lo; w_lo = lo + b_lo (hi - lo) / bins, w_hi =
+ * lo + (b_hi + 1)(hi - lo) / bins, in double, each rounded once to f32.  VK_ERR_INVALID: a NULL argument, bins outside
+ * 1 .. VK_HIST_MAX_BINS, lo or hi not finite or hi <= lo, N == 0, not 0 <= p_lo < p_hi <= 1, a rounded w_lo >= w_hi (its message is
+ * read with vk_last_error(NULL)). */
+#define VK_HIST_MAX_BINS 4096
+enum { VK_HIST_CLIP_BOX = 1 };
+typedef struct vk_histogram {
+    float lo, hi;    /* the domain in sample values, like vk_set_transfer_function's */
+    uint32_t bins;   /* 1 .. VK_HIST_MAX_BINS */
+    uint32_t flags;  /* VK_HIST_CLIP_BOX */
+} vk_histogram;      /* 16 bytes */
+typedef struct vk_voxel_box {
+    uint32_t x0, y0, z0, x1, y1, z1;
+} vk_voxel_box;      /* 24 bytes */
+typedef struct vk_volume_stats {
+    uint64_t n_voxels, n_nan, n_below, n_above, n_finite;
+    double sum, sum_sq;  /* on the kernel's scale */
+    float min, max;      /* on the kernel's scale */
+    float scale;         /* S: divide by it (sum_sq by its square) for sample values */
+    uint32_t pad;
+} vk_volume_stats;       /* 72 bytes */
+int vk_volume_histogram(vk_ctx *ctx, const vk_histogram *hist, const vk_voxel_box *box, uint64_t *counts, vk_volume_stats *stats);
+int vk_histogram_window(const uint64_t *counts, uint32_t bins, float lo, float hi, double p_lo, double p_hi, float *w_lo, float *w_hi);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

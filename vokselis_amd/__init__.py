@@ -7,6 +7,7 @@ Only the raycast hot path and the host surface that drives it live here (SURVEY.
   context    Context, Uniform, HdrBackBuffer, VolumeTexture, RaycastPipeline, Demo, run_headless
   volumes    deterministic synthetic volumes (bonsai stand-in, fog)
   slices     Slice: planes for the slice pass (axial / coronal / sagittal / oblique, thick slabs)
+  histogram  Histogram: the result of Context.volume_histogram (counts, statistics, percentile window)
   dist       tile-parallel multi-GPU frame (one process per GPU, RCCL gather over xGMI)
 """
 from . import _native as native
@@ -14,9 +15,11 @@ from . import volumes
 from ._native import (FMT_R8_UNORM, FMT_R16_FLOAT, FMT_RGBA16F_PAIR, FMT_R16_UNORM, LAYOUT_AUTO, LAYOUT_LINEAR, LAYOUT_PACKED, LAYOUT_PACKED_PAIRS, LAYOUT_BRICKED, LAYOUT_QUADS, LAYOUT_STAGED, RENDER_SAFE, RENDER_FORCE_SKIP,
                       GEN_BONSAI_STANDIN, GEN_FOG, GEN_FOG_DENSE_CORE, MODE_COMPUTE_NEAREST, MODE_NAIVE_TRILINEAR, MODE_PROCEDURAL, OUT_RGBA16F, OUT_RGBA32F, RENDER_COUNT,
                       RENDER_NO_SKIP, RENDER_PROBE_ALWAYS, RENDER_FAST_WALK, RENDER_PRESENT, RENDER_PRESENT_BGRA, RENDER_PRESENT_ONLY, RENDER_DEVICE_SINE, WIRE_RGB, WIRE_RGBA, TF_MAX_ENTRIES, PROJ_COMPOSITE, PROJ_MAX, ISO_MAX_REFINE, VkLighting, VkIsosurface, VkClipBox, VkHit, VokselisError,
-                      SLAB_MAX, SLAB_MIN, SLAB_MEAN, SLICE_VALUES, SLICE_MAX_SAMPLES, VkSlice, VkSliceSample)
+                      SLAB_MAX, SLAB_MIN, SLAB_MEAN, SLICE_VALUES, SLICE_MAX_SAMPLES, VkSlice, VkSliceSample,
+                      HIST_MAX_BINS, HIST_CLIP_BOX, VkHistogram, VkVoxelBox, VkVolumeStats)
 from .camera import Camera
 from .slices import Slice
+from .histogram import Histogram
 from .context import (Context, Demo, FrameCounter, HdrBackBuffer, Hit, ImageDimentions, RaycastPipeline, Uniform,
                       VolumeTexture, dispatch_optimal, partition_slots, render_batch, run_headless, transfer_table, untile_batch)
 
@@ -27,4 +30,5 @@ __all__ = [
     "MODE_COMPUTE_NEAREST", "MODE_NAIVE_TRILINEAR", "MODE_PROCEDURAL", "OUT_RGBA16F", "OUT_RGBA32F", "RENDER_COUNT", "RENDER_NO_SKIP", "RENDER_PROBE_ALWAYS", "RENDER_FAST_WALK", "RENDER_PRESENT", "RENDER_PRESENT_BGRA", "RENDER_PRESENT_ONLY", "RENDER_DEVICE_SINE", "WIRE_RGB", "WIRE_RGBA", "TF_MAX_ENTRIES", "PROJ_COMPOSITE", "PROJ_MAX", "ISO_MAX_REFINE", "VkIsosurface", "VkClipBox",
     "VkHit", "Hit",
     "SLAB_MAX", "SLAB_MIN", "SLAB_MEAN", "SLICE_VALUES", "SLICE_MAX_SAMPLES", "VkSlice", "VkSliceSample", "Slice",
+    "HIST_MAX_BINS", "HIST_CLIP_BOX", "VkHistogram", "VkVoxelBox", "VkVolumeStats", "Histogram",
 ]

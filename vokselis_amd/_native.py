@@ -94,6 +94,35 @@ class VkSliceSample(C.Structure):
 assert C.sizeof(VkSliceSample) == 20
 
 
+HIST_MAX_BINS = 4096
+HIST_CLIP_BOX = 1
+
+
+class VkHistogram(C.Structure):
+    """vk_histogram (16 bytes): the request of vk_volume_histogram -- the domain in sample values, the bins, the flags."""
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("bins", C.c_uint32), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(VkHistogram) == 16
+
+
+class VkVoxelBox(C.Structure):
+    """vk_voxel_box (24 bytes): the voxels [x0, x1) x [y0, y1) x [z0, z1)."""
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("z0", C.c_uint32), ("x1", C.c_uint32), ("y1", C.c_uint32), ("z1", C.c_uint32)]
+
+
+assert C.sizeof(VkVoxelBox) == 24
+
+
+class VkVolumeStats(C.Structure):
+    """vk_volume_stats (72 bytes): the categories, the f64 sums over the finite texels, min and max -- all on the kernel's scale -- and that scale."""
+    _fields_ = [("n_voxels", C.c_uint64), ("n_nan", C.c_uint64), ("n_below", C.c_uint64), ("n_above", C.c_uint64), ("n_finite", C.c_uint64),
+                ("sum", C.c_double), ("sum_sq", C.c_double), ("min", C.c_float), ("max", C.c_float), ("scale", C.c_float), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(VkVolumeStats) == 72
+
+
 def clip_box(lo, hi) -> VkClipBox:
     """A VkClipBox from two triples, held to vk_set_clip_box's rules before the library sees it: finite components (as f32) and
     0 <= lo < hi <= 1 on every axis.  Raises ValueError."""
@@ -147,6 +176,8 @@ SYMBOLS = {
     "vk_readback_slice_values": (C.c_int, [_vp, _vp, _sz]),
     "vk_frame_slice_values": (C.c_int, [_vp, C.c_uint64, _vp, _sz]),
     "vk_slice_probe": (C.c_int, [_vp, _vp, _u32, _u32, _vp]),  # const vk_slice *, vk_slice_sample * (VkSliceSample above)
+    "vk_volume_histogram": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_uint64), _vp]),  # const vk_histogram *, const vk_voxel_box * (NULL: the volume), counts, vk_volume_stats *
+    "vk_histogram_window": (C.c_int, [C.POINTER(C.c_uint64), _u32, _f32, _f32, C.c_double, C.c_double, C.POINTER(_f32), C.POINTER(_f32)]),
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),
     "vk_set_uniform": (C.c_int, [_vp, _vp]),
     "vk_set_camera": (C.c_int, [_vp, _vp]),

@@ -463,6 +463,30 @@ class Context:
         N.check(self._h, N.lib().vk_slice_probe(self._h, C.byref(slice) if slice is not None else None, int(x), int(y), C.byref(out)))
         return out
 
+    # -- the histogram and region statistics of the volume (vk_volume_histogram)
+    def volume_histogram(self, bins: int = 256, domain=(0.0, 1.0), box=None):
+        """vk_volume_histogram: the histogram of the stored texels over `domain` (sample values, like set_transfer_function's) in `bins` bins,
+        and the statistics of the region, as a Histogram.  box: None -- the whole volume; "clip" -- the voxels whose centres lie in the clip
+        box in force; ((x0, y0, z0), (x1, y1, z1)) -- the voxels [x0, x1) x [y0, y1) x [z0, z1).  Blocks; changes no state of the context."""
+        from .histogram import Histogram
+
+        req = N.VkHistogram(float(domain[0]), float(domain[1]), int(bins), 0)
+        vb = None
+        if isinstance(box, str):
+            if box != "clip":
+                raise ValueError('box: None, "clip" or ((x0, y0, z0), (x1, y1, z1))')
+            req.flags = N.HIST_CLIP_BOX
+        elif box is not None:
+            lo, hi = (tuple(int(v) for v in c) for c in box)
+            if len(lo) != 3 or len(hi) != 3 or min(lo + hi) < 0:
+                raise ValueError("box: two triples of voxel indices >= 0")
+            vb = N.VkVoxelBox(*lo, *hi)
+        counts = np.zeros(max(int(bins), 0), np.uint64)
+        stats = N.VkVolumeStats()
+        N.check(self._h, N.lib().vk_volume_histogram(self._h, C.byref(req), C.byref(vb) if vb is not None else None,
+                                                     counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(stats)))
+        return Histogram(counts, (req.lo, req.hi), stats)
+
     def set_root_skip(self, k: int):
         """vk_partition_root_skip: rank 0 sits out every k-th round of the tile deal (0: never)."""
         N.check(self._h, N.lib().vk_partition_root_skip(self._h, int(k)))

@@ -535,6 +535,8 @@ int vk_debug_set_param(vk_ctx *ctx, const char *name, double value) {
     else if (n == "pair_walk_min") ctx->pair_walk_min = (uint32_t)std::min(std::max(2.0, value), 1e6);
     else if (n == "order_rays") { ctx->order_rays = ctx->order_rays_batch = (uint32_t)std::min<double>(std::max<double>(value, 1), 8); ctx->batch_key.clear(); ctx->order_key.clear(); }
     else if (n == "naive_lds_pad") ctx->naive_lds_pad = (uint32_t)value;          // experiments: caps the cell kernels' waves per SIMD
+    else if (n == "hist_max_blocks") ctx->hist_max_blocks = (uint32_t)value;      // vk_volume_histogram: cap of the grid (0: none)
+    else if (n == "hist_flush_passes") ctx->hist_flush_passes = (uint32_t)value;  // ... passes between merges of a workgroup's counters (0: the bound of vk_hist.hpp)
     else if (n == "stage_copies_mask") ctx->stage_copies_mask = (uint32_t)value; // which brick copies to build (next upload)
     else return fail(ctx, VK_ERR_INVALID, "vk_debug_set_param: unknown parameter " + n);
     return VK_OK;

@@ -14,6 +14,7 @@
 //   vk_launch_iso_shadow.hip  instantiates the isosurface march with light-direction shadows (vk_march_iso.hpp, vk_shadow.hpp)
 //   vk_launch_geom.hip     instantiates the geometry pass of the isosurface march (vk_march_iso.hpp, vk_geom.hpp)
 //   vk_launch_slice.hip    the slice pass: a plane through the volume, thick slabs (vk_slice.hpp)
+//   vk_launch_hist.hip     vk_volume_histogram, vk_histogram_window: histogram and statistics of a voxel box (vk_hist.hpp)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)
@@ -157,6 +158,8 @@ struct vk_ctx {
     uint32_t wave_prio = 1;      // issue priority by ray length (set_wave_priority); 0 for A/B measurements
     uint32_t naive_lds_pad = 0;  // debug: extra dynamic LDS per workgroup of the cell kernels (caps the waves per SIMD)
     uint32_t root_skip = 0;  // dealing: rank 0 sits out every root_skip-th round (vk_partition_root_skip)
+    uint32_t hist_max_blocks = 0;    // vk_volume_histogram: cap of the grid (0: none) -- lets a small volume drive the grid-stride loop
+    uint32_t hist_flush_passes = 0;  // ... and passes of that loop between merges of a workgroup's counters (0: vk_hist.hpp's bound)
 
     // present targets (next row N1/N2)
     uint32_t *rgba8 = nullptr, *bgra8 = nullptr;

@@ -30,6 +30,11 @@
 //                                                            normal (NX, NY, NZ) whose frame is EXTENT wide, in units of the volume's longest side; pixels
 //                                                            are square in voxel space.  With either: --ppm, --tf, --raw / --raw-u16, --dims, --clip, and
 //          [--slab SAMPLES THICKNESS max|min|mean]            a thick slab: SAMPLES (1 .. 256) planes over THICKNESS along the normal, reduced
+//          [--histogram BINS [LO HI]]                         in place of the raycast (vk_volume_histogram): the statistics of the volume and one `bin count` line per
+//                                                            non-empty bin of BINS (1 .. 4096) bins over the sample values [LO, HI] (default 0 1)
+//          [--auto-window P_LO P_HI]                          before the first frame, the table's domain -- of --tf, or of the grey ramp of --mip / --slice -- becomes the
+//                                                            window that holds the percentiles P_LO .. P_HI (0 <= P_LO < P_HI <= 1) of a 4096-bin histogram over
+//                                                            [0, 1] (vk_histogram_window); needs --tf, --mip, --slice or --slice-plane
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -57,6 +62,8 @@ static vk_shadows g_shadows = {0.7f, 2.0f};
 static bool g_clip_on = false;  // --clip: clip box (the library checks the bounds)
 static vk_clip_box g_clip = {{0.0f, 0.0f, 0.0f}, {1.0f, 1.0f, 1.0f}};
 static vk_lighting g_light = {{0.0f, 0.0f, 0.0f}, 0, 0.3f, 0.7f, 0.2f, 32.0f};
+static bool g_auto_window = false;  // --auto-window: the table's domain from the volume's percentiles
+static double g_auto_lo = 0.0, g_auto_hi = 1.0;
 
 // --tf PATH: the whole file as little-endian f32 RGBA rows (the library checks n, finiteness and alpha)
 static std::vector<float> read_tf(const std::string &path) {
@@ -71,19 +78,56 @@ static std::vector<float> read_tf(const std::string &path) {
     return t;
 }
 
+// --auto-window, once the volume is there: the percentiles' window becomes the table's domain; without --tf the table is the grey ramp
+static void apply_auto_window(Context &ctx) {
+    const Histogram h = ctx.volume_histogram(VK_HIST_MAX_BINS, 0.0f, 1.0f);
+    const std::pair<float, float> w = h.window(g_auto_lo, g_auto_hi);
+    g_tf_lo = w.first; g_tf_hi = w.second;
+    if (g_tf.empty()) g_tf = {0.0f, 0.0f, 0.0f, 1.0f, 1.0f, 1.0f, 1.0f, 1.0f};
+    std::printf("auto window: percentiles %g .. %g of %llu voxels -> [%g, %g]\n", g_auto_lo, g_auto_hi, (unsigned long long)h.stats.n_voxels, g_tf_lo, g_tf_hi);
+    ctx.set_transfer_function(g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi);
+}
+
+// --histogram in place of the raycast: the statistics in sample values, then `bin count` for every non-empty bin
+static int run_histogram(uint32_t bins, float lo, float hi) {
+    try {
+        HdrBackBuffer bb; bb.width = 8; bb.height = 8;
+        Context ctx(8, 8, nullptr, 0, bb);
+        if (g_clip_on) ctx.set_clip_box(&g_clip);
+        if (!g_raw.empty()) VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt);
+        else VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, g_dims[0], g_dims[1], g_dims[2]);
+        const Histogram h = ctx.volume_histogram(bins, lo, hi, nullptr, g_clip_on);
+        const vk_volume_stats &s = h.stats;
+        const double S = s.scale, n = (double)s.n_finite, mean = n > 0 ? s.sum / n : NAN, var = n > 0 ? std::max(s.sum_sq / n - mean * mean, 0.0) : NAN;
+        std::printf("histogram: %u bins over [%g, %g], %llu voxels: %llu NaN, %llu below, %llu above\n", bins, lo, hi, (unsigned long long)s.n_voxels,
+                    (unsigned long long)s.n_nan, (unsigned long long)s.n_below, (unsigned long long)s.n_above);
+        std::printf("min %g max %g mean %g std %g (%llu finite)\n", s.min / S, s.max / S, mean / S, std::sqrt(var) / S, (unsigned long long)s.n_finite);
+        for (uint32_t b = 0; b < bins; b++)
+            if (h.counts[b]) std::printf("%u %llu\n", b, (unsigned long long)h.counts[b]);
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "bonsai: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 struct Bonsai : Demo {
     std::unique_ptr<VolumeTexture> volume_texture;
     RaycastPipeline pipeline;
     static std::unique_ptr<Bonsai> init(Context &ctx) {  // examples/bonsai/main.rs:16-25
         auto self = std::make_unique<Bonsai>();
-        if (!g_tf.empty()) ctx.set_transfer_function(g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi);
-        if (g_lit) ctx.set_lighting(&g_light);
+        if (!g_tf.empty() && !g_auto_window) ctx.set_transfer_function(g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi);
+        if (g_lit && !g_auto_window) ctx.set_lighting(&g_light);
         if (g_mip) ctx.set_projection(VK_PROJ_MAX);
         if (g_iso_on) ctx.set_isosurface(&g_iso);
         if (g_shadows_on) ctx.set_shadows(&g_shadows);
         if (g_clip_on) ctx.set_clip_box(&g_clip);
         if (!g_raw.empty()) self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt));
         else self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, 256, 256, 256));
+        if (g_auto_window) {  // the table follows the volume it is windowed to (and lighting its table)
+            apply_auto_window(ctx);
+            if (g_lit) ctx.set_lighting(&g_light);
+        }
         self->pipeline = RaycastPipeline{VK_MODE_NAIVE_TRILINEAR, g_dt, 0};
         return self;
     }
@@ -195,10 +239,11 @@ static int run_slice(const SliceArgs &a, uint32_t w, uint32_t h, const std::stri
     try {
         HdrBackBuffer bb; bb.width = w; bb.height = h; bb.format = VK_OUT_RGBA32F;
         Context ctx(w, h, nullptr, 0, bb);
-        if (!g_tf.empty()) ctx.set_transfer_function(g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi);
+        if (!g_tf.empty() && !g_auto_window) ctx.set_transfer_function(g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi);
         if (g_clip_on) ctx.set_clip_box(&g_clip);
         if (!g_raw.empty()) VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt);
         else VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, g_dims[0], g_dims[1], g_dims[2]);
+        if (g_auto_window) apply_auto_window(ctx);
         const vk_slice s = make_slice(a, w, h);
         ctx.render_slice(s, true);
         const std::vector<float> val = ctx.read_slice_values();
@@ -248,6 +293,9 @@ int main(int argc, char **argv) {
     uint32_t pick_x = 0, pick_y = 0;
     SliceArgs sl;
     bool slab = false;
+    bool hist = false;
+    uint32_t hist_bins = 256;
+    float hist_lo = 0.0f, hist_hi = 1.0f;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -316,16 +364,35 @@ int main(int argc, char **argv) {
             sl.samples = (uint32_t)n;
             sl.reduce = red == "max" ? VK_SLAB_MAX : (red == "min" ? VK_SLAB_MIN : VK_SLAB_MEAN);
         }
+        else if (a == "--histogram") {
+            hist = true;
+            const int n = std::atoi(next());
+            if (n < 1 || n > VK_HIST_MAX_BINS) { std::fprintf(stderr, "bonsai: --histogram BINS [LO HI]: BINS lies in 1 .. %d\n", VK_HIST_MAX_BINS); return 2; }
+            hist_bins = (uint32_t)n;
+            if (i + 2 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0 && std::string(argv[i + 2]).rfind("--", 0) != 0) { hist_lo = (float)std::atof(next()); hist_hi = (float)std::atof(next()); }
+            else if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) { std::fprintf(stderr, "bonsai: --histogram BINS [LO HI]: LO needs HI\n"); return 2; }
+            if (!std::isfinite(hist_lo) || !std::isfinite(hist_hi) || !(hist_hi > hist_lo)) { std::fprintf(stderr, "bonsai: --histogram BINS [LO HI]: LO and HI must be finite, LO < HI\n"); return 2; }
+        }
+        else if (a == "--auto-window") {
+            g_auto_window = true;
+            g_auto_lo = std::atof(next()); g_auto_hi = std::atof(next());
+            if (!(0.0 <= g_auto_lo && g_auto_lo < g_auto_hi && g_auto_hi <= 1.0)) { std::fprintf(stderr, "bonsai: --auto-window P_LO P_HI: needs 0 <= P_LO < P_HI <= 1\n"); return 2; }
+        }
         else if (a == "--camera-blobs") { std::string in = next(); return dump_camera_blobs(in, next()); }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
     if (g_iso_on && g_mip) { std::fprintf(stderr, "bonsai: --iso and --mip exclude each other (an isosurface ignores the projection)\n"); return 2; }
     if (g_shadows_on && !(g_iso_on && g_lit && !g_light.headlight)) { std::fprintf(stderr, "bonsai: --shadows needs --iso and --light (shadows are cast along a light direction, under an isosurface)\n"); return 2; }
-    if (g_clip_on && g_tf.empty() && !g_mip && !g_iso_on && !sl.on) { std::fprintf(stderr, "bonsai: --clip needs --tf, --mip or --iso (the built-in march has no clip kernels)\n"); return 2; }
+    if (g_clip_on && g_tf.empty() && !g_mip && !g_iso_on && !sl.on && !hist) { std::fprintf(stderr, "bonsai: --clip needs --tf, --mip or --iso (the built-in march has no clip kernels)\n"); return 2; }
     if ((pick || !depth_ppm.empty()) && !g_iso_on) { std::fprintf(stderr, "bonsai: --pick and --depth-ppm need --iso (the geometry pass is the isosurface's)\n"); return 2; }
     if (slab && !sl.on) { std::fprintf(stderr, "bonsai: --slab needs --slice or --slice-plane (a slab is a thick slice)\n"); return 2; }
     if (sl.on && gpus > 0) { std::fprintf(stderr, "bonsai: --slice and --slice-plane render on one GPU (groups have no slice output)\n"); return 2; }
     if (sl.on && (pick || !depth_ppm.empty() || !dump_rgba.empty() || !dump_steps.empty())) { std::fprintf(stderr, "bonsai: --slice and --slice-plane replace the raycast: no --pick, --depth-ppm, --dump-rgba or --dump-steps\n"); return 2; }
+    if (hist && (sl.on || gpus > 0 || g_auto_window)) { std::fprintf(stderr, "bonsai: --histogram replaces the render: no --slice, --slice-plane, --gpus or --auto-window\n"); return 2; }
+    if (g_auto_window && g_tf.empty() && !g_mip && !sl.on) { std::fprintf(stderr, "bonsai: --auto-window needs a mode that has a window: --tf, --mip, --slice or --slice-plane\n"); return 2; }
+    if (g_auto_window && g_iso_on) { std::fprintf(stderr, "bonsai: --auto-window sets a table's domain: an isosurface (--iso) has none\n"); return 2; }
+    if (g_auto_window && gpus > 0) { std::fprintf(stderr, "bonsai: --auto-window runs on one GPU\n"); return 2; }
+    if (hist) return run_histogram(hist_bins, hist_lo, hist_hi);
     if (sl.on) return run_slice(sl, w, h, ppm);
     if (gpus > 0) return run_group(gpus, frames, batch, w, h, peer_direct);
     try {

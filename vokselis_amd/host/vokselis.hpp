@@ -175,6 +175,20 @@ static_assert(sizeof(vk_clip_box) == 24, "vk_clip_box is 24 bytes (vk_set_clip_b
 static_assert(sizeof(vk_shadows) == 8, "vk_shadows is 8 bytes (vk_set_shadows)");
 static_assert(sizeof(vk_hit) == 36, "vk_hit is 36 bytes (vk_pick)");
 static_assert(sizeof(vk_slice) == 56 && sizeof(vk_slice_sample) == 20, "vk_slice is 56 bytes, vk_slice_sample 20 (vk_render_slice, vk_slice_probe)");
+static_assert(sizeof(vk_histogram) == 16 && sizeof(vk_voxel_box) == 24 && sizeof(vk_volume_stats) == 72, "vk_histogram is 16 bytes, vk_voxel_box 24, vk_volume_stats 72 (vk_volume_histogram)");
+
+// What Context::volume_histogram returns: the counts over the domain and the region's statistics (on the kernel's scale; stats.scale divides it out).
+struct Histogram {
+    std::vector<uint64_t> counts;
+    float lo = 0.0f, hi = 1.0f;
+    vk_volume_stats stats{};
+    // The window that holds the percentiles p_lo .. p_hi of the counted texels (vk_histogram_window): a domain for set_transfer_function.
+    std::pair<float, float> window(double p_lo, double p_hi) const {
+        float a = 0.0f, b = 0.0f;
+        check(nullptr, vk_histogram_window(counts.data(), (uint32_t)counts.size(), lo, hi, p_lo, p_hi, &a, &b));
+        return {a, b};
+    }
+};
 
 // src/context/hdr_backbuffer.rs:10-11
 struct HdrBackBuffer {
@@ -295,6 +309,16 @@ class Context {
     void *slice_values_device_ptr() const { void *p = nullptr; check(ctx_, vk_slice_values_info(ctx_, nullptr, nullptr, &p)); return p; }  // (does not synchronise)
     // The value under pixel (x, y) of the plane (vk_slice_probe; blocks): inside == 0 where the position lies outside the box.
     vk_slice_sample slice_probe(const vk_slice &s, uint32_t x, uint32_t y) { vk_slice_sample o{}; check(ctx_, vk_slice_probe(ctx_, &s, x, y, &o)); return o; }
+    // The histogram of the stored texels over [lo, hi] (sample values) and the statistics of the voxel box (vk_volume_histogram; blocks; changes no
+    // state): box == nullptr is the whole volume, or with clip == true the voxels whose centres lie in the clip box in force.
+    Histogram volume_histogram(uint32_t bins = 256, float lo = 0.0f, float hi = 1.0f, const vk_voxel_box *box = nullptr, bool clip = false) {
+        Histogram h;
+        h.lo = lo; h.hi = hi;
+        h.counts.assign(bins <= (uint32_t)VK_HIST_MAX_BINS ? bins : 0u, 0u);
+        const vk_histogram req = {lo, hi, bins, clip ? (uint32_t)VK_HIST_CLIP_BOX : 0u};
+        check(ctx_, vk_volume_histogram(ctx_, &req, box, h.counts.data(), &h.stats));
+        return h;
+    }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
     void frames_in_flight(uint32_t k) { check(ctx_, vk_ctx_frames_in_flight(ctx_, k)); }
