@@ -738,6 +738,14 @@ int vk_speckle_census(vk_ctx *ctx, uint64_t out[2]);
  * current order, the only ones a launch marches -- in front; anything else is VK_ERR_INVALID.  It stays until the partition's
  * key (camera, volume, tile size, rectangle) changes.  The frame does not depend on the order. */
 int vk_debug_set_tile_order(vk_ctx *ctx, const uint32_t *order, uint32_t n);
+/* Debug: the skip maps of the current volume as the marches read them; read-only.  grid: the stored grid in cells per axis (4 per
+ * brick, padding bricks included); n_maps: 0 for a layout without maps (LINEAR, BRICKED, QUADS, STAGED), 1 for the isotropic map, 8 for
+ * the one-sided octant maps (octant o = ux | uy << 1 | uz << 2, bit set: the rays go up that axis); bytes: n_maps * cells.  dst == NULL
+ * only queries the three; otherwise the frame slots are drained and the maps are copied out as stored: one byte per cell, cell
+ * (x, y, z) of brick (x >> 2, y >> 2, z >> 2) at 64 * ((bz * nby + by) * nbx + bx) + (z & 3) << 4 | (y & 3) << 2 | (x & 3), octant o at
+ * o * cells.  A PACKED RGBA16F_PAIR volume reports one map over its record grid, each byte taken out of its record.  NULL grid,
+ * n_maps or bytes, dst_bytes < bytes, or no volume uploaded: VK_ERR_INVALID.  Blocking. */
+int vk_debug_read_skip_maps(vk_ctx *ctx, uint32_t grid[3], uint32_t *n_maps, size_t *bytes, void *dst, size_t dst_bytes);
 /* Debug: per-8x8-block {first start, last end, HW_ID | XCC_ID << 32, work} of the next VK_RENDER_COUNT NAIVE
  * launch (s_memrealtime stamps).  enable != 0 arms it; out != NULL copies n_blocks quadruples back. */
 int vk_debug_wave_trace(vk_ctx *ctx, int enable, uint64_t *out, size_t n_blocks);

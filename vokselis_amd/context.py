@@ -506,6 +506,18 @@ class Context:
         """Debug / tuning knob of the library (vk_debug_set_param)."""
         N.check(self._h, N.lib().vk_debug_set_param(self._h, name.encode(), float(value)))
 
+    def read_skip_maps(self):
+        """Debug (vk_debug_read_skip_maps): (grid, maps) of the current volume -- grid = (cells in x, y, z), maps uint8 [n_maps, cells] as
+        stored (bricked order); n_maps is 0 for a layout without maps, 1 for the isotropic map, 8 for the octant maps.  Blocks."""
+        grid, n_maps, nbytes = (C.c_uint32 * 3)(), C.c_uint32(), C.c_size_t()
+        N.check(self._h, N.lib().vk_debug_read_skip_maps(self._h, grid, C.byref(n_maps), C.byref(nbytes), None, 0))
+        n_cells = int(grid[0]) * int(grid[1]) * int(grid[2])
+        maps = np.zeros((n_maps.value, n_cells), np.uint8)
+        assert maps.size == nbytes.value
+        if maps.size:
+            N.check(self._h, N.lib().vk_debug_read_skip_maps(self._h, grid, C.byref(n_maps), C.byref(nbytes), maps.ctypes.data, maps.size))
+        return tuple(int(g) for g in grid), maps
+
     # -- results
     def read_backbuffer(self) -> np.ndarray:
         """The backbuffer as [H, W, 4] float32 (RGBA32F) or float16 (RGBA16F)."""

@@ -204,6 +204,38 @@ int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float l
     return VK_OK;
 }
 
+// Debug: the skip maps as the marches read them (include/vokselis_hip.h).  Read-only: drains the frame slots, copies, changes nothing.
+extern "C" int vk_debug_read_skip_maps(vk_ctx *ctx, uint32_t grid[3], uint32_t *n_maps, size_t *bytes, void *dst, size_t dst_bytes) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (!grid || !n_maps || !bytes) return fail(ctx, VK_ERR_INVALID, "vk_debug_read_skip_maps: grid, n_maps and bytes must not be NULL");
+    if (ctx->format < 0) return fail(ctx, VK_ERR_INVALID, "no volume uploaded");
+    const bool cells = is_cell_layout(ctx->vol_kind), records = ctx->vol_kind == VOL_PAIRB;
+    const uint64_t n_cells = (cells || records) ? (uint64_t)ctx->nbx * ctx->nby * ctx->nbz * kBrickCells : 0;
+    const uint32_t maps = cells ? (ctx->vdesc.dist_oct_stride ? 8u : 1u) : (records ? 1u : 0u);
+    const uint64_t need = (uint64_t)maps * n_cells;
+    if (dst && dst_bytes < need) return fail(ctx, VK_ERR_INVALID, "vk_debug_read_skip_maps: the buffer holds fewer than n_maps * cells bytes");
+    grid[0] = maps ? ctx->nbx * 4u : 0u; grid[1] = maps ? ctx->nby * 4u : 0u; grid[2] = maps ? ctx->nbz * 4u : 0u;
+    *n_maps = maps;
+    *bytes = (size_t)need;
+    if (!dst || need == 0) return VK_OK;
+    int rc = frames_drain(ctx);
+    if (rc) return rc;
+    if (cells) {  // octant o at o * n_cells, as stored (dist_oct_stride == n_cells)
+        HIP_TRY(ctx, hipMemcpy(dst, ctx->dist, (size_t)need, hipMemcpyDeviceToHost));
+        return VK_OK;
+    }
+    // records: the map is the eighth half of each 16-byte record (embed_pair_dist_kernel), taken out here a piece at a time
+    const uint64_t piece = 1ull << 18;
+    std::vector<uint4> host((size_t)std::min<uint64_t>(piece, n_cells));
+    uint8_t *out = static_cast<uint8_t *>(dst);
+    for (uint64_t r0 = 0; r0 < n_cells; r0 += piece) {
+        const uint64_t n = std::min<uint64_t>(piece, n_cells - r0);
+        HIP_TRY(ctx, hipMemcpy(host.data(), static_cast<const uint4 *>(ctx->vol) + r0, (size_t)n * sizeof(uint4), hipMemcpyDeviceToHost));
+        for (uint64_t k = 0; k < n; k++) out[r0 + k] = (uint8_t)(host[(size_t)k].w >> 16);
+    }
+    return VK_OK;
+}
+
 static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, bool own_src, uint32_t nx,
                             uint32_t ny, uint32_t nz, int format, int layout) {
     // d_src is dense device memory; with own_src the LINEAR layout adopts it, every other layout frees it.
