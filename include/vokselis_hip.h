@@ -501,6 +501,53 @@ typedef struct vk_volume_stats {
 int vk_volume_histogram(vk_ctx *ctx, const vk_histogram *hist, const vk_voxel_box *box, uint64_t *counts, vk_volume_stats *stats);
 int vk_histogram_window(const uint64_t *counts, uint32_t bins, float lo, float hi, double p_lo, double p_hi, float *w_lo, float *w_hi);
 
+/* The isosurface as a triangle mesh, by marching tetrahedra: the surface the first-hit render shows, handed over.
+ * Every f32 operation below is rounded once and nothing is fused.
+ * Box.  `box` is a voxel box [x0, x1) x [y0, y1) x [z0, z1) under vk_volume_histogram's rules: it lies within the volume, may be empty,
+ * NULL is the whole volume, and VK_MESH_CLIP_BOX derives it from the clip box exactly as VK_HIST_CLIP_BOX does.  A cube is a low-corner
+ * voxel (x, y, z) with x0 <= x < x1 - 1, likewise on y and z; its 8 corners are the stored texels V(x+i, y+j, z+k) as f32 on the kernel's
+ * scale (R8 0..255, R16_UNORM 0..65535, R16F the value).  A box thinner than 2 voxels on an axis has no cubes.  The surface is open where
+ * it leaves the box (no caps).
+ * Threshold.  iso_k is formed from iso exactly as vk_set_isosurface does: iso * 255.0f, iso * 65535.0f, or iso.  A corner is inside iff
+ * v >= iso_k, the render's hit predicate.
+ * Empty cubes.  A cube with a corner that is NaN or infinite emits nothing; a cube whose corners are all inside or all outside emits
+ * nothing.
+ * Tetrahedra.  Otherwise, k = 0..5 in this order; pi_k is the k-th permutation of the axes in lexicographic order: (x,y,z), (x,z,y),
+ * (y,x,z), (y,z,x), (z,x,y), (z,y,x).  The tetrahedron has vertices v0 = (0,0,0), v1 = v0 + e[pi_k(0)], v2 = v1 + e[pi_k(1)], v3 =
+ * (1,1,1), as offsets from the low corner.  mask has bit i set iff v_i is inside; masks 0 and 15 emit nothing, otherwise the triangles
+ * of T[mask] in order, each three tetrahedron edges (a,b) with a < b; for an odd permutation (k = 1, 2, 5) the second and third vertex of
+ * every triangle are swapped.
+ *     mask  1: (01,02,03)             mask  8: (03,23,13)
+ *     mask  2: (01,13,12)             mask  9: (01,02,23) (01,23,13)
+ *     mask  3: (02,03,13) (02,13,12)  mask 10: (01,23,12) (01,03,23)
+ *     mask  4: (02,12,23)             mask 11: (02,23,12)
+ *     mask  5: (01,23,03) (01,12,23)  mask 12: (02,12,13) (02,13,03)
+ *     mask  6: (01,13,23) (01,23,02)  mask 13: (01,12,13)
+ *     mask  7: (03,13,23)             mask 14: (01,03,02)
+ * Vertex.  The vertex on edge (a,b) uses the lattice points A = low corner + v_a and B = low corner + v_b; A <= B holds componentwise
+ * whichever cube or tetrahedron the edge is seen from, which makes shared vertices bitwise equal.  With vA, vB their texels:
+ *     f     = (iso_k - vA) / (vB - vA)                                              a true divide
+ *     pos.c = (((float)A.c + 0.5f) + (B.c > A.c ? f : 0.0f)) / (float)n.c          per axis, a true divide
+ * Positions are in unit-cube coordinates with texel centres at (i + 0.5) / n: the convention of the march's filter and of vk_hit.pos.
+ * f lies in [0, 1].  A vertex that lands on a lattice point yields zero-area triangles, which are kept.
+ * Orientation.  (p1 - p0) x (p2 - p0) points from inside to outside, towards lower values: the -g / |g| of the geometry pass.
+ * Order.  Cubes in the volume's index order restricted to the box, x fastest, then y, then z; within a cube k = 0..5; within a
+ * tetrahedron the table's order.  The output is one array of n triangles x 3 vertices x 3 f32 (36 bytes per triangle), bit for bit
+ * the same on every layout, every launch shape and every run.
+ * vk_extract_isosurface is blocking; it runs on the context's current stream (inside vk_frame_begin / _end: that frame's), allocates and
+ * frees its own buffers and changes no context state: no surface, counter, slot, skip map or stored isosurface; req->iso is independent of
+ * vk_set_isosurface.  *n_triangles always receives the total.  triangles == NULL: only the count pass runs.  Otherwise the first
+ * min(n, cap_triangles) triangles are written, in order: a truncated call returns a bitwise prefix of the full one.
+ * VK_ERR_INVALID, decided before any launch, outputs untouched: a NULL req or n_triangles, a non-finite iso, an unknown flag, a box that
+ * is inverted or leaves the volume, a box together with VK_MESH_CLIP_BOX, no volume.  VK_ERR_UNSUPPORTED ("mesh: ..."): a BRICKED /
+ * QUADS / STAGED or RGBA16F_PAIR volume -- the set the histogram refuses.  VK_ERR_OOM: the output buffer cannot be allocated. */
+enum { VK_MESH_CLIP_BOX = 1 };
+typedef struct vk_mesh_request {
+    float iso;       /* the threshold in sample values, like vk_isosurface.iso */
+    uint32_t flags;  /* VK_MESH_CLIP_BOX */
+} vk_mesh_request;   /* 8 bytes */
+int vk_extract_isosurface(vk_ctx *ctx, const vk_mesh_request *req, const vk_voxel_box *box, float *triangles, uint64_t cap_triangles, uint64_t *n_triangles);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

@@ -39,7 +39,7 @@ keeping are copied to `profiles/`.  Scripts whose question is closed, and reject
 `ubench/`: %s (`valu_rate.hip`: the issue-cost table of `profiles/r03_ubench_valu_issue_rate.txt`; `semantics.hip`: `v_fract` / `v_cvt_flr`
 against the oracle's text; `exec_half.hip`: instruction cost against the number of active lanes, `profiles/r05_ubench_exec_lanes.txt`; `lds_gather.hip`:
 the staged march's window fill on its own and against its steps, `profiles/r05_c4_fill.txt`; `stream_read.hip`: a sum with 16-byte loads, the
-yardstick of `hist_quick.py`).
+yardstick of `hist_quick.py` and `mesh_quick.py`).
 """ % ("\n".join(rows), ", ".join("`%s`" % f for f in ub))
 open(os.path.join(HERE, "README.md"), "w").write(out)
 print("tools/README.md: %d tools" % len(rows))

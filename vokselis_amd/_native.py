@@ -123,6 +123,17 @@ class VkVolumeStats(C.Structure):
 assert C.sizeof(VkVolumeStats) == 72
 
 
+MESH_CLIP_BOX = 1
+
+
+class VkMeshRequest(C.Structure):
+    """vk_mesh_request (8 bytes): the request of vk_extract_isosurface -- the threshold in sample values, the flags."""
+    _fields_ = [("iso", C.c_float), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(VkMeshRequest) == 8
+
+
 def clip_box(lo, hi) -> VkClipBox:
     """A VkClipBox from two triples, held to vk_set_clip_box's rules before the library sees it: finite components (as f32) and
     0 <= lo < hi <= 1 on every axis.  Raises ValueError."""
@@ -178,6 +189,7 @@ SYMBOLS = {
     "vk_slice_probe": (C.c_int, [_vp, _vp, _u32, _u32, _vp]),  # const vk_slice *, vk_slice_sample * (VkSliceSample above)
     "vk_volume_histogram": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_uint64), _vp]),  # const vk_histogram *, const vk_voxel_box * (NULL: the volume), counts, vk_volume_stats *
     "vk_histogram_window": (C.c_int, [C.POINTER(C.c_uint64), _u32, _f32, _f32, C.c_double, C.c_double, C.POINTER(_f32), C.POINTER(_f32)]),
+    "vk_extract_isosurface": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), C.c_uint64, C.POINTER(C.c_uint64)]),  # const vk_mesh_request *, const vk_voxel_box * (NULL: the volume), triangles (NULL: count only), cap, n
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),
     "vk_set_uniform": (C.c_int, [_vp, _vp]),
     "vk_set_camera": (C.c_int, [_vp, _vp]),

@@ -487,6 +487,35 @@ class Context:
                                                      counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(stats)))
         return Histogram(counts, (req.lo, req.hi), stats)
 
+    # -- the isosurface as a triangle mesh (vk_extract_isosurface)
+    def extract_isosurface(self, iso: float, box=None, max_triangles=None) -> np.ndarray:
+        """vk_extract_isosurface: the surface `stored texel >= iso` (sample values, like set_isosurface's; independent of it) by marching
+        tetrahedra, as a float32 array (n, 3, 3) of triangles in unit-cube coordinates, normals towards lower values.  box: None -- the whole
+        volume; "clip" -- the voxels whose centres lie in the clip box in force; ((x0, y0, z0), (x1, y1, z1)).  max_triangles: at most that
+        many, the first ones in order.  A count call, then a fill call; blocks; changes no state of the context.  See V.weld, V.write_stl
+        and V.write_obj."""
+        req = N.VkMeshRequest(float(iso), 0)
+        vb = None
+        if isinstance(box, str):
+            if box != "clip":
+                raise ValueError('box: None, "clip" or ((x0, y0, z0), (x1, y1, z1))')
+            req.flags = N.MESH_CLIP_BOX
+        elif box is not None:
+            lo, hi = (tuple(int(v) for v in c) for c in box)
+            if len(lo) != 3 or len(hi) != 3 or min(lo + hi) < 0:
+                raise ValueError("box: two triples of voxel indices >= 0")
+            vb = N.VkVoxelBox(*lo, *hi)
+        if max_triangles is not None and int(max_triangles) < 0:
+            raise ValueError("max_triangles: None or >= 0")
+        bp = C.byref(vb) if vb is not None else None
+        n = C.c_uint64(0)
+        N.check(self._h, N.lib().vk_extract_isosurface(self._h, C.byref(req), bp, None, 0, C.byref(n)))
+        m = int(n.value) if max_triangles is None else min(int(n.value), int(max_triangles))
+        tris = np.zeros((m, 3, 3), np.float32)
+        if m:
+            N.check(self._h, N.lib().vk_extract_isosurface(self._h, C.byref(req), bp, tris.ctypes.data_as(C.POINTER(C.c_float)), m, C.byref(n)))
+        return tris
+
     def set_root_skip(self, k: int):
         """vk_partition_root_skip: rank 0 sits out every k-th round of the tile deal (0: never)."""
         N.check(self._h, N.lib().vk_partition_root_skip(self._h, int(k)))

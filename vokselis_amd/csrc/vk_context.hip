@@ -537,6 +537,8 @@ int vk_debug_set_param(vk_ctx *ctx, const char *name, double value) {
     else if (n == "naive_lds_pad") ctx->naive_lds_pad = (uint32_t)value;          // experiments: caps the cell kernels' waves per SIMD
     else if (n == "hist_max_blocks") ctx->hist_max_blocks = (uint32_t)value;      // vk_volume_histogram: cap of the grid (0: none)
     else if (n == "hist_flush_passes") ctx->hist_flush_passes = (uint32_t)value;  // ... passes between merges of a workgroup's counters (0: the bound of vk_hist.hpp)
+    else if (n == "mesh_chunk_cubes") ctx->mesh_chunk_cubes = (uint32_t)value;    // vk_extract_isosurface: cubes per chunk (0: the default; clamped to 64 .. 4096)
+    else if (n == "mesh_max_blocks") ctx->mesh_max_blocks = (uint32_t)value;      // ... cap of its grids (0: none)
     else if (n == "stage_copies_mask") ctx->stage_copies_mask = (uint32_t)value; // which brick copies to build (next upload)
     else return fail(ctx, VK_ERR_INVALID, "vk_debug_set_param: unknown parameter " + n);
     return VK_OK;

@@ -15,6 +15,7 @@
 //   vk_launch_geom.hip     instantiates the geometry pass of the isosurface march (vk_march_iso.hpp, vk_geom.hpp)
 //   vk_launch_slice.hip    the slice pass: a plane through the volume, thick slabs (vk_slice.hpp)
 //   vk_launch_hist.hip     vk_volume_histogram, vk_histogram_window: histogram and statistics of a voxel box (vk_hist.hpp)
+//   vk_launch_mesh.hip     vk_extract_isosurface: the isosurface as a triangle mesh, count / scan / emit (vk_mesh.hpp)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)
@@ -160,6 +161,8 @@ struct vk_ctx {
     uint32_t root_skip = 0;  // dealing: rank 0 sits out every root_skip-th round (vk_partition_root_skip)
     uint32_t hist_max_blocks = 0;    // vk_volume_histogram: cap of the grid (0: none) -- lets a small volume drive the grid-stride loop
     uint32_t hist_flush_passes = 0;  // ... and passes of that loop between merges of a workgroup's counters (0: vk_hist.hpp's bound)
+    uint32_t mesh_chunk_cubes = 0;   // vk_extract_isosurface: cubes per chunk of the scan (0: vk_mesh.hpp's 1024; 64 .. 4096) -- lets a small volume have many chunks
+    uint32_t mesh_max_blocks = 0;    // ... and cap of the count and emit grids (0: none)
 
     // present targets (next row N1/N2)
     uint32_t *rgba8 = nullptr, *bgra8 = nullptr;

@@ -35,11 +35,17 @@
 //          [--auto-window P_LO P_HI]                          before the first frame, the table's domain -- of --tf, or of the grey ramp of --mip / --slice -- becomes the
 //                                                            window that holds the percentiles P_LO .. P_HI (0 <= P_LO < P_HI <= 1) of a 4096-bin histogram over
 //                                                            [0, 1] (vk_histogram_window); needs --tf, --mip, --slice or --slice-plane
+//          [--mesh OUT.stl|OUT.obj [--mesh-iso V] [--mesh-scale SX SY SZ]]   in place of the raycast (vk_extract_isosurface): the isosurface at sample value V
+//                                                            (default: --iso's) as binary STL or welded OBJ, the unit cube scaled by SX SY SZ (default 1 1 1);
+//                                                            honours --clip (the voxels whose centres lie in the box), --raw / --raw-u16 and --dims
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
+#include <map>
 #include <string>
 
 #include "vokselis.hpp"
@@ -104,6 +110,72 @@ static int run_histogram(uint32_t bins, float lo, float hi) {
         std::printf("min %g max %g mean %g std %g (%llu finite)\n", s.min / S, s.max / S, mean / S, std::sqrt(var) / S, (unsigned long long)s.n_finite);
         for (uint32_t b = 0; b < bins; b++)
             if (h.counts[b]) std::printf("%u %llu\n", b, (unsigned long long)h.counts[b]);
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "bonsai: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
+// --mesh in place of the raycast: the triangles as binary STL (facet normals formed in double) or as OBJ welded by bit pattern
+static int run_mesh(const std::string &path, bool obj, float iso, const double scale[3]) {
+    try {
+        HdrBackBuffer bb; bb.width = 8; bb.height = 8;
+        Context ctx(8, 8, nullptr, 0, bb);
+        if (g_clip_on) ctx.set_clip_box(&g_clip);
+        if (!g_raw.empty()) VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt);
+        else VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, g_dims[0], g_dims[1], g_dims[2]);
+        const std::vector<float> tris = ctx.extract_isosurface(iso, nullptr, g_clip_on);
+        const size_t n = tris.size() / 9;
+        if (!obj && n > 0xffffffffull) throw std::runtime_error("binary STL holds at most 2^32 - 1 triangles");
+        std::ofstream f(path, std::ios::binary);
+        if (!f) throw std::runtime_error("cannot open " + path);
+        size_t n_vertices = 3 * n;
+        if (obj) {
+            std::map<std::array<uint32_t, 3>, uint32_t> seen;  // a vertex's bit pattern -> its 1-based index
+            std::vector<uint32_t> faces(3 * n);
+            char line[128];
+            for (size_t v = 0; v < 3 * n; v++) {
+                std::array<uint32_t, 3> key;
+                std::memcpy(key.data(), &tris[3 * v], 12);
+                auto it = seen.find(key);
+                if (it == seen.end()) {
+                    it = seen.emplace(key, (uint32_t)seen.size() + 1u).first;
+                    const int len = std::snprintf(line, sizeof line, "v %.9g %.9g %.9g\n", tris[3 * v] * scale[0], tris[3 * v + 1] * scale[1], tris[3 * v + 2] * scale[2]);
+                    f.write(line, len);
+                }
+                faces[v] = it->second;
+            }
+            for (size_t t = 0; t < n; t++) {
+                const int len = std::snprintf(line, sizeof line, "f %u %u %u\n", faces[3 * t], faces[3 * t + 1], faces[3 * t + 2]);
+                f.write(line, len);
+            }
+            n_vertices = seen.size();
+        } else {
+            char header[80];
+            std::memset(header, ' ', sizeof header);
+            std::memcpy(header, "vokselis_amd isosurface", 23);
+            f.write(header, 80);
+            const uint32_t n32 = (uint32_t)n;
+            f.write(reinterpret_cast<const char *>(&n32), 4);
+            for (size_t t = 0; t < n; t++) {
+                double p[3][3];
+                for (int v = 0; v < 3; v++)
+                    for (int c = 0; c < 3; c++) p[v][c] = (double)tris[9 * t + 3 * v + c] * scale[c];
+                const double a[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]}, b[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
+                double nr[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+                const double len = std::sqrt(nr[0] * nr[0] + nr[1] * nr[1] + nr[2] * nr[2]);
+                float rec[12];
+                for (int c = 0; c < 3; c++) rec[c] = len > 0.0 ? (float)(nr[c] / len) : 0.0f;
+                for (int v = 0; v < 3; v++)
+                    for (int c = 0; c < 3; c++) rec[3 + 3 * v + c] = (float)p[v][c];
+                const uint16_t attr = 0;
+                f.write(reinterpret_cast<const char *>(rec), 48);
+                f.write(reinterpret_cast<const char *>(&attr), 2);
+            }
+        }
+        if (!f) throw std::runtime_error("cannot write " + path);
+        std::printf("mesh: iso %g, %zu triangles, %zu vertices -> %s\n", iso, n, n_vertices, path.c_str());
     } catch (const std::exception &e) {
         std::fprintf(stderr, "bonsai: %s\n", e.what());
         return 1;
@@ -296,6 +368,10 @@ int main(int argc, char **argv) {
     bool hist = false;
     uint32_t hist_bins = 256;
     float hist_lo = 0.0f, hist_hi = 1.0f;
+    std::string mesh_path;
+    bool mesh_iso_on = false, mesh_obj = false;
+    float mesh_iso = 0.0f;
+    double mesh_scale[3] = {1.0, 1.0, 1.0};
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -373,6 +449,20 @@ int main(int argc, char **argv) {
             else if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) { std::fprintf(stderr, "bonsai: --histogram BINS [LO HI]: LO needs HI\n"); return 2; }
             if (!std::isfinite(hist_lo) || !std::isfinite(hist_hi) || !(hist_hi > hist_lo)) { std::fprintf(stderr, "bonsai: --histogram BINS [LO HI]: LO and HI must be finite, LO < HI\n"); return 2; }
         }
+        else if (a == "--mesh") {
+            mesh_path = next();
+            const std::string ext = mesh_path.size() >= 4 ? mesh_path.substr(mesh_path.size() - 4) : "";
+            if (ext != ".stl" && ext != ".obj") { std::fprintf(stderr, "bonsai: --mesh OUT.stl|OUT.obj: the file name ends in .stl or .obj\n"); return 2; }
+            mesh_obj = ext == ".obj";
+        }
+        else if (a == "--mesh-iso") {
+            mesh_iso_on = true; mesh_iso = (float)std::atof(next());
+            if (!std::isfinite(mesh_iso)) { std::fprintf(stderr, "bonsai: --mesh-iso V: V must be finite\n"); return 2; }
+        }
+        else if (a == "--mesh-scale") {
+            for (int k = 0; k < 3; k++) mesh_scale[k] = std::atof(next());
+            for (int k = 0; k < 3; k++) if (!(mesh_scale[k] > 0.0) || !std::isfinite(mesh_scale[k])) { std::fprintf(stderr, "bonsai: --mesh-scale SX SY SZ: finite and > 0\n"); return 2; }
+        }
         else if (a == "--auto-window") {
             g_auto_window = true;
             g_auto_lo = std::atof(next()); g_auto_hi = std::atof(next());
@@ -383,7 +473,7 @@ int main(int argc, char **argv) {
     }
     if (g_iso_on && g_mip) { std::fprintf(stderr, "bonsai: --iso and --mip exclude each other (an isosurface ignores the projection)\n"); return 2; }
     if (g_shadows_on && !(g_iso_on && g_lit && !g_light.headlight)) { std::fprintf(stderr, "bonsai: --shadows needs --iso and --light (shadows are cast along a light direction, under an isosurface)\n"); return 2; }
-    if (g_clip_on && g_tf.empty() && !g_mip && !g_iso_on && !sl.on && !hist) { std::fprintf(stderr, "bonsai: --clip needs --tf, --mip or --iso (the built-in march has no clip kernels)\n"); return 2; }
+    if (g_clip_on && g_tf.empty() && !g_mip && !g_iso_on && !sl.on && !hist && mesh_path.empty()) { std::fprintf(stderr, "bonsai: --clip needs --tf, --mip or --iso (the built-in march has no clip kernels)\n"); return 2; }
     if ((pick || !depth_ppm.empty()) && !g_iso_on) { std::fprintf(stderr, "bonsai: --pick and --depth-ppm need --iso (the geometry pass is the isosurface's)\n"); return 2; }
     if (slab && !sl.on) { std::fprintf(stderr, "bonsai: --slab needs --slice or --slice-plane (a slab is a thick slice)\n"); return 2; }
     if (sl.on && gpus > 0) { std::fprintf(stderr, "bonsai: --slice and --slice-plane render on one GPU (groups have no slice output)\n"); return 2; }
@@ -392,7 +482,12 @@ int main(int argc, char **argv) {
     if (g_auto_window && g_tf.empty() && !g_mip && !sl.on) { std::fprintf(stderr, "bonsai: --auto-window needs a mode that has a window: --tf, --mip, --slice or --slice-plane\n"); return 2; }
     if (g_auto_window && g_iso_on) { std::fprintf(stderr, "bonsai: --auto-window sets a table's domain: an isosurface (--iso) has none\n"); return 2; }
     if (g_auto_window && gpus > 0) { std::fprintf(stderr, "bonsai: --auto-window runs on one GPU\n"); return 2; }
+    if (mesh_path.empty() && (mesh_iso_on || mesh_scale[0] != 1.0 || mesh_scale[1] != 1.0 || mesh_scale[2] != 1.0)) { std::fprintf(stderr, "bonsai: --mesh-iso and --mesh-scale need --mesh\n"); return 2; }
+    if (!mesh_path.empty() && !mesh_iso_on && !g_iso_on) { std::fprintf(stderr, "bonsai: --mesh needs an isovalue: --mesh-iso V or --iso V\n"); return 2; }
+    if (!mesh_path.empty() && !mesh_iso_on && !std::isfinite(g_iso.iso)) { std::fprintf(stderr, "bonsai: --mesh: the isovalue must be finite\n"); return 2; }
+    if (!mesh_path.empty() && (sl.on || hist || gpus > 0 || g_auto_window)) { std::fprintf(stderr, "bonsai: --mesh replaces the render: no --slice, --slice-plane, --histogram, --gpus or --auto-window\n"); return 2; }
     if (hist) return run_histogram(hist_bins, hist_lo, hist_hi);
+    if (!mesh_path.empty()) return run_mesh(mesh_path, mesh_obj, mesh_iso_on ? mesh_iso : g_iso.iso, mesh_scale);
     if (sl.on) return run_slice(sl, w, h, ppm);
     if (gpus > 0) return run_group(gpus, frames, batch, w, h, peer_direct);
     try {

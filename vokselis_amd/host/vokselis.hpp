@@ -177,6 +177,8 @@ static_assert(sizeof(vk_hit) == 36, "vk_hit is 36 bytes (vk_pick)");
 static_assert(sizeof(vk_slice) == 56 && sizeof(vk_slice_sample) == 20, "vk_slice is 56 bytes, vk_slice_sample 20 (vk_render_slice, vk_slice_probe)");
 static_assert(sizeof(vk_histogram) == 16 && sizeof(vk_voxel_box) == 24 && sizeof(vk_volume_stats) == 72, "vk_histogram is 16 bytes, vk_voxel_box 24, vk_volume_stats 72 (vk_volume_histogram)");
 
+static_assert(sizeof(vk_mesh_request) == 8, "vk_mesh_request is 8 bytes (vk_extract_isosurface)");
+
 // What Context::volume_histogram returns: the counts over the domain and the region's statistics (on the kernel's scale; stats.scale divides it out).
 struct Histogram {
     std::vector<uint64_t> counts;
@@ -318,6 +320,17 @@ class Context {
         const vk_histogram req = {lo, hi, bins, clip ? (uint32_t)VK_HIST_CLIP_BOX : 0u};
         check(ctx_, vk_volume_histogram(ctx_, &req, box, h.counts.data(), &h.stats));
         return h;
+    }
+    // The isosurface `stored texel >= iso` (sample values; independent of set_isosurface) as triangles by marching tetrahedra
+    // (vk_extract_isosurface; blocks; changes no state): 9 floats per triangle, unit-cube coordinates, normals towards lower values.  box ==
+    // nullptr is the whole volume, or with clip == true the voxels whose centres lie in the clip box in force.  A count call, then a fill call.
+    std::vector<float> extract_isosurface(float iso, const vk_voxel_box *box = nullptr, bool clip = false) {
+        const vk_mesh_request req = {iso, clip ? (uint32_t)VK_MESH_CLIP_BOX : 0u};
+        uint64_t n = 0;
+        check(ctx_, vk_extract_isosurface(ctx_, &req, box, nullptr, 0, &n));
+        std::vector<float> tris((size_t)n * 9u);
+        if (n) check(ctx_, vk_extract_isosurface(ctx_, &req, box, tris.data(), n, &n));
+        return tris;
     }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
