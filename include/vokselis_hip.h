@@ -548,6 +548,52 @@ typedef struct vk_mesh_request {
 } vk_mesh_request;   /* 8 bytes */
 int vk_extract_isosurface(vk_ctx *ctx, const vk_mesh_request *req, const vk_voxel_box *box, float *triangles, uint64_t cap_triangles, uint64_t *n_triangles);
 
+/* The volume filter pass: the volume the context holds into another volume of the same dimensions and format -- a
+ * separable convolution (a Gaussian smooth, a sharpen) or a 3x3x3 median -- so that the isosurface, the mesh, the histogram and every
+ * march see denoised data without a round trip through the host.  Every f32 operation below is rounded once; fmaf is fused where
+ * written and nothing else is.
+ * t(x, y, z) is the STORED texel as f32 on the kernel's scale (R8 0..255, R16_UNORM 0..65535, R16F the value); indices are clamped to the
+ * edge per axis, c(i, n) = min(max(i, 0), n - 1).
+ * VK_FILTER_CONVOLVE.  Three axis passes in the order x, y, z over unrounded f32 intermediates, never requantised.  An axis with radius
+ * 0 is skipped entirely and its weights are not read.  For the x axis, r = radius[0], w = weights[0]:
+ *     acc = w[0] * t(c(x - r, nx), y, z)
+ *     for k = 1 .. 2 r:  acc = fmaf(w[k], t(c(x - r + k, nx), y, z), acc)
+ *     a(x, y, z) = acc
+ * the y pass runs the same loop over a with clamped y, the z pass over that result with clamped z.  (Clamping the index of an
+ * intermediate is taking the intermediate of the clamped voxel: the rule does not say whether one kernel or three run.)
+ * Store, v the final value:  R8 (uint8) rintf(fminf(fmaxf(v, 0.0f), 255.0f)), ties to even; R16_UNORM the same with 65535 (with the
+ * weight bound and radius <= VK_FILTER_MAX_RADIUS v is finite for the integer formats); R16F f32 -> f16 round to nearest even, f16
+ * denormals kept, overflow +-inf, any NaN stored as 0x7E00.  f32 denormals are kept (the library is built without flush-to-zero).  With
+ * all three radii 0 the output is the stored volume bit for bit, NaN payloads apart.
+ * VK_FILTER_MEDIAN3.  The output texel is the 14th smallest of the 27 stored texels t(c(x+i), c(y+j), c(z+k)), i, j, k in {-1, 0, 1}:
+ * integer formats by value, R16F by the IEEE totalOrder of the stored halves (key = bits ^ (bits & 0x8000 ? 0xFFFF : 0x8000) as u16).
+ * The chosen texel is stored unchanged: a selection.  radius and weights are ignored.
+ * Output.  dense_out (may be NULL): host memory of nx ny nz elements of the volume's format, x fastest; the call blocks, like
+ * vk_volume_histogram.  VK_FILTER_INSTALL: the result replaces the context's volume, re-laid out in the layout vk_volume_info reports
+ * now; census and skip maps are rebuilt under the (isosurface | projection, table) state in force; table, projection, isosurface,
+ * lighting, shadows and clip box stay in force exactly as across vk_volume_upload_device; frames in flight drain and batches are
+ * invalidated.  Without VK_FILTER_INSTALL no context state changes: no surface, counter, slot or map is touched.
+ * The call runs on the context's current stream (inside vk_frame_begin / _end: that frame's) and allocates and frees its own buffers.
+ * VK_ERR_INVALID, decided before any launch, outputs untouched: a NULL request, an unknown op or flag, a radius above
+ * VK_FILTER_MAX_RADIUS, a used weight that is not finite or beyond +-VK_FILTER_MAX_WEIGHT, neither dense_out nor VK_FILTER_INSTALL,
+ * VK_FILTER_INSTALL while a frame is being recorded, no volume.  VK_ERR_UNSUPPORTED ("filter: ..."): a BRICKED / QUADS / STAGED or
+ * RGBA16F_PAIR volume -- the set the histogram and the mesh refuse.  VK_ERR_OOM: a buffer cannot be allocated; the old volume stays.
+ * vk_filter_gaussian is host arithmetic and needs no context: g[k] = exp(-(k - r)^2 / (2 sigma^2)) in double, each divided by their
+ * double sum (added in the order of k) and rounded once to f32.  VK_ERR_INVALID: sigma not finite or <= 0, radius outside
+ * 1 .. VK_FILTER_MAX_RADIUS, NULL weights (its message is read with vk_last_error(NULL)). */
+#define VK_FILTER_MAX_RADIUS 6
+#define VK_FILTER_MAX_WEIGHT 1024.0f
+enum { VK_FILTER_CONVOLVE = 0, VK_FILTER_MEDIAN3 = 1 };
+enum { VK_FILTER_INSTALL = 1 };
+struct vk_volume_filter {  /* no typedef: the function below bears the same name, so the type is always `struct vk_volume_filter` */
+    int32_t  op;                                       /* VK_FILTER_CONVOLVE / _MEDIAN3 */
+    uint32_t flags;                                    /* VK_FILTER_INSTALL */
+    uint32_t radius[3];                                /* CONVOLVE: taps 2 r + 1 per axis (x, y, z); 0: the axis is skipped */
+    float    weights[3][2 * VK_FILTER_MAX_RADIUS + 1]; /* CONVOLVE: w[axis][0 .. 2 r]; entries beyond 2 r are ignored */
+};  /* 176 bytes */
+int vk_volume_filter(vk_ctx *ctx, const struct vk_volume_filter *f, void *dense_out);
+int vk_filter_gaussian(double sigma_voxels, uint32_t radius, float *weights /* 2 radius + 1 */);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

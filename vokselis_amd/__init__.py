@@ -9,6 +9,7 @@ Only the raycast hot path and the host surface that drives it live here (SURVEY.
   slices     Slice: planes for the slice pass (axial / coronal / sagittal / oblique, thick slabs)
   histogram  Histogram: the result of Context.volume_histogram (counts, statistics, percentile window)
   mesh       weld, write_stl, write_obj: the triangles of Context.extract_isosurface as a welded mesh, binary STL, OBJ
+  filter     gaussian_weights, filter_request: the weights and the request of Context.filter_volume / smooth_volume / median_volume
   dist       tile-parallel multi-GPU frame (one process per GPU, RCCL gather over xGMI)
 """
 from . import _native as native
@@ -17,11 +18,13 @@ from ._native import (FMT_R8_UNORM, FMT_R16_FLOAT, FMT_RGBA16F_PAIR, FMT_R16_UNO
                       GEN_BONSAI_STANDIN, GEN_FOG, GEN_FOG_DENSE_CORE, MODE_COMPUTE_NEAREST, MODE_NAIVE_TRILINEAR, MODE_PROCEDURAL, OUT_RGBA16F, OUT_RGBA32F, RENDER_COUNT,
                       RENDER_NO_SKIP, RENDER_PROBE_ALWAYS, RENDER_FAST_WALK, RENDER_PRESENT, RENDER_PRESENT_BGRA, RENDER_PRESENT_ONLY, RENDER_DEVICE_SINE, WIRE_RGB, WIRE_RGBA, TF_MAX_ENTRIES, PROJ_COMPOSITE, PROJ_MAX, ISO_MAX_REFINE, VkLighting, VkIsosurface, VkClipBox, VkHit, VokselisError,
                       SLAB_MAX, SLAB_MIN, SLAB_MEAN, SLICE_VALUES, SLICE_MAX_SAMPLES, VkSlice, VkSliceSample,
-                      HIST_MAX_BINS, HIST_CLIP_BOX, VkHistogram, VkVoxelBox, VkVolumeStats, MESH_CLIP_BOX, VkMeshRequest)
+                      HIST_MAX_BINS, HIST_CLIP_BOX, VkHistogram, VkVoxelBox, VkVolumeStats, MESH_CLIP_BOX, VkMeshRequest,
+                      FILTER_MAX_RADIUS, FILTER_MAX_WEIGHT, FILTER_CONVOLVE, FILTER_MEDIAN3, FILTER_INSTALL, VkVolumeFilter)
 from .camera import Camera
 from .slices import Slice
 from .histogram import Histogram
 from .mesh import weld, write_obj, write_stl
+from .filter import gaussian_weights
 from .context import (Context, Demo, FrameCounter, HdrBackBuffer, Hit, ImageDimentions, RaycastPipeline, Uniform,
                       VolumeTexture, dispatch_optimal, partition_slots, render_batch, run_headless, transfer_table, untile_batch)
 
@@ -34,4 +37,5 @@ __all__ = [
     "SLAB_MAX", "SLAB_MIN", "SLAB_MEAN", "SLICE_VALUES", "SLICE_MAX_SAMPLES", "VkSlice", "VkSliceSample", "Slice",
     "HIST_MAX_BINS", "HIST_CLIP_BOX", "VkHistogram", "VkVoxelBox", "VkVolumeStats", "Histogram",
     "MESH_CLIP_BOX", "VkMeshRequest", "weld", "write_stl", "write_obj",
+    "FILTER_MAX_RADIUS", "FILTER_MAX_WEIGHT", "FILTER_CONVOLVE", "FILTER_MEDIAN3", "FILTER_INSTALL", "VkVolumeFilter", "gaussian_weights",
 ]

@@ -134,6 +134,21 @@ class VkMeshRequest(C.Structure):
 assert C.sizeof(VkMeshRequest) == 8
 
 
+FILTER_MAX_RADIUS = 6
+FILTER_MAX_WEIGHT = 1024.0
+FILTER_CONVOLVE, FILTER_MEDIAN3 = 0, 1
+FILTER_INSTALL = 1
+
+
+class VkVolumeFilter(C.Structure):
+    """struct vk_volume_filter (176 bytes): the request of vk_volume_filter -- the op, the flags, the radius per axis (x, y, z) and the
+    2 r + 1 weights of each axis."""
+    _fields_ = [("op", C.c_int32), ("flags", C.c_uint32), ("radius", C.c_uint32 * 3), ("weights", (C.c_float * (2 * FILTER_MAX_RADIUS + 1)) * 3)]
+
+
+assert C.sizeof(VkVolumeFilter) == 176
+
+
 def clip_box(lo, hi) -> VkClipBox:
     """A VkClipBox from two triples, held to vk_set_clip_box's rules before the library sees it: finite components (as f32) and
     0 <= lo < hi <= 1 on every axis.  Raises ValueError."""
@@ -190,6 +205,8 @@ SYMBOLS = {
     "vk_volume_histogram": (C.c_int, [_vp, _vp, _vp, C.POINTER(C.c_uint64), _vp]),  # const vk_histogram *, const vk_voxel_box * (NULL: the volume), counts, vk_volume_stats *
     "vk_histogram_window": (C.c_int, [C.POINTER(C.c_uint64), _u32, _f32, _f32, C.c_double, C.c_double, C.POINTER(_f32), C.POINTER(_f32)]),
     "vk_extract_isosurface": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), C.c_uint64, C.POINTER(C.c_uint64)]),  # const vk_mesh_request *, const vk_voxel_box * (NULL: the volume), triangles (NULL: count only), cap, n
+    "vk_volume_filter": (C.c_int, [_vp, _vp, _vp]),  # const struct vk_volume_filter * (VkVolumeFilter above), dense_out (NULL: install only)
+    "vk_filter_gaussian": (C.c_int, [C.c_double, _u32, C.POINTER(_f32)]),
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),
     "vk_set_uniform": (C.c_int, [_vp, _vp]),
     "vk_set_camera": (C.c_int, [_vp, _vp]),

@@ -516,6 +516,40 @@ class Context:
             N.check(self._h, N.lib().vk_extract_isosurface(self._h, C.byref(req), bp, tris.ctypes.data_as(C.POINTER(C.c_float)), m, C.byref(n)))
         return tris
 
+    # -- the volume filter pass (vk_volume_filter: separable convolution, 3x3x3 median)
+    def filter_volume(self, weights=None, op: str = "convolve", install: bool = True, out: bool = False):
+        """vk_volume_filter: the stored volume through a separable convolution -- weights=(wx, wy, wz), each None (the axis is skipped) or
+        2 r + 1 weights, r <= FILTER_MAX_RADIUS -- or, op="median3", the 3x3x3 median, into a volume of the same dimensions and format.
+        install: the result replaces the context's volume in its layout, under the table / projection / isosurface in force (outside
+        frame_begin / frame_end).  out: also return it as a dense array [nz, ny, nx] (uint8; uint16 for R16_UNORM; float16).  Blocks when
+        out; needs install or out."""
+        from .filter import filter_request
+
+        req = filter_request(weights, op, install)
+        dense = None
+        if out:
+            dims, fmt = (C.c_uint32 * 3)(), C.c_int()
+            N.check(self._h, N.lib().vk_volume_info(self._h, dims, C.byref(fmt), None, None))
+            dtype = {N.FMT_R8_UNORM: np.uint8, N.FMT_R16_UNORM: np.uint16, N.FMT_R16_FLOAT: np.float16}.get(fmt.value)
+            # (RGBA16F_PAIR: the library refuses before it writes)
+            dense = np.zeros((dims[2], dims[1], dims[0]) if dtype is not None else (1, 1, 1), dtype or np.uint8)
+        N.check(self._h, N.lib().vk_volume_filter(self._h, C.byref(req), dense.ctypes.data if dense is not None else None))
+        return dense
+
+    def smooth_volume(self, sigma, radius=None, install: bool = True, out: bool = False):
+        """filter_volume with Gaussian weights (V.gaussian_weights) of `sigma` voxels: one number, or (sx, sy, sz) with None or 0 for an
+        axis to skip.  radius: None -- min(6, ceil(3 sigma)) per axis."""
+        from .filter import gaussian_weights
+
+        sig = tuple(sigma) if isinstance(sigma, (tuple, list, np.ndarray)) else (sigma, sigma, sigma)
+        if len(sig) != 3:
+            raise ValueError("sigma: one number or (sx, sy, sz)")
+        return self.filter_volume(tuple(None if s is None or float(s) == 0.0 else gaussian_weights(s, radius) for s in sig), "convolve", install, out)
+
+    def median_volume(self, install: bool = True, out: bool = False):
+        """filter_volume(op="median3"): every texel becomes the median of its 3x3x3 neighbourhood -- lone speckles vanish, edges stay."""
+        return self.filter_volume(None, "median3", install, out)
+
     def set_root_skip(self, k: int):
         """vk_partition_root_skip: rank 0 sits out every k-th round of the tile deal (0: never)."""
         N.check(self._h, N.lib().vk_partition_root_skip(self._h, int(k)))

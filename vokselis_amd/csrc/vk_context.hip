@@ -539,6 +539,8 @@ int vk_debug_set_param(vk_ctx *ctx, const char *name, double value) {
     else if (n == "hist_flush_passes") ctx->hist_flush_passes = (uint32_t)value;  // ... passes between merges of a workgroup's counters (0: the bound of vk_hist.hpp)
     else if (n == "mesh_chunk_cubes") ctx->mesh_chunk_cubes = (uint32_t)value;    // vk_extract_isosurface: cubes per chunk (0: the default; clamped to 64 .. 4096)
     else if (n == "mesh_max_blocks") ctx->mesh_max_blocks = (uint32_t)value;      // ... cap of its grids (0: none)
+    else if (n == "filter_max_blocks") ctx->filter_max_blocks = (uint32_t)value;  // vk_volume_filter: cap of the grid (0: none)
+    else if (n == "filter_timing") ctx->filter_timing = (uint32_t)value;          // ... 1: the call times its kernel alone (vk_timer_elapsed_ms)
     else if (n == "stage_copies_mask") ctx->stage_copies_mask = (uint32_t)value; // which brick copies to build (next upload)
     else return fail(ctx, VK_ERR_INVALID, "vk_debug_set_param: unknown parameter " + n);
     return VK_OK;

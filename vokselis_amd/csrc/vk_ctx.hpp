@@ -16,6 +16,7 @@
 //   vk_launch_slice.hip    the slice pass: a plane through the volume, thick slabs (vk_slice.hpp)
 //   vk_launch_hist.hip     vk_volume_histogram, vk_histogram_window: histogram and statistics of a voxel box (vk_hist.hpp)
 //   vk_launch_mesh.hip     vk_extract_isosurface: the isosurface as a triangle mesh, count / scan / emit (vk_mesh.hpp)
+//   vk_launch_filter.hip   vk_volume_filter, vk_filter_gaussian: separable convolution and 3x3x3 median of the volume (vk_filter.hpp)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)
@@ -163,6 +164,8 @@ struct vk_ctx {
     uint32_t hist_flush_passes = 0;  // ... and passes of that loop between merges of a workgroup's counters (0: vk_hist.hpp's bound)
     uint32_t mesh_chunk_cubes = 0;   // vk_extract_isosurface: cubes per chunk of the scan (0: vk_mesh.hpp's 1024; 64 .. 4096) -- lets a small volume have many chunks
     uint32_t mesh_max_blocks = 0;    // ... and cap of the count and emit grids (0: none)
+    uint32_t filter_max_blocks = 0;  // vk_volume_filter: cap of the grid (0: none) -- lets a small volume drive the grid-stride loop over tiles
+    uint32_t filter_timing = 0;      // ... 1 (measurements): the call brackets its kernel with the timer's events, vk_timer_elapsed_ms then reads the kernel alone
 
     // present targets (next row N1/N2)
     uint32_t *rgba8 = nullptr, *bgra8 = nullptr;
@@ -233,6 +236,7 @@ inline size_t wire_px_bytes(int fmt, int wire) { return wire == VK_WIRE_RGB ? px
 int rebuild_skip_maps(vk_ctx *ctx, const uint32_t *d_prefix, uint32_t n, float lo, float hi, int projection, const float *iso = nullptr);  // vk_volume.hip: the current volume's maps under a table (nullptr: built-in) and a projection, or under an isosurface (iso: its threshold in sample values; nullptr: none)
 int frames_drain(vk_ctx *ctx);   // vk_context.hip: wait for the work of every frame slot (one stream when fif_k == 1)
 void free_volume(vk_ctx *ctx);   // vk_volume.hip
+int install_dense(vk_ctx *ctx, void *d_dense, uint32_t nx, uint32_t ny, uint32_t nz, int format, int layout);  // vk_volume.hip: a dense device array of the context's own becomes its volume (adopted or freed, also on failure), under the state in force
 void comm_release(vk_ctx *ctx);  // vk_comm.hip
 
 // vk_order.hip: screen-space geometry of a camera, the tile order and its device ring

@@ -465,6 +465,11 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
     return commit_volume(ctx, nb);
 }
 
+// vk_volume_filter's VK_FILTER_INSTALL (vk_launch_filter.hip): the filtered dense array, which the build adopts or frees
+int install_dense(vk_ctx *ctx, void *d_dense, uint32_t nx, uint32_t ny, uint32_t nz, int format, int layout) {
+    return build_from_dense(ctx, d_dense, nullptr, true, nx, ny, nz, format, layout);
+}
+
 static int check_volume_args(vk_ctx *ctx, const void *p, const void *p2, uint32_t nx, uint32_t ny, uint32_t nz, int format,
                              int layout) {
     if (!ctx) return VK_ERR_INVALID;

@@ -38,6 +38,10 @@
 //          [--mesh OUT.stl|OUT.obj [--mesh-iso V] [--mesh-scale SX SY SZ]]   in place of the raycast (vk_extract_isosurface): the isosurface at sample value V
 //                                                            (default: --iso's) as binary STL or welded OBJ, the unit cube scaled by SX SY SZ (default 1 1 1);
 //                                                            honours --clip (the voxels whose centres lie in the box), --raw / --raw-u16 and --dims
+//          [--median] [--smooth SX SY SZ] [--save-raw PATH]    the volume filter pass (vk_volume_filter), applied once the volume is loaded and before anything else,
+//                                                            so --iso, --mesh, --histogram and --auto-window see the filtered data: first the 3x3x3 median,
+//                                                            then a Gaussian of SX SY SZ voxels (0: the axis is skipped); --save-raw writes the filtered dense
+//                                                            volume, x fastest, in the volume's format (needs --median or --smooth; one GPU)
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -71,6 +75,31 @@ static vk_lighting g_light = {{0.0f, 0.0f, 0.0f}, 0, 0.3f, 0.7f, 0.2f, 32.0f};
 static bool g_auto_window = false;  // --auto-window: the table's domain from the volume's percentiles
 static double g_auto_lo = 0.0, g_auto_hi = 1.0;
 
+static bool g_median = false;      // --median: the 3x3x3 median of the loaded volume
+static bool g_smooth = false;      // --smooth: then a Gaussian of g_sigma voxels per axis
+static double g_sigma[3] = {0.0, 0.0, 0.0};
+static std::string g_save_raw;     // --save-raw: the filtered dense volume
+
+// --median, then --smooth, once the volume is there and before anything reads it; the last of them also fills --save-raw's file
+static void apply_filters(Context &ctx) {
+    if (!g_median && !g_smooth) return;
+    std::vector<unsigned char> dense;
+    if (!g_save_raw.empty()) {
+        uint32_t dims[3] = {0, 0, 0};
+        int fmt = 0;
+        check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
+        dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    }
+    if (g_median) ctx.median_volume(true, g_smooth || dense.empty() ? nullptr : dense.data());
+    if (g_smooth) ctx.smooth_volume(g_sigma[0], g_sigma[1], g_sigma[2], true, dense.empty() ? nullptr : dense.data());
+    std::printf("filter:%s%s\n", g_median ? " median 3x3x3" : "", g_smooth ? (" gaussian sigma " + std::to_string(g_sigma[0]) + " " + std::to_string(g_sigma[1]) + " " + std::to_string(g_sigma[2])).c_str() : "");
+    if (!dense.empty()) {
+        std::ofstream f(g_save_raw, std::ios::binary);
+        if (!f || !f.write(reinterpret_cast<const char *>(dense.data()), (std::streamsize)dense.size())) throw std::runtime_error("cannot write " + g_save_raw);
+        std::printf("filtered volume: %zu bytes -> %s\n", dense.size(), g_save_raw.c_str());
+    }
+}
+
 // --tf PATH: the whole file as little-endian f32 RGBA rows (the library checks n, finiteness and alpha)
 static std::vector<float> read_tf(const std::string &path) {
     std::ifstream f(path, std::ios::binary | std::ios::ate);
@@ -102,6 +131,7 @@ static int run_histogram(uint32_t bins, float lo, float hi) {
         if (g_clip_on) ctx.set_clip_box(&g_clip);
         if (!g_raw.empty()) VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt);
         else VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, g_dims[0], g_dims[1], g_dims[2]);
+        apply_filters(ctx);
         const Histogram h = ctx.volume_histogram(bins, lo, hi, nullptr, g_clip_on);
         const vk_volume_stats &s = h.stats;
         const double S = s.scale, n = (double)s.n_finite, mean = n > 0 ? s.sum / n : NAN, var = n > 0 ? std::max(s.sum_sq / n - mean * mean, 0.0) : NAN;
@@ -125,6 +155,7 @@ static int run_mesh(const std::string &path, bool obj, float iso, const double s
         if (g_clip_on) ctx.set_clip_box(&g_clip);
         if (!g_raw.empty()) VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt);
         else VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, g_dims[0], g_dims[1], g_dims[2]);
+        apply_filters(ctx);
         const std::vector<float> tris = ctx.extract_isosurface(iso, nullptr, g_clip_on);
         const size_t n = tris.size() / 9;
         if (!obj && n > 0xffffffffull) throw std::runtime_error("binary STL holds at most 2^32 - 1 triangles");
@@ -196,6 +227,7 @@ struct Bonsai : Demo {
         if (g_clip_on) ctx.set_clip_box(&g_clip);
         if (!g_raw.empty()) self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt));
         else self->volume_texture = std::make_unique<VolumeTexture>(VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, 256, 256, 256));
+        apply_filters(ctx);
         if (g_auto_window) {  // the table follows the volume it is windowed to (and lighting its table)
             apply_auto_window(ctx);
             if (g_lit) ctx.set_lighting(&g_light);
@@ -315,6 +347,7 @@ static int run_slice(const SliceArgs &a, uint32_t w, uint32_t h, const std::stri
         if (g_clip_on) ctx.set_clip_box(&g_clip);
         if (!g_raw.empty()) VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt);
         else VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, g_dims[0], g_dims[1], g_dims[2]);
+        apply_filters(ctx);
         if (g_auto_window) apply_auto_window(ctx);
         const vk_slice s = make_slice(a, w, h);
         ctx.render_slice(s, true);
@@ -468,6 +501,14 @@ int main(int argc, char **argv) {
             g_auto_lo = std::atof(next()); g_auto_hi = std::atof(next());
             if (!(0.0 <= g_auto_lo && g_auto_lo < g_auto_hi && g_auto_hi <= 1.0)) { std::fprintf(stderr, "bonsai: --auto-window P_LO P_HI: needs 0 <= P_LO < P_HI <= 1\n"); return 2; }
         }
+        else if (a == "--median") g_median = true;
+        else if (a == "--smooth") {
+            g_smooth = true;
+            for (int k = 0; k < 3; k++) g_sigma[k] = std::atof(next());
+            for (int k = 0; k < 3; k++) if (!(g_sigma[k] >= 0.0) || !std::isfinite(g_sigma[k])) { std::fprintf(stderr, "bonsai: --smooth SX SY SZ: finite and >= 0 (0: the axis is skipped)\n"); return 2; }
+            if (g_sigma[0] == 0.0 && g_sigma[1] == 0.0 && g_sigma[2] == 0.0) { std::fprintf(stderr, "bonsai: --smooth SX SY SZ: at least one sigma above 0\n"); return 2; }
+        }
+        else if (a == "--save-raw") g_save_raw = next();
         else if (a == "--camera-blobs") { std::string in = next(); return dump_camera_blobs(in, next()); }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -486,6 +527,8 @@ int main(int argc, char **argv) {
     if (!mesh_path.empty() && !mesh_iso_on && !g_iso_on) { std::fprintf(stderr, "bonsai: --mesh needs an isovalue: --mesh-iso V or --iso V\n"); return 2; }
     if (!mesh_path.empty() && !mesh_iso_on && !std::isfinite(g_iso.iso)) { std::fprintf(stderr, "bonsai: --mesh: the isovalue must be finite\n"); return 2; }
     if (!mesh_path.empty() && (sl.on || hist || gpus > 0 || g_auto_window)) { std::fprintf(stderr, "bonsai: --mesh replaces the render: no --slice, --slice-plane, --histogram, --gpus or --auto-window\n"); return 2; }
+    if (!g_save_raw.empty() && !g_median && !g_smooth) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
+    if ((g_median || g_smooth) && gpus > 0) { std::fprintf(stderr, "bonsai: --median and --smooth run on one GPU\n"); return 2; }
     if (hist) return run_histogram(hist_bins, hist_lo, hist_hi);
     if (!mesh_path.empty()) return run_mesh(mesh_path, mesh_obj, mesh_iso_on ? mesh_iso : g_iso.iso, mesh_scale);
     if (sl.on) return run_slice(sl, w, h, ppm);

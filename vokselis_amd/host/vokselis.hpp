@@ -5,6 +5,7 @@
 // Window, input, hot reload and the present pass are out of scope.
 #pragma once
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -178,6 +179,15 @@ static_assert(sizeof(vk_slice) == 56 && sizeof(vk_slice_sample) == 20, "vk_slice
 static_assert(sizeof(vk_histogram) == 16 && sizeof(vk_voxel_box) == 24 && sizeof(vk_volume_stats) == 72, "vk_histogram is 16 bytes, vk_voxel_box 24, vk_volume_stats 72 (vk_volume_histogram)");
 
 static_assert(sizeof(vk_mesh_request) == 8, "vk_mesh_request is 8 bytes (vk_extract_isosurface)");
+static_assert(sizeof(struct vk_volume_filter) == 176, "struct vk_volume_filter is 176 bytes (vk_volume_filter)");
+
+// The 2 radius + 1 normalised weights of a Gaussian of `sigma` voxels (vk_filter_gaussian); radius 0: min(6, ceil(3 sigma)).
+inline std::vector<float> gaussian_weights(double sigma, uint32_t radius = 0) {
+    if (radius == 0u && sigma > 0.0 && sigma < 1e6) radius = (uint32_t)std::min(std::max(std::ceil(3.0 * sigma), 1.0), (double)VK_FILTER_MAX_RADIUS);
+    std::vector<float> w(2u * std::min(radius, (uint32_t)VK_FILTER_MAX_RADIUS) + 1u, 0.0f);
+    check(nullptr, vk_filter_gaussian(sigma, radius, w.data()));
+    return w;
+}
 
 // What Context::volume_histogram returns: the counts over the domain and the region's statistics (on the kernel's scale; stats.scale divides it out).
 struct Histogram {
@@ -331,6 +341,36 @@ class Context {
         std::vector<float> tris((size_t)n * 9u);
         if (n) check(ctx_, vk_extract_isosurface(ctx_, &req, box, tris.data(), n, &n));
         return tris;
+    }
+    // The volume filter pass (vk_volume_filter): the stored volume through a separable convolution -- wx, wy, wz each empty (the axis is
+    // skipped) or 2 r + 1 weights, r <= VK_FILTER_MAX_RADIUS -- into a volume of the same dimensions and format.  install: the result replaces
+    // the context's volume in its layout, under the table / projection / isosurface in force (outside frame_begin / frame_end).  dense_out:
+    // nullptr, or host memory of nx ny nz elements of the volume's format (the call then blocks).
+    void filter_volume(const std::vector<float> &wx, const std::vector<float> &wy, const std::vector<float> &wz, bool install = true, void *dense_out = nullptr) {
+        struct vk_volume_filter f{};
+        f.op = VK_FILTER_CONVOLVE;
+        f.flags = install ? (uint32_t)VK_FILTER_INSTALL : 0u;
+        const std::vector<float> *w[3] = {&wx, &wy, &wz};
+        for (int a = 0; a < 3; a++) {
+            if (w[a]->empty()) continue;
+            if (w[a]->size() % 2u == 0u || w[a]->size() < 3u || w[a]->size() > 2u * VK_FILTER_MAX_RADIUS + 1u)
+                throw std::invalid_argument("filter_volume: an odd number 2 r + 1 of weights per axis, 1 <= r <= VK_FILTER_MAX_RADIUS (empty: the axis is skipped)");
+            f.radius[a] = (uint32_t)(w[a]->size() / 2u);
+            for (size_t k = 0; k < w[a]->size(); k++) f.weights[a][k] = (*w[a])[k];
+        }
+        check(ctx_, vk_volume_filter(ctx_, &f, dense_out));
+    }
+    // ... with Gaussian weights of (sx, sy, sz) voxels; a sigma of 0 skips its axis
+    void smooth_volume(double sx, double sy, double sz, bool install = true, void *dense_out = nullptr) {
+        const std::vector<float> none;
+        filter_volume(sx != 0.0 ? gaussian_weights(sx) : none, sy != 0.0 ? gaussian_weights(sy) : none, sz != 0.0 ? gaussian_weights(sz) : none, install, dense_out);
+    }
+    // ... the 3x3x3 median: every texel becomes the 14th smallest of its 27 neighbours
+    void median_volume(bool install = true, void *dense_out = nullptr) {
+        struct vk_volume_filter f{};
+        f.op = VK_FILTER_MEDIAN3;
+        f.flags = install ? (uint32_t)VK_FILTER_INSTALL : 0u;
+        check(ctx_, vk_volume_filter(ctx_, &f, dense_out));
     }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
