@@ -7,7 +7,7 @@
 //    yields a bin, never an undefined conversion.
 // 4. vk::hist_key against `<` on all f16 values (sorted by key, the sequence must ascend, -0 directly below +0) and on random f32 pairs;
 //    hist_key_value inverts it; hist_minmax_decode on the empty pair.
-// 5. vk::hist_clip_axis / hist_clip_box against brute force over the voxel centres, (i + 0.5) / n in double within the closed interval.
+// 5. vk::voxel_clip_axis / voxel_clip_box against brute force over the voxel centres, (i + 0.5) / n in double within the closed interval.
 // 6. vk::hist_window against a brute-force percentile of the sorted samples on small counts, and its refusals.
 // 7. vk::hist_flush_passes: passes x voxels-per-pass stays within 2^32 - 1, one more pass would not.
 // 8. vk::hist_grid, hist_runs (the runs enumerate exactly the box's voxels, each once), hist_run_chunks (no alignment makes a run touch
@@ -187,7 +187,7 @@ static void check_clip(long c) {
     }
     if (hi < lo) { const float t = lo; lo = hi; hi = t; }
     uint32_t i0, i1;
-    vk::hist_clip_axis(lo, hi, n, i0, i1);
+    vk::voxel_clip_axis(lo, hi, n, i0, i1);
     if (i0 > i1 || i1 > n) { fail(c, "clip axis: a range outside the axis", i0, i1); return; }
     uint32_t first = n, count = 0;
     for (uint32_t i = 0; i < n; i++) {
@@ -196,9 +196,9 @@ static void check_clip(long c) {
     }
     if (count != i1 - i0 || (count && first != i0)) fail(c, "clip axis differs from brute force over the centres", lo, hi);
     const float l3[3] = {lo, 0.0f, lo}, h3[3] = {hi, 1.0f, hi};
-    const vk_voxel_box b = vk::hist_clip_box(l3, h3, n, 5, n);
-    if (b.x0 != i0 || b.x1 != i1 || b.y0 != 0u || b.y1 != 5u || b.z0 != i0 || b.z1 != i1 || !vk::hist_box_ok(b, n, 5, n)) fail(c, "clip box", lo, hi);
-    if (vk::hist_box_voxels(b) != (uint64_t)(i1 - i0) * 5u * (uint64_t)(i1 - i0)) fail(c, "box voxels", 0, 0);
+    const vk_voxel_box b = vk::voxel_clip_box(l3, h3, n, 5, n);
+    if (b.x0 != i0 || b.x1 != i1 || b.y0 != 0u || b.y1 != 5u || b.z0 != i0 || b.z1 != i1 || !vk::voxel_box_ok(b, n, 5, n)) fail(c, "clip box", lo, hi);
+    if (vk::voxel_box_voxels(b) != (uint64_t)(i1 - i0) * 5u * (uint64_t)(i1 - i0)) fail(c, "box voxels", 0, 0);
 }
 
 static void check_window(long c) {
@@ -277,9 +277,9 @@ static void check_runs(long c) {
     for (uint32_t z = b.z0; z < b.z1; z++)
         for (uint32_t y = b.y0; y < b.y1; y++)
             for (uint32_t x = b.x0; x < b.x1; x++) want[x + (size_t)nx * (y + (size_t)ny * z)]++;
-    if (vk::hist_box_voxels(b) != 0u) {
+    if (vk::voxel_box_voxels(b) != 0u) {
         const vk::HistRuns R = vk::hist_runs(b, nx, ny);
-        if ((uint64_t)R.len * R.na * R.nb != vk::hist_box_voxels(b)) fail(c, "runs: the runs do not hold the box's voxel count", R.len, R.na);
+        if ((uint64_t)R.len * R.na * R.nb != vk::voxel_box_voxels(b)) fail(c, "runs: the runs do not hold the box's voxel count", R.len, R.na);
         for (uint32_t rb = 0; rb < R.nb; rb++)
             for (uint32_t ra = 0; ra < R.na; ra++)
                 for (uint64_t k = 0; k < R.len; k++) {

@@ -11,7 +11,7 @@
 //    and its 64-bit path.
 // 5. The chunk, grid and scan arithmetic: mesh_chunk_cubes for every knob, mesh_chunks, mesh_chunk_passes, mesh_totals_padded, mesh_grid, and mesh_scan_host
 //    over totals whose sum passes 2^32.
-// 6. The validation table: mesh_validate, and the box rules the pass takes from the histogram (hist_box_ok) with mesh_axis_cubes.
+// 6. The validation table: mesh_validate, and the box rules the pass shares with the histogram (vk_box.hpp: voxel_box_ok) with mesh_axis_cubes.
 // usage: mesh_fuzz <cases> <seed>; prints "OK (<cases> cases)" or the first violations, and exits non-zero on any.
 #include "vk_mesh.hpp"
 
@@ -266,7 +266,7 @@ static void check_validation(long c) {
     b.y0 = (uint32_t)(rnd() % (ny + 2u)); b.y1 = (uint32_t)(rnd() % (ny + 2u));
     b.z0 = (uint32_t)(rnd() % (nz + 2u)); b.z1 = (uint32_t)(rnd() % (nz + 2u));
     const bool ok = b.x0 <= b.x1 && b.y0 <= b.y1 && b.z0 <= b.z1 && b.x1 <= nx && b.y1 <= ny && b.z1 <= nz;
-    if (vk::hist_box_ok(b, nx, ny, nz) != ok) fail(c, "hist_box_ok", b.x0, b.x1);
+    if (vk::voxel_box_ok(b, nx, ny, nz) != ok) fail(c, "voxel_box_ok", b.x0, b.x1);
     if (ok) {
         uint64_t cubes = 0;
         for (uint32_t z = b.z0; z + 1u < b.z1; z++)

@@ -1,6 +1,6 @@
 """Compare the device code of two trees, kernel by kernel, and say for every kernel symbol whether it is identical (A), identical up
 to register names (B) or different (C): tools/isa_diff.py OLD_TREE NEW_TREE [unit ...] (unit: vk_launch_cells or vk_launch_cells.hip;
-default: all seven launch units).
+default: every vk_launch_*.hip that both trees have).
 
 Each named vk_launch_*.hip of both trees is compiled with the product's flags plus -S --cuda-device-only, the assembly is split per
 kernel symbol, debug directives and comments are stripped, and every symbol lands in one class:
@@ -20,9 +20,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as g  # noqa: E402
 
-UNITS = ["vk_launch_cells", "vk_launch_tf", "vk_launch_lit", "vk_launch_mip", "vk_launch_iso", "vk_launch_staged", "vk_launch_compute"]
 FOOTER = ("TotalNumSgprs", "NumVgprs", "NumAgprs", "TotalNumVgprs", "ScratchSize", "Occupancy", "LDSByteSize", "codeLenInByte")
 REG = re.compile(r"\b[vsa](?:\d+|\[\d+:\d+\])")
+
+
+def launch_units(tree):
+    return {os.path.splitext(f)[0] for f in os.listdir(os.path.join(tree, "vokselis_amd", "csrc")) if f.startswith("vk_launch_") and f.endswith(".hip")}
 
 
 def assembly(tree, unit):
@@ -89,7 +92,7 @@ def fmt(foot):
 
 def main(argv):
     old_tree, new_tree = os.path.abspath(argv[0]), os.path.abspath(argv[1])
-    units = [os.path.splitext(u)[0] for u in argv[2:]] or UNITS
+    units = [os.path.splitext(u)[0] for u in argv[2:]] or sorted(launch_units(old_tree) & launch_units(new_tree))
     with ThreadPoolExecutor(max_workers=7) as ex:
         asm = list(ex.map(lambda j: assembly(*j), [(t, u) for u in units for t in (old_tree, new_tree)]))
     for i, u in enumerate(units):

@@ -55,6 +55,10 @@ enum VolKind : int { VOL_LINEAR_U8 = 0, VOL_LINEAR_F16 = 1, VOL_P8 = 2, VOL_P16 
 // the cell layouts (PACKED, PACKED_PAIRS): one aligned load per sample, skip maps, index tables; and the kinds of an R16_UNORM volume
 constexpr bool is_cell_layout(int VOL) { return VOL == VOL_P8 || VOL == VOL_P16 || VOL == VOL_PF16 || VOL == VOL_PU16; }
 constexpr bool is_u16_kind(int VOL) { return VOL == VOL_LINEAR_U16 || VOL == VOL_PU16; }
+// ... and of an R16_FLOAT one among the scalar LINEAR / PACKED / PACKED_PAIRS kinds; what a stored texel of those kinds holds (P16: u8 values in f16 pairs)
+constexpr bool is_f16_kind(int VOL) { return VOL == VOL_LINEAR_F16 || VOL == VOL_PF16; }
+enum TexelClass : int { TEXEL_U8 = 0, TEXEL_U16 = 1, TEXEL_F16 = 2 };
+constexpr TexelClass texel_class(int VOL) { return is_f16_kind(VOL) ? TEXEL_F16 : (is_u16_kind(VOL) ? TEXEL_U16 : TEXEL_U8); }
 enum OutKind : int { OUT_RGBA32F = 0, OUT_RGBA16F = 1 };
 
 struct VolumeDesc {

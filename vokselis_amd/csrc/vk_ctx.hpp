@@ -220,6 +220,26 @@ inline int fail(vk_ctx *ctx, int code, const std::string &msg) {
         }                                                                                      \
     } while (0)
 
+// A hipMalloc'd temporary of one call: freed when the call returns, whichever way; release() hands the pointer on (install_dense).
+struct DeviceTemp {
+    void *p = nullptr;
+    DeviceTemp() = default;
+    DeviceTemp(DeviceTemp &&o) noexcept : p(o.release()) {}
+    DeviceTemp(const DeviceTemp &) = delete;
+    DeviceTemp &operator=(const DeviceTemp &) = delete;
+    ~DeviceTemp() { if (p) (void)hipFree(p); }
+    void *release() { void *q = p; p = nullptr; return q; }
+};
+
+// the context's volume as the kernels' argument
+inline vk::VolumeDesc volume_desc(const vk_ctx *ctx) {
+    vk::VolumeDesc V = ctx->vdesc;
+    V.data = ctx->vol; V.data2 = ctx->vol2; V.dist = ctx->dist; V.lut = ctx->lut;
+    V.nx = ctx->nx; V.ny = ctx->ny; V.nz = ctx->nz;
+    V.nbx = ctx->nbx; V.nby = ctx->nby; V.nbz = ctx->nbz;
+    return V;
+}
+
 // Frames in flight: how many of the ring's frames execute at once (vk_frame_begin holds the others back), and whether the launch being recorded
 // belongs to a frame of a CROWDED ring -- three executing (k = 4) -- where the machine is full and the leaner kernel variants win.
 inline uint32_t frames_concurrent(const vk_ctx *ctx) { return ctx->fif_concurrent ? ctx->fif_concurrent : (ctx->fif_k >= 3u ? ctx->fif_k - 1u : ctx->fif_k); }

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "../../include/vokselis_hip.h"
+#include "vk_box.hpp"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -121,7 +122,7 @@ VK_FILTER_HD void filter_tile_origin(uint64_t i, uint32_t ntx, uint32_t nty, Fil
     y0 = (uint32_t)(rest - tz * nty) * t.ty;
     z0 = (uint32_t)tz * t.tz;
 }
-VK_FILTER_HD uint64_t filter_voxel_offset(uint32_t x, uint32_t y, uint32_t z, uint32_t nx, uint32_t ny) { return (uint64_t)x + (uint64_t)nx * ((uint64_t)y + (uint64_t)ny * (uint64_t)z); }
+VK_FILTER_HD uint64_t filter_voxel_offset(uint32_t x, uint32_t y, uint32_t z, uint32_t nx, uint32_t ny) { return voxel_index(x, y, z, nx, ny); }  // (the name the host fuzz checks the tiles under)
 
 // ---- the store rule ----------------------------------------------------------------------------------------------------------
 VK_FILTER_HD uint32_t filter_f32_bits(float f) {

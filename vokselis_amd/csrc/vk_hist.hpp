@@ -1,6 +1,6 @@
 // vk_hist.hpp -- the volume histogram and region statistics (vk_volume_histogram, vk_histogram_window): the validation of
 // a caller's vk_histogram (which forms lo_k, hi_k, k1, k2), the classification of one texel, the order-preserving key of min and max, the
-// clip box as a voxel box, the window of two percentiles, and the grid and flush arithmetic of the kernels, shared by the kernels and
+// window of two percentiles, and the grid and flush arithmetic of the kernels (the box rules: vk_box.hpp), shared by the kernels and
 // their host (vk_launch_hist.hip) and the host fuzz (tests/hist_fuzz.cpp, plain g++ under ASan / UBSan).
 #pragma once
 
@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "../../include/vokselis_hip.h"
+#include "vk_box.hpp"
 #include "vk_tf.hpp"
 
 #if defined(__HIPCC__)
@@ -81,36 +82,6 @@ inline void hist_minmax_decode(uint32_t inv_min, uint32_t max_key, float &mn, fl
     mx = max_key == 0u ? -INFINITY : hist_key_value(max_key);
 }
 
-// A box against the volume: not inverted, inside.
-inline bool hist_box_ok(const vk_voxel_box &b, uint32_t nx, uint32_t ny, uint32_t nz) {
-    return b.x0 <= b.x1 && b.y0 <= b.y1 && b.z0 <= b.z1 && b.x1 <= nx && b.y1 <= ny && b.z1 <= nz;
-}
-inline uint64_t hist_box_voxels(const vk_voxel_box &b) { return (uint64_t)(b.x1 - b.x0) * (uint64_t)(b.y1 - b.y0) * (uint64_t)(b.z1 - b.z0); }
-
-// One axis of the clip box as an index range [i0, i1): the voxels i of n whose centre (i + 0.5) / n, formed in double, lies in [lo, hi].
-// The estimate from lo n - 0.5 is moved until the predicate itself holds on one side and fails on the other (it is monotone in i).
-inline bool hist_centre_ge(uint32_t i, uint32_t n, float lo) { return ((double)i + 0.5) / (double)n >= (double)lo; }
-inline bool hist_centre_le(uint32_t i, uint32_t n, float hi) { return ((double)i + 0.5) / (double)n <= (double)hi; }
-inline void hist_clip_axis(float lo, float hi, uint32_t n, uint32_t &i0, uint32_t &i1) {
-    double a = ceil((double)lo * (double)n - 0.5), b = floor((double)hi * (double)n - 0.5) + 1.0;
-    a = a < 0.0 ? 0.0 : (a > (double)n ? (double)n : a);
-    b = b < 0.0 ? 0.0 : (b > (double)n ? (double)n : b);
-    i0 = (uint32_t)a;
-    i1 = (uint32_t)b;
-    while (i0 > 0u && hist_centre_ge(i0 - 1u, n, lo)) i0--;
-    while (i0 < n && !hist_centre_ge(i0, n, lo)) i0++;
-    while (i1 < n && hist_centre_le(i1, n, hi)) i1++;
-    while (i1 > 0u && !hist_centre_le(i1 - 1u, n, hi)) i1--;
-    if (i1 < i0) i1 = i0;  // no centre inside: an empty range
-}
-inline vk_voxel_box hist_clip_box(const float lo[3], const float hi[3], uint32_t nx, uint32_t ny, uint32_t nz) {
-    vk_voxel_box b;
-    hist_clip_axis(lo[0], hi[0], nx, b.x0, b.x1);
-    hist_clip_axis(lo[1], hi[1], ny, b.y0, b.y1);
-    hist_clip_axis(lo[2], hi[2], nz, b.z0, b.z1);
-    return b;
-}
-
 // The window of two percentiles (vk_histogram_window).  Returns nullptr, or what is wrong.
 inline const char *hist_window(const uint64_t *counts, uint32_t bins, float lo, float hi, double p_lo, double p_hi, float &w_lo, float &w_hi) {
     if (!counts) return "counts is NULL";
@@ -174,7 +145,7 @@ struct HistRuns {
 };
 inline HistRuns hist_runs(const vk_voxel_box &b, uint32_t nx, uint32_t ny) {
     HistRuns R;
-    R.off0 = (uint64_t)b.x0 + (uint64_t)nx * ((uint64_t)b.y0 + (uint64_t)ny * (uint64_t)b.z0);
+    R.off0 = voxel_index(b.x0, b.y0, b.z0, nx, ny);
     R.len = b.x1 - b.x0; R.na = b.y1 - b.y0; R.sa = nx; R.nb = b.z1 - b.z0; R.sb = (uint64_t)nx * ny;
     for (int k = 0; k < 2; k++)
         if (R.na == 1u || R.len == R.sa) { R.len *= R.na; R.na = R.nb; R.sa = R.sb; R.nb = 1u; }

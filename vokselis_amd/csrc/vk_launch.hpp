@@ -1,9 +1,11 @@
-// vk_launch.hpp -- host side of the vk_launch_*.hip files (included by them, and by vk_render.hip for has_table_layout): the runtime choices that
-// select a kernel instantiation, each written once.  A helper turns its runtime values into compile-time tags and hands them to a generic lambda that names the kernel:
+// vk_launch.hpp -- host side of the vk_launch_*.hip files (included by them, and by vk_render.hip for has_table_layout and pass_needs): the runtime
+// choices that select a kernel instantiation, each written once, and what the entry points of the passes that are not a march share (DESIGN.md
+// section 23).  A helper turns its runtime values into compile-time tags and hands them to a generic lambda that names the kernel:
 //     with_out_count(ctx, count, [&](auto OUT, auto COUNT) { hipLaunchKernelGGL((kernel<..., OUT(), COUNT()>), ...); });
 // A helper calls its lambda with exactly the combinations the ladder it replaces spelled out: the set of instantiated kernels is the same.
 #pragma once
 
+#include "vk_box.hpp"
 #include "vk_ctx.hpp"
 
 #include <type_traits>
@@ -20,6 +22,9 @@ static_assert(kernargs_fit<TfDesc, ClipDesc>, "raymarch_tf_kernel, raymarch_mip_
 static_assert(kernargs_fit<TfDesc, LightDesc, ClipDesc>, "raymarch_lit_kernel, raymarch_lit_clip_kernel: LaunchDesc + VolumeDesc + TfDesc + LightDesc (+ ClipDesc)");
 static_assert(kernargs_fit<IsoDesc, ClipDesc>, "raymarch_iso_kernel, raymarch_iso_clip_kernel: LaunchDesc + VolumeDesc + IsoDesc (+ ClipDesc)");
 static_assert(kernargs_fit<IsoDesc, GeomDesc, ClipDesc>, "raymarch_geom_kernel, raymarch_u16_geom_kernel and their _clip_ kernels: LaunchDesc + VolumeDesc + IsoDesc + GeomDesc (+ ClipDesc)");
+// ... and of a pass that is not a march: VolumeDesc and the pass's own descriptors, no LaunchDesc
+template <class... D>
+constexpr bool pass_kernargs_fit = sizeof(VolumeDesc) + (sizeof(D) + ... + 0) + 256 <= 4096;
 
 template <int I>
 using int_tag = std::integral_constant<int, I>;
@@ -60,6 +65,42 @@ void with_table_layout(const vk_ctx *ctx, bool skip, bool safe, F &&f) {
         case VOL_LINEAR_F16: f(int_tag<VOL_LINEAR_F16>(), bool_tag<false>(), bool_tag<true>()); break;
         default: f(int_tag<VOL_LINEAR_U8>(), bool_tag<false>(), bool_tag<true>()); break;
     }
+}
+
+// ---- the passes that are not a march (slice, histogram, mesh, filter): kernels on the seven scalar kinds of has_table_layout ----------
+// f(VOL) over those kinds.  A caller whose kernel covers fewer of them says so with `if constexpr` in its lambda: nothing else is instantiated.
+template <class F>
+void with_scalar_kind(int kind, F &&f) {
+    switch (kind) {
+        case VOL_P8: f(int_tag<VOL_P8>()); break;
+        case VOL_P16: f(int_tag<VOL_P16>()); break;
+        case VOL_PF16: f(int_tag<VOL_PF16>()); break;
+        case VOL_PU16: f(int_tag<VOL_PU16>()); break;
+        case VOL_LINEAR_F16: f(int_tag<VOL_LINEAR_F16>()); break;
+        case VOL_LINEAR_U16: f(int_tag<VOL_LINEAR_U16>()); break;
+        default: f(int_tag<VOL_LINEAR_U8>()); break;
+    }
+}
+
+// The two refusals of such a pass, made one at a time because other checks stand between them: VK_OK, or the error set.  entry: the function's name;
+// word: what the pass's kernels are called; subject: what the pass calls itself.
+enum PassNeed { PASS_NEEDS_VOLUME, PASS_NEEDS_SCALAR_KIND };
+inline int pass_needs(vk_ctx *ctx, PassNeed need, const char *entry, const char *word, const char *subject = "pass") {
+    if (need == PASS_NEEDS_VOLUME) return ctx->format < 0 ? fail(ctx, VK_ERR_INVALID, std::string(entry) + ": no volume uploaded") : VK_OK;
+    if (ctx->format == VK_FMT_RGBA16F_PAIR || !has_table_layout(ctx->vol_kind))
+        return fail(ctx, VK_ERR_UNSUPPORTED, std::string(word) + ": the " + subject + " needs a scalar LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED and RGBA16F_PAIR have no " + word + " kernels)");
+    return VK_OK;
+}
+
+// The voxel box of a call (histogram, mesh): the caller's, else the clip box where the request's flag (its name: flag) asks for it and
+// one is set, else the whole volume.  VK_OK, or the error set.
+inline int pass_voxel_box(vk_ctx *ctx, const char *entry, const char *flag, const vk_voxel_box *box, bool clip_flag, vk_voxel_box &B) {
+    if (box && clip_flag) return fail(ctx, VK_ERR_INVALID, std::string(entry) + ": " + flag + " takes the box from the clip box: box must be NULL");
+    if (box && !voxel_box_ok(*box, ctx->nx, ctx->ny, ctx->nz)) return fail(ctx, VK_ERR_INVALID, std::string(entry) + ": the box is inverted or leaves the volume");
+    if (box) B = *box;
+    else if (clip_flag && ctx->clip_on) B = voxel_clip_box(ctx->clip_lo, ctx->clip_hi, ctx->nx, ctx->ny, ctx->nz);
+    else B = vk_voxel_box{0u, 0u, 0u, ctx->nx, ctx->ny, ctx->nz};
+    return VK_OK;
 }
 
 // Dynamic LDS of a cell kernel (vk_march_kernel_body.hpp) -- the fast path of the cell layouts keeps its per-axis index tables there

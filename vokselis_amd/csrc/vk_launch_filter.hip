@@ -12,12 +12,14 @@
 // consecutive x of one row: consecutive banks whatever the pitch; the pitch is odd, so the two halves start in different banks.
 // Median.  The same tiling with halo 1, keys of 16 bits in LDS (the value, or the totalOrder key of a half); a lane selects the 14th of
 // its 27 keys with the min / max network of vk_filter.hpp, in registers.
-// Reading.  A texel is read by its voxel index: LINEAR one element, lanes along x coalesced; the cell layouts one tap of the even cell
-// that holds the voxel (the cell of an even low corner holds 8 voxels of its own), a narrow load the neighbouring lanes share lines with.
+// Reading.  A texel is read by its voxel index (vk_texel.hpp: voxel_texel_bits): LINEAR one element, lanes along x coalesced; the cell
+// layouts one tap of the even cell that holds the voxel (the cell of an even low corner holds 8 voxels of its own), a narrow load the
+// neighbouring lanes share lines with.
 //
 // Loop bounds are block-uniform wherever a barrier stands.  Plain C++; no inline assembly.
 #include "vk_launch.hpp"
 #include "vk_filter.hpp"
+#include "vk_texel.hpp"
 
 using namespace vk;
 
@@ -29,48 +31,17 @@ struct FilterDesc {
     float w[3][2 * VK_FILTER_MAX_RADIUS + 1];
     uint32_t pad;
 };
-static_assert(sizeof(FilterDesc) % 8 == 0 && sizeof(VolumeDesc) + sizeof(FilterDesc) + 256 <= 4096, "filter kernels: VolumeDesc + FilterDesc");
-
-enum : int { FILTER_U8 = 0, FILTER_U16 = 1, FILTER_F16 = 2 };
-constexpr int filter_fmt(int VOL) { return (VOL == VOL_LINEAR_F16 || VOL == VOL_PF16) ? FILTER_F16 : (is_u16_kind(VOL) ? FILTER_U16 : FILTER_U8); }
-
-// the byte offset of the cell with low-corner voxel (ix, iy, iz) (vk_common.hpp: VolumeDesc), held inside the cell array
-__device__ __forceinline__ int64_t filter_cell_offset(const VolumeDesc &V, uint32_t ix, uint32_t iy, uint32_t iz) {
-    const int64_t off = (int64_t)(iz >> 2) * V.kz + (int64_t)(iy >> 2) * (int64_t)V.ky + (int64_t)(ix >> 2) * (int64_t)V.kx +
-                        (((int64_t)iz << V.sh_z) + ((int64_t)iy << V.sh_y) + ((int64_t)ix << V.sh_x)) + V.c0;
-    return off < 0 ? 0 : (off > V.max_off ? V.max_off : off);
-}
-
-// The stored texel of voxel (x, y, z), x < nx (likewise y, z), as its bits: the u8 or u16 value, or the half.  Cell layouts: tap
-// (x & 1) + 2 (y & 1) + 4 (z & 1) of the cell whose low corner is the voxel with its low bits cleared -- a voxel of the volume, so the
-// cell exists and the tap is a stored texel, not one of the clamp's duplicates.
-template <int VOL>
-__device__ __forceinline__ uint32_t filter_texel_bits(const VolumeDesc &V, uint32_t x, uint32_t y, uint32_t z) {
-    if constexpr (is_cell_layout(VOL)) {
-        const char *cptr = reinterpret_cast<const char *>(V.data) + filter_cell_offset(V, x & ~1u, y & ~1u, z & ~1u);
-        const uint32_t b = (x & 1u) | ((y & 1u) << 1) | ((z & 1u) << 2);
-        if constexpr (VOL == VOL_P8) return reinterpret_cast<const uint8_t *>(cptr)[b];
-        else if constexpr (VOL == VOL_P16) {  // (tap, delta) pairs of f16 that hold u8 values: tap + delta is exact
-            const uint32_t q = reinterpret_cast<const uint32_t *>(cptr)[b >> 1];
-            const float a = h2f(q & 0xffffu), d = h2f(q >> 16);
-            return (uint32_t)((b & 1u) ? a + d : a);
-        } else return reinterpret_cast<const uint16_t *>(cptr)[b];
-    } else {
-        const uint64_t i = filter_voxel_offset(x, y, z, V.nx, V.ny);
-        if constexpr (VOL == VOL_LINEAR_U8) return reinterpret_cast<const uint8_t *>(V.data)[i];
-        else return reinterpret_cast<const uint16_t *>(V.data)[i];
-    }
-}
+static_assert(sizeof(FilterDesc) % 8 == 0 && pass_kernargs_fit<FilterDesc>, "filter kernels: VolumeDesc + FilterDesc");
 
 template <int FMT>
 __device__ __forceinline__ void filter_store_bits(void *__restrict__ out, uint64_t i, uint32_t bits) {
-    if constexpr (FMT == FILTER_U8) reinterpret_cast<uint8_t *>(out)[i] = (uint8_t)bits;
+    if constexpr (FMT == TEXEL_U8) reinterpret_cast<uint8_t *>(out)[i] = (uint8_t)bits;
     else reinterpret_cast<uint16_t *>(out)[i] = (uint16_t)bits;
 }
 template <int FMT>
 __device__ __forceinline__ uint32_t filter_store_rule(float v) {
-    if constexpr (FMT == FILTER_U8) return filter_store_unorm(v, 255.0f);
-    else if constexpr (FMT == FILTER_U16) return filter_store_unorm(v, 65535.0f);
+    if constexpr (FMT == TEXEL_U8) return filter_store_unorm(v, 255.0f);
+    else if constexpr (FMT == TEXEL_U16) return filter_store_unorm(v, 65535.0f);
     else return filter_store_f16(v);
 }
 
@@ -85,7 +56,7 @@ template <int VOL, int CLS>
 __global__ __launch_bounds__(kFilterThreads, 2) void filter_convolve_kernel(const VolumeDesc V, const FilterDesc D, void *__restrict__ out) {
     constexpr FilterTile T = kFilterTiles[CLS];
     constexpr uint32_t PX = filter_pitch_x(T), PY = filter_rows(T), PZ = filter_planes(T);
-    constexpr int FMT = filter_fmt(VOL);
+    constexpr int FMT = texel_class(VOL);
     constexpr uint32_t KX = filter_per_thread(T.tx * PY * PZ), KY = filter_per_thread(T.tx * T.ty * PZ), KZ = filter_per_thread(T.tx * T.ty * T.tz);
     __shared__ float lds[PX * PY * PZ];
     const uint32_t rx = D.rx, ry = D.ry, rz = D.rz;
@@ -99,8 +70,8 @@ __global__ __launch_bounds__(kFilterThreads, 2) void filter_convolve_kernel(cons
         for (uint32_t e = threadIdx.x; e < n_halo; e += kFilterThreads) {
             const uint32_t row = filter_div(e, mx), lx = e - row * hx, lz = filter_div(row, my), ly = row - lz * hy;
             const uint32_t gx = filter_clamp((int64_t)x0 + lx - rx, D.nx), gy = filter_clamp((int64_t)y0 + ly - ry, D.ny), gz = filter_clamp((int64_t)z0 + lz - rz, D.nz);
-            const uint32_t bits = filter_texel_bits<VOL>(V, gx, gy, gz);
-            lds[filter_lds_index(T, lx, ly, lz)] = FMT == FILTER_F16 ? h2f(bits) : (float)bits;
+            const uint32_t bits = voxel_texel_bits<VOL>(V, gx, gy, gz);
+            lds[filter_lds_index(T, lx, ly, lz)] = texel_f32<VOL>(bits);
         }
         __syncthreads();
         if (rx) {  // x: tile columns, every row of the y and z halo; the result of column lx at lx + rx
@@ -168,7 +139,7 @@ template <int VOL>
 __global__ __launch_bounds__(kFilterThreads) void filter_median_kernel(const VolumeDesc V, const FilterDesc D, void *__restrict__ out) {
     constexpr FilterTile T = kMedianTile;
     constexpr uint32_t PX = filter_pitch_x(T), PY = filter_rows(T), PZ = filter_planes(T);
-    constexpr int FMT = filter_fmt(VOL);
+    constexpr int FMT = texel_class(VOL);
     constexpr uint32_t HX = T.tx + 2u, HY = T.ty + 2u, HZ = T.tz + 2u;
     constexpr uint32_t KZ = filter_per_thread(T.tx * T.ty * T.tz);
     __shared__ uint16_t lds[PX * PY * PZ];
@@ -178,8 +149,8 @@ __global__ __launch_bounds__(kFilterThreads) void filter_median_kernel(const Vol
         for (uint32_t e = threadIdx.x; e < HX * HY * HZ; e += kFilterThreads) {
             const uint32_t row = e / HX, lx = e - row * HX, lz = row / HY, ly = row - lz * HY;
             const uint32_t gx = filter_clamp((int64_t)x0 + lx - 1, D.nx), gy = filter_clamp((int64_t)y0 + ly - 1, D.ny), gz = filter_clamp((int64_t)z0 + lz - 1, D.nz);
-            const uint32_t bits = filter_texel_bits<VOL>(V, gx, gy, gz);
-            lds[filter_lds_index(T, lx, ly, lz)] = (uint16_t)(FMT == FILTER_F16 ? filter_f16_key(bits) : bits);
+            const uint32_t bits = voxel_texel_bits<VOL>(V, gx, gy, gz);
+            lds[filter_lds_index(T, lx, ly, lz)] = (uint16_t)(FMT == TEXEL_F16 ? filter_f16_key(bits) : bits);
         }
         __syncthreads();
 #pragma unroll
@@ -195,25 +166,12 @@ __global__ __launch_bounds__(kFilterThreads) void filter_median_kernel(const Vol
                     for (uint32_t a = 0; a < 3u; a++) v[a + 3u * b + 9u * c] = lds[filter_lds_index(T, lx + a, ly + b, lz + c)];
             const uint32_t m = filter_median27(v);
             const uint32_t gx = x0 + lx, gy = y0 + ly, gz = z0 + lz;
-            if (gx < D.nx && gy < D.ny && gz < D.nz) filter_store_bits<FMT>(out, filter_voxel_offset(gx, gy, gz, D.nx, D.ny), FMT == FILTER_F16 ? filter_f16_unkey(m) : m);
+            if (gx < D.nx && gy < D.ny && gz < D.nz) filter_store_bits<FMT>(out, filter_voxel_offset(gx, gy, gz, D.nx, D.ny), FMT == TEXEL_F16 ? filter_f16_unkey(m) : m);
         }
         __syncthreads();  // the next tile's load overwrites the keys
     }
 }
 
-// f(int_tag<VOL>) over the seven volume kinds the pass covers
-template <class F>
-static void filter_for_kind(int kind, F &&f) {
-    switch (kind) {
-        case VOL_P8: f(int_tag<VOL_P8>()); break;
-        case VOL_P16: f(int_tag<VOL_P16>()); break;
-        case VOL_PF16: f(int_tag<VOL_PF16>()); break;
-        case VOL_PU16: f(int_tag<VOL_PU16>()); break;
-        case VOL_LINEAR_F16: f(int_tag<VOL_LINEAR_F16>()); break;
-        case VOL_LINEAR_U16: f(int_tag<VOL_LINEAR_U16>()); break;
-        default: f(int_tag<VOL_LINEAR_U8>()); break;
-    }
-}
 template <int VOL>
 static void filter_launch_convolve(vk_ctx *ctx, uint32_t cls, uint32_t grid, const VolumeDesc &V, const FilterDesc &D, void *out) {
     switch (cls) {
@@ -221,10 +179,6 @@ static void filter_launch_convolve(vk_ctx *ctx, uint32_t cls, uint32_t grid, con
         case 1: hipLaunchKernelGGL((filter_convolve_kernel<VOL, 1>), dim3(grid), dim3(kFilterThreads), 0, ctx->stream, V, D, out); break;
         default: hipLaunchKernelGGL((filter_convolve_kernel<VOL, 2>), dim3(grid), dim3(kFilterThreads), 0, ctx->stream, V, D, out); break;
     }
-}
-template <int VOL>
-static void filter_launch_median(vk_ctx *ctx, uint32_t grid, const VolumeDesc &V, const FilterDesc &D, void *out) {
-    hipLaunchKernelGGL(filter_median_kernel<VOL>, dim3(grid), dim3(kFilterThreads), 0, ctx->stream, V, D, out);
 }
 
 extern "C" {
@@ -234,9 +188,8 @@ int vk_volume_filter(vk_ctx *ctx, const struct vk_volume_filter *f, void *dense_
     if (const char *why = filter_validate(f, dense_out != nullptr)) return fail(ctx, VK_ERR_INVALID, std::string("vk_volume_filter: ") + why);
     const bool install = (f->flags & VK_FILTER_INSTALL) != 0u;
     if (install && ctx->fif_open) return fail(ctx, VK_ERR_INVALID, "vk_volume_filter: VK_FILTER_INSTALL while a frame is being recorded (call it outside vk_frame_begin / vk_frame_end)");
-    if (ctx->format < 0) return fail(ctx, VK_ERR_INVALID, "vk_volume_filter: no volume uploaded");
-    if (ctx->format == VK_FMT_RGBA16F_PAIR || !has_table_layout(ctx->vol_kind))
-        return fail(ctx, VK_ERR_UNSUPPORTED, "filter: the pass needs a scalar LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED and RGBA16F_PAIR have no filter kernels)");
+    if (int rc = pass_needs(ctx, PASS_NEEDS_VOLUME, "vk_volume_filter", "filter")) return rc;
+    if (int rc = pass_needs(ctx, PASS_NEEDS_SCALAR_KIND, "vk_volume_filter", "filter")) return rc;
 
     const int kind = ctx->vol_kind;
     const bool median = f->op == VK_FILTER_MEDIAN3;
@@ -254,24 +207,20 @@ int vk_volume_filter(vk_ctx *ctx, const struct vk_volume_filter *f, void *dense_
     const FilterGrid G = filter_grid(D.nx, D.ny, D.nz, median ? kMedianTile : kFilterTiles[cls], ctx->filter_max_blocks);
     D.ntx = G.ntx; D.nty = G.nty; D.tiles = G.tiles;
 
-    VolumeDesc V = ctx->vdesc;
-    V.data = ctx->vol; V.data2 = ctx->vol2; V.dist = ctx->dist; V.lut = ctx->lut;
-    V.nx = ctx->nx; V.ny = ctx->ny; V.nz = ctx->nz;
-    V.nbx = ctx->nbx; V.nby = ctx->nby; V.nbz = ctx->nbz;
-
+    const VolumeDesc V = volume_desc(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t bytes = (size_t)D.nx * D.ny * D.nz * (ctx->format == VK_FMT_R8_UNORM ? 1u : 2u);
-    void *d_out = nullptr;
-    hipError_t e = hipMalloc(&d_out, bytes);
+    DeviceTemp d_out;
+    hipError_t e = hipMalloc(&d_out.p, bytes);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("vk_volume_filter: the output buffer: ") + hipGetErrorString(e));
     }
     // (debug, vk_debug_set_param("filter_timing", 1): the kernel alone between the context's timer events, read with vk_timer_elapsed_ms)
     if (ctx->filter_timing) e = hipEventRecord(ctx->ev0, ctx->stream);
-    filter_for_kind(kind, [&](auto vol) {
-        if (median) filter_launch_median<decltype(vol)::value>(ctx, G.blocks, V, D, d_out);
-        else filter_launch_convolve<decltype(vol)::value>(ctx, cls, G.blocks, V, D, d_out);
+    with_scalar_kind(kind, [&](auto VOL) {
+        if (median) hipLaunchKernelGGL(filter_median_kernel<VOL()>, dim3(G.blocks), dim3(kFilterThreads), 0, ctx->stream, V, D, d_out.p);
+        else filter_launch_convolve<VOL()>(ctx, cls, G.blocks, V, D, d_out.p);
     });
     if (e == hipSuccess) e = hipGetLastError();
     if (ctx->filter_timing && e == hipSuccess) {
@@ -279,18 +228,12 @@ int vk_volume_filter(vk_ctx *ctx, const struct vk_volume_filter *f, void *dense_
         ctx->timing_open = false;
         ctx->timing_done = true;
     }
-    if (e == hipSuccess && dense_out) e = hipMemcpyAsync(dense_out, d_out, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && dense_out) e = hipMemcpyAsync(dense_out, d_out.p, bytes, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess && (dense_out || !install)) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(d_out);
-        return fail(ctx, VK_ERR_HIP, std::string("vk_volume_filter: ") + hipGetErrorString(e));
-    }
-    if (!install) {
-        HIP_TRY(ctx, hipFree(d_out));
-        return VK_OK;
-    }
+    if (e != hipSuccess) return fail(ctx, VK_ERR_HIP, std::string("vk_volume_filter: ") + hipGetErrorString(e));
+    if (!install) return VK_OK;
     // the build runs on the same stream behind the kernel, adopts or frees d_out, and commits only when it stands: the old volume stays otherwise
-    return install_dense(ctx, d_out, D.nx, D.ny, D.nz, ctx->format, ctx->layout);
+    return install_dense(ctx, d_out.release(), D.nx, D.ny, D.nz, ctx->format, ctx->layout);
 }
 
 int vk_filter_gaussian(double sigma_voxels, uint32_t radius, float *weights) {

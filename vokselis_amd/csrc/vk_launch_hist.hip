@@ -2,7 +2,8 @@
 // family of its own: a reduction over the stored texels of a voxel box, no ray and no plane.  The classification of a texel, the key of min
 // and max and all launch arithmetic are vk_hist.hpp's, shared with the host fuzz.
 //
-// Reading.  LINEAR: the box is a set of runs of contiguous voxels (full rows merge into planes, full planes into one run); a lane loads
+// Reading.  Where a cell is, its load, its taps and the decode of a texel are vk_texel.hpp's; which texels a lane takes is this unit's.
+// LINEAR: the box is a set of runs of contiguous voxels (full rows merge into planes, full planes into one run); a lane loads
 // one aligned 16-byte chunk of a run and masks the elements before the run's first and behind its last voxel.  Cell layouts: only the
 // cells whose low-corner voxel is even on all three axes are read -- one in eight, every tap of them a voxel of its own -- one cell per
 // lane, a wave taking 8 bricks along x with the 8 even cells of each; taps outside the box are masked, which also drops the duplicate the
@@ -21,6 +22,7 @@
 // Plain C++; no inline assembly.
 #include "vk_launch.hpp"
 #include "vk_hist.hpp"
+#include "vk_texel.hpp"
 
 #include <vector>
 
@@ -37,7 +39,7 @@ struct HistDesc {
     unsigned long long *out;          // counts[bins], NaN, below, above, n_finite, (max ~key, max key), then two f64 per block
     uint32_t pad[2];
 };
-static_assert(sizeof(HistDesc) % 8 == 0 && sizeof(VolumeDesc) + sizeof(HistDesc) + 256 <= 4096, "hist kernels: VolumeDesc + HistDesc");
+static_assert(sizeof(HistDesc) % 8 == 0 && pass_kernargs_fit<HistDesc>, "hist kernels: VolumeDesc + HistDesc");
 
 constexpr uint32_t kLdsCounters = VK_HIST_MAX_BINS + kHistCats;
 
@@ -48,12 +50,11 @@ struct HistAcc {
     uint32_t vmin = 0xffffffffu, vmax = 0u;  // integer formats: min and max as integers, keyed once at the end (hist_acc_close)
 };
 
-// How a kernel's elements are counted.  HIST_F16: e[] holds f32 bits, classified by hist_bin, keyed and summed in f64 one by one.
-// HIST_U16: e[] holds the integer value -- min and max as integers, the pass's sum and sum of squares as integers (8 x 65535^2 fits a u64),
-// added to the f64 sums once per pass: the same sums, every partial an integer.  HIST_U8: as HIST_U16, and the slot of each of the 256
-// values is read from a table the workgroup builds in LDS with hist_bin at its start (8 x 255^2 fits a u32).
-enum : int { HIST_F16 = 0, HIST_U16 = 1, HIST_U8 = 2 };
-constexpr int hist_fmt(int VOL) { return (VOL == VOL_LINEAR_F16 || VOL == VOL_PF16) ? HIST_F16 : (is_u16_kind(VOL) ? HIST_U16 : HIST_U8); }
+// How a kernel's elements are counted, by the texel class of its kind (vk_common.hpp).  TEXEL_F16: e[] holds f32 bits, classified by
+// hist_bin, keyed and summed in f64 one by one.  TEXEL_U16: e[] holds the integer value -- min and max as integers, the pass's sum and sum
+// of squares as integers (8 x 65535^2 fits a u64), added to the f64 sums once per pass: the same sums, every partial an integer.
+// TEXEL_U8: as TEXEL_U16, and the slot of each of the 256 values is read from a table the workgroup builds in LDS with hist_bin at its
+// start (8 x 255^2 fits a u32).
 
 __device__ __forceinline__ void hist_lds_clear(uint32_t *lds, uint32_t n) {
     for (uint32_t i = threadIdx.x; i < n; i += kHistThreads) lds[i] = 0u;
@@ -81,7 +82,7 @@ __device__ __forceinline__ void hist_count(uint32_t *lds, const uint16_t *lut, c
 #pragma unroll
     for (int e = 0; e < N; e++) {
         const bool v = (valid >> e) & 1u;
-        if constexpr (FMT == HIST_F16) {
+        if constexpr (FMT == TEXEL_F16) {
             const float x = __uint_as_float(el[e]);
             slot[e] = hist_slot(hist_bin(x, D.lo_k, D.hi_k, D.k1, D.k2, D.bins), D.bins);
             if (v) {
@@ -99,12 +100,12 @@ __device__ __forceinline__ void hist_count(uint32_t *lds, const uint16_t *lut, c
             }
         } else {
             const uint32_t u = el[e];  // 0 where not valid: adds nothing to the sums and leaves vmax alone
-            if constexpr (FMT == HIST_U8) slot[e] = lut[u & 0xffu];
+            if constexpr (FMT == TEXEL_U8) slot[e] = lut[u & 0xffu];
             else slot[e] = hist_slot(hist_bin((float)u, D.lo_k, D.hi_k, D.k1, D.k2, D.bins), D.bins);
             A.vmin = min(A.vmin, v ? u : 0xffffffffu);
             A.vmax = max(A.vmax, u);
             isum += u;
-            if constexpr (FMT == HIST_U8) isq32 += u * u;
+            if constexpr (FMT == TEXEL_U8) isq32 += u * u;
             else isq64 += (unsigned long long)(u * u);  // u <= 65535: the product fits 32 bits
         }
         if (v) {
@@ -112,10 +113,10 @@ __device__ __forceinline__ void hist_count(uint32_t *lds, const uint16_t *lut, c
             else same = same && slot[e] == s0;
         }
     }
-    if constexpr (FMT != HIST_F16) {
+    if constexpr (FMT != TEXEL_F16) {
         A.n_finite += (unsigned long long)__popc(valid);
         A.sum += (double)isum;
-        A.sq += FMT == HIST_U8 ? (double)isq32 : (double)isq64;
+        A.sq += FMT == TEXEL_U8 ? (double)isq32 : (double)isq64;
     }
     const unsigned long long with_work = __ballot(have);
     if (with_work == 0ull) return;  // wave-uniform
@@ -150,7 +151,7 @@ __device__ __forceinline__ void hist_count(uint32_t *lds, const uint16_t *lut, c
 // the integer formats' min and max into the keys (a lane that saw no voxel keeps the empty marks)
 template <int FMT>
 __device__ __forceinline__ void hist_acc_close(HistAcc &A) {
-    if constexpr (FMT != HIST_F16) {
+    if constexpr (FMT != TEXEL_F16) {
         if (A.n_finite) { A.inv_min = ~hist_key((float)A.vmin); A.max_key = hist_key((float)A.vmax); }
     }
 }
@@ -158,7 +159,7 @@ __device__ __forceinline__ void hist_acc_close(HistAcc &A) {
 // the slots of the 256 values of a u8 format (kHistThreads == 256: one each)
 template <int FMT>
 __device__ __forceinline__ void hist_lut_build(uint16_t *lut, const HistDesc &D) {
-    if constexpr (FMT == HIST_U8) lut[threadIdx.x] = (uint16_t)hist_slot(hist_bin((float)threadIdx.x, D.lo_k, D.hi_k, D.k1, D.k2, D.bins), D.bins);
+    if constexpr (FMT == TEXEL_U8) lut[threadIdx.x] = (uint16_t)hist_slot(hist_bin((float)threadIdx.x, D.lo_k, D.hi_k, D.k1, D.k2, D.bins), D.bins);
 }
 static_assert(kHistThreads == 256u && VK_HIST_MAX_BINS + kHistCats <= 65535u, "the u8 table: one thread per value, a slot fits 16 bits");
 
@@ -194,11 +195,11 @@ __device__ __forceinline__ void hist_finish(HistAcc A, const HistDesc &D) {
     }
 }
 
-// a 16-bit texel as hist_count's element: the f32 bits of a half, or the integer
+// a stored texel as hist_count's element: the f32 bits of a half, or the integer
 template <int VOL>
-__device__ __forceinline__ uint32_t hist_element16(uint32_t bits) {
-    if constexpr (hist_fmt(VOL) == HIST_F16) return __float_as_uint(h2f(bits));
-    else return bits & 0xffffu;
+__device__ __forceinline__ uint32_t hist_element(uint32_t bits) {
+    if constexpr (texel_class(VOL) == TEXEL_F16) return __float_as_uint(texel_f32<VOL>(bits));
+    else return bits;
 }
 
 // LINEAR: one aligned 16-byte chunk of a run per lane.
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_linear_kernel(const void *_
     __shared__ uint16_t lut[256];
     constexpr uint32_t E = VOL == VOL_LINEAR_U8 ? 1u : 2u;
     constexpr int N = (int)(kHistLinearChunk / E);
-    constexpr int FMT = hist_fmt(VOL);
+    constexpr int FMT = texel_class(VOL);
     const uint32_t n_lds = D.bins + kHistCats;
     hist_lut_build<FMT>(lut, D);
     hist_lds_clear(lds, n_lds);
@@ -244,8 +245,8 @@ __global__ __launch_bounds__(kHistThreads) void hist_linear_kernel(const void *_
                 valid = ((1u << e1) - 1u) & ~((1u << e0) - 1u);
 #pragma unroll
                 for (int e = 0; e < N; e++) {  // (an element outside the run is 0: hist_count)
-                    const uint32_t bits = E == 1u ? (w[e >> 2] >> (8 * (e & 3))) & 0xffu : (w[e >> 1] >> (16 * (e & 1))) & 0xffffu;
-                    t[e] = ((valid >> e) & 1u) ? (E == 1u ? bits : hist_element16<VOL>(bits)) : 0u;
+                    const uint32_t bits = texel_field<8 * (int)E>(w, (uint32_t)e);
+                    t[e] = ((valid >> e) & 1u) ? hist_element<VOL>(bits) : 0u;
                 }
             }
         }
@@ -257,19 +258,12 @@ __global__ __launch_bounds__(kHistThreads) void hist_linear_kernel(const void *_
     hist_finish(A, D);
 }
 
-// the byte offset of the cell with low-corner voxel (ix, iy, iz) (vk_common.hpp: VolumeDesc), held inside the cell array
-__device__ __forceinline__ int64_t hist_cell_offset(const VolumeDesc &V, uint32_t ix, uint32_t iy, uint32_t iz) {
-    const int64_t off = (int64_t)(iz >> 2) * V.kz + (int64_t)(iy >> 2) * (int64_t)V.ky + (int64_t)(ix >> 2) * (int64_t)V.kx +
-                        (((int64_t)iz << V.sh_z) + ((int64_t)iy << V.sh_y) + ((int64_t)ix << V.sh_x)) + V.c0;
-    return off < 0 ? 0 : (off > V.max_off ? V.max_off : off);
-}
-
 // Cell layouts: the even cells, one per lane; a wave takes 8 bricks along x.
 template <int VOL>
 __global__ __launch_bounds__(kHistThreads) void hist_cells_kernel(const VolumeDesc V, const HistDesc D) {
     __shared__ uint32_t lds[kLdsCounters];
     __shared__ uint16_t lut[256];
-    constexpr int FMT = hist_fmt(VOL);
+    constexpr int FMT = texel_class(VOL);
     const uint32_t n_lds = D.bins + kHistCats;
     hist_lut_build<FMT>(lut, D);
     hist_lds_clear(lds, n_lds);
@@ -297,26 +291,10 @@ __global__ __launch_bounds__(kHistThreads) void hist_cells_kernel(const VolumeDe
             for (int b = 0; b < 8; b++)
                 if (((vx >> (b & 1)) & 1u) && ((vy >> ((b >> 1) & 1)) & 1u) && ((vz >> (b >> 2)) & 1u)) valid |= 1u << b;
             if (valid) {  // a tap inside the box: ix, iy, iz lie inside the volume, the cell exists
-                const char *cptr = reinterpret_cast<const char *>(V.data) + hist_cell_offset(V, ix, iy, iz);
-                if constexpr (VOL == VOL_P8) {
-                    const uint2 c = *reinterpret_cast<const uint2 *>(cptr);
+                uint32_t c[cell_words(VOL)];
+                load_cell<VOL>(cell_ptr(V, ix, iy, iz), c);
 #pragma unroll
-                    for (int b = 0; b < 4; b++) { t[b] = (c.x >> (8 * b)) & 0xffu; t[4 + b] = (c.y >> (8 * b)) & 0xffu; }
-                } else {
-                    const uint4 c = *reinterpret_cast<const uint4 *>(cptr);
-                    const uint32_t q[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        if constexpr (VOL == VOL_P16) {  // (tap, delta) pairs of f16 that hold u8 values: tap + delta is exact
-                            const float a = h2f(q[k] & 0xffffu), d = h2f(q[k] >> 16);
-                            t[2 * k] = (uint32_t)a;
-                            t[2 * k + 1] = (uint32_t)(a + d);
-                        } else {
-                            t[2 * k] = hist_element16<VOL>(q[k] & 0xffffu);
-                            t[2 * k + 1] = hist_element16<VOL>(q[k] >> 16);
-                        }
-                    }
-                }
+                for (int b = 0; b < 8; b++) t[b] = hist_element<VOL>(cell_tap_bits<VOL>(c, (uint32_t)b));
 #pragma unroll
                 for (int b = 0; b < 8; b++)
                     if (!((valid >> b) & 1u)) t[b] = 0u;  // (an element outside the box is 0: hist_count)
@@ -330,24 +308,15 @@ __global__ __launch_bounds__(kHistThreads) void hist_cells_kernel(const VolumeDe
     hist_finish(A, D);
 }
 
-static int hist_fail(vk_ctx *ctx, void *d, int code, const std::string &msg) {
-    if (d) (void)hipFree(d);
-    return fail(ctx, code, msg);
-}
-
 int vk_volume_histogram(vk_ctx *ctx, const vk_histogram *hist, const vk_voxel_box *box, uint64_t *counts, vk_volume_stats *stats) {
     if (!ctx) return VK_ERR_INVALID;
     HistConsts K{};
     if (const char *why = hist_validate(hist, format_scale(ctx->format), K)) return fail(ctx, VK_ERR_INVALID, std::string("vk_volume_histogram: ") + why);
-    if (ctx->format < 0) return fail(ctx, VK_ERR_INVALID, "vk_volume_histogram: no volume uploaded");
-    if (box && (hist->flags & VK_HIST_CLIP_BOX)) return fail(ctx, VK_ERR_INVALID, "vk_volume_histogram: VK_HIST_CLIP_BOX takes the box from the clip box: box must be NULL");
-    if (box && !hist_box_ok(*box, ctx->nx, ctx->ny, ctx->nz)) return fail(ctx, VK_ERR_INVALID, "vk_volume_histogram: the box is inverted or leaves the volume");
-    if (ctx->format == VK_FMT_RGBA16F_PAIR || !has_table_layout(ctx->vol_kind))
-        return fail(ctx, VK_ERR_UNSUPPORTED, "histogram: the pass needs a scalar LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED and RGBA16F_PAIR have no histogram kernels)");
-    vk_voxel_box B{0u, 0u, 0u, ctx->nx, ctx->ny, ctx->nz};
-    if (box) B = *box;
-    else if ((hist->flags & VK_HIST_CLIP_BOX) && ctx->clip_on) B = hist_clip_box(ctx->clip_lo, ctx->clip_hi, ctx->nx, ctx->ny, ctx->nz);
-    const uint64_t n_voxels = hist_box_voxels(B);
+    if (int rc = pass_needs(ctx, PASS_NEEDS_VOLUME, "vk_volume_histogram", "histogram")) return rc;
+    vk_voxel_box B;
+    if (int rc = pass_voxel_box(ctx, "vk_volume_histogram", "VK_HIST_CLIP_BOX", box, (hist->flags & VK_HIST_CLIP_BOX) != 0u, B)) return rc;
+    if (int rc = pass_needs(ctx, PASS_NEEDS_SCALAR_KIND, "vk_volume_histogram", "histogram")) return rc;
+    const uint64_t n_voxels = voxel_box_voxels(B);
 
     const int kind = ctx->vol_kind;
     const bool cells = is_cell_layout(kind);
@@ -382,34 +351,19 @@ int vk_volume_histogram(vk_ctx *ctx, const vk_histogram *hist, const vk_voxel_bo
     std::vector<unsigned long long> h(words, 0ull);
     if (D.items) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        void *d = nullptr;
-        HIP_TRY(ctx, hipMalloc(&d, words * sizeof(unsigned long long)));
-        D.out = reinterpret_cast<unsigned long long *>(d);
-        hipError_t e = hipMemsetAsync(d, 0, words * sizeof(unsigned long long), ctx->stream);
-        if (e != hipSuccess) return hist_fail(ctx, d, VK_ERR_HIP, std::string("vk_volume_histogram: ") + hipGetErrorString(e));
-        if (cells) {
-            VolumeDesc V = ctx->vdesc;
-            V.data = ctx->vol; V.data2 = ctx->vol2; V.dist = ctx->dist; V.lut = ctx->lut;
-            V.nx = ctx->nx; V.ny = ctx->ny; V.nz = ctx->nz;
-            V.nbx = ctx->nbx; V.nby = ctx->nby; V.nbz = ctx->nbz;
-            switch (kind) {
-                case VOL_P8: hipLaunchKernelGGL(hist_cells_kernel<VOL_P8>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, V, D); break;
-                case VOL_P16: hipLaunchKernelGGL(hist_cells_kernel<VOL_P16>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, V, D); break;
-                case VOL_PF16: hipLaunchKernelGGL(hist_cells_kernel<VOL_PF16>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, V, D); break;
-                default: hipLaunchKernelGGL(hist_cells_kernel<VOL_PU16>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, V, D); break;
-            }
-        } else {
-            switch (kind) {
-                case VOL_LINEAR_F16: hipLaunchKernelGGL(hist_linear_kernel<VOL_LINEAR_F16>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, (const void *)ctx->vol, D); break;
-                case VOL_LINEAR_U16: hipLaunchKernelGGL(hist_linear_kernel<VOL_LINEAR_U16>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, (const void *)ctx->vol, D); break;
-                default: hipLaunchKernelGGL(hist_linear_kernel<VOL_LINEAR_U8>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, (const void *)ctx->vol, D); break;
-            }
-        }
+        DeviceTemp d;
+        HIP_TRY(ctx, hipMalloc(&d.p, words * sizeof(unsigned long long)));
+        D.out = reinterpret_cast<unsigned long long *>(d.p);
+        hipError_t e = hipMemsetAsync(d.p, 0, words * sizeof(unsigned long long), ctx->stream);
+        if (e != hipSuccess) return fail(ctx, VK_ERR_HIP, std::string("vk_volume_histogram: ") + hipGetErrorString(e));
+        with_scalar_kind(kind, [&](auto VOL) {
+            if constexpr (is_cell_layout(VOL())) hipLaunchKernelGGL(hist_cells_kernel<VOL()>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, volume_desc(ctx), D);
+            else hipLaunchKernelGGL(hist_linear_kernel<VOL()>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, (const void *)ctx->vol, D);
+        });
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return hist_fail(ctx, d, VK_ERR_HIP, std::string("vk_volume_histogram: ") + hipGetErrorString(e));
-        HIP_TRY(ctx, hipFree(d));
+        if (e != hipSuccess) return fail(ctx, VK_ERR_HIP, std::string("vk_volume_histogram: ") + hipGetErrorString(e));
     }
     if (counts)
         for (uint32_t i = 0; i < K.bins; i++) counts[i] = h[i];

@@ -2,7 +2,8 @@
 // family of its own: a deterministic count, scan and emit stream compaction over the cubes of a voxel box, no ray and no atomic append.
 // The tetrahedra, the table, the vertex formula, the cube mapping and all launch arithmetic are vk_mesh.hpp's, shared with the host fuzz.
 //
-// Count.  One cube per lane and pass, four passes' loads in flight.  On the cell layouts the cell of the cube's low-corner voxel holds its eight corners: one load.  LINEAR reads
+// Count.  One cube per lane and pass, four passes' loads in flight.  Where a cell is, its load, its taps as f32 and a LINEAR element are
+// vk_texel.hpp's.  On the cell layouts the cell of the cube's low-corner voxel holds its eight corners: one load.  LINEAR reads
 // the two rows of two planes with plain loads -- neighbouring lanes are neighbouring cubes of a row, so the eight loads of a wave fall into
 // the same few cache lines and every texel comes from memory once.  A cube is rejected by the minimum and maximum of its corners before the
 // tetrahedra are looked at.  A workgroup takes a chunk -- a contiguous range of the box-ordered cube index -- per trip of its grid-stride
@@ -16,6 +17,7 @@
 // Loop bounds are block-uniform wherever a barrier stands.  Plain C++; no inline assembly.
 #include "vk_launch.hpp"
 #include "vk_mesh.hpp"
+#include "vk_texel.hpp"
 
 using namespace vk;
 
@@ -29,20 +31,7 @@ struct MeshDesc {
     uint32_t pad2;
     uint64_t n_cubes, n_chunks;
 };
-static_assert(sizeof(MeshDesc) % 8 == 0 && sizeof(VolumeDesc) + sizeof(MeshDesc) + 256 <= 4096, "mesh kernels: VolumeDesc + MeshDesc");
-
-// the byte offset of the cell with low-corner voxel (ix, iy, iz) (vk_common.hpp: VolumeDesc), held inside the cell array
-__device__ __forceinline__ int64_t mesh_cell_offset(const VolumeDesc &V, uint32_t ix, uint32_t iy, uint32_t iz) {
-    const int64_t off = (int64_t)(iz >> 2) * V.kz + (int64_t)(iy >> 2) * (int64_t)V.ky + (int64_t)(ix >> 2) * (int64_t)V.kx +
-                        (((int64_t)iz << V.sh_z) + ((int64_t)iy << V.sh_y) + ((int64_t)ix << V.sh_x)) + V.c0;
-    return off < 0 ? 0 : (off > V.max_off ? V.max_off : off);
-}
-
-template <int VOL>
-__device__ __forceinline__ float mesh_texel16(uint32_t bits) {
-    if constexpr (VOL == VOL_LINEAR_F16 || VOL == VOL_PF16) return h2f(bits & 0xffffu);
-    else return (float)(bits & 0xffffu);
-}
+static_assert(sizeof(MeshDesc) % 8 == 0 && pass_kernargs_fit<MeshDesc>, "mesh kernels: VolumeDesc + MeshDesc");
 
 // The eight corners of the cube with low-corner voxel (x, y, z), in two steps so that a kernel can issue several cubes' loads before it looks
 // at the first: mesh_fetch loads the raw words, mesh_unpack turns them into f32, corner i + 2 j + 4 k at v[...].  x + 1 < nx (likewise y,
@@ -50,50 +39,25 @@ __device__ __forceinline__ float mesh_texel16(uint32_t bits) {
 // indices lie inside the array.
 template <int VOL>
 struct MeshTaps {
-    uint32_t w[is_cell_layout(VOL) ? (VOL == VOL_P8 ? 2 : 4) : 8];  // a cell's words, or the eight texels' bits
+    uint32_t w[is_cell_layout(VOL) ? cell_words(VOL) : 8];  // a cell's words, or the eight texels' bits
 };
 template <int VOL>
 __device__ __forceinline__ void mesh_fetch(const VolumeDesc &V, uint32_t x, uint32_t y, uint32_t z, MeshTaps<VOL> &T) {
-    if constexpr (is_cell_layout(VOL)) {
-        const char *cptr = reinterpret_cast<const char *>(V.data) + mesh_cell_offset(V, x, y, z);
-        if constexpr (VOL == VOL_P8) {
-            const uint2 c = *reinterpret_cast<const uint2 *>(cptr);
-            T.w[0] = c.x; T.w[1] = c.y;
-        } else {
-            const uint4 c = *reinterpret_cast<const uint4 *>(cptr);
-            T.w[0] = c.x; T.w[1] = c.y; T.w[2] = c.z; T.w[3] = c.w;
-        }
-    } else {
+    if constexpr (is_cell_layout(VOL)) load_cell<VOL>(cell_ptr(V, x, y, z), T.w);
+    else {
         const uint64_t row = V.nx, plane = (uint64_t)V.nx * V.ny;
-        const uint64_t i0 = (uint64_t)x + row * ((uint64_t)y + (uint64_t)V.ny * (uint64_t)z);
+        const uint64_t i0 = voxel_index(x, y, z, V.nx, V.ny);
 #pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const uint64_t i = i0 + (b & 1) + ((b >> 1) & 1) * row + (b >> 2) * plane;
-            if constexpr (VOL == VOL_LINEAR_U8) T.w[b] = reinterpret_cast<const uint8_t *>(V.data)[i];
-            else T.w[b] = reinterpret_cast<const uint16_t *>(V.data)[i];
-        }
+        for (int b = 0; b < 8; b++) T.w[b] = linear_texel_bits<VOL>(V.data, i0 + (b & 1) + ((b >> 1) & 1) * row + (b >> 2) * plane);
     }
 }
 template <int VOL>
 __device__ __forceinline__ void mesh_unpack(const MeshTaps<VOL> &T, float (&v)[8]) {
-    if constexpr (VOL == VOL_P8) {
 #pragma unroll
-        for (int b = 0; b < 4; b++) { v[b] = (float)((T.w[0] >> (8 * b)) & 0xffu); v[4 + b] = (float)((T.w[1] >> (8 * b)) & 0xffu); }
-    } else if constexpr (is_cell_layout(VOL)) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if constexpr (VOL == VOL_P16) {  // (tap, delta) pairs of f16 that hold u8 values: tap + delta is exact
-                const float a = h2f(T.w[k] & 0xffffu), d = h2f(T.w[k] >> 16);
-                v[2 * k] = a;
-                v[2 * k + 1] = a + d;
-            } else {
-                v[2 * k] = mesh_texel16<VOL>(T.w[k]);
-                v[2 * k + 1] = mesh_texel16<VOL>(T.w[k] >> 16);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int b = 0; b < 8; b++) v[b] = VOL == VOL_LINEAR_U8 ? (float)T.w[b] : mesh_texel16<VOL>(T.w[b]);
+    for (int i = 0; i < 8; i++) {
+        const int b = VOL == VOL_P8 ? (i >> 1) + 4 * (i & 1) : i;  // (P8: the two words' bytes in turn -- the count kernel's schedule follows the order)
+        if constexpr (is_cell_layout(VOL)) v[b] = cell_tap_f32<VOL>(T.w, (uint32_t)b);
+        else v[b] = texel_f32<VOL>(T.w[b]);
     }
 }
 template <int VOL>
@@ -112,7 +76,7 @@ __device__ __forceinline__ uint32_t mesh_classify(const VolumeDesc &V, const Mes
     mesh_cube_xyz(B, in_chunk, D.cx, D.cy, x, y, z);
     x += D.x0; y += D.y0; z += D.z0;
     mesh_corners<VOL>(V, x, y, z, v);
-    return mesh_cube_inside<VOL == VOL_LINEAR_F16 || VOL == VOL_PF16>(v, D.iso_k);
+    return mesh_cube_inside<is_f16_kind(VOL)>(v, D.iso_k);
 }
 
 // The workgroup's exclusive prefix of c in thread order, and the total.  Two barriers: w_tot is free again on return.
@@ -166,7 +130,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_count_kernel(const VolumeDe
             for (uint32_t u = 0; u < kMeshCountUnroll; u++) {
                 float v[8];
                 mesh_unpack<VOL>(taps[u], v);
-                const uint32_t n = mesh_cube_count(mesh_cube_inside<VOL == VOL_LINEAR_F16 || VOL == VOL_PF16>(v, D.iso_k));
+                const uint32_t n = mesh_cube_count(mesh_cube_inside<is_f16_kind(VOL)>(v, D.iso_k));
                 mine += has[u] ? n : 0u;
             }
         }
@@ -294,46 +258,14 @@ __global__ __launch_bounds__(kMeshScanThreads) void mesh_scan_kernel(const uint3
     if (threadIdx.x == 0u) { hdr->n_triangles = run; hdr->n_active = n_act; }
 }
 
-static int mesh_fail(vk_ctx *ctx, void *d0, void *d1, int code, const std::string &msg) {
-    if (d0) (void)hipFree(d0);
-    if (d1) (void)hipFree(d1);
-    return fail(ctx, code, msg);
-}
-
-template <int VOL>
-static void mesh_launch_count(vk_ctx *ctx, uint32_t grid, const VolumeDesc &V, const MeshDesc &D, uint32_t *totals) {
-    hipLaunchKernelGGL(mesh_count_kernel<VOL>, dim3(grid), dim3(kMeshThreads), 0, ctx->stream, V, D, totals);
-}
-template <int VOL>
-static void mesh_launch_emit(vk_ctx *ctx, uint32_t grid, const VolumeDesc &V, const MeshDesc &D, const MeshActive *act, uint64_t n_active, float *out, uint64_t cap) {
-    hipLaunchKernelGGL(mesh_emit_kernel<VOL>, dim3(grid), dim3(kMeshThreads), 0, ctx->stream, V, D, act, n_active, out, cap);
-}
-// f(int_tag<VOL>) over the seven volume kinds the pass covers
-template <class F>
-static void mesh_for_kind(int kind, F &&f) {
-    switch (kind) {
-        case VOL_P8: f(int_tag<VOL_P8>()); break;
-        case VOL_P16: f(int_tag<VOL_P16>()); break;
-        case VOL_PF16: f(int_tag<VOL_PF16>()); break;
-        case VOL_PU16: f(int_tag<VOL_PU16>()); break;
-        case VOL_LINEAR_F16: f(int_tag<VOL_LINEAR_F16>()); break;
-        case VOL_LINEAR_U16: f(int_tag<VOL_LINEAR_U16>()); break;
-        default: f(int_tag<VOL_LINEAR_U8>()); break;
-    }
-}
-
 int vk_extract_isosurface(vk_ctx *ctx, const vk_mesh_request *req, const vk_voxel_box *box, float *triangles, uint64_t cap_triangles, uint64_t *n_triangles) {
     if (!ctx) return VK_ERR_INVALID;
     if (const char *why = mesh_validate(req)) return fail(ctx, VK_ERR_INVALID, std::string("vk_extract_isosurface: ") + why);
     if (!n_triangles) return fail(ctx, VK_ERR_INVALID, "vk_extract_isosurface: n_triangles is NULL");
-    if (ctx->format < 0) return fail(ctx, VK_ERR_INVALID, "vk_extract_isosurface: no volume uploaded");
-    if (box && (req->flags & VK_MESH_CLIP_BOX)) return fail(ctx, VK_ERR_INVALID, "vk_extract_isosurface: VK_MESH_CLIP_BOX takes the box from the clip box: box must be NULL");
-    if (box && !hist_box_ok(*box, ctx->nx, ctx->ny, ctx->nz)) return fail(ctx, VK_ERR_INVALID, "vk_extract_isosurface: the box is inverted or leaves the volume");
-    if (ctx->format == VK_FMT_RGBA16F_PAIR || !has_table_layout(ctx->vol_kind))
-        return fail(ctx, VK_ERR_UNSUPPORTED, "mesh: the pass needs a scalar LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED and RGBA16F_PAIR have no mesh kernels)");
-    vk_voxel_box B{0u, 0u, 0u, ctx->nx, ctx->ny, ctx->nz};
-    if (box) B = *box;
-    else if ((req->flags & VK_MESH_CLIP_BOX) && ctx->clip_on) B = hist_clip_box(ctx->clip_lo, ctx->clip_hi, ctx->nx, ctx->ny, ctx->nz);
+    if (int rc = pass_needs(ctx, PASS_NEEDS_VOLUME, "vk_extract_isosurface", "mesh")) return rc;
+    vk_voxel_box B;
+    if (int rc = pass_voxel_box(ctx, "vk_extract_isosurface", "VK_MESH_CLIP_BOX", box, (req->flags & VK_MESH_CLIP_BOX) != 0u, B)) return rc;
+    if (int rc = pass_needs(ctx, PASS_NEEDS_SCALAR_KIND, "vk_extract_isosurface", "mesh")) return rc;
 
     MeshDesc D{};
     D.iso_k = iso_k(req->iso, format_scale(ctx->format));
@@ -349,20 +281,19 @@ int vk_extract_isosurface(vk_ctx *ctx, const vk_mesh_request *req, const vk_voxe
 
     const int kind = ctx->vol_kind;
     const uint32_t cus = (uint32_t)ctx->prop.multiProcessorCount;
-    VolumeDesc V = ctx->vdesc;
-    V.data = ctx->vol; V.data2 = ctx->vol2; V.dist = ctx->dist; V.lut = ctx->lut;
-    V.nx = ctx->nx; V.ny = ctx->ny; V.nz = ctx->nz;
-    V.nbx = ctx->nbx; V.nby = ctx->nby; V.nbz = ctx->nbz;
+    const VolumeDesc V = volume_desc(ctx);
 
     // one work buffer: the header, the list of active chunks, the chunk totals
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t work_bytes = sizeof(MeshScanHeader) + (size_t)D.n_chunks * sizeof(MeshActive) + (size_t)mesh_totals_padded(D.n_chunks) * sizeof(uint32_t);
-    void *work = nullptr;
-    HIP_TRY(ctx, hipMalloc(&work, work_bytes));
-    MeshScanHeader *d_hdr = reinterpret_cast<MeshScanHeader *>(work);
+    DeviceTemp work;
+    HIP_TRY(ctx, hipMalloc(&work.p, work_bytes));
+    MeshScanHeader *d_hdr = reinterpret_cast<MeshScanHeader *>(work.p);
     MeshActive *d_act = reinterpret_cast<MeshActive *>(d_hdr + 1);
     uint32_t *d_totals = reinterpret_cast<uint32_t *>(d_act + D.n_chunks);
-    mesh_for_kind(kind, [&](auto vol) { mesh_launch_count<decltype(vol)::value>(ctx, mesh_grid(D.n_chunks, cus, ctx->mesh_max_blocks), V, D, d_totals); });
+    with_scalar_kind(kind, [&](auto VOL) {
+        hipLaunchKernelGGL(mesh_count_kernel<VOL()>, dim3(mesh_grid(D.n_chunks, cus, ctx->mesh_max_blocks)), dim3(kMeshThreads), 0, ctx->stream, V, D, d_totals);
+    });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) {
         hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(kMeshScanThreads), 0, ctx->stream, (const uint32_t *)d_totals, D.n_chunks, d_act, d_hdr);
@@ -371,27 +302,26 @@ int vk_extract_isosurface(vk_ctx *ctx, const vk_mesh_request *req, const vk_voxe
     MeshScanHeader hdr{};
     if (e == hipSuccess) e = hipMemcpyAsync(&hdr, d_hdr, sizeof(hdr), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return mesh_fail(ctx, work, nullptr, VK_ERR_HIP, std::string("vk_extract_isosurface: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, VK_ERR_HIP, std::string("vk_extract_isosurface: ") + hipGetErrorString(e));
 
     const uint64_t n_write = hdr.n_triangles < cap_triangles ? hdr.n_triangles : cap_triangles;
     if (triangles && n_write) {  // (no triangle to write: no emit launch)
         const size_t out_bytes = (size_t)n_write * 9u * sizeof(float);
-        void *d_out = nullptr;
-        e = hipMalloc(&d_out, out_bytes);
+        DeviceTemp d_out;
+        e = hipMalloc(&d_out.p, out_bytes);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            return mesh_fail(ctx, work, nullptr, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("vk_extract_isosurface: the output buffer: ") + hipGetErrorString(e));
+            return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("vk_extract_isosurface: the output buffer: ") + hipGetErrorString(e));
         }
-        mesh_for_kind(kind, [&](auto vol) {
-            mesh_launch_emit<decltype(vol)::value>(ctx, mesh_grid(hdr.n_active, cus, ctx->mesh_max_blocks), V, D, d_act, hdr.n_active, reinterpret_cast<float *>(d_out), n_write);
+        with_scalar_kind(kind, [&](auto VOL) {
+            hipLaunchKernelGGL(mesh_emit_kernel<VOL()>, dim3(mesh_grid(hdr.n_active, cus, ctx->mesh_max_blocks)), dim3(kMeshThreads), 0, ctx->stream, V, D, (const MeshActive *)d_act,
+                               hdr.n_active, reinterpret_cast<float *>(d_out.p), n_write);
         });
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(triangles, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(triangles, d_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return mesh_fail(ctx, work, d_out, VK_ERR_HIP, std::string("vk_extract_isosurface: ") + hipGetErrorString(e));
-        HIP_TRY(ctx, hipFree(d_out));
+        if (e != hipSuccess) return fail(ctx, VK_ERR_HIP, std::string("vk_extract_isosurface: ") + hipGetErrorString(e));
     }
-    HIP_TRY(ctx, hipFree(work));
     *n_triangles = hdr.n_triangles;
     return VK_OK;
 }

@@ -13,7 +13,7 @@
 
 using namespace vk;
 
-static_assert(sizeof(VolumeDesc) + sizeof(SliceDesc) + 256 <= 4096, "slice_kernel: VolumeDesc + SliceDesc");
+static_assert(pass_kernargs_fit<SliceDesc>, "slice_kernel: VolumeDesc + SliceDesc");
 
 template <int VOL>
 __device__ __forceinline__ float slice_sample(const VolumeDesc &V, const float x, const float y, const float z) {
@@ -83,19 +83,10 @@ __global__ __launch_bounds__(64) void slice_kernel(const VolumeDesc V, const Sli
 // The caller (vk_render_slice) has refused the layouts without slice kernels and clipped the tile to the backbuffer.
 void launch_slice(vk_ctx *ctx, const VolumeDesc &V, const SliceDesc &S) {
     const dim3 grid((S.x1 - S.x0 + 7u) / 8u, (S.y1 - S.y0 + 7u) / 8u);
-    auto launch = [&](auto VOL) {
+    with_scalar_kind(ctx->vol_kind, [&](auto VOL) {
         with_out(ctx, [&](auto OUT) {
             if (S.values) hipLaunchKernelGGL((slice_kernel<VOL(), OUT(), true>), grid, dim3(64), 0, ctx->stream, V, S);
             else hipLaunchKernelGGL((slice_kernel<VOL(), OUT(), false>), grid, dim3(64), 0, ctx->stream, V, S);
         });
-    };
-    switch (ctx->vol_kind) {
-        case VOL_P8: launch(int_tag<VOL_P8>()); break;
-        case VOL_P16: launch(int_tag<VOL_P16>()); break;
-        case VOL_PF16: launch(int_tag<VOL_PF16>()); break;
-        case VOL_PU16: launch(int_tag<VOL_PU16>()); break;
-        case VOL_LINEAR_F16: launch(int_tag<VOL_LINEAR_F16>()); break;
-        case VOL_LINEAR_U16: launch(int_tag<VOL_LINEAR_U16>()); break;
-        default: launch(int_tag<VOL_LINEAR_U8>()); break;
-    }
+    });
 }

@@ -8,6 +8,7 @@
 #pragma once
 
 #include "vk_common.hpp"
+#include "vk_texel.hpp"  // CellBits, load_cell through a pointer
 
 namespace vk {
 
@@ -88,11 +89,6 @@ __device__ __forceinline__ SkipBound skip_bound(float sx, float sy, float sz, fl
 }
 
 // ---- the cells of the PACKED layouts ------------------------------------------------------------------------------------------
-template <int VOL>
-struct CellBits { u32x4_t v; };
-template <>
-struct CellBits<VOL_P8> { u32x2_t v; };
-
 // PIN: mark the load volatile (aux bit 31: compiler-only, nothing changes in the encoding) so that it
 // is issued where it is written -- a prefetch must not be sunk behind the loop's exit branch.
 template <int VOL, bool PIN = false>
@@ -105,19 +101,13 @@ __device__ __forceinline__ CellBits<VOL> load_cell(__amdgpu_buffer_rsrc_t rs, ui
 }
 
 // SAFE (no index tables): the byte offset of voxel (ix, iy, iz)'s cell, the 64-bit closed form of the tables' sum, clamped into
-// the cell array whatever the indices are; and the cell at that offset through a plain pointer
+// the cell array whatever the indices are; the cell at that offset comes through a plain pointer (vk_texel.hpp: load_cell, and cell_offset,
+// this function's twin on uint32_t indices in 64-bit arithmetic)
 __device__ __forceinline__ int64_t safe_cell_offset(const VolumeDesc &V, int ix, int iy, int iz) {
     const int bx = ix >> 2, by = iy >> 2, bz = iz >> 2;
     int64_t off = (int64_t)bz * (int64_t)V.kz + (int64_t)(by * (int)V.ky + bx * (int)V.kx) +
                   (int64_t)((iz << V.sh_z) + (iy << V.sh_y) + (ix << V.sh_x)) + (int64_t)V.c0;
     return off < 0 ? 0 : (off > (int64_t)V.max_off ? (int64_t)V.max_off : off);
-}
-template <int VOL>
-__device__ __forceinline__ CellBits<VOL> load_cell(const char *cptr) {
-    CellBits<VOL> cb;
-    if constexpr (VOL == VOL_P8) { const uint2 c = *reinterpret_cast<const uint2 *>(cptr); cb.v.x = c.x; cb.v.y = c.y; }
-    else { const uint4 c = *reinterpret_cast<const uint4 *>(cptr); cb.v.x = c.x; cb.v.y = c.y; cb.v.z = c.z; cb.v.w = c.w; }
-    return cb;
 }
 
 // Where voxel (ix, iy, iz)'s cell is, and under DIST its distance byte in the ray's map (`doff`: the octant's offset).  SAFE: the clamped

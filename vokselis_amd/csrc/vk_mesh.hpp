@@ -18,7 +18,7 @@
 #include <string.h>
 
 #include "../../include/vokselis_hip.h"
-#include "vk_hist.hpp"  // hist_box_ok, hist_clip_box: the box rules are the histogram's
+#include "vk_box.hpp"
 
 #if defined(__HIPCC__)
 #define VK_MESH_HD __host__ __device__ __forceinline__

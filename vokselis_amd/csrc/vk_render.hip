@@ -69,11 +69,7 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
     // at most ~1.5 cells (vk_march.hpp: locate)
     if (!(L.dt_scale <= 1.25f)) L.flags &= ~(uint32_t)LF_PROBE_AHEAD;
     const bool count = (flags & VK_RENDER_COUNT) != 0;
-    VolumeDesc V = ctx->vdesc;
-    V.data = ctx->vol; V.data2 = ctx->vol2; V.dist = ctx->dist;
-    V.lut = ctx->lut;  // the no-skip variants take the byte-offset copy (set where the variant is chosen)
-    V.nx = ctx->nx; V.ny = ctx->ny; V.nz = ctx->nz;
-    V.nbx = ctx->nbx; V.nby = ctx->nby; V.nbz = ctx->nbz;
+    VolumeDesc V = volume_desc(ctx);  // (V.lut: the no-skip variants take the byte-offset copy, set where the variant is chosen)
     const uint64_t n_blocks = L.n_blocks;
     uint32_t grid = (uint32_t)((n_blocks + 511) / 512 * 512);
     L.grid_march = grid;
@@ -418,14 +414,13 @@ int vk_pick(vk_ctx *ctx, uint32_t x, uint32_t y, float dt_scale, vk_hit *out) {
 int vk_render_slice(vk_ctx *ctx, const vk_slice *slice, int32_t tile_x, int32_t tile_y, uint32_t tile_w, uint32_t tile_h, uint32_t flags) {
     if (!ctx) return VK_ERR_INVALID;
     if (flags & ~(uint32_t)VK_SLICE_VALUES) return fail(ctx, VK_ERR_INVALID, "vk_render_slice: takes VK_SLICE_VALUES only");
-    if (ctx->format < 0) return fail(ctx, VK_ERR_INVALID, "vk_render_slice: no volume uploaded");
+    if (int rc = pass_needs(ctx, PASS_NEEDS_VOLUME, "vk_render_slice", "slice")) return rc;
     if (!ctx->backbuffer) return fail(ctx, VK_ERR_INVALID, "vk_render_slice: no backbuffer (vk_backbuffer_resize)");
     SliceDesc S{};
     const bool tf = ctx->d_tf != nullptr;
     if (const char *why = slice_validate(slice, tf ? ctx->tf_n : 0u, ctx->tf_lo, ctx->tf_hi, format_scale(ctx->format), S))
         return fail(ctx, VK_ERR_INVALID, std::string("vk_render_slice: ") + why);
-    if (ctx->format == VK_FMT_RGBA16F_PAIR || !has_table_layout(ctx->vol_kind))
-        return fail(ctx, VK_ERR_UNSUPPORTED, "slice: the slice pass needs a scalar LINEAR, PACKED or PACKED_PAIRS volume (BRICKED / QUADS / STAGED and RGBA16F_PAIR have no slice kernels)");
+    if (int rc = pass_needs(ctx, PASS_NEEDS_SCALAR_KIND, "vk_render_slice", "slice", "slice pass")) return rc;
     if (!slice_tile_clip(tile_x, tile_y, tile_w, tile_h, ctx->width, ctx->height, S.x0, S.y0, S.x1, S.y1)) return VK_OK;  // no pixel of the tile on the backbuffer
     if ((S.y1 - S.y0 + 7u) / 8u > 65535u) return fail(ctx, VK_ERR_UNSUPPORTED, "slice: tile too tall for one launch");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -438,11 +433,7 @@ int vk_render_slice(vk_ctx *ctx, const vk_slice *slice, int32_t tile_x, int32_t 
     S.out = ctx->backbuffer;
     S.values = (flags & VK_SLICE_VALUES) ? ctx->slice_values : nullptr;
     S.W = ctx->width; S.H = ctx->height;
-    VolumeDesc V = ctx->vdesc;
-    V.data = ctx->vol; V.data2 = ctx->vol2; V.dist = ctx->dist; V.lut = ctx->lut;
-    V.nx = ctx->nx; V.ny = ctx->ny; V.nz = ctx->nz;
-    V.nbx = ctx->nbx; V.nby = ctx->nby; V.nbz = ctx->nbz;
-    launch_slice(ctx, V, S);
+    launch_slice(ctx, volume_desc(ctx), S);
     HIP_TRY(ctx, hipGetLastError());
     return VK_OK;
 }
