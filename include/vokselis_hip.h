@@ -594,6 +594,67 @@ struct vk_volume_filter {  /* no typedef: the function below bears the same name
 int vk_volume_filter(vk_ctx *ctx, const struct vk_volume_filter *f, void *dense_out);
 int vk_filter_gaussian(double sigma_voxels, uint32_t radius, float *weights /* 2 radius + 1 */);
 
+/* Connected components of a value range: the voxels whose stored texel lies in [lo, hi] are labelled by component,
+ * and components are kept or dropped -- "only the largest connected thing above 0.3", "nothing smaller than 500 voxels", "the thing under
+ * this pixel" -- so that the mesh, the histogram and every march see the cleaned volume without a round trip through the host.  Every
+ * result is an integer or a stored texel: there is no rounding anywhere but in the fill.
+ * Foreground.  t is the STORED texel as f32 on the kernel's scale (R8 0..255, R16_UNORM 0..65535, R16F the value).  lo_k and hi_k are
+ * formed from lo and hi exactly as vk_set_isosurface forms iso_k: lo * 255.0f, lo * 65535.0f, or lo.  A voxel is foreground iff it lies
+ * in the voxel box and t >= lo_k && t <= hi_k: a NaN never is, an R16F infinity is when the range reaches it.  The box is
+ * vk_volume_histogram's: `box`, the clip box under VK_LABEL_CLIP_BOX (box must then be NULL), or NULL for the whole volume; an empty
+ * box means no foreground.
+ * Neighbours.  Two foreground voxels are adjacent when their index difference d has max |d_c| = 1 and sum |d_c| <= 1 (connectivity
+ * 6), <= 2 (18) or <= 3 (26).  No wrap and no clamping at the volume's or the box's edge.  A component is a class of the transitive
+ * closure of adjacency.
+ * Numbering.  `first` of a component is its smallest linear index x + nx (y + ny z).  Components are numbered 1 .. n by increasing
+ * first: raster order of first encounter.  labels_out (may be NULL): nx ny nz uint32, x fastest, over the whole volume; 0 is background,
+ * which includes every voxel outside the box.  components (may be NULL): the first min(n, cap_components) entries in id order, each
+ * n_voxels, first and the tight half-open bounding box.  result (may be NULL): n_components, n_foreground (the voxels of all
+ * components), n_kept_components, n_kept_voxels.  The output is bit for bit the same on every layout, launch shape and run.
+ * Selection.  VK_LABEL_KEEP_ALL: every component.  _KEEP_LARGEST: the first min(count, n) components in the order
+ * n_voxels descending, then first ascending.  _KEEP_MIN_SIZE: the components with n_voxels >= count.  _KEEP_SEEDS: the components that contain
+ * one of the seeds[0 .. n_seeds) voxels; a seed on background (also: outside the box) selects nothing.  M(v) holds iff v belongs to a
+ * selected component.  The output texel is M(v) ? the stored bits unchanged : F; under VK_LABEL_INVERT it is M(v) ? F : stored.  F is
+ * `fill` through vk_volume_filter's store rule: R8 (uint8) rintf(fminf(fmaxf(fill * 255.0f, 0.0f), 255.0f)), ties to even;
+ * R16_UNORM the same with 65535; R16F round to nearest even.  (PACKED_PAIRS: the stored texel is the u8 value tap + delta.)
+ * n_kept_components and n_kept_voxels count the selected components and their voxels, inverted or not.
+ * Output and state.  dense_out (may be NULL; host memory of nx ny nz elements of the volume's format) and VK_LABEL_INSTALL behave
+ * exactly as vk_volume_filter's dense_out and VK_FILTER_INSTALL: the same re-layout, the same state kept in force, the old volume
+ * stays on any failure.  Without VK_LABEL_INSTALL no context state changes.  The call blocks, runs on the context's current stream
+ * and allocates and frees its own buffers.
+ * VK_ERR_INVALID, decided before any launch, outputs untouched: a NULL request; lo or hi NaN, lo > hi, a fill that is not finite; a
+ * connectivity other than 6, 18, 26; an unknown flag or keep value; pad != 0; count or n_seeds that does not fit the keep mode (see the
+ * struct); a seed outside the volume; components != NULL with cap_components == 0; none of labels_out, components, dense_out,
+ * VK_LABEL_INSTALL and result requested; VK_LABEL_INSTALL while a frame is being recorded; a box that is inverted or leaves the
+ * volume, a box together with VK_LABEL_CLIP_BOX; no volume.  VK_ERR_UNSUPPORTED ("label: ..."): a BRICKED / QUADS / STAGED or
+ * RGBA16F_PAIR volume; a volume of more than 2^32 - 2 voxels (labels are 32-bit).  VK_ERR_OOM: a buffer cannot be allocated.
+ * "Outputs untouched" holds for these refusals.  A call that fails later -- an allocation, a launch, or under VK_LABEL_INSTALL the
+ * re-layout of the result, which runs last -- may have written labels_out, components, dense_out and *result already; the context's
+ * volume is the old one whenever the call does not return VK_OK. */
+#define VK_LABEL_MAX_SEEDS 16
+enum { VK_LABEL_KEEP_ALL = 0, VK_LABEL_KEEP_LARGEST = 1, VK_LABEL_KEEP_MIN_SIZE = 2, VK_LABEL_KEEP_SEEDS = 3 };
+enum { VK_LABEL_CLIP_BOX = 1, VK_LABEL_INSTALL = 2, VK_LABEL_INVERT = 4 };
+typedef struct vk_label_request {
+    float    lo, hi;          /* sample values, like vk_isosurface.iso; -inf / +inf allowed, NaN and lo > hi refused */
+    uint32_t connectivity;    /* 6, 18 or 26 */
+    uint32_t flags;           /* VK_LABEL_CLIP_BOX | VK_LABEL_INSTALL | VK_LABEL_INVERT */
+    int32_t  keep;            /* VK_LABEL_KEEP_* */
+    uint32_t n_seeds;         /* KEEP_SEEDS: 1 .. VK_LABEL_MAX_SEEDS; otherwise 0 */
+    uint64_t count;           /* KEEP_LARGEST: how many (>= 1); KEEP_MIN_SIZE: the least number of voxels (>= 1); otherwise 0 */
+    float    fill;            /* sample value that replaces a voxel that is not kept; finite */
+    uint32_t pad;             /* 0 */
+    uint32_t seeds[VK_LABEL_MAX_SEEDS][3];   /* voxel indices x, y, z, inside the volume */
+} vk_label_request;           /* 232 bytes */
+typedef struct vk_component {
+    uint64_t n_voxels, first;
+    vk_voxel_box box;         /* tight, half-open */
+} vk_component;               /* 40 bytes */
+typedef struct vk_label_result {
+    uint64_t n_components, n_foreground, n_kept_components, n_kept_voxels;
+} vk_label_result;            /* 32 bytes */
+int vk_label_components(vk_ctx *ctx, const vk_label_request *req, const vk_voxel_box *box, uint32_t *labels_out, vk_component *components,
+                        uint64_t cap_components, void *dense_out, vk_label_result *result);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

@@ -10,6 +10,7 @@ Only the raycast hot path and the host surface that drives it live here (SURVEY.
   histogram  Histogram: the result of Context.volume_histogram (counts, statistics, percentile window)
   mesh       weld, write_stl, write_obj: the triangles of Context.extract_isosurface as a welded mesh, binary STL, OBJ
   filter     gaussian_weights, filter_request: the weights and the request of Context.filter_volume / smooth_volume / median_volume
+  label      Components, label_request, voxel_of: the result and the request of Context.label_components / keep_components
   dist       tile-parallel multi-GPU frame (one process per GPU, RCCL gather over xGMI)
 """
 from . import _native as native
@@ -19,12 +20,15 @@ from ._native import (FMT_R8_UNORM, FMT_R16_FLOAT, FMT_RGBA16F_PAIR, FMT_R16_UNO
                       RENDER_NO_SKIP, RENDER_PROBE_ALWAYS, RENDER_FAST_WALK, RENDER_PRESENT, RENDER_PRESENT_BGRA, RENDER_PRESENT_ONLY, RENDER_DEVICE_SINE, WIRE_RGB, WIRE_RGBA, TF_MAX_ENTRIES, PROJ_COMPOSITE, PROJ_MAX, ISO_MAX_REFINE, VkLighting, VkIsosurface, VkClipBox, VkHit, VokselisError,
                       SLAB_MAX, SLAB_MIN, SLAB_MEAN, SLICE_VALUES, SLICE_MAX_SAMPLES, VkSlice, VkSliceSample,
                       HIST_MAX_BINS, HIST_CLIP_BOX, VkHistogram, VkVoxelBox, VkVolumeStats, MESH_CLIP_BOX, VkMeshRequest,
-                      FILTER_MAX_RADIUS, FILTER_MAX_WEIGHT, FILTER_CONVOLVE, FILTER_MEDIAN3, FILTER_INSTALL, VkVolumeFilter)
+                      FILTER_MAX_RADIUS, FILTER_MAX_WEIGHT, FILTER_CONVOLVE, FILTER_MEDIAN3, FILTER_INSTALL, VkVolumeFilter,
+                      LABEL_MAX_SEEDS, LABEL_KEEP_ALL, LABEL_KEEP_LARGEST, LABEL_KEEP_MIN_SIZE, LABEL_KEEP_SEEDS, LABEL_CLIP_BOX, LABEL_INSTALL, LABEL_INVERT,
+                      VkLabelRequest, VkComponent, VkLabelResult)
 from .camera import Camera
 from .slices import Slice
 from .histogram import Histogram
 from .mesh import weld, write_obj, write_stl
 from .filter import gaussian_weights
+from .label import Components, voxel_of
 from .context import (Context, Demo, FrameCounter, HdrBackBuffer, Hit, ImageDimentions, RaycastPipeline, Uniform,
                       VolumeTexture, dispatch_optimal, partition_slots, render_batch, run_headless, transfer_table, untile_batch)
 
@@ -38,4 +42,6 @@ __all__ = [
     "HIST_MAX_BINS", "HIST_CLIP_BOX", "VkHistogram", "VkVoxelBox", "VkVolumeStats", "Histogram",
     "MESH_CLIP_BOX", "VkMeshRequest", "weld", "write_stl", "write_obj",
     "FILTER_MAX_RADIUS", "FILTER_MAX_WEIGHT", "FILTER_CONVOLVE", "FILTER_MEDIAN3", "FILTER_INSTALL", "VkVolumeFilter", "gaussian_weights",
+    "LABEL_MAX_SEEDS", "LABEL_KEEP_ALL", "LABEL_KEEP_LARGEST", "LABEL_KEEP_MIN_SIZE", "LABEL_KEEP_SEEDS", "LABEL_CLIP_BOX", "LABEL_INSTALL", "LABEL_INVERT",
+    "VkLabelRequest", "VkComponent", "VkLabelResult", "Components", "voxel_of",
 ]

@@ -149,6 +149,31 @@ class VkVolumeFilter(C.Structure):
 assert C.sizeof(VkVolumeFilter) == 176
 
 
+LABEL_MAX_SEEDS = 16
+LABEL_KEEP_ALL, LABEL_KEEP_LARGEST, LABEL_KEEP_MIN_SIZE, LABEL_KEEP_SEEDS = 0, 1, 2, 3
+LABEL_CLIP_BOX, LABEL_INSTALL, LABEL_INVERT = 1, 2, 4
+
+
+class VkLabelRequest(C.Structure):
+    """vk_label_request (232 bytes): the request of vk_label_components -- the value range, the connectivity, the flags, what to keep
+    (with its count or its seeds) and the fill."""
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("connectivity", C.c_uint32), ("flags", C.c_uint32), ("keep", C.c_int32), ("n_seeds", C.c_uint32),
+                ("count", C.c_uint64), ("fill", C.c_float), ("pad", C.c_uint32), ("seeds", (C.c_uint32 * 3) * LABEL_MAX_SEEDS)]
+
+
+class VkComponent(C.Structure):
+    """vk_component (40 bytes): a component's voxels, its smallest linear index and its tight half-open bounding box."""
+    _fields_ = [("n_voxels", C.c_uint64), ("first", C.c_uint64), ("box", VkVoxelBox)]
+
+
+class VkLabelResult(C.Structure):
+    """vk_label_result (32 bytes): the totals of vk_label_components."""
+    _fields_ = [("n_components", C.c_uint64), ("n_foreground", C.c_uint64), ("n_kept_components", C.c_uint64), ("n_kept_voxels", C.c_uint64)]
+
+
+assert C.sizeof(VkLabelRequest) == 232 and C.sizeof(VkComponent) == 40 and C.sizeof(VkLabelResult) == 32
+
+
 def clip_box(lo, hi) -> VkClipBox:
     """A VkClipBox from two triples, held to vk_set_clip_box's rules before the library sees it: finite components (as f32) and
     0 <= lo < hi <= 1 on every axis.  Raises ValueError."""
@@ -207,6 +232,7 @@ SYMBOLS = {
     "vk_extract_isosurface": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), C.c_uint64, C.POINTER(C.c_uint64)]),  # const vk_mesh_request *, const vk_voxel_box * (NULL: the volume), triangles (NULL: count only), cap, n
     "vk_volume_filter": (C.c_int, [_vp, _vp, _vp]),  # const struct vk_volume_filter * (VkVolumeFilter above), dense_out (NULL: install only)
     "vk_filter_gaussian": (C.c_int, [C.c_double, _u32, C.POINTER(_f32)]),
+    "vk_label_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp]),  # const vk_label_request *, const vk_voxel_box *, labels_out, vk_component *, cap, dense_out, vk_label_result *
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),
     "vk_set_uniform": (C.c_int, [_vp, _vp]),
     "vk_set_camera": (C.c_int, [_vp, _vp]),

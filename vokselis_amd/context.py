@@ -550,6 +550,57 @@ class Context:
         """filter_volume(op="median3"): every texel becomes the median of its 3x3x3 neighbourhood -- lone speckles vanish, edges stay."""
         return self.filter_volume(None, "median3", install, out)
 
+    # -- connected components of a value range (vk_label_components)
+    def _volume_dtype(self):
+        dims, fmt = (C.c_uint32 * 3)(), C.c_int()
+        N.check(self._h, N.lib().vk_volume_info(self._h, dims, C.byref(fmt), None, None))
+        return tuple(dims), {N.FMT_R8_UNORM: np.uint8, N.FMT_R16_UNORM: np.uint16, N.FMT_R16_FLOAT: np.float16}.get(fmt.value)
+
+    def label_components(self, lo, hi=float("inf"), connectivity: int = 6, box=None, labels: bool = False):
+        """vk_label_components: the connected components of the voxels whose stored texel lies in [lo, hi] (sample values, like
+        set_isosurface's), as a Components -- .n, .sizes, .first, .boxes in id order (ids 1 .. n by first voxel in raster order),
+        .n_foreground, and with labels=True .labels, uint32 [nz, ny, nx] (0: background).  connectivity: 6, 18 or 26.  box: None,
+        "clip" or ((x0, y0, z0), (x1, y1, z1)).  One call with room for 4096 components, a second only when there are more; blocks; changes
+        no state of the context."""
+        from .label import Components, label_request, voxel_box
+
+        req, vb = label_request(lo, hi, connectivity=connectivity, box=box), voxel_box(box)
+        bp = C.byref(vb) if vb is not None else None
+        res = N.VkLabelResult()
+        lab = None
+        if labels:
+            dims, _ = self._volume_dtype()
+            lab = np.zeros((dims[2], dims[1], dims[0]), np.uint32)
+        room = 4096
+        table = (N.VkComponent * room)()
+        N.check(self._h, N.lib().vk_label_components(self._h, C.byref(req), bp, lab.ctypes.data if lab is not None else None, table, room, None, C.byref(res)))
+        n = int(res.n_components)
+        if n > room:  # more components than the table had room for: once more, for the table alone
+            table = (N.VkComponent * n)()
+            N.check(self._h, N.lib().vk_label_components(self._h, C.byref(req), bp, None, table, n, None, C.byref(res)))
+        return Components(table, n, int(res.n_foreground), lab)
+
+    def keep_components(self, lo, hi=float("inf"), keep: str = "largest", count: int = 1, seeds=(), invert: bool = False, fill: float = 0.0, connectivity: int = 6,
+                        box=None, install: bool = True, out: bool = False):
+        """vk_label_components with a selection: the components of [lo, hi] that are kept -- keep="largest" (the `count` largest),
+        "min_size" (those of at least `count` voxels), "seeds" (those that hold one of the voxels `seeds`, (x, y, z) each: see
+        V.voxel_of) or "all" -- keep their stored texels, every other voxel becomes `fill`; invert=True: the kept components become `fill`
+        and everything else stays.  install: the result replaces the context's volume (outside frame_begin / frame_end).  out: also
+        return it as a dense array [nz, ny, nx].  Returns (dense or None, VkLabelResult); needs install or out."""
+        from .label import label_request, voxel_box
+
+        req, vb = label_request(lo, hi, connectivity=connectivity, box=box, keep=keep, count=count, seeds=seeds, invert=invert, fill=fill, install=install), voxel_box(box)
+        if not (install or out):
+            raise ValueError("keep_components: needs install or out")
+        dense = None
+        if out:
+            dims, dtype = self._volume_dtype()
+            dense = np.zeros((dims[2], dims[1], dims[0]) if dtype is not None else (1, 1, 1), dtype or np.uint8)
+        res = N.VkLabelResult()
+        N.check(self._h, N.lib().vk_label_components(self._h, C.byref(req), C.byref(vb) if vb is not None else None, None, None, 0,
+                                                     dense.ctypes.data if dense is not None else None, C.byref(res)))
+        return dense, res
+
     def set_root_skip(self, k: int):
         """vk_partition_root_skip: rank 0 sits out every k-th round of the tile deal (0: never)."""
         N.check(self._h, N.lib().vk_partition_root_skip(self._h, int(k)))

@@ -541,6 +541,8 @@ int vk_debug_set_param(vk_ctx *ctx, const char *name, double value) {
     else if (n == "mesh_max_blocks") ctx->mesh_max_blocks = (uint32_t)value;      // ... cap of its grids (0: none)
     else if (n == "filter_max_blocks") ctx->filter_max_blocks = (uint32_t)value;  // vk_volume_filter: cap of the grid (0: none)
     else if (n == "filter_timing") ctx->filter_timing = (uint32_t)value;          // ... 1: the call times its kernel alone (vk_timer_elapsed_ms)
+    else if (n == "label_max_blocks") ctx->label_max_blocks = (uint32_t)value;    // vk_label_components: cap of every grid (0: none)
+    else if (n == "label_timing") ctx->label_timing = (uint32_t)value;            // ... k: the call times its k-th kernel alone (vk_timer_elapsed_ms)
     else if (n == "stage_copies_mask") ctx->stage_copies_mask = (uint32_t)value; // which brick copies to build (next upload)
     else return fail(ctx, VK_ERR_INVALID, "vk_debug_set_param: unknown parameter " + n);
     return VK_OK;

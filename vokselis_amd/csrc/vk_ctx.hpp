@@ -17,6 +17,7 @@
 //   vk_launch_hist.hip     vk_volume_histogram, vk_histogram_window: histogram and statistics of a voxel box (vk_hist.hpp)
 //   vk_launch_mesh.hip     vk_extract_isosurface: the isosurface as a triangle mesh, count / scan / emit (vk_mesh.hpp)
 //   vk_launch_filter.hip   vk_volume_filter, vk_filter_gaussian: separable convolution and 3x3x3 median of the volume (vk_filter.hpp)
+//   vk_launch_label.hip    vk_label_components: connected components of a value range, keep or drop them (vk_label.hpp)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)
@@ -166,6 +167,8 @@ struct vk_ctx {
     uint32_t mesh_max_blocks = 0;    // ... and cap of the count and emit grids (0: none)
     uint32_t filter_max_blocks = 0;  // vk_volume_filter: cap of the grid (0: none) -- lets a small volume drive the grid-stride loop over tiles
     uint32_t filter_timing = 0;      // ... 1 (measurements): the call brackets its kernel with the timer's events, vk_timer_elapsed_ms then reads the kernel alone
+    uint32_t label_max_blocks = 0;   // vk_label_components: cap of every grid (0: none) -- lets a small volume drive the grid-stride loops over tiles and chunks
+    uint32_t label_timing = 0;       // ... k (measurements): the call brackets its k-th kernel with the timer's events (1 tile, 2 seam, 3 flatten, 4 scan, 5 number, 6 label, 7 mask)
 
     // present targets (next row N1/N2)
     uint32_t *rgba8 = nullptr, *bgra8 = nullptr;

@@ -42,6 +42,16 @@
 //                                                            so --iso, --mesh, --histogram and --auto-window see the filtered data: first the 3x3x3 median,
 //                                                            then a Gaussian of SX SY SZ voxels (0: the axis is skipped); --save-raw writes the filtered dense
 //                                                            volume, x fastest, in the volume's format (needs --median or --smooth; one GPU)
+//          [--components LO HI [CONN]]                        connected components of the voxels whose stored texel lies in the sample values [LO, HI] (HI may be inf;
+//                                                            vk_label_components), connectivity CONN = 6 (default), 18 or 26: prints the totals and the ten largest;
+//                                                            runs after --median / --smooth and before --histogram, --auto-window, --mesh, --save-raw and the frames
+//          [--keep-largest K] [--drop-islands N] [--keep-voxel X Y Z] [--remove-voxel X Y Z] [--keep-pick PX PY] [--label-fill V]
+//                                                            keep or drop components of that range (each flag up to 16 times; they need --components, or --iso V
+//                                                            for the range [V, inf) at connectivity 6), in this order: the components under the --remove-voxel
+//                                                            voxels become the fill; only those under the --keep-voxel voxels and --keep-pick pixels stay
+//                                                            (--keep-pick: what the ray through pixel (PX, PY) hits; needs --iso); components below N voxels go;
+//                                                            the K largest stay.  A voxel that goes becomes the sample value V of --label-fill (default 0).  The
+//                                                            cleaned volume replaces the loaded one; --save-raw writes it
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -80,11 +90,84 @@ static bool g_smooth = false;      // --smooth: then a Gaussian of g_sigma voxel
 static double g_sigma[3] = {0.0, 0.0, 0.0};
 static std::string g_save_raw;     // --save-raw: the filtered dense volume
 
-// --median, then --smooth, once the volume is there and before anything reads it; the last of them also fills --save-raw's file
-static void apply_filters(Context &ctx) {
-    if (!g_median && !g_smooth) return;
+// --components and the keep flags (vk_label_components)
+static bool g_components = false;  // --components LO HI [CONN]
+static float g_label_lo = 0.0f, g_label_hi = INFINITY, g_label_fill = 0.0f;
+static uint32_t g_label_conn = 6;
+static bool g_label_fill_on = false;
+static std::vector<uint64_t> g_keep_largest, g_drop_islands;                      // --keep-largest K, --drop-islands N, in the order given
+static std::vector<std::array<uint32_t, 3>> g_keep_voxels, g_remove_voxels;      // --keep-voxel, --remove-voxel
+static std::vector<std::array<uint32_t, 2>> g_keep_picks;                        // --keep-pick PX PY
+static uint32_t g_w = 1280, g_h = 720;                                           // --size: --keep-pick's pixels are this frame's
+static bool label_ops() { return !g_keep_largest.empty() || !g_drop_islands.empty() || !g_keep_voxels.empty() || !g_remove_voxels.empty() || !g_keep_picks.empty(); }
+
+// the context of a run that replaces the render: 8 x 8, or the frame's size under the render's camera when --keep-pick casts rays through it
+static HdrBackBuffer pass_backbuffer() { HdrBackBuffer bb; bb.width = g_keep_picks.empty() ? 8u : g_w; bb.height = g_keep_picks.empty() ? 8u : g_h; return bb; }
+static Camera pass_camera() { return Camera(1.f, 0.5f, 1.f, {0.5f, 0.5f, 0.5f}, (float)g_w / (float)g_h); }
+
+static void write_dense(const std::vector<unsigned char> &dense, const char *what) {
+    std::ofstream f(g_save_raw, std::ios::binary);
+    if (!f || !f.write(reinterpret_cast<const char *>(dense.data()), (std::streamsize)dense.size())) throw std::runtime_error("cannot write " + g_save_raw);
+    std::printf("%s volume: %zu bytes -> %s\n", what, dense.size(), g_save_raw.c_str());
+}
+
+// --components, then the keep flags in their fixed order, after the filters and before anything else reads the volume; the last of them fills --save-raw's file
+static void apply_labels(Context &ctx) {
+    if (!g_components && !label_ops()) return;
+    uint32_t dims[3] = {0, 0, 0};
+    int fmt = 0;
+    check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
+    if (g_components) {
+        const Components c = ctx.label_components(g_label_lo, g_label_hi, g_label_conn);
+        std::printf("components: [%g, %g] connectivity %u: %llu components, %llu foreground voxels of %llu\n", g_label_lo, g_label_hi, g_label_conn,
+                    (unsigned long long)c.totals.n_components, (unsigned long long)c.totals.n_foreground, (unsigned long long)dims[0] * dims[1] * dims[2]);
+        for (uint64_t id : c.largest(10)) {
+            const vk_component &k = c.table[id - 1];
+            std::printf("component %llu: %llu voxels, first %llu, box %u %u %u .. %u %u %u\n", (unsigned long long)id, (unsigned long long)k.n_voxels, (unsigned long long)k.first, k.box.x0,
+                        k.box.y0, k.box.z0, k.box.x1, k.box.y1, k.box.z1);
+        }
+    }
+    if (!label_ops()) return;
+    std::vector<std::array<uint32_t, 3>> keep = g_keep_voxels;
+    if (!g_keep_picks.empty()) {  // the rays of the render's camera through the frame's pixels, under --iso
+        const CameraUniform cu = ctx.camera.get_proj_view_matrix();
+        check(ctx.handle(), vk_set_camera(ctx.handle(), &cu));
+        ctx.set_isosurface(&g_iso);
+        for (const auto &p : g_keep_picks) {
+            const vk_hit hit = ctx.pick(p[0], p[1], g_dt);
+            if (!hit.hit) { std::printf("keep-pick (%u, %u): miss\n", p[0], p[1]); continue; }
+            keep.push_back(voxel_of(hit.pos, dims[0], dims[1], dims[2]));
+            std::printf("keep-pick (%u, %u): voxel %u %u %u\n", p[0], p[1], keep.back()[0], keep.back()[1], keep.back()[2]);
+        }
+        if (keep.size() > (size_t)VK_LABEL_MAX_SEEDS) throw std::runtime_error("--keep-voxel and --keep-pick: at most 16 seeds together");
+    }
+    struct Op { const char *name; int keep; uint64_t count; const std::vector<std::array<uint32_t, 3>> *seeds; bool invert; };
+    static const std::vector<std::array<uint32_t, 3>> none;
+    std::vector<Op> ops;
+    if (!g_remove_voxels.empty()) ops.push_back({"remove-voxel", VK_LABEL_KEEP_SEEDS, 0, &g_remove_voxels, true});
+    if (!g_keep_voxels.empty() || !g_keep_picks.empty()) {
+        if (keep.empty()) throw std::runtime_error("--keep-pick: every ray missed, nothing would be kept");
+        ops.push_back({"keep-voxel", VK_LABEL_KEEP_SEEDS, 0, &keep, false});
+    }
+    for (uint64_t n : g_drop_islands) ops.push_back({"drop-islands", VK_LABEL_KEEP_MIN_SIZE, n, &none, false});
+    for (uint64_t k : g_keep_largest) ops.push_back({"keep-largest", VK_LABEL_KEEP_LARGEST, k, &none, false});
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty()) {
+    if (!g_save_raw.empty()) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    for (size_t k = 0; k < ops.size(); k++) {
+        const Op &op = ops[k];
+        const vk_label_result r = ctx.keep_components(g_label_lo, g_label_hi, op.keep, op.count, *op.seeds, op.invert, g_label_fill, g_label_conn, nullptr, false, true,
+                                                      k + 1 == ops.size() && !dense.empty() ? dense.data() : nullptr);
+        std::printf("%s: %llu of %llu components selected, %llu of %llu foreground voxels\n", op.name, (unsigned long long)r.n_kept_components, (unsigned long long)r.n_components,
+                    (unsigned long long)r.n_kept_voxels, (unsigned long long)r.n_foreground);
+    }
+    if (!dense.empty()) write_dense(dense, "cleaned");
+}
+
+// --median, then --smooth, once the volume is there and before anything reads it; the last of them also fills --save-raw's file (unless a keep flag follows)
+static void apply_filters(Context &ctx) {
+    if (!g_median && !g_smooth) { apply_labels(ctx); return; }
+    std::vector<unsigned char> dense;
+    if (!g_save_raw.empty() && !label_ops()) {
         uint32_t dims[3] = {0, 0, 0};
         int fmt = 0;
         check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
@@ -93,11 +176,8 @@ static void apply_filters(Context &ctx) {
     if (g_median) ctx.median_volume(true, g_smooth || dense.empty() ? nullptr : dense.data());
     if (g_smooth) ctx.smooth_volume(g_sigma[0], g_sigma[1], g_sigma[2], true, dense.empty() ? nullptr : dense.data());
     std::printf("filter:%s%s\n", g_median ? " median 3x3x3" : "", g_smooth ? (" gaussian sigma " + std::to_string(g_sigma[0]) + " " + std::to_string(g_sigma[1]) + " " + std::to_string(g_sigma[2])).c_str() : "");
-    if (!dense.empty()) {
-        std::ofstream f(g_save_raw, std::ios::binary);
-        if (!f || !f.write(reinterpret_cast<const char *>(dense.data()), (std::streamsize)dense.size())) throw std::runtime_error("cannot write " + g_save_raw);
-        std::printf("filtered volume: %zu bytes -> %s\n", dense.size(), g_save_raw.c_str());
-    }
+    if (!dense.empty()) write_dense(dense, "filtered");
+    apply_labels(ctx);
 }
 
 // --tf PATH: the whole file as little-endian f32 RGBA rows (the library checks n, finiteness and alpha)
@@ -126,8 +206,9 @@ static void apply_auto_window(Context &ctx) {
 // --histogram in place of the raycast: the statistics in sample values, then `bin count` for every non-empty bin
 static int run_histogram(uint32_t bins, float lo, float hi) {
     try {
-        HdrBackBuffer bb; bb.width = 8; bb.height = 8;
-        Context ctx(8, 8, nullptr, 0, bb);
+        const HdrBackBuffer bb = pass_backbuffer();
+        const Camera cam = pass_camera();
+        Context ctx(bb.width, bb.height, &cam, 0, bb);
         if (g_clip_on) ctx.set_clip_box(&g_clip);
         if (!g_raw.empty()) VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt);
         else VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, g_dims[0], g_dims[1], g_dims[2]);
@@ -150,8 +231,9 @@ static int run_histogram(uint32_t bins, float lo, float hi) {
 // --mesh in place of the raycast: the triangles as binary STL (facet normals formed in double) or as OBJ welded by bit pattern
 static int run_mesh(const std::string &path, bool obj, float iso, const double scale[3]) {
     try {
-        HdrBackBuffer bb; bb.width = 8; bb.height = 8;
-        Context ctx(8, 8, nullptr, 0, bb);
+        const HdrBackBuffer bb = pass_backbuffer();
+        const Camera cam = pass_camera();
+        Context ctx(bb.width, bb.height, &cam, 0, bb);
         if (g_clip_on) ctx.set_clip_box(&g_clip);
         if (!g_raw.empty()) VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt);
         else VolumeTexture::generate(ctx, VK_GEN_BONSAI_STANDIN, g_dims[0], g_dims[1], g_dims[2]);
@@ -342,7 +424,8 @@ static vk_slice make_slice(const SliceArgs &a, uint32_t w, uint32_t h) {
 static int run_slice(const SliceArgs &a, uint32_t w, uint32_t h, const std::string &ppm) {
     try {
         HdrBackBuffer bb; bb.width = w; bb.height = h; bb.format = VK_OUT_RGBA32F;
-        Context ctx(w, h, nullptr, 0, bb);
+        const Camera cam = pass_camera();
+        Context ctx(w, h, &cam, 0, bb);
         if (!g_tf.empty() && !g_auto_window) ctx.set_transfer_function(g_tf.data(), (uint32_t)(g_tf.size() / 4), g_tf_lo, g_tf_hi);
         if (g_clip_on) ctx.set_clip_box(&g_clip);
         if (!g_raw.empty()) VolumeTexture::from_raw(ctx, g_raw, g_dims[0], g_dims[1], g_dims[2], g_raw_fmt);
@@ -509,6 +592,40 @@ int main(int argc, char **argv) {
             if (g_sigma[0] == 0.0 && g_sigma[1] == 0.0 && g_sigma[2] == 0.0) { std::fprintf(stderr, "bonsai: --smooth SX SY SZ: at least one sigma above 0\n"); return 2; }
         }
         else if (a == "--save-raw") g_save_raw = next();
+        else if (a == "--components") {
+            g_components = true;
+            g_label_lo = (float)std::atof(next()); g_label_hi = (float)std::atof(next());
+            if (std::isnan(g_label_lo) || std::isnan(g_label_hi) || g_label_lo > g_label_hi) { std::fprintf(stderr, "bonsai: --components LO HI [CONN]: needs LO <= HI, neither a NaN (HI may be inf)\n"); return 2; }
+            if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) {
+                const int c = std::atoi(next());
+                if (c != 6 && c != 18 && c != 26) { std::fprintf(stderr, "bonsai: --components LO HI [CONN]: CONN is 6, 18 or 26\n"); return 2; }
+                g_label_conn = (uint32_t)c;
+            }
+        }
+        else if (a == "--keep-largest" || a == "--drop-islands") {
+            const long long n = std::atoll(next());
+            if (n < 1) { std::fprintf(stderr, "bonsai: %s: a count of at least 1\n", a.c_str()); return 2; }
+            std::vector<uint64_t> &list = a == "--keep-largest" ? g_keep_largest : g_drop_islands;
+            if (list.size() >= 16u) { std::fprintf(stderr, "bonsai: %s: at most 16 times\n", a.c_str()); return 2; }
+            list.push_back((uint64_t)n);
+        }
+        else if (a == "--keep-voxel" || a == "--remove-voxel") {
+            std::array<uint32_t, 3> v{};
+            for (int k = 0; k < 3; k++) { const long long c = std::atoll(next()); if (c < 0 || c > 0xffffffffll) { std::fprintf(stderr, "bonsai: %s X Y Z: voxel indices >= 0\n", a.c_str()); return 2; } v[k] = (uint32_t)c; }
+            std::vector<std::array<uint32_t, 3>> &list = a == "--keep-voxel" ? g_keep_voxels : g_remove_voxels;
+            if (list.size() >= 16u) { std::fprintf(stderr, "bonsai: %s: at most 16 times\n", a.c_str()); return 2; }
+            list.push_back(v);
+        }
+        else if (a == "--keep-pick") {
+            std::array<uint32_t, 2> p{};
+            for (int k = 0; k < 2; k++) p[k] = (uint32_t)std::max(0, std::atoi(next()));
+            if (g_keep_picks.size() >= 16u) { std::fprintf(stderr, "bonsai: --keep-pick: at most 16 times\n"); return 2; }
+            g_keep_picks.push_back(p);
+        }
+        else if (a == "--label-fill") {
+            g_label_fill_on = true; g_label_fill = (float)std::atof(next());
+            if (!std::isfinite(g_label_fill)) { std::fprintf(stderr, "bonsai: --label-fill V: V must be finite\n"); return 2; }
+        }
         else if (a == "--camera-blobs") { std::string in = next(); return dump_camera_blobs(in, next()); }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -527,7 +644,14 @@ int main(int argc, char **argv) {
     if (!mesh_path.empty() && !mesh_iso_on && !g_iso_on) { std::fprintf(stderr, "bonsai: --mesh needs an isovalue: --mesh-iso V or --iso V\n"); return 2; }
     if (!mesh_path.empty() && !mesh_iso_on && !std::isfinite(g_iso.iso)) { std::fprintf(stderr, "bonsai: --mesh: the isovalue must be finite\n"); return 2; }
     if (!mesh_path.empty() && (sl.on || hist || gpus > 0 || g_auto_window)) { std::fprintf(stderr, "bonsai: --mesh replaces the render: no --slice, --slice-plane, --histogram, --gpus or --auto-window\n"); return 2; }
-    if (!g_save_raw.empty() && !g_median && !g_smooth) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
+    if (label_ops() && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel and --keep-pick need a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
+    if (!g_keep_picks.empty() && !g_iso_on) { std::fprintf(stderr, "bonsai: --keep-pick needs --iso (the ray stops at the isosurface)\n"); return 2; }
+    if (g_label_fill_on && !label_ops()) { std::fprintf(stderr, "bonsai: --label-fill needs a flag that drops voxels: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel or --keep-pick\n"); return 2; }
+    if (g_keep_voxels.size() + g_keep_picks.size() > 16u) { std::fprintf(stderr, "bonsai: --keep-voxel and --keep-pick: at most 16 seeds together\n"); return 2; }
+    if ((g_components || label_ops()) && gpus > 0) { std::fprintf(stderr, "bonsai: --components and the keep flags run on one GPU\n"); return 2; }
+    if (label_ops() && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
+    g_w = w; g_h = h;
+    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops()) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
     if ((g_median || g_smooth) && gpus > 0) { std::fprintf(stderr, "bonsai: --median and --smooth run on one GPU\n"); return 2; }
     if (hist) return run_histogram(hist_bins, hist_lo, hist_hi);
     if (!mesh_path.empty()) return run_mesh(mesh_path, mesh_obj, mesh_iso_on ? mesh_iso : g_iso.iso, mesh_scale);

@@ -6,6 +6,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -180,6 +181,33 @@ static_assert(sizeof(vk_histogram) == 16 && sizeof(vk_voxel_box) == 24 && sizeof
 
 static_assert(sizeof(vk_mesh_request) == 8, "vk_mesh_request is 8 bytes (vk_extract_isosurface)");
 static_assert(sizeof(struct vk_volume_filter) == 176, "struct vk_volume_filter is 176 bytes (vk_volume_filter)");
+
+static_assert(sizeof(vk_label_request) == 232 && sizeof(vk_component) == 40 && sizeof(vk_label_result) == 32, "vk_label_request is 232 bytes, vk_component 40, vk_label_result 32 (vk_label_components)");
+
+// What Context::label_components returns: the components in id order (id k + 1 at index k), the totals, and the labels when asked for.
+struct Components {
+    std::vector<vk_component> table;
+    vk_label_result totals{};
+    std::vector<uint32_t> labels;  // nx ny nz, x fastest, 0: background; empty unless asked for
+    // the ids of the min(k, n) largest components: by size descending, then by first voxel -- VK_LABEL_KEEP_LARGEST's order
+    std::vector<uint64_t> largest(size_t k) const {
+        std::vector<uint64_t> ids(table.size());
+        for (size_t i = 0; i < ids.size(); i++) ids[i] = i + 1;
+        std::stable_sort(ids.begin(), ids.end(), [&](uint64_t a, uint64_t b) { return table[a - 1].n_voxels > table[b - 1].n_voxels; });
+        ids.resize(std::min(k, ids.size()));
+        return ids;
+    }
+};
+// The voxel of a volume of nx x ny x nz that holds the unit-cube position pos (vk_hit.pos): min(floor(pos_c n_c), n_c - 1) per axis.
+inline std::array<uint32_t, 3> voxel_of(const float pos[3], uint32_t nx, uint32_t ny, uint32_t nz) {
+    const uint32_t n[3] = {nx, ny, nz};
+    std::array<uint32_t, 3> v{};
+    for (int c = 0; c < 3; c++) {
+        if (!(pos[c] >= 0.0f && pos[c] <= 1.0f) || n[c] == 0u) throw std::invalid_argument("voxel_of: the position lies outside the unit cube");
+        v[c] = std::min((uint32_t)std::floor((double)pos[c] * (double)n[c]), n[c] - 1u);
+    }
+    return v;
+}
 
 // The 2 radius + 1 normalised weights of a Gaussian of `sigma` voxels (vk_filter_gaussian); radius 0: min(6, ceil(3 sigma)).
 inline std::vector<float> gaussian_weights(double sigma, uint32_t radius = 0) {
@@ -371,6 +399,46 @@ class Context {
         f.op = VK_FILTER_MEDIAN3;
         f.flags = install ? (uint32_t)VK_FILTER_INSTALL : 0u;
         check(ctx_, vk_volume_filter(ctx_, &f, dense_out));
+    }
+    // Connected components of the voxels whose stored texel lies in [lo, hi] (sample values; vk_label_components; blocks; changes no state):
+    // connectivity 6, 18 or 26; box == nullptr: the whole volume, or with clip the clip box in force.  One call with room for 4096
+    // components; a second only when there are more.
+    Components label_components(float lo, float hi = INFINITY, uint32_t connectivity = 6, const vk_voxel_box *box = nullptr, bool clip = false, bool want_labels = false) {
+        vk_label_request req{};
+        req.lo = lo; req.hi = hi; req.connectivity = connectivity;
+        req.flags = clip ? (uint32_t)VK_LABEL_CLIP_BOX : 0u;
+        Components c;
+        if (want_labels) {
+            uint32_t dims[3] = {0, 0, 0};
+            check(ctx_, vk_volume_info(ctx_, dims, nullptr, nullptr, nullptr));
+            c.labels.assign((size_t)dims[0] * dims[1] * dims[2], 0u);
+        }
+        c.table.resize(4096);
+        check(ctx_, vk_label_components(ctx_, &req, box, want_labels ? c.labels.data() : nullptr, c.table.data(), c.table.size(), nullptr, &c.totals));
+        if (c.totals.n_components > c.table.size()) {
+            c.table.resize((size_t)c.totals.n_components);
+            check(ctx_, vk_label_components(ctx_, &req, box, nullptr, c.table.data(), c.table.size(), nullptr, &c.totals));
+        }
+        c.table.resize((size_t)c.totals.n_components);
+        return c;
+    }
+    // ... with a selection: keep = VK_LABEL_KEEP_ALL / _LARGEST (the `count` largest) / _MIN_SIZE (at least `count` voxels) / _SEEDS (the
+    // components that hold one of `seeds`, voxels (x, y, z)).  Kept components keep their stored texels, every other voxel becomes `fill`;
+    // invert: the other way round.  install: the result replaces the context's volume (outside frame_begin / frame_end).  dense_out: nullptr,
+    // or host memory of nx ny nz elements of the volume's format.  Needs install or dense_out.
+    vk_label_result keep_components(float lo, float hi, int keep, uint64_t count = 0, const std::vector<std::array<uint32_t, 3>> &seeds = {}, bool invert = false, float fill = 0.0f,
+                                    uint32_t connectivity = 6, const vk_voxel_box *box = nullptr, bool clip = false, bool install = true, void *dense_out = nullptr) {
+        if (seeds.size() > (size_t)VK_LABEL_MAX_SEEDS) throw std::invalid_argument("keep_components: at most VK_LABEL_MAX_SEEDS seeds");
+        if (!install && !dense_out) throw std::invalid_argument("keep_components: needs install or dense_out");
+        vk_label_request req{};
+        req.lo = lo; req.hi = hi; req.connectivity = connectivity; req.keep = keep; req.count = count; req.fill = fill;
+        req.flags = (clip ? (uint32_t)VK_LABEL_CLIP_BOX : 0u) | (install ? (uint32_t)VK_LABEL_INSTALL : 0u) | (invert ? (uint32_t)VK_LABEL_INVERT : 0u);
+        req.n_seeds = (uint32_t)seeds.size();
+        for (size_t k = 0; k < seeds.size(); k++)
+            for (int c = 0; c < 3; c++) req.seeds[k][c] = seeds[k][c];
+        vk_label_result res{};
+        check(ctx_, vk_label_components(ctx_, &req, box, nullptr, nullptr, 0, dense_out, &res));
+        return res;
     }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
