@@ -655,6 +655,66 @@ typedef struct vk_label_result {
 int vk_label_components(vk_ctx *ctx, const vk_label_request *req, const vk_voxel_box *box, uint32_t *labels_out, vk_component *components,
                         uint64_t cap_components, void *dense_out, vk_label_result *result);
 
+/* Exact Euclidean distance transform of a value range, and morphology by a radius: how far every voxel is from
+ * the set S of voxels whose stored texel lies in [lo, hi], as a squared distance over integer spacings -- an integer -- and the four
+ * operations built on it: grow, shrink, close and open S by a Euclidean ball.  Every result is an integer or a stored texel: there is
+ * no rounding anywhere but in the two fills.
+ * The set S is exactly vk_label_components' foreground: t, lo_k and hi_k as there; a voxel is in S iff it lies in the voxel box and
+ * t >= lo_k && t <= hi_k.  A NaN never is.  The box is `box`, the clip box under VK_DIST_CLIP_BOX (box must then be NULL), or NULL for
+ * the whole volume.  The box restricts S only: the transform and every output cover the whole volume, and not S means every voxel of
+ * the volume that is not in S, inside the box or outside it.
+ * Distance.  For a set A of voxels of the volume, D2(A, v) = min over u in A of sum_c (spacing[c] * (v_c - u_c))^2 with c over x, y, z,
+ * and D2(A, v) = VK_DIST_INF when A is empty.  Only voxels of the volume are candidates: nothing outside the volume is foreground or
+ * background.  The call returns VK_ERR_UNSUPPORTED before any launch when sum_c (spacing[c] * (n_c - 1))^2 > 0xFFFFFFFE, so every
+ * finite D2 fits in 32 bits and is never VK_DIST_INF.
+ * Distance ops.  VK_DIST_OUTSIDE: d2_out[v] = D2(S, v), 0 on S.  VK_DIST_INSIDE: d2_out[v] = D2(not S, v), 0 off S.  d2_out (may be
+ * NULL): nx ny nz uint32, x fastest.
+ * Morphology ops.  R2 = (uint64_t)floor((double)radius * (double)radius).  dil(A) = { v : D2(A, v) <= R2 };
+ * ero(A) = { v : D2(not A, v) > R2 }.  VK_DIST_DILATE: M = dil(S).  _ERODE: M = ero(S).  _CLOSE: M = ero(dil(S)).  _OPEN:
+ * M = dil(ero(S)).  VK_DIST_INF is never <= R2: the empty set dilates to the empty set, the full volume erodes to the full volume.
+ * Output texel.  A voxel in M and not in S becomes fill_in, a voxel in S and not in M becomes fill_out, each through
+ * vk_label_components' fill rule F; every other voxel keeps its stored bits unchanged (PACKED_PAIRS: the u8 value tap + delta).
+ * dense_out (may be NULL; host memory of nx ny nz elements of the volume's format) and VK_DIST_INSTALL behave exactly as
+ * vk_label_components' dense_out and VK_LABEL_INSTALL: the same re-layout, the same state kept in force, the old volume stays on any
+ * failure.  Without VK_DIST_INSTALL no context state changes.  The call blocks, runs on the context's current stream and allocates and
+ * frees its own buffers.
+ * result (may be NULL).  n_foreground = |S|.  Morphology ops: n_result = |M|, n_added = |M \ S|, n_removed = |S \ M|, max_d2 = 0.
+ * Distance ops: n_result = n_foreground, n_added = n_removed = 0, max_d2 = the largest d2_out that is not VK_DIST_INF (0 if none).
+ * VK_ERR_INVALID, decided before any launch, outputs untouched: a NULL request; lo or hi NaN, lo > hi; an unknown op or flag; a
+ * spacing of 0 or above VK_DIST_MAX_SPACING; a radius that is not finite, is negative or lies above VK_DIST_MAX_RADIUS; a nonzero
+ * radius with a distance op; a fill that is not finite; d2_out with a morphology op; dense_out or VK_DIST_INSTALL with a distance op;
+ * nothing requested (distance op: neither d2_out nor result; morphology op: none of dense_out, VK_DIST_INSTALL and result);
+ * VK_DIST_INSTALL while a frame is being recorded; a box that is inverted or leaves the volume, a box together with
+ * VK_DIST_CLIP_BOX; no volume.  VK_ERR_UNSUPPORTED ("distance: ..."): a BRICKED / QUADS / STAGED or RGBA16F_PAIR volume; a volume of
+ * more than 2^32 - 2 voxels; the overflow condition above.  VK_ERR_OOM: a buffer cannot be allocated.  A call that fails later may
+ * have written its outputs already; the context's volume is the old one whenever the call does not return VK_OK. */
+#define VK_DIST_INF         0xFFFFFFFFu
+#define VK_DIST_MAX_SPACING 64
+#define VK_DIST_MAX_RADIUS  65535.0f
+enum { VK_DIST_OUTSIDE = 0, VK_DIST_INSIDE = 1, VK_DIST_DILATE = 2, VK_DIST_ERODE = 3, VK_DIST_CLOSE = 4, VK_DIST_OPEN = 5 };
+enum { VK_DIST_CLIP_BOX = 1, VK_DIST_INSTALL = 2 };
+typedef struct vk_distance_request {
+    float    lo, hi;         /* the value range, formed exactly as vk_label_components forms lo_k, hi_k */
+    int32_t  op;             /* VK_DIST_OUTSIDE .. VK_DIST_OPEN */
+    uint32_t flags;          /* VK_DIST_CLIP_BOX | VK_DIST_INSTALL */
+    uint32_t spacing[3];     /* integer voxel pitch per axis x, y, z: 1 .. VK_DIST_MAX_SPACING */
+    float    radius;         /* DILATE .. OPEN: in the units of spacing; otherwise 0 */
+    float    fill_in;        /* sample value of a voxel that joins the set; finite */
+    float    fill_out;       /* sample value of a voxel that leaves it; finite */
+} vk_distance_request;       /* 40 bytes */
+typedef struct vk_distance_result {
+    uint64_t n_foreground, n_result, n_added, n_removed;
+    uint32_t max_d2;         /* OUTSIDE / INSIDE: the largest D2 that is not VK_DIST_INF (0 if none); otherwise 0 */
+    uint32_t pad;
+} vk_distance_result;        /* 40 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(vk_distance_request) == 40 && sizeof(vk_distance_result) == 40, "vk_distance_request, vk_distance_result: 40 bytes each");
+#else
+_Static_assert(sizeof(vk_distance_request) == 40 && sizeof(vk_distance_result) == 40, "vk_distance_request, vk_distance_result: 40 bytes each");
+#endif
+int vk_distance_transform(vk_ctx *ctx, const vk_distance_request *req, const vk_voxel_box *box, uint32_t *d2_out, void *dense_out,
+                          vk_distance_result *result);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

@@ -11,6 +11,7 @@ Only the raycast hot path and the host surface that drives it live here (SURVEY.
   mesh       weld, write_stl, write_obj: the triangles of Context.extract_isosurface as a welded mesh, binary STL, OBJ
   filter     gaussian_weights, filter_request: the weights and the request of Context.filter_volume / smooth_volume / median_volume
   label      Components, label_request, voxel_of: the result and the request of Context.label_components / keep_components
+  distance   distance_request, default_fill_in: the request of Context.distance_transform / morph_volume
   dist       tile-parallel multi-GPU frame (one process per GPU, RCCL gather over xGMI)
 """
 from . import _native as native
@@ -22,13 +23,16 @@ from ._native import (FMT_R8_UNORM, FMT_R16_FLOAT, FMT_RGBA16F_PAIR, FMT_R16_UNO
                       HIST_MAX_BINS, HIST_CLIP_BOX, VkHistogram, VkVoxelBox, VkVolumeStats, MESH_CLIP_BOX, VkMeshRequest,
                       FILTER_MAX_RADIUS, FILTER_MAX_WEIGHT, FILTER_CONVOLVE, FILTER_MEDIAN3, FILTER_INSTALL, VkVolumeFilter,
                       LABEL_MAX_SEEDS, LABEL_KEEP_ALL, LABEL_KEEP_LARGEST, LABEL_KEEP_MIN_SIZE, LABEL_KEEP_SEEDS, LABEL_CLIP_BOX, LABEL_INSTALL, LABEL_INVERT,
-                      VkLabelRequest, VkComponent, VkLabelResult)
+                      VkLabelRequest, VkComponent, VkLabelResult,
+                      DIST_INF, DIST_MAX_SPACING, DIST_MAX_RADIUS, DIST_OUTSIDE, DIST_INSIDE, DIST_DILATE, DIST_ERODE, DIST_CLOSE, DIST_OPEN, DIST_CLIP_BOX, DIST_INSTALL,
+                      VkDistanceRequest, VkDistanceResult)
 from .camera import Camera
 from .slices import Slice
 from .histogram import Histogram
 from .mesh import weld, write_obj, write_stl
 from .filter import gaussian_weights
 from .label import Components, voxel_of
+from .distance import distance_request
 from .context import (Context, Demo, FrameCounter, HdrBackBuffer, Hit, ImageDimentions, RaycastPipeline, Uniform,
                       VolumeTexture, dispatch_optimal, partition_slots, render_batch, run_headless, transfer_table, untile_batch)
 
@@ -44,4 +48,6 @@ __all__ = [
     "FILTER_MAX_RADIUS", "FILTER_MAX_WEIGHT", "FILTER_CONVOLVE", "FILTER_MEDIAN3", "FILTER_INSTALL", "VkVolumeFilter", "gaussian_weights",
     "LABEL_MAX_SEEDS", "LABEL_KEEP_ALL", "LABEL_KEEP_LARGEST", "LABEL_KEEP_MIN_SIZE", "LABEL_KEEP_SEEDS", "LABEL_CLIP_BOX", "LABEL_INSTALL", "LABEL_INVERT",
     "VkLabelRequest", "VkComponent", "VkLabelResult", "Components", "voxel_of",
+    "DIST_INF", "DIST_MAX_SPACING", "DIST_MAX_RADIUS", "DIST_OUTSIDE", "DIST_INSIDE", "DIST_DILATE", "DIST_ERODE", "DIST_CLOSE", "DIST_OPEN", "DIST_CLIP_BOX", "DIST_INSTALL",
+    "VkDistanceRequest", "VkDistanceResult", "distance_request",
 ]

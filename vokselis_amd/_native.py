@@ -174,6 +174,28 @@ class VkLabelResult(C.Structure):
 assert C.sizeof(VkLabelRequest) == 232 and C.sizeof(VkComponent) == 40 and C.sizeof(VkLabelResult) == 32
 
 
+DIST_INF = 0xFFFFFFFF
+DIST_MAX_SPACING = 64
+DIST_MAX_RADIUS = 65535.0
+DIST_OUTSIDE, DIST_INSIDE, DIST_DILATE, DIST_ERODE, DIST_CLOSE, DIST_OPEN = 0, 1, 2, 3, 4, 5
+DIST_CLIP_BOX, DIST_INSTALL = 1, 2
+
+
+class VkDistanceRequest(C.Structure):
+    """vk_distance_request (40 bytes): the request of vk_distance_transform -- the value range, the op, the flags, the integer spacing
+    per axis (x, y, z), the radius of a morphology op and the two fills."""
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("op", C.c_int32), ("flags", C.c_uint32), ("spacing", C.c_uint32 * 3), ("radius", C.c_float),
+                ("fill_in", C.c_float), ("fill_out", C.c_float)]
+
+
+class VkDistanceResult(C.Structure):
+    """vk_distance_result (40 bytes): the counts of vk_distance_transform, and the largest finite squared distance of a distance op."""
+    _fields_ = [("n_foreground", C.c_uint64), ("n_result", C.c_uint64), ("n_added", C.c_uint64), ("n_removed", C.c_uint64), ("max_d2", C.c_uint32), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(VkDistanceRequest) == 40 and C.sizeof(VkDistanceResult) == 40
+
+
 def clip_box(lo, hi) -> VkClipBox:
     """A VkClipBox from two triples, held to vk_set_clip_box's rules before the library sees it: finite components (as f32) and
     0 <= lo < hi <= 1 on every axis.  Raises ValueError."""
@@ -233,6 +255,7 @@ SYMBOLS = {
     "vk_volume_filter": (C.c_int, [_vp, _vp, _vp]),  # const struct vk_volume_filter * (VkVolumeFilter above), dense_out (NULL: install only)
     "vk_filter_gaussian": (C.c_int, [C.c_double, _u32, C.POINTER(_f32)]),
     "vk_label_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp]),  # const vk_label_request *, const vk_voxel_box *, labels_out, vk_component *, cap, dense_out, vk_label_result *
+    "vk_distance_transform": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_distance_request *, const vk_voxel_box *, d2_out, dense_out, vk_distance_result *
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),
     "vk_set_uniform": (C.c_int, [_vp, _vp]),
     "vk_set_camera": (C.c_int, [_vp, _vp]),

@@ -601,6 +601,45 @@ class Context:
                                                      dense.ctypes.data if dense is not None else None, C.byref(res)))
         return dense, res
 
+    # -- exact Euclidean distance transform of a value range, morphology by a radius (vk_distance_transform)
+    def distance_transform(self, lo, hi=float("inf"), which: str = "outside", spacing=(1, 1, 1), box=None):
+        """vk_distance_transform, a distance op: the squared Euclidean distance of every voxel to the set S of voxels whose stored texel
+        lies in [lo, hi] (which="outside": 0 on S) or to its complement (which="inside": 0 off S), over the integer voxel pitch `spacing`
+        = (sx, sy, sz), as a uint32 array [nz, ny, nx]; DIST_INF where the target set is empty.  box: None, "clip" or
+        ((x0, y0, z0), (x1, y1, z1)) restricts S only.  Blocks; changes no state of the context."""
+        from .distance import distance_request
+        from .label import voxel_box
+
+        if which not in ("outside", "inside"):
+            raise ValueError('which: "outside" or "inside"')
+        req, vb = distance_request(lo, hi, op=which, spacing=spacing, box=box), voxel_box(box)
+        dims, _ = self._volume_dtype()
+        d2 = np.zeros((dims[2], dims[1], dims[0]), np.uint32)
+        N.check(self._h, N.lib().vk_distance_transform(self._h, C.byref(req), C.byref(vb) if vb is not None else None, d2.ctypes.data, None, None))
+        return d2
+
+    def morph_volume(self, lo, hi=float("inf"), op: str = "close", radius: float = 1.0, spacing=(1, 1, 1), fill_in=None, fill_out: float = 0.0, install: bool = True,
+                     out: bool = False, box=None):
+        """vk_distance_transform, a morphology op: the set S of voxels whose stored texel lies in [lo, hi] is closed, opened, dilated or
+        eroded (op) by a Euclidean ball of `radius`, in the units of the integer voxel pitch `spacing`.  A voxel that joins the set
+        becomes fill_in (None: hi where it is finite, else max(lo, 1) -- a value of the range), one that leaves it fill_out; every other
+        voxel keeps its bits.  install: the result replaces the context's volume (outside frame_begin / frame_end).  Returns the
+        VkDistanceResult (n_foreground, n_result, n_added, n_removed); with out=True (dense [nz, ny, nx], VkDistanceResult)."""
+        from .distance import MORPH_OPS, distance_request
+        from .label import voxel_box
+
+        if op not in MORPH_OPS:
+            raise ValueError('op: "close", "open", "dilate" or "erode"')
+        req, vb = distance_request(lo, hi, op=op, radius=radius, spacing=spacing, fill_in=fill_in, fill_out=fill_out, install=install, box=box), voxel_box(box)
+        dense = None
+        if out:
+            dims, dtype = self._volume_dtype()
+            dense = np.zeros((dims[2], dims[1], dims[0]) if dtype is not None else (1, 1, 1), dtype or np.uint8)
+        res = N.VkDistanceResult()
+        N.check(self._h, N.lib().vk_distance_transform(self._h, C.byref(req), C.byref(vb) if vb is not None else None, None, dense.ctypes.data if dense is not None else None,
+                                                       C.byref(res)))
+        return (dense, res) if out else res
+
     def set_root_skip(self, k: int):
         """vk_partition_root_skip: rank 0 sits out every k-th round of the tile deal (0: never)."""
         N.check(self._h, N.lib().vk_partition_root_skip(self._h, int(k)))

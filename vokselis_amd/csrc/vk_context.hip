@@ -543,6 +543,9 @@ int vk_debug_set_param(vk_ctx *ctx, const char *name, double value) {
     else if (n == "filter_timing") ctx->filter_timing = (uint32_t)value;          // ... 1: the call times its kernel alone (vk_timer_elapsed_ms)
     else if (n == "label_max_blocks") ctx->label_max_blocks = (uint32_t)value;    // vk_label_components: cap of every grid (0: none)
     else if (n == "label_timing") ctx->label_timing = (uint32_t)value;            // ... k: the call times its k-th kernel alone (vk_timer_elapsed_ms)
+    else if (n == "dist_max_blocks") ctx->dist_max_blocks = (uint32_t)value;      // vk_distance_transform: cap of every grid (0: none)
+    else if (n == "dist_x_plain") ctx->dist_x_plain = (uint32_t)value;            // ... 1: the x pass without the transposes (measurements, tests)
+    else if (n == "dist_timing") ctx->dist_timing = (uint32_t)value;              // ... k: the call times its k-th kernel alone (vk_timer_elapsed_ms)
     else if (n == "stage_copies_mask") ctx->stage_copies_mask = (uint32_t)value; // which brick copies to build (next upload)
     else return fail(ctx, VK_ERR_INVALID, "vk_debug_set_param: unknown parameter " + n);
     return VK_OK;

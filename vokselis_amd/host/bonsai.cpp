@@ -52,6 +52,12 @@
 //                                                            (--keep-pick: what the ray through pixel (PX, PY) hits; needs --iso); components below N voxels go;
 //                                                            the K largest stay.  A voxel that goes becomes the sample value V of --label-fill (default 0).  The
 //                                                            cleaned volume replaces the loaded one; --save-raw writes it
+//          [--morph close|open|dilate|erode RADIUS] [--morph-spacing SX SY SZ] [--morph-fill IN OUT]
+//                                                            morphology of that range by a Euclidean ball (vk_distance_transform; up to 16 times, in the order
+//                                                            given): RADIUS in the units of the integer voxel pitch SX SY SZ (default 1 1 1); a voxel that joins
+//                                                            the range becomes the sample value IN (default: HI, or max(LO, 1) under an open range), one that
+//                                                            leaves it OUT (default 0).  Runs after --median / --smooth and before --components and the keep
+//                                                            flags, so close-then-keep-largest and open-then-label both work; --save-raw writes the result
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -99,6 +105,12 @@ static std::vector<uint64_t> g_keep_largest, g_drop_islands;                    
 static std::vector<std::array<uint32_t, 3>> g_keep_voxels, g_remove_voxels;      // --keep-voxel, --remove-voxel
 static std::vector<std::array<uint32_t, 2>> g_keep_picks;                        // --keep-pick PX PY
 static uint32_t g_w = 1280, g_h = 720;                                           // --size: --keep-pick's pixels are this frame's
+// --morph (vk_distance_transform), on the same range
+struct MorphOp { int op; const char *name; float radius; };
+static std::vector<MorphOp> g_morph;                                             // --morph OP RADIUS, in the order given
+static uint32_t g_morph_spacing[3] = {1u, 1u, 1u};                               // --morph-spacing SX SY SZ
+static float g_morph_fill[2] = {0.0f, 0.0f};                                     // --morph-fill IN OUT
+static bool g_morph_spacing_on = false, g_morph_fill_on = false;
 static bool label_ops() { return !g_keep_largest.empty() || !g_drop_islands.empty() || !g_keep_voxels.empty() || !g_remove_voxels.empty() || !g_keep_picks.empty(); }
 
 // the context of a run that replaces the render: 8 x 8, or the frame's size under the render's camera when --keep-pick casts rays through it
@@ -111,8 +123,28 @@ static void write_dense(const std::vector<unsigned char> &dense, const char *wha
     std::printf("%s volume: %zu bytes -> %s\n", what, dense.size(), g_save_raw.c_str());
 }
 
-// --components, then the keep flags in their fixed order, after the filters and before anything else reads the volume; the last of them fills --save-raw's file
+// --morph, in the order given, after the filters and before --components and the keep flags; the last of them fills --save-raw's file unless a keep flag follows
+static void apply_morph(Context &ctx) {
+    if (g_morph.empty()) return;
+    uint32_t dims[3] = {0, 0, 0};
+    int fmt = 0;
+    check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
+    std::vector<unsigned char> dense;
+    if (!g_save_raw.empty() && !label_ops()) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    const float fill_in = g_morph_fill_on ? g_morph_fill[0] : (std::isfinite(g_label_hi) ? g_label_hi : (std::isfinite(g_label_lo) ? std::max(g_label_lo, 1.0f) : 1.0f));
+    for (size_t k = 0; k < g_morph.size(); k++) {
+        const MorphOp &op = g_morph[k];
+        const vk_distance_result r = ctx.morph_volume(g_label_lo, g_label_hi, op.op, op.radius, g_morph_spacing, fill_in, g_morph_fill[1], nullptr, false, true,
+                                                      k + 1 == g_morph.size() && !dense.empty() ? dense.data() : nullptr);
+        std::printf("morph %s %g: %llu voxels in the range, %llu afterwards (%llu added, %llu removed)\n", op.name, op.radius, (unsigned long long)r.n_foreground,
+                    (unsigned long long)r.n_result, (unsigned long long)r.n_added, (unsigned long long)r.n_removed);
+    }
+    if (!dense.empty()) write_dense(dense, "morphed");
+}
+
+// --morph, then --components, then the keep flags in their fixed order, after the filters and before anything else reads the volume; the last of them fills --save-raw's file
 static void apply_labels(Context &ctx) {
+    apply_morph(ctx);
     if (!g_components && !label_ops()) return;
     uint32_t dims[3] = {0, 0, 0};
     int fmt = 0;
@@ -167,7 +199,7 @@ static void apply_labels(Context &ctx) {
 static void apply_filters(Context &ctx) {
     if (!g_median && !g_smooth) { apply_labels(ctx); return; }
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !label_ops()) {
+    if (!g_save_raw.empty() && !label_ops() && g_morph.empty()) {
         uint32_t dims[3] = {0, 0, 0};
         int fmt = 0;
         check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
@@ -626,6 +658,29 @@ int main(int argc, char **argv) {
             g_label_fill_on = true; g_label_fill = (float)std::atof(next());
             if (!std::isfinite(g_label_fill)) { std::fprintf(stderr, "bonsai: --label-fill V: V must be finite\n"); return 2; }
         }
+        else if (a == "--morph") {
+            const std::string name = next();
+            const float radius = (float)std::atof(next());
+            static const struct { const char *name; int op; } known[] = {{"close", VK_DIST_CLOSE}, {"open", VK_DIST_OPEN}, {"dilate", VK_DIST_DILATE}, {"erode", VK_DIST_ERODE}};
+            const auto *found = std::find_if(std::begin(known), std::end(known), [&](const auto &k) { return name == k.name; });
+            if (found == std::end(known)) { std::fprintf(stderr, "bonsai: --morph OP RADIUS: OP is close, open, dilate or erode\n"); return 2; }
+            if (!std::isfinite(radius) || radius < 0.0f || radius > VK_DIST_MAX_RADIUS) { std::fprintf(stderr, "bonsai: --morph OP RADIUS: a finite RADIUS of 0 .. 65535\n"); return 2; }
+            if (g_morph.size() >= 16u) { std::fprintf(stderr, "bonsai: --morph: at most 16 times\n"); return 2; }
+            g_morph.push_back({found->op, found->name, radius});
+        }
+        else if (a == "--morph-spacing") {
+            g_morph_spacing_on = true;
+            for (int k = 0; k < 3; k++) {
+                const long long v = std::atoll(next());
+                if (v < 1 || v > VK_DIST_MAX_SPACING) { std::fprintf(stderr, "bonsai: --morph-spacing SX SY SZ: integers of 1 .. 64\n"); return 2; }
+                g_morph_spacing[k] = (uint32_t)v;
+            }
+        }
+        else if (a == "--morph-fill") {
+            g_morph_fill_on = true;
+            for (int k = 0; k < 2; k++) g_morph_fill[k] = (float)std::atof(next());
+            if (!std::isfinite(g_morph_fill[0]) || !std::isfinite(g_morph_fill[1])) { std::fprintf(stderr, "bonsai: --morph-fill IN OUT: finite values\n"); return 2; }
+        }
         else if (a == "--camera-blobs") { std::string in = next(); return dump_camera_blobs(in, next()); }
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
@@ -649,9 +704,12 @@ int main(int argc, char **argv) {
     if (g_label_fill_on && !label_ops()) { std::fprintf(stderr, "bonsai: --label-fill needs a flag that drops voxels: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel or --keep-pick\n"); return 2; }
     if (g_keep_voxels.size() + g_keep_picks.size() > 16u) { std::fprintf(stderr, "bonsai: --keep-voxel and --keep-pick: at most 16 seeds together\n"); return 2; }
     if ((g_components || label_ops()) && gpus > 0) { std::fprintf(stderr, "bonsai: --components and the keep flags run on one GPU\n"); return 2; }
-    if (label_ops() && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
+    if (!g_morph.empty() && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --morph needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
+    if ((g_morph_spacing_on || g_morph_fill_on) && g_morph.empty()) { std::fprintf(stderr, "bonsai: %s needs --morph\n", g_morph_spacing_on ? "--morph-spacing" : "--morph-fill"); return 2; }
+    if (!g_morph.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --morph runs on one GPU\n"); return 2; }
+    if ((label_ops() || !g_morph.empty()) && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
     g_w = w; g_h = h;
-    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops()) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
+    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty()) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
     if ((g_median || g_smooth) && gpus > 0) { std::fprintf(stderr, "bonsai: --median and --smooth run on one GPU\n"); return 2; }
     if (hist) return run_histogram(hist_bins, hist_lo, hist_hi);
     if (!mesh_path.empty()) return run_mesh(mesh_path, mesh_obj, mesh_iso_on ? mesh_iso : g_iso.iso, mesh_scale);

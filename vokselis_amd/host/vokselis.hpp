@@ -440,6 +440,34 @@ class Context {
         check(ctx_, vk_label_components(ctx_, &req, box, nullptr, nullptr, 0, dense_out, &res));
         return res;
     }
+    // The squared Euclidean distance of every voxel to the set S of voxels whose stored texel lies in [lo, hi] (inside == false: 0 on S) or to
+    // its complement (inside: 0 off S), over the integer voxel pitch spacing = {sx, sy, sz} (nullptr: 1 1 1): nx ny nz uint32, x fastest,
+    // VK_DIST_INF where the target set is empty (vk_distance_transform; blocks; changes no state).  box / clip restrict S only.
+    std::vector<uint32_t> distance_transform(float lo, float hi = INFINITY, bool inside = false, const uint32_t *spacing = nullptr, const vk_voxel_box *box = nullptr, bool clip = false,
+                                             vk_distance_result *result = nullptr) {
+        vk_distance_request req{};
+        req.lo = lo; req.hi = hi; req.op = inside ? VK_DIST_INSIDE : VK_DIST_OUTSIDE;
+        req.flags = clip ? (uint32_t)VK_DIST_CLIP_BOX : 0u;
+        for (int c = 0; c < 3; c++) req.spacing[c] = spacing ? spacing[c] : 1u;
+        uint32_t dims[3] = {0, 0, 0};
+        check(ctx_, vk_volume_info(ctx_, dims, nullptr, nullptr, nullptr));
+        std::vector<uint32_t> d2((size_t)dims[0] * dims[1] * dims[2], 0u);
+        check(ctx_, vk_distance_transform(ctx_, &req, box, d2.data(), nullptr, result));
+        return d2;
+    }
+    // ... and morphology on it: op = VK_DIST_DILATE / _ERODE / _CLOSE / _OPEN by a Euclidean ball of `radius`, in the units of spacing.  A voxel
+    // that joins the set becomes fill_in, one that leaves it fill_out, every other voxel keeps its bits.  install: the result replaces the
+    // context's volume (outside frame_begin / frame_end).  dense_out: nullptr, or host memory of nx ny nz elements of the volume's format.
+    vk_distance_result morph_volume(float lo, float hi, int op, float radius, const uint32_t *spacing = nullptr, float fill_in = 1.0f, float fill_out = 0.0f, const vk_voxel_box *box = nullptr,
+                                    bool clip = false, bool install = true, void *dense_out = nullptr) {
+        vk_distance_request req{};
+        req.lo = lo; req.hi = hi; req.op = op; req.radius = radius; req.fill_in = fill_in; req.fill_out = fill_out;
+        req.flags = (clip ? (uint32_t)VK_DIST_CLIP_BOX : 0u) | (install ? (uint32_t)VK_DIST_INSTALL : 0u);
+        for (int c = 0; c < 3; c++) req.spacing[c] = spacing ? spacing[c] : 1u;
+        vk_distance_result res{};
+        check(ctx_, vk_distance_transform(ctx_, &req, box, nullptr, dense_out, &res));
+        return res;
+    }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
     void frames_in_flight(uint32_t k) { check(ctx_, vk_ctx_frames_in_flight(ctx_, k)); }
