@@ -715,6 +715,81 @@ _Static_assert(sizeof(vk_distance_request) == 40 && sizeof(vk_distance_result) =
 int vk_distance_transform(vk_ctx *ctx, const vk_distance_request *req, const vk_voxel_box *box, uint32_t *d2_out, void *dense_out,
                           vk_distance_result *result);
 
+/* The resample pass: a voxel box of the volume the context holds into a volume of caller-chosen dimensions, by
+ * one of three rules, optionally mapped into another scalar format -- crop, resize, make isotropic, window 16-bit data into u8 --
+ * without a trip through the host.  Every f32 operation below is rounded once; fmaf is fused where written and nowhere else.
+ * Volume and box.  t(x, y, z) is the STORED texel as f32 on the kernel's scale, as in vk_volume_filter (R8 0..255, R16_UNORM 0..65535,
+ * R16F the value; PACKED_PAIRS: the u8 value tap + delta).  B is the voxel box, half-open: `box`, the clip box under
+ * VK_RESAMPLE_CLIP_BOX (box must then be NULL), or NULL for the whole volume; an empty box is refused.  Per axis nb is B's extent and n
+ * the output extent (dims[axis], or nb where that is 0).  Source indices below are relative to B's low corner, and every index is
+ * clamped to B, not to the volume: resampling a box equals resampling an upload of that box alone.
+ * Geometry.  Output voxel j of an axis covers [j nb / n, (j + 1) nb / n) in box voxels (the voxel-area convention).  All index
+ * arithmetic is in 64-bit integers; floor is towards minus infinity; c(i) = min(max(i, 0), nb - 1).
+ * VK_RESAMPLE_NEAREST.  The source index per axis is floor((2 j + 1) nb / (2 n)): the voxel that holds the output voxel's centre.
+ * Without a value map the stored bits are copied unchanged (labels, masks, NaN payloads).
+ * VK_RESAMPLE_LINEAR.  Per axis num = (2 j + 1) nb - n, den = 2 n, i = floor(num / den), r = num - i den,
+ * f = (float)((double)r / (double)den); the taps are c(i) and c(i + 1).  lerp(a, b, f) = (f == 0) ? a : fmaf(f, b - a, a) -- an exact
+ * hit never meets its neighbour, so an infinite neighbour cannot make it NaN, and the identity resample is exact.  Four lerps along x
+ * (with fx, of the tap pairs at (y, z) = (c(iy), c(iz)), (c(iy+1), c(iz)), (c(iy), c(iz+1)), (c(iy+1), c(iz+1))), then two along y
+ * with fy (of the first two results, of the last two), then one along z with fz.
+ * VK_RESAMPLE_AREA.  Source voxel k of an axis overlaps output voxel j by o = min((j + 1) nb, (k + 1) n) - max(j nb, k n), for
+ * k = floor(j nb / n) .. floor(((j + 1) nb - 1) / n) (every such o is > 0), with weight w_k = (float)((double)o / (double)nb).  Three
+ * axis reductions in the order x, y, z over unrounded f32 intermediates, as in VK_FILTER_CONVOLVE: acc = w_first * t, then
+ * acc = fmaf(w_k, t, acc) in ascending k.  Refused (VK_ERR_UNSUPPORTED) where nb > VK_RESAMPLE_MAX_RATIO * n on some axis: an output
+ * voxel has at most VK_RESAMPLE_MAX_RATIO + 1 taps per axis.
+ * Value map.  S is the scale of a format: 255 for R8, 65535 for R16_UNORM, 1 for R16F.  The map runs iff the output format differs
+ * from the volume's or VK_RESAMPLE_WINDOW is set.  Without the flag lo = 0, hi = 1.  a = S_out / ((hi - lo) S_in) and
+ * b = -lo S_out / (hi - lo), both in double from lo and hi as double, each rounded once to f32; v' = fmaf(a, v, b), with v the
+ * interpolated value, or under NEAREST the texel as f32.  The window [lo, hi] is in sample values, like a table's domain.
+ * Store.  NEAREST without a map copies bits.  Everything else goes through vk_volume_filter's store rule for the output format (the
+ * volume's own without a map): R8 and R16_UNORM (uint) rintf(fminf(fmaxf(v, 0), S)), ties to even, a NaN stores 0; R16F f32 -> f16
+ * round to nearest even, subnormals kept, overflow to +-inf, any NaN stored as 0x7E00.
+ * Output and state.  dense_out (may be NULL): host memory of n_x n_y n_z elements of the output format, x fastest.  result (may be
+ * NULL): the output's dimensions and format, the layout installed (0 without VK_RESAMPLE_INSTALL) and the box B.  The call blocks.
+ * VK_RESAMPLE_INSTALL behaves exactly as VK_FILTER_INSTALL: the result replaces the context's volume under the table / projection /
+ * isosurface / lighting / shadows in force, frames in flight drain, batches are invalidated, the old volume stays on any failure;
+ * vk_volume_info then reports the new dimensions, format and layout.  The clip box stays in force in unit-cube coordinates of the
+ * NEW volume: after a crop to the clip box, turn it off (vk_set_clip_box(ctx, NULL)) unless the same fractions of the crop are meant.
+ * Without VK_RESAMPLE_INSTALL no context state changes.
+ * VK_ERR_INVALID, decided before any launch, outputs untouched ("resample: ..."): a NULL request; an unknown mode, flag or format;
+ * RGBA16F_PAIR as the output format; an output extent above 65535; under VK_RESAMPLE_WINDOW lo or hi not finite, lo >= hi, or an a or b
+ * that is not finite in f32; neither dense_out nor VK_RESAMPLE_INSTALL; an unknown layout; VK_RESAMPLE_INSTALL while a frame is being
+ * recorded; a box that is inverted, empty or leaves the volume, a box together with VK_RESAMPLE_CLIP_BOX; no volume.
+ * VK_ERR_UNSUPPORTED ("resample: ..."): a BRICKED / QUADS / STAGED or RGBA16F_PAIR source volume; the AREA ratio above
+ * VK_RESAMPLE_MAX_RATIO; under VK_RESAMPLE_INSTALL what vk_volume_upload_device refuses for the output: an extent above 8192,
+ * PACKED_PAIRS with an output that is not u8, a layout other than LINEAR / PACKED with an R16_UNORM output.  VK_ERR_OOM: a buffer
+ * cannot be allocated; the old volume stays. */
+enum { VK_RESAMPLE_NEAREST = 0, VK_RESAMPLE_LINEAR = 1, VK_RESAMPLE_AREA = 2 };
+enum { VK_RESAMPLE_INSTALL = 1, VK_RESAMPLE_CLIP_BOX = 2, VK_RESAMPLE_WINDOW = 4 };
+#define VK_RESAMPLE_KEEP_FORMAT (-1)
+#define VK_RESAMPLE_MAX_RATIO 16
+typedef struct vk_resample_request {
+    int32_t  mode;         /* VK_RESAMPLE_NEAREST / _LINEAR / _AREA */
+    uint32_t flags;        /* VK_RESAMPLE_INSTALL | VK_RESAMPLE_CLIP_BOX | VK_RESAMPLE_WINDOW */
+    uint32_t dims[3];      /* output extents x, y, z; 0: that axis keeps the box's extent */
+    int32_t  format;       /* VK_RESAMPLE_KEEP_FORMAT, VK_FMT_R8_UNORM, VK_FMT_R16_UNORM or VK_FMT_R16_FLOAT */
+    int32_t  layout;       /* with INSTALL.  VK_LAYOUT_AUTO: the layout vk_volume_info reports now, or PACKED where that is
+                              PACKED_PAIRS and the output is not u8; otherwise any layout vk_volume_upload_device accepts for the
+                              output, with its refusals */
+    float    lo, hi;       /* with VK_RESAMPLE_WINDOW: the window in sample values */
+} vk_resample_request;     /* 36 bytes */
+typedef struct vk_resample_result {
+    uint32_t dims[3];
+    int32_t  format, layout;
+    vk_voxel_box box;
+} vk_resample_result;      /* 44 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(vk_resample_request) == 36 && sizeof(vk_resample_result) == 44, "vk_resample_request: 36 bytes, vk_resample_result: 44 bytes");
+#else
+_Static_assert(sizeof(vk_resample_request) == 36 && sizeof(vk_resample_result) == 44, "vk_resample_request: 36 bytes, vk_resample_result: 44 bytes");
+#endif
+int vk_volume_resample(vk_ctx *ctx, const vk_resample_request *req, const vk_voxel_box *box, void *dense_out, vk_resample_result *result);
+/* What vk_volume_resample would produce for req and box, without launching or writing anything: the output's extents and format (the size
+ * of dense_out), the layout an install would land on (0 without VK_RESAMPLE_INSTALL) and the voxel box -- the clip box's voxels under
+ * VK_RESAMPLE_CLIP_BOX.  The refusals are vk_volume_resample's, but for "neither dense_out nor VK_RESAMPLE_INSTALL"; a NULL result is
+ * VK_ERR_INVALID.  Does not synchronise; changes no state. */
+int vk_resample_output(vk_ctx *ctx, const vk_resample_request *req, const vk_voxel_box *box, vk_resample_result *result);
+
 /* GlobalUniformBinding::update, src/context/global_ubo.rs:47-49 (48-byte Uniform, :52-65). */
 int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 /* CameraBinding::update, src/camera.rs:62-71 (144-byte CameraUniform, :5-11).  Always uploads

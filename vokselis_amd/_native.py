@@ -196,6 +196,26 @@ class VkDistanceResult(C.Structure):
 assert C.sizeof(VkDistanceRequest) == 40 and C.sizeof(VkDistanceResult) == 40
 
 
+RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_AREA = 0, 1, 2
+RESAMPLE_INSTALL, RESAMPLE_CLIP_BOX, RESAMPLE_WINDOW = 1, 2, 4
+RESAMPLE_KEEP_FORMAT = -1
+RESAMPLE_MAX_RATIO = 16
+
+
+class VkResampleRequest(C.Structure):
+    """vk_resample_request (36 bytes): the request of vk_volume_resample -- the mode, the flags, the output extents (x, y, z; 0 keeps
+    the box's), the output format and layout, the window of the value map."""
+    _fields_ = [("mode", C.c_int32), ("flags", C.c_uint32), ("dims", C.c_uint32 * 3), ("format", C.c_int32), ("layout", C.c_int32), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+class VkResampleResult(C.Structure):
+    """vk_resample_result (44 bytes): the output's extents and format, the layout installed (0: none) and the voxel box that was read."""
+    _fields_ = [("dims", C.c_uint32 * 3), ("format", C.c_int32), ("layout", C.c_int32), ("box", VkVoxelBox)]
+
+
+assert C.sizeof(VkResampleRequest) == 36 and C.sizeof(VkResampleResult) == 44
+
+
 def clip_box(lo, hi) -> VkClipBox:
     """A VkClipBox from two triples, held to vk_set_clip_box's rules before the library sees it: finite components (as f32) and
     0 <= lo < hi <= 1 on every axis.  Raises ValueError."""
@@ -256,6 +276,8 @@ SYMBOLS = {
     "vk_filter_gaussian": (C.c_int, [C.c_double, _u32, C.POINTER(_f32)]),
     "vk_label_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp]),  # const vk_label_request *, const vk_voxel_box *, labels_out, vk_component *, cap, dense_out, vk_label_result *
     "vk_distance_transform": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_distance_request *, const vk_voxel_box *, d2_out, dense_out, vk_distance_result *
+    "vk_volume_resample": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, dense_out, vk_resample_result *
+    "vk_resample_output": (C.c_int, [_vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, vk_resample_result *: the output's extents, format, layout and box, nothing launched
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),
     "vk_set_uniform": (C.c_int, [_vp, _vp]),
     "vk_set_camera": (C.c_int, [_vp, _vp]),

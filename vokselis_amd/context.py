@@ -550,6 +550,72 @@ class Context:
         """filter_volume(op="median3"): every texel becomes the median of its 3x3x3 neighbourhood -- lone speckles vanish, edges stay."""
         return self.filter_volume(None, "median3", install, out)
 
+    # -- the resample pass (vk_volume_resample: crop, resize, convert the format)
+    def resample_volume(self, dims=None, scale=None, box=None, mode: str = "linear", fmt=None, window=None, layout=None, install: bool = True, out: bool = False):
+        """vk_volume_resample: the voxel box `box` (None: the whole volume; "clip": the clip box's voxels; ((x0, y0, z0), (x1, y1, z1)))
+        of the stored volume resampled to dims = (nx, ny, nz) (None or 0 per axis keeps the box's extent) -- or to
+        max(1, round(extent * scale)) per axis, scale one number or three -- by mode "nearest", "linear" or "area" (the area-weighted
+        mean: the mode for shrinking, at most RESAMPLE_MAX_RATIO per axis).  fmt: None (the volume's format), "u8", "u16" or "f16";
+        window = (lo, hi): sample values lo .. hi are mapped onto the whole range of the output format (16-bit data into u8).  install:
+        the result replaces the context's volume, in `layout` (None: the current one, PACKED where that cannot hold the new format), under
+        the table / projection / isosurface in force (outside frame_begin / frame_end); the clip box stays in force in unit-cube
+        coordinates of the new volume.  Returns the VkResampleResult (dims, format, layout, box); with out=True (dense [nz, ny, nx],
+        VkResampleResult).  Blocks; needs install or out."""
+        from .label import voxel_box
+        from .resample import DTYPE, resample_request
+
+        vb = voxel_box(box)
+        if scale is not None:
+            if dims is not None:
+                raise ValueError("resample: dims or scale, not both")
+            sc = tuple(scale) if isinstance(scale, (tuple, list, np.ndarray)) else (scale, scale, scale)
+            if len(sc) != 3 or not all(np.isfinite(float(s)) and float(s) > 0.0 for s in sc):
+                raise ValueError("resample: scale is one finite number > 0, or three")
+            dims = tuple(max(1, int(round(n * float(s)))) for n, s in zip(self._box_dims(box), sc))
+        req = resample_request(dims, mode, fmt, window, layout, box, install, out)
+        res = N.VkResampleResult()
+        bp = C.byref(vb) if vb is not None else None
+        dense = None
+        if out:  # the library says what the call will write (vk_resample_output), or refuses as the call would
+            N.check(self._h, N.lib().vk_resample_output(self._h, C.byref(req), bp, C.byref(res)))
+            dense = np.zeros((res.dims[2], res.dims[1], res.dims[0]), DTYPE[res.format])
+        N.check(self._h, N.lib().vk_volume_resample(self._h, C.byref(req), bp, dense.ctypes.data if dense is not None else None, C.byref(res)))
+        return (dense, res) if out else res
+
+    def _box_dims(self, box):
+        """The extents (x, y, z) of a pass's voxel box (None: the volume; "clip": the clip box's voxels; two triples), from the library."""
+        from .label import voxel_box
+        from .resample import resample_request
+
+        vb, res = voxel_box(box), N.VkResampleResult()
+        req = resample_request(None, "nearest", box=box, install=False, out=True)
+        N.check(self._h, N.lib().vk_resample_output(self._h, C.byref(req), C.byref(vb) if vb is not None else None, C.byref(res)))
+        return tuple(int(v) for v in res.dims)
+
+    def crop_volume(self, box, install: bool = True, out: bool = False):
+        """resample_volume(mode="nearest") at the box's own extents: the voxels of `box` -- ((x0, y0, z0), (x1, y1, z1)) or "clip" --
+        become the volume, bit for bit.  crop_volume("clip") turns the clip box off after a successful install: the crop is what it showed."""
+        if box is None:
+            raise ValueError('crop: box is "clip" or ((x0, y0, z0), (x1, y1, z1))')
+        r = self.resample_volume(None, None, box, "nearest", None, None, None, install, out)
+        if box == "clip" and install:
+            self.set_clip_box(None)
+        return r
+
+    def downsample_volume(self, factor, box=None, install: bool = True, out: bool = False):
+        """resample_volume(mode="area") to ceil(n / factor) voxels per axis (factor: one integer or three, at most RESAMPLE_MAX_RATIO):
+        every output voxel is the mean of the voxels it covers."""
+        from .resample import downsample_dims
+
+        return self.resample_volume(downsample_dims(self._box_dims(box), factor), None, box, "area", None, None, None, install, out)
+
+    def isotropic_volume(self, spacing, mode: str = "linear", install: bool = True, out: bool = False):
+        """resample_volume to max(1, round(n_c * spacing_c / min(spacing))) voxels per axis: a scan whose voxels measure
+        spacing = (sx, sy, sz) becomes one of cubic voxels of the finest of the three."""
+        from .resample import isotropic_dims
+
+        return self.resample_volume(isotropic_dims(self._box_dims(None), spacing), None, None, mode, None, None, None, install, out)
+
     # -- connected components of a value range (vk_label_components)
     def _volume_dtype(self):
         dims, fmt = (C.c_uint32 * 3)(), C.c_int()

@@ -19,6 +19,7 @@
 //   vk_launch_filter.hip   vk_volume_filter, vk_filter_gaussian: separable convolution and 3x3x3 median of the volume (vk_filter.hpp)
 //   vk_launch_label.hip    vk_label_components: connected components of a value range, keep or drop them (vk_label.hpp)
 //   vk_launch_dist.hip     vk_distance_transform: exact Euclidean distance transform of a value range, morphology by a radius (vk_dist.hpp)
+//   vk_launch_resample.hip vk_volume_resample: a voxel box of the volume into other dimensions and another scalar format (vk_resample.hpp)
 //   vk_launch_staged.hip   instantiates the LDS-staged march kernels       (vk_staged.hpp)
 //   vk_launch_compute.hip  instantiates the compute twin and C3            (vk_compute.hpp)
 //   vk_post.hip            clear, un-tile, present, capture                (vk_post.hpp)
@@ -173,6 +174,10 @@ struct vk_ctx {
     uint32_t dist_max_blocks = 0;    // vk_distance_transform: cap of every grid (0: none) -- lets a small volume drive the grid-stride loops over columns, lines and voxels
     uint32_t dist_x_plain = 0;       // ... 1 (measurements, tests): the x pass runs the line function along rows instead of transposing
     uint32_t dist_timing = 0;        // ... k (measurements): the call brackets its k-th kernel with the timer's events (1 column, 2 line y, 3 line x; 4 .. 6 the second round; 7 stats or mask)
+    uint32_t resample_max_blocks = 0;  // vk_volume_resample: cap of the grid (0: none) -- lets a small volume drive the loop over tiles
+    uint32_t resample_area_passes = 0; // ... 1 (measurements, tests): AREA as three axis passes through f32 intermediates instead of the fused footprint loop
+    uint32_t resample_area_unroll = 1; // ... 0 (measurements, tests): AREA by an integer ratio of 2 .. 4 runs the table-driven footprint loops, not the unrolled ones
+    uint32_t resample_timing = 0;      // ... 1 (measurements): the call brackets its kernel with the timer's events (the pass has one phase)
 
     // present targets (next row N1/N2)
     uint32_t *rgba8 = nullptr, *bgra8 = nullptr;

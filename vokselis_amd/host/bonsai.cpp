@@ -38,6 +38,14 @@
 //          [--mesh OUT.stl|OUT.obj [--mesh-iso V] [--mesh-scale SX SY SZ]]   in place of the raycast (vk_extract_isosurface): the isosurface at sample value V
 //                                                            (default: --iso's) as binary STL or welded OBJ, the unit cube scaled by SX SY SZ (default 1 1 1);
 //                                                            honours --clip (the voxels whose centres lie in the box), --raw / --raw-u16 and --dims
+//          [--crop X0 Y0 Z0 X1 Y1 Z1 | clip] [--resample NX NY NZ [nearest|linear|area]] [--downsample F] [--isotropic SX SY SZ] [--to-u8 LO HI] [--to-u16 LO HI]
+//                                                            the resample pass (vk_volume_resample), as installing calls right after the volume is loaded, before
+//                                                            --median / --smooth, in the order given (up to 16): --crop keeps the voxels of a box (clip: of the --clip
+//                                                            box, which is then turned off), --resample resizes to NX NY NZ (0: that axis stays; default linear),
+//                                                            --downsample F takes the mean of F^3 voxels (area, 1 .. 16), --isotropic resizes a scan of voxel
+//                                                            spacing SX SY SZ to cubic voxels (linear), --to-u8 / --to-u16 map the sample values LO .. HI onto the
+//                                                            whole range of the new format (nearest, same size; either may stand beside a resize).  Every later
+//                                                            flag sees the new volume; the new dimensions and format are printed; --save-raw writes the new array
 //          [--median] [--smooth SX SY SZ] [--save-raw PATH]    the volume filter pass (vk_volume_filter), applied once the volume is loaded and before anything else,
 //                                                            so --iso, --mesh, --histogram and --auto-window see the filtered data: first the 3x3x3 median,
 //                                                            then a Gaussian of SX SY SZ voxels (0: the axis is skipped); --save-raw writes the filtered dense
@@ -95,6 +103,18 @@ static bool g_median = false;      // --median: the 3x3x3 median of the loaded v
 static bool g_smooth = false;      // --smooth: then a Gaussian of g_sigma voxels per axis
 static double g_sigma[3] = {0.0, 0.0, 0.0};
 static std::string g_save_raw;     // --save-raw: the filtered dense volume
+// --crop, --resample, --downsample, --isotropic, --to-u8, --to-u16 (vk_volume_resample), in the order given
+struct ResampleOp {
+    enum Kind { CROP, CROP_CLIP, RESIZE, DOWNSAMPLE, ISOTROPIC, CONVERT } kind;
+    const char *name;
+    vk_voxel_box box;      // CROP
+    uint32_t dims[3];      // RESIZE; DOWNSAMPLE: the factor in dims[0]
+    int mode;              // RESIZE
+    double spacing[3];     // ISOTROPIC
+    int format;            // CONVERT
+    float window[2];       // CONVERT
+};
+static std::vector<ResampleOp> g_resample;
 
 // --components and the keep flags (vk_label_components)
 static bool g_components = false;  // --components LO HI [CONN]
@@ -195,8 +215,37 @@ static void apply_labels(Context &ctx) {
     if (!dense.empty()) write_dense(dense, "cleaned");
 }
 
+// --crop, --resample, --downsample, --isotropic, --to-u8, --to-u16 in the order given, right after the volume is loaded; the last of them fills --save-raw's
+// file unless a filter, a --morph or a keep flag follows
+static void apply_resample(Context &ctx) {
+    if (g_resample.empty()) return;
+    static const char *const fmt_name[] = {"R8_UNORM", "R16_FLOAT", "RGBA16F_PAIR", "R16_UNORM"};
+    const bool save = !g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty();
+    std::vector<unsigned char> dense;
+    for (size_t k = 0; k < g_resample.size(); k++) {
+        const ResampleOp &op = g_resample[k];
+        std::vector<unsigned char> *out = save && k + 1 == g_resample.size() ? &dense : nullptr;
+        vk_resample_result r{};
+        switch (op.kind) {
+            case ResampleOp::CROP: r = ctx.crop_volume(&op.box, true, out); break;
+            case ResampleOp::CROP_CLIP:
+                if (!g_clip_on) throw std::runtime_error("--crop clip needs --clip");
+                r = ctx.crop_volume(nullptr, true, out);
+                g_clip_on = false;  // the crop is what the box showed
+                break;
+            case ResampleOp::RESIZE: r = ctx.resample_volume(op.dims, op.mode, nullptr, false, VK_RESAMPLE_KEEP_FORMAT, nullptr, VK_LAYOUT_AUTO, true, out); break;
+            case ResampleOp::DOWNSAMPLE: r = ctx.downsample_volume(op.dims[0], true, out); break;
+            case ResampleOp::ISOTROPIC: r = ctx.isotropic_volume(op.spacing, VK_RESAMPLE_LINEAR, true, out); break;
+            case ResampleOp::CONVERT: r = ctx.resample_volume(nullptr, VK_RESAMPLE_NEAREST, nullptr, false, op.format, op.window, VK_LAYOUT_AUTO, true, out); break;
+        }
+        std::printf("%s: volume %u x %u x %u %s\n", op.name, r.dims[0], r.dims[1], r.dims[2], fmt_name[r.format & 3]);
+    }
+    if (save) write_dense(dense, "resampled");
+}
+
 // --median, then --smooth, once the volume is there and before anything reads it; the last of them also fills --save-raw's file (unless a keep flag follows)
 static void apply_filters(Context &ctx) {
+    apply_resample(ctx);
     if (!g_median && !g_smooth) { apply_labels(ctx); return; }
     std::vector<unsigned char> dense;
     if (!g_save_raw.empty() && !label_ops() && g_morph.empty()) {
@@ -624,6 +673,52 @@ int main(int argc, char **argv) {
             if (g_sigma[0] == 0.0 && g_sigma[1] == 0.0 && g_sigma[2] == 0.0) { std::fprintf(stderr, "bonsai: --smooth SX SY SZ: at least one sigma above 0\n"); return 2; }
         }
         else if (a == "--save-raw") g_save_raw = next();
+        else if (a == "--crop" || a == "--resample" || a == "--downsample" || a == "--isotropic" || a == "--to-u8" || a == "--to-u16") {
+            ResampleOp op{};
+            if (a == "--crop") {
+                op.name = "crop";
+                const std::string first = next();
+                if (first == "clip") op.kind = ResampleOp::CROP_CLIP;
+                else {
+                    op.kind = ResampleOp::CROP;
+                    long v[6];
+                    v[0] = std::atol(first.c_str());
+                    for (int k = 1; k < 6; k++) v[k] = std::atol(next());
+                    for (int k = 0; k < 6; k++) if (v[k] < 0 || v[k] > 65535) { std::fprintf(stderr, "bonsai: --crop X0 Y0 Z0 X1 Y1 Z1: voxel indices of 0 .. 65535, or --crop clip\n"); return 2; }
+                    if (v[0] >= v[3] || v[1] >= v[4] || v[2] >= v[5]) { std::fprintf(stderr, "bonsai: --crop X0 Y0 Z0 X1 Y1 Z1: a half-open box with X0 < X1, Y0 < Y1, Z0 < Z1\n"); return 2; }
+                    op.box = vk_voxel_box{(uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2], (uint32_t)v[3], (uint32_t)v[4], (uint32_t)v[5]};
+                }
+            } else if (a == "--resample") {
+                op.kind = ResampleOp::RESIZE; op.name = "resample"; op.mode = VK_RESAMPLE_LINEAR;
+                for (int k = 0; k < 3; k++) {
+                    const long v = std::atol(next());
+                    if (v < 0 || v > 65535) { std::fprintf(stderr, "bonsai: --resample NX NY NZ: extents of 0 .. 65535 (0: the axis keeps its extent)\n"); return 2; }
+                    op.dims[k] = (uint32_t)v;
+                }
+                if (i + 1 < argc && argv[i + 1][0] != '-') {
+                    const std::string m = argv[++i];
+                    if (m == "nearest") op.mode = VK_RESAMPLE_NEAREST; else if (m == "linear") op.mode = VK_RESAMPLE_LINEAR; else if (m == "area") op.mode = VK_RESAMPLE_AREA;
+                    else { std::fprintf(stderr, "bonsai: --resample NX NY NZ [MODE]: MODE is nearest, linear or area\n"); return 2; }
+                }
+            } else if (a == "--downsample") {
+                op.kind = ResampleOp::DOWNSAMPLE; op.name = "downsample";
+                const long f = std::atol(next());
+                if (f < 1 || f > VK_RESAMPLE_MAX_RATIO) { std::fprintf(stderr, "bonsai: --downsample F: an integer of 1 .. 16\n"); return 2; }
+                op.dims[0] = (uint32_t)f;
+            } else if (a == "--isotropic") {
+                op.kind = ResampleOp::ISOTROPIC; op.name = "isotropic";
+                for (int k = 0; k < 3; k++) {
+                    op.spacing[k] = std::atof(next());
+                    if (!std::isfinite(op.spacing[k]) || !(op.spacing[k] > 0.0)) { std::fprintf(stderr, "bonsai: --isotropic SX SY SZ: finite spacings above 0\n"); return 2; }
+                }
+            } else {
+                op.kind = ResampleOp::CONVERT; op.name = a == "--to-u8" ? "to-u8" : "to-u16"; op.format = a == "--to-u8" ? VK_FMT_R8_UNORM : VK_FMT_R16_UNORM;
+                for (int k = 0; k < 2; k++) op.window[k] = (float)std::atof(next());
+                if (!std::isfinite(op.window[0]) || !std::isfinite(op.window[1]) || !(op.window[0] < op.window[1])) { std::fprintf(stderr, "bonsai: %s LO HI: finite sample values with LO < HI\n", a.c_str()); return 2; }
+            }
+            if (g_resample.size() >= 16u) { std::fprintf(stderr, "bonsai: --crop, --resample, --downsample, --isotropic, --to-u8 and --to-u16: at most 16 together\n"); return 2; }
+            g_resample.push_back(op);
+        }
         else if (a == "--components") {
             g_components = true;
             g_label_lo = (float)std::atof(next()); g_label_hi = (float)std::atof(next());
@@ -686,7 +781,9 @@ int main(int argc, char **argv) {
     }
     if (g_iso_on && g_mip) { std::fprintf(stderr, "bonsai: --iso and --mip exclude each other (an isosurface ignores the projection)\n"); return 2; }
     if (g_shadows_on && !(g_iso_on && g_lit && !g_light.headlight)) { std::fprintf(stderr, "bonsai: --shadows needs --iso and --light (shadows are cast along a light direction, under an isosurface)\n"); return 2; }
-    if (g_clip_on && g_tf.empty() && !g_mip && !g_iso_on && !sl.on && !hist && mesh_path.empty()) { std::fprintf(stderr, "bonsai: --clip needs --tf, --mip or --iso (the built-in march has no clip kernels)\n"); return 2; }
+    bool crop_clip = false;  // --crop clip consumes the box: nothing marches under it afterwards
+    for (const ResampleOp &op : g_resample) crop_clip = crop_clip || op.kind == ResampleOp::CROP_CLIP;
+    if (g_clip_on && !crop_clip && g_tf.empty() && !g_mip && !g_iso_on && !sl.on && !hist && mesh_path.empty()) { std::fprintf(stderr, "bonsai: --clip needs --tf, --mip or --iso (the built-in march has no clip kernels)\n"); return 2; }
     if ((pick || !depth_ppm.empty()) && !g_iso_on) { std::fprintf(stderr, "bonsai: --pick and --depth-ppm need --iso (the geometry pass is the isosurface's)\n"); return 2; }
     if (slab && !sl.on) { std::fprintf(stderr, "bonsai: --slab needs --slice or --slice-plane (a slab is a thick slice)\n"); return 2; }
     if (sl.on && gpus > 0) { std::fprintf(stderr, "bonsai: --slice and --slice-plane render on one GPU (groups have no slice output)\n"); return 2; }
@@ -709,7 +806,10 @@ int main(int argc, char **argv) {
     if (!g_morph.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --morph runs on one GPU\n"); return 2; }
     if ((label_ops() || !g_morph.empty()) && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
     g_w = w; g_h = h;
-    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty()) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
+    if (!g_resample.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --crop, --resample, --downsample, --isotropic, --to-u8 and --to-u16 run on one GPU\n"); return 2; }
+    for (const ResampleOp &op : g_resample)
+        if (op.kind == ResampleOp::CROP_CLIP && !g_clip_on) { std::fprintf(stderr, "bonsai: --crop clip needs --clip\n"); return 2; }
+    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && g_resample.empty()) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
     if ((g_median || g_smooth) && gpus > 0) { std::fprintf(stderr, "bonsai: --median and --smooth run on one GPU\n"); return 2; }
     if (hist) return run_histogram(hist_bins, hist_lo, hist_hi);
     if (!mesh_path.empty()) return run_mesh(mesh_path, mesh_obj, mesh_iso_on ? mesh_iso : g_iso.iso, mesh_scale);

@@ -400,6 +400,64 @@ class Context {
         f.flags = install ? (uint32_t)VK_FILTER_INSTALL : 0u;
         check(ctx_, vk_volume_filter(ctx_, &f, dense_out));
     }
+    // The extents of a pass's voxel box: `box`, else with clip the voxels whose centres lie in the clip box in force, else the volume
+    // (vk_resample_output: the library's own rule; an empty box is refused).
+    std::array<uint32_t, 3> box_dims(const vk_voxel_box *box = nullptr, bool clip = false) const {
+        vk_resample_request req{};
+        req.mode = VK_RESAMPLE_NEAREST;
+        req.flags = clip ? (uint32_t)VK_RESAMPLE_CLIP_BOX : 0u;
+        req.format = VK_RESAMPLE_KEEP_FORMAT;
+        vk_resample_result res{};
+        check(ctx_, vk_resample_output(ctx_, &req, box, &res));
+        return {res.dims[0], res.dims[1], res.dims[2]};
+    }
+    // The resample pass (vk_volume_resample): the voxel box (box; with clip the clip box's voxels; neither: the whole volume) resampled to
+    // dims (nullptr or 0 per axis: the box's extent) by mode = VK_RESAMPLE_NEAREST / _LINEAR / _AREA, into format (VK_RESAMPLE_KEEP_FORMAT:
+    // the volume's), under window = {lo, hi} in sample values (nullptr: none).  install: the result replaces the context's volume in
+    // `layout` (VK_LAYOUT_AUTO: the current one, PACKED where that cannot hold the new format; outside frame_begin / frame_end).  dense:
+    // nullptr, or a vector that is sized to the output and filled.  Needs install or dense.
+    vk_resample_result resample_volume(const uint32_t *dims = nullptr, int mode = VK_RESAMPLE_LINEAR, const vk_voxel_box *box = nullptr, bool clip = false,
+                                       int format = VK_RESAMPLE_KEEP_FORMAT, const float *window = nullptr, int layout = VK_LAYOUT_AUTO, bool install = true,
+                                       std::vector<unsigned char> *dense = nullptr) {
+        if (!install && !dense) throw std::invalid_argument("resample_volume: needs install or dense");
+        vk_resample_request req{};
+        req.mode = mode;
+        req.flags = (install ? (uint32_t)VK_RESAMPLE_INSTALL : 0u) | (clip ? (uint32_t)VK_RESAMPLE_CLIP_BOX : 0u) | (window ? (uint32_t)VK_RESAMPLE_WINDOW : 0u);
+        for (int a = 0; a < 3; a++) req.dims[a] = dims ? dims[a] : 0u;
+        req.format = format;
+        req.layout = layout;
+        if (window) { req.lo = window[0]; req.hi = window[1]; }
+        vk_resample_result res{};
+        if (dense) {  // the library says what the call will write, or refuses as the call would
+            check(ctx_, vk_resample_output(ctx_, &req, box, &res));
+            dense->assign((size_t)res.dims[0] * res.dims[1] * res.dims[2] * (res.format == VK_FMT_R8_UNORM ? 1u : 2u), 0);
+        }
+        check(ctx_, vk_volume_resample(ctx_, &req, box, dense ? dense->data() : nullptr, &res));
+        return res;
+    }
+    // ... the voxels of a box become the volume, bit for bit (NEAREST at the box's own extents); box == nullptr: the clip box, which is turned
+    // off after a successful install -- the crop is what it showed
+    vk_resample_result crop_volume(const vk_voxel_box *box, bool install = true, std::vector<unsigned char> *dense = nullptr) {
+        const vk_resample_result r = resample_volume(nullptr, VK_RESAMPLE_NEAREST, box, box == nullptr, VK_RESAMPLE_KEEP_FORMAT, nullptr, VK_LAYOUT_AUTO, install, dense);
+        if (!box && install) check(ctx_, vk_set_clip_box(ctx_, nullptr));
+        return r;
+    }
+    // ... every output voxel the mean of the factor^3 voxels it covers (AREA to ceil(n / factor) per axis; factor 1 .. VK_RESAMPLE_MAX_RATIO)
+    vk_resample_result downsample_volume(uint32_t factor, bool install = true, std::vector<unsigned char> *dense = nullptr) {
+        if (factor < 1u) throw std::invalid_argument("downsample_volume: factor >= 1");
+        const std::array<uint32_t, 3> bd = box_dims();
+        const uint32_t dims[3] = {(bd[0] + factor - 1u) / factor, (bd[1] + factor - 1u) / factor, (bd[2] + factor - 1u) / factor};
+        return resample_volume(dims, VK_RESAMPLE_AREA, nullptr, false, VK_RESAMPLE_KEEP_FORMAT, nullptr, VK_LAYOUT_AUTO, install, dense);
+    }
+    // ... a scan whose voxels measure spacing = {sx, sy, sz} into cubic voxels of the finest of the three: max(1, round(n_c s_c / min(s))) per axis
+    vk_resample_result isotropic_volume(const double spacing[3], int mode = VK_RESAMPLE_LINEAR, bool install = true, std::vector<unsigned char> *dense = nullptr) {
+        const double m = std::min(spacing[0], std::min(spacing[1], spacing[2]));
+        if (!(m > 0.0) || !std::isfinite(spacing[0]) || !std::isfinite(spacing[1]) || !std::isfinite(spacing[2])) throw std::invalid_argument("isotropic_volume: three finite spacings > 0");
+        const std::array<uint32_t, 3> bd = box_dims();
+        uint32_t dims[3];
+        for (int a = 0; a < 3; a++) dims[a] = (uint32_t)std::max(1.0, std::nearbyint((double)bd[a] * spacing[a] / m));
+        return resample_volume(dims, mode, nullptr, false, VK_RESAMPLE_KEEP_FORMAT, nullptr, VK_LAYOUT_AUTO, install, dense);
+    }
     // Connected components of the voxels whose stored texel lies in [lo, hi] (sample values; vk_label_components; blocks; changes no state):
     // connectivity 6, 18 or 26; box == nullptr: the whole volume, or with clip the clip box in force.  One call with room for 4096
     // components; a second only when there are more.
