@@ -715,6 +715,69 @@ _Static_assert(sizeof(vk_distance_request) == 40 && sizeof(vk_distance_result) =
 int vk_distance_transform(vk_ctx *ctx, const vk_distance_request *req, const vk_voxel_box *box, uint32_t *d2_out, void *dense_out,
                           vk_distance_result *result);
 
+/* Split touching objects: the set S of voxels whose stored texel lies in [lo, hi] is eroded by a radius, what
+ * survives is labelled as markers, the markers grow back over S -- every voxel joins the marker that reaches it first -- and S is cut
+ * where two regions meet, so that vk_label_components, the keep modes and the mesh see separate objects afterwards.  Every result is
+ * an integer or a stored texel: there is no rounding anywhere but in the fill.
+ * Foreground.  S, t, lo_k, hi_k and the box are exactly vk_distance_transform's: a voxel is in S iff it lies in the voxel box (`box`,
+ * the clip box under VK_SPLIT_CLIP_BOX, or NULL for the whole volume) and t >= lo_k && t <= hi_k.  The box restricts S only.
+ * Adjacency.  connectivity is 6, 18 or 26, exactly as in vk_label_components: two voxels are adjacent when their index difference d
+ * has max |d_c| = 1 and sum |d_c| <= 1, 2 or 3.  No wrap and no clamping.
+ * Markers.  R2 = (uint64_t)floor((double)radius * (double)radius).  K = ero(S) = { v in S : D2(not S, v) > R2 }, with D2 over the
+ * integer `spacing` exactly as VK_DIST_ERODE.  VK_DIST_INF > R2 always holds, so when S is the whole volume K = S.  The marker
+ * components are the components of K under `connectivity`.
+ * Steps.  g(v) = 0 on K.  For v in S \ K, g(v) is the least k for which a path v0 in K, v1, ..., vk = v exists whose every vi lies in
+ * S and whose consecutive voxels are adjacent.  A voxel of S with no such path is unreached; a component of S is unreached either as
+ * a whole or not at all.
+ * Anchors and regions.  A marker component's anchor is its smallest linear index x + nx (y + ny z).  a(v) on K is the anchor of v's
+ * marker component.  For a reached v with g(v) = k > 0: a(v) = min { a(u) : u in S, u adjacent to v, g(u) = k - 1 }.  The unreached
+ * voxels are labelled as vk_label_components would label them: components under `connectivity`, each with its smallest linear index
+ * as anchor.  A region is the set of voxels that share one a.  Regions are numbered 1 .. N by increasing anchor; marker regions and
+ * unreached (residue) regions share this one numbering.  radius = 0, or any radius that leaves K empty, gives bit for bit
+ * vk_label_components' labels and table; every region is connected under `connectivity`; the result depends on no launch shape,
+ * schedule or layout.
+ * Outputs.  labels_out (may be NULL): nx ny nz uint32, x fastest, 0 off S.  components (may be NULL): the first
+ * min(N, cap_components) regions in id order; `first` is the region's ANCHOR -- a grown region can hold smaller indices than its
+ * anchor -- and n_voxels and box cover the whole region.  result (may be NULL): n_regions = N, n_foreground = |S|, n_markers (the
+ * marker components), n_marker_voxels = |K|, n_residue_regions and n_residue_voxels (the unreached regions and their voxels), n_cut,
+ * and rounds: the largest finite g, or 0 if there is none -- defined by the rule, not by the implementation.
+ * Cut.  A voxel v of S is cut iff some adjacent u in S lies in a region with a smaller id.  The output texel of a cut voxel is
+ * fill_out through vk_label_components' fill rule F; every other voxel keeps its stored bits.  Only the later region's side is cut,
+ * so the cut is one voxel thick; afterwards no two adjacent voxels of S that were not cut lie in different regions.  dense_out (may be
+ * NULL) and VK_SPLIT_INSTALL behave exactly as vk_label_components' dense_out and VK_LABEL_INSTALL.  The call blocks, runs on the
+ * context's current stream and allocates and frees its own buffers.
+ * VK_ERR_INVALID, decided before any launch, outputs untouched ("vk_split_components: ..."): a NULL request; lo or hi NaN,
+ * lo > hi; a connectivity other than 6, 18, 26; an unknown flag; pad != 0; a spacing of 0 or above VK_DIST_MAX_SPACING; a radius that
+ * is not finite, is negative or lies above VK_DIST_MAX_RADIUS; a fill_out that is not finite; components != NULL with
+ * cap_components == 0; none of labels_out, components, dense_out, VK_SPLIT_INSTALL and result requested; with dense_out or
+ * VK_SPLIT_INSTALL an F(fill_out) whose value on the kernel's scale lies inside [lo_k, hi_k] (such a cut would cut nothing);
+ * VK_SPLIT_INSTALL while a frame is being recorded; a box that is inverted or leaves the volume, a box together with
+ * VK_SPLIT_CLIP_BOX; no volume.  VK_ERR_UNSUPPORTED ("split: ..."): a BRICKED / QUADS / STAGED or RGBA16F_PAIR volume; a volume of
+ * more than 2^32 - 2 voxels; sum_c (spacing[c] * (n_c - 1))^2 > 0xFFFFFFFE.  VK_ERR_OOM: a buffer cannot be allocated.  A call that
+ * fails later may have written its outputs already; the context's volume is the old one whenever the call does not return VK_OK. */
+enum { VK_SPLIT_CLIP_BOX = 1, VK_SPLIT_INSTALL = 2 };
+typedef struct vk_split_request {
+    float    lo, hi;         /* the value range, formed exactly as vk_label_components forms lo_k, hi_k */
+    uint32_t connectivity;   /* 6, 18 or 26 */
+    uint32_t flags;          /* VK_SPLIT_CLIP_BOX | VK_SPLIT_INSTALL */
+    uint32_t spacing[3];     /* integer voxel pitch per axis x, y, z: 1 .. VK_DIST_MAX_SPACING */
+    float    radius;         /* the erosion radius in the units of spacing: 0 .. VK_DIST_MAX_RADIUS */
+    float    fill_out;       /* sample value of a cut voxel; finite, outside [lo, hi] once stored */
+    uint32_t pad;            /* 0 */
+} vk_split_request;          /* 40 bytes */
+typedef struct vk_split_result {
+    uint64_t n_regions, n_foreground, n_markers, n_marker_voxels, n_residue_regions, n_residue_voxels, n_cut;
+    uint32_t rounds;         /* the largest finite g (0: none) */
+    uint32_t pad;
+} vk_split_result;           /* 64 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(vk_split_request) == 40 && sizeof(vk_split_result) == 64, "vk_split_request: 40 bytes, vk_split_result: 64 bytes");
+#else
+_Static_assert(sizeof(vk_split_request) == 40 && sizeof(vk_split_result) == 64, "vk_split_request: 40 bytes, vk_split_result: 64 bytes");
+#endif
+int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel_box *box, uint32_t *labels_out, vk_component *components,
+                        uint64_t cap_components, void *dense_out, vk_split_result *result);
+
 /* The resample pass: a voxel box of the volume the context holds into a volume of caller-chosen dimensions, by
  * one of three rules, optionally mapped into another scalar format -- crop, resize, make isotropic, window 16-bit data into u8 --
  * without a trip through the host.  Every f32 operation below is rounded once; fmaf is fused where written and nowhere else.

@@ -3,7 +3,8 @@ to register names (B) or different (C): tools/isa_diff.py OLD_TREE NEW_TREE [uni
 default: every vk_launch_*.hip that both trees have).
 
 Each named vk_launch_*.hip of both trees is compiled with the product's flags plus -S --cuda-device-only, the assembly is split per
-kernel symbol, debug directives and comments are stripped, and every symbol lands in one class:
+kernel symbol, debug directives and comments are stripped, block labels lose their function's number in the unit (.LBB7_3 -> .LBB_3: a
+function added to the unit shifts it), and every symbol lands in one class:
     A  instruction text and resource footer identical
     B  identical once every register token (vN, sN, aN, v[N:M], s[N:M], a[N:M]) is a placeholder, footers identical: renaming only
     C  anything else
@@ -62,6 +63,7 @@ def kernels(text):
             in_body = True
         elif in_body:
             s = re.sub(r"\s+", " ", line.split(";")[0].strip())
+            s = re.sub(r"\.LBB\d+_", ".LBB_", s)  # a block's label carries its function's number in the unit: an added function renumbers the others
             if s.startswith(".Lfunc_end") or s.startswith(".section"):
                 in_body = False
             elif s and (not s.startswith(".") or s.endswith(":")):  # instructions and branch targets; no .loc / .p2align / ...

@@ -196,6 +196,25 @@ class VkDistanceResult(C.Structure):
 assert C.sizeof(VkDistanceRequest) == 40 and C.sizeof(VkDistanceResult) == 40
 
 
+SPLIT_CLIP_BOX, SPLIT_INSTALL = 1, 2
+
+
+class VkSplitRequest(C.Structure):
+    """vk_split_request (40 bytes): the request of vk_split_components -- the value range, the connectivity, the flags, the integer
+    spacing per axis (x, y, z), the erosion radius and the fill of a cut voxel."""
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("connectivity", C.c_uint32), ("flags", C.c_uint32), ("spacing", C.c_uint32 * 3), ("radius", C.c_float),
+                ("fill_out", C.c_float), ("pad", C.c_uint32)]
+
+
+class VkSplitResult(C.Structure):
+    """vk_split_result (64 bytes): the totals of vk_split_components."""
+    _fields_ = [("n_regions", C.c_uint64), ("n_foreground", C.c_uint64), ("n_markers", C.c_uint64), ("n_marker_voxels", C.c_uint64), ("n_residue_regions", C.c_uint64),
+                ("n_residue_voxels", C.c_uint64), ("n_cut", C.c_uint64), ("rounds", C.c_uint32), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(VkSplitRequest) == 40 and C.sizeof(VkSplitResult) == 64
+
+
 RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_AREA = 0, 1, 2
 RESAMPLE_INSTALL, RESAMPLE_CLIP_BOX, RESAMPLE_WINDOW = 1, 2, 4
 RESAMPLE_KEEP_FORMAT = -1
@@ -276,6 +295,7 @@ SYMBOLS = {
     "vk_filter_gaussian": (C.c_int, [C.c_double, _u32, C.POINTER(_f32)]),
     "vk_label_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp]),  # const vk_label_request *, const vk_voxel_box *, labels_out, vk_component *, cap, dense_out, vk_label_result *
     "vk_distance_transform": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_distance_request *, const vk_voxel_box *, d2_out, dense_out, vk_distance_result *
+    "vk_split_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp]),  # const vk_split_request *, const vk_voxel_box *, labels_out, vk_component *, cap, dense_out, vk_split_result *
     "vk_volume_resample": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, dense_out, vk_resample_result *
     "vk_resample_output": (C.c_int, [_vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, vk_resample_result *: the output's extents, format, layout and box, nothing launched
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),

@@ -706,6 +706,37 @@ class Context:
                                                        C.byref(res)))
         return (dense, res) if out else res
 
+    # -- split touching objects: eroded markers grown back over the set, cut where regions meet (vk_split_components)
+    def split_components(self, lo, hi=float("inf"), radius: float = 0.0, spacing=(1, 1, 1), connectivity: int = 6, box=None, labels: bool = False, fill_out: float = 0.0,
+                         install: bool = False, out: bool = False):
+        """vk_split_components: the set S of voxels whose stored texel lies in [lo, hi] is eroded by a Euclidean ball of `radius` (in the
+        units of the integer voxel pitch `spacing`), the components of what survives grow back over S -- every voxel joins the marker that
+        reaches it first, ties go to the smaller anchor -- and a voxel that touches a region of smaller id is cut: it becomes fill_out, which
+        must lie outside [lo, hi].  Returns a Regions, shaped like label_components' result (.n, .sizes, .first -- a region's anchor --,
+        .boxes, .largest(k), .labels with labels=True) plus .n_markers, .n_residue_regions, .n_cut, .rounds and, with out=True, .dense
+        [nz, ny, nx].  install: the cut volume replaces the context's (outside frame_begin / frame_end); label_components and
+        keep_components then see the regions as separate components.  One call with room for 4096 regions, a second only when there are
+        more and nothing was installed: after an install the context holds the cut volume, a second call would split that one, so the
+        table then stays at its first 4096 regions (.n) while .n_regions tells how many there are; blocks."""
+        from .label import voxel_box
+        from .split import Regions, split_request
+
+        req, vb = split_request(lo, hi, radius=radius, spacing=spacing, connectivity=connectivity, box=box, fill_out=fill_out, install=install), voxel_box(box)
+        bp = C.byref(vb) if vb is not None else None
+        res = N.VkSplitResult()
+        dims, dtype = self._volume_dtype()
+        lab = np.zeros((dims[2], dims[1], dims[0]), np.uint32) if labels else None
+        dense = np.zeros((dims[2], dims[1], dims[0]) if dtype is not None else (1, 1, 1), dtype or np.uint8) if out else None
+        room = 4096
+        table = (N.VkComponent * room)()
+        N.check(self._h, N.lib().vk_split_components(self._h, C.byref(req), bp, lab.ctypes.data if lab is not None else None, table, room,
+                                                     dense.ctypes.data if dense is not None else None, C.byref(res)))
+        n = int(res.n_regions)
+        if n > room and not install:  # more regions than the table had room for: once more, for the table alone
+            table = (N.VkComponent * n)()
+            N.check(self._h, N.lib().vk_split_components(self._h, C.byref(req), bp, None, table, n, None, C.byref(res)))
+        return Regions(table, res, lab, dense)
+
     def set_root_skip(self, k: int):
         """vk_partition_root_skip: rank 0 sits out every k-th round of the tile deal (0: never)."""
         N.check(self._h, N.lib().vk_partition_root_skip(self._h, int(k)))

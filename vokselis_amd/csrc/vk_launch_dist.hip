@@ -16,8 +16,7 @@
 // kernel boundaries: no workgroup waits for another, and no address is written by two threads of a launch.  Integers only; plain C++,
 // no inline assembly, no per-thread arrays.  Every loop has a bound: the grid-stride loops their item count, the sweeps nz, dist_line
 // 2 n and n (vk_dist.hpp).  The counts reach memory as per-workgroup partial results that the host adds: no global atomics at all.
-#include "vk_launch.hpp"
-#include "vk_dist.hpp"
+#include "vk_dist_launch.hpp"
 #include "vk_label.hpp"
 #include "vk_texel.hpp"
 
@@ -158,6 +157,55 @@ __global__ __launch_bounds__(kDistThreads) void dist_mask_kernel(const DistVolum
     if (threadIdx.x < kDistMaskWords) partial[(size_t)kDistMaskWords * blockIdx.x + threadIdx.x] = s_n[threadIdx.x];
 }
 
+// ---- a round's launches, written once: vk_distance_transform brackets them with its timing phases, dist_launch_inside (vk_dist_launch.hpp)
+// runs them for another pass ----
+struct DistGrids { uint32_t column, y, x, tile, voxel; };
+static DistGrids dist_grids(const vk_ctx *ctx, const DistDesc &D) {
+    auto blocks_for = [&](uint64_t items) { return label_blocks((items + kDistThreads - 1u) / kDistThreads, ctx->dist_max_blocks); };
+    DistGrids G;
+    G.column = blocks_for(D.slice); G.y = blocks_for((uint64_t)D.nx * D.nz); G.x = blocks_for((uint64_t)D.ny * D.nz);
+    G.tile = label_blocks((uint64_t)((D.nx + kDistTile - 1u) / kDistTile) * ((D.ny + kDistTile - 1u) / kDistTile) * D.nz, ctx->dist_max_blocks);
+    G.voxel = std::min<uint32_t>(blocks_for(D.n), 8192u);  // the counting kernels: a partial result per workgroup
+    return G;
+}
+// the columns of the volume's predicate into a
+static void dist_launch_column(vk_ctx *ctx, const VolumeDesc &V, const DistDesc &D, const DistGrids &G, uint32_t *a) {
+    with_scalar_kind(ctx->vol_kind, [&](auto VOL) {
+        hipLaunchKernelGGL(dist_column_kernel<DistVolumeTarget<VOL()>>, dim3(G.column), dim3(kDistThreads), 0, ctx->stream, DistVolumeTarget<VOL()>{V}, D, a);
+    });
+}
+// a -> b along y
+static void dist_launch_line_y(vk_ctx *ctx, const DistDesc &D, const DistGrids &G, uint32_t *a, uint32_t *b, uint32_t *stack) {
+    hipLaunchKernelGGL(dist_line_kernel<1>, dim3(G.y), dim3(kDistThreads), 0, ctx->stream, D, (const uint32_t *)a, stack, b);
+}
+// b -> a along x: b is transposed into a, slice by slice, the y kernel runs on the volume with x and y exchanged (a -> b), and b is transposed
+// back into a; under dist_x_plain the line function runs along the rows instead
+static void dist_launch_line_x(vk_ctx *ctx, const DistDesc &D, const DistGrids &G, uint32_t *a, uint32_t *b, uint32_t *stack) {
+    if (ctx->dist_x_plain) {
+        hipLaunchKernelGGL(dist_line_kernel<0>, dim3(G.x), dim3(kDistThreads), 0, ctx->stream, D, (const uint32_t *)b, stack, a);
+        return;
+    }
+    DistDesc Dt = D;
+    Dt.nx = D.ny; Dt.ny = D.nx; Dt.w[0] = D.w[1]; Dt.w[1] = D.w[0];
+    hipLaunchKernelGGL(dist_transpose_kernel, dim3(G.tile), dim3(kDistThreads), 0, ctx->stream, D.nx, D.ny, D.nz, (const uint32_t *)b, a);
+    hipLaunchKernelGGL(dist_line_kernel<1>, dim3(G.x), dim3(kDistThreads), 0, ctx->stream, Dt, (const uint32_t *)a, stack, b);
+    hipLaunchKernelGGL(dist_transpose_kernel, dim3(G.tile), dim3(kDistThreads), 0, ctx->stream, D.ny, D.nx, D.nz, (const uint32_t *)b, a);
+}
+
+void dist_launch_inside(vk_ctx *ctx, const vk_voxel_box &B, float lo_k, float hi_k, const uint32_t spacing[3], uint32_t *a, uint32_t *b, uint32_t *stack) {
+    DistDesc D{};
+    D.nx = ctx->nx; D.ny = ctx->ny; D.nz = ctx->nz;
+    D.n = (uint64_t)ctx->nx * ctx->ny * ctx->nz; D.slice = (uint64_t)ctx->nx * ctx->ny;
+    for (int c = 0; c < 3; c++) D.w[c] = spacing[c];
+    D.complement = 1u;
+    D.box = B;
+    D.lo_k = lo_k; D.hi_k = hi_k;
+    const DistGrids G = dist_grids(ctx, D);
+    dist_launch_column(ctx, volume_desc(ctx), D, G, a);
+    dist_launch_line_y(ctx, D, G, a, b, stack);
+    dist_launch_line_x(ctx, D, G, a, b, stack);
+}
+
 extern "C" {
 
 int vk_distance_transform(vk_ctx *ctx, const vk_distance_request *req, const vk_voxel_box *box, uint32_t *d2_out, void *dense_out, vk_distance_result *result) {
@@ -189,9 +237,8 @@ int vk_distance_transform(vk_ctx *ctx, const vk_distance_request *req, const vk_
     D.hi_k = label_scale_bound(req->hi, ctx->format);
     D.fill_in_bits = label_fill_bits(req->fill_in, ctx->format);
     D.fill_out_bits = label_fill_bits(req->fill_out, ctx->format);
-    auto blocks_for = [&](uint64_t items) { return label_blocks((items + kDistThreads - 1u) / kDistThreads, ctx->dist_max_blocks); };
-    const uint32_t column_blocks = blocks_for(D.slice), y_blocks = blocks_for((uint64_t)D.nx * D.nz), x_blocks = blocks_for((uint64_t)D.ny * D.nz);
-    const uint32_t voxel_blocks = std::min<uint32_t>(blocks_for(n), 8192u);  // the counting kernels: a partial result per workgroup
+    const DistGrids G = dist_grids(ctx, D);
+    const uint32_t column_blocks = G.column, voxel_blocks = G.voxel;
 
     const VolumeDesc V = volume_desc(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -228,28 +275,12 @@ int vk_distance_transform(vk_ctx *ctx, const vk_distance_request *req, const vk_
     uint32_t *a = (uint32_t *)d_a.p, *b = (uint32_t *)d_b.p, *stack = (uint32_t *)d_stack.p;
     unsigned long long *partial = (unsigned long long *)d_partial.p;
 
-    // a round: the columns of the target into a, then a -> b along y and b -> a along x.  Along x: b is transposed into a, slice by slice, the
-    // y kernel runs on the volume with x and y exchanged (a -> b), and b is transposed back into a.
-    DistDesc Dt = D;
-    Dt.nx = D.ny; Dt.ny = D.nx; Dt.w[0] = D.w[1]; Dt.w[1] = D.w[0];
-    const uint32_t tile_blocks = label_blocks((uint64_t)((D.nx + kDistTile - 1u) / kDistTile) * ((D.ny + kDistTile - 1u) / kDistTile) * D.nz, ctx->dist_max_blocks);
+    // a round: the columns of the target into a, then a -> b along y and b -> a along x
     auto lines = [&](uint32_t k) {
-        phase(k + 1u, [&] { hipLaunchKernelGGL(dist_line_kernel<1>, dim3(y_blocks), dim3(kDistThreads), 0, ctx->stream, D, (const uint32_t *)a, stack, b); });
-        phase(k + 2u, [&] {
-            if (ctx->dist_x_plain) {
-                hipLaunchKernelGGL(dist_line_kernel<0>, dim3(x_blocks), dim3(kDistThreads), 0, ctx->stream, D, (const uint32_t *)b, stack, a);
-                return;
-            }
-            hipLaunchKernelGGL(dist_transpose_kernel, dim3(tile_blocks), dim3(kDistThreads), 0, ctx->stream, D.nx, D.ny, D.nz, (const uint32_t *)b, a);
-            hipLaunchKernelGGL(dist_line_kernel<1>, dim3(x_blocks), dim3(kDistThreads), 0, ctx->stream, Dt, (const uint32_t *)a, stack, b);
-            hipLaunchKernelGGL(dist_transpose_kernel, dim3(tile_blocks), dim3(kDistThreads), 0, ctx->stream, D.ny, D.nx, D.nz, (const uint32_t *)b, a);
-        });
+        phase(k + 1u, [&] { dist_launch_line_y(ctx, D, G, a, b, stack); });
+        phase(k + 2u, [&] { dist_launch_line_x(ctx, D, G, a, b, stack); });
     };
-    phase(1u, [&] {
-        with_scalar_kind(kind, [&](auto VOL) {
-            hipLaunchKernelGGL(dist_column_kernel<DistVolumeTarget<VOL()>>, dim3(column_blocks), dim3(kDistThreads), 0, ctx->stream, DistVolumeTarget<VOL()>{V}, D, a);
-        });
-    });
+    phase(1u, [&] { dist_launch_column(ctx, V, D, G, a); });
     lines(1u);
     if (dist_two_rounds(req->op)) {
         phase(4u, [&] { hipLaunchKernelGGL(dist_column_kernel<DistAboveTarget>, dim3(column_blocks), dim3(kDistThreads), 0, ctx->stream, DistAboveTarget{a}, D, a); });

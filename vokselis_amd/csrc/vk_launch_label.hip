@@ -16,24 +16,15 @@
 // Phases are separated by kernel boundaries: no flags, tickets or grid barriers, and no wave ever waits for another workgroup.  Every
 // loop whose trip count depends on data names what decreases.  Loop bounds are block-uniform wherever a barrier stands.  Plain C++;
 // no inline assembly.  wave64 is assumed in label_stats_kernel alone (the ballot is 64 bits wide).
-#include "vk_launch.hpp"
-#include "vk_label.hpp"
+// The tile kernel's body, label_tile, takes its predicate as a parameter: the volume's texels here, a word array for the split pass, which
+// borrows the other kernels as they are through the launchers at the end (vk_label_launch.hpp).
+#include "vk_label_launch.hpp"
 #include "vk_texel.hpp"
 
 #include <vector>
 
 using namespace vk;
 
-struct LabelDesc {
-    uint32_t nx, ny, nz, conn_sum;
-    vk_voxel_box box;
-    uint32_t ntx, nty;
-    uint64_t tiles;
-    uint64_t n;  // voxels
-    uint32_t chunks;
-    float lo_k, hi_k;
-    uint32_t fill_bits, invert, pad;
-};
 static_assert(sizeof(LabelDesc) % 8 == 0 && pass_kernargs_fit<LabelDesc>, "label kernels: VolumeDesc + LabelDesc");
 
 // the parent array in LDS, shared by the waves of a workgroup between two barriers
@@ -47,8 +38,25 @@ struct GlobalParent {
     static __device__ __forceinline__ uint32_t fetch_min(uint32_t *p, uint32_t i, uint32_t v) { return __hip_atomic_fetch_min(p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 };
 
+// Where a tile's predicate comes from: the volume's stored texel against [lo_k, hi_k] inside the box, or a word array against [lo, hi]
+// (vk_label_launch.hpp: the split pass's markers and residue).  Called for voxels inside the volume only.
 template <int VOL>
-__global__ __launch_bounds__(kLabelThreads) void label_tile_kernel(const VolumeDesc V, const LabelDesc D, uint32_t *__restrict__ parent) {
+struct LabelVolumePredicate {
+    const VolumeDesc V;
+    __device__ __forceinline__ bool operator()(const LabelDesc &D, uint32_t gx, uint32_t gy, uint32_t gz) const {
+        return label_in_box(gx, gy, gz, D.box) && label_foreground(texel_f32<VOL>(voxel_texel_bits<VOL>(V, gx, gy, gz)), D.lo_k, D.hi_k);
+    }
+};
+struct LabelWordsPredicate {
+    const LabelWords W;
+    __device__ __forceinline__ bool operator()(const LabelDesc &D, uint32_t gx, uint32_t gy, uint32_t gz) const {
+        const uint32_t w = W.w[voxel_index(gx, gy, gz, D.nx, D.ny)];
+        return w >= W.lo && w <= W.hi;
+    }
+};
+
+template <class PRED>
+__device__ __forceinline__ void label_tile(const PRED pred, const LabelDesc D, uint32_t *__restrict__ parent) {
     __shared__ uint32_t lds[kLabelTileVoxels];
     for (uint64_t tile = blockIdx.x; tile < D.tiles; tile += gridDim.x) {  // block-uniform
         uint32_t x0, y0, z0;
@@ -59,8 +67,7 @@ __global__ __launch_bounds__(kLabelThreads) void label_tile_kernel(const VolumeD
             label_local_coords(e, lx, ly, lz);
             const uint32_t gx = x0 + lx, gy = y0 + ly, gz = z0 + lz;
             bool fg = false;
-            if (gx < D.nx && gy < D.ny && gz < D.nz && label_in_box(gx, gy, gz, D.box))
-                fg = label_foreground(texel_f32<VOL>(voxel_texel_bits<VOL>(V, gx, gy, gz)), D.lo_k, D.hi_k);
+            if (gx < D.nx && gy < D.ny && gz < D.nz) fg = pred(D, gx, gy, gz);
             lds[e] = fg ? e : kLabelBackground;
         }
         __syncthreads();
@@ -95,6 +102,14 @@ __global__ __launch_bounds__(kLabelThreads) void label_tile_kernel(const VolumeD
         }
         __syncthreads();  // the next tile's load overwrites the labels
     }
+}
+
+template <int VOL>
+__global__ __launch_bounds__(kLabelThreads) void label_tile_kernel(const VolumeDesc V, const LabelDesc D, uint32_t *__restrict__ parent) {
+    label_tile(LabelVolumePredicate<VOL>{V}, D, parent);
+}
+__global__ __launch_bounds__(kLabelThreads) void label_tile_words_kernel(const LabelWords W, const LabelDesc D, uint32_t *__restrict__ parent) {
+    label_tile(LabelWordsPredicate{W}, D, parent);
 }
 
 __global__ __launch_bounds__(kLabelThreads) void label_seam_kernel(const LabelDesc D, uint32_t *parent) {
@@ -182,11 +197,6 @@ __global__ __launch_bounds__(kLabelThreads) void label_scan_kernel(uint32_t chun
     __syncthreads();
     if (threadIdx.x == 0) { totals[0] = carry; totals[1] = s_fg; }
 }
-
-// A component's record on the device: what the label kernel gathers into.
-struct LabelRecords {
-    uint32_t *first, *size, *box;  // box: 6 words per component -- the smallest x, y, z, then the largest
-};
 
 // Roots take their ids, 1 + the exclusive scan of the root flags in index order: a thread holds 16 consecutive voxels.
 __global__ __launch_bounds__(kLabelThreads) void label_number_kernel(const LabelDesc D, const uint32_t *__restrict__ parent, const uint32_t *__restrict__ chunk_offset, uint32_t *__restrict__ labels,
@@ -295,6 +305,26 @@ __global__ __launch_bounds__(kLabelThreads) void label_mask_kernel(const VolumeD
             else reinterpret_cast<uint16_t *>(out)[i] = (uint16_t)bits;
         }
     }
+}
+
+// ---- the kernels as another pass launches them (vk_label_launch.hpp) ----------------------------------------------------------------
+void label_launch_tile_words(hipStream_t stream, uint32_t blocks, const LabelDesc &D, const LabelWords &W, uint32_t *parent) {
+    hipLaunchKernelGGL(label_tile_words_kernel, dim3(blocks), dim3(kLabelThreads), 0, stream, W, D, parent);
+}
+void label_launch_seam(hipStream_t stream, uint32_t blocks, const LabelDesc &D, uint32_t *parent) {
+    hipLaunchKernelGGL(label_seam_kernel, dim3(blocks), dim3(kLabelThreads), 0, stream, D, parent);
+}
+void label_launch_flatten(hipStream_t stream, uint32_t blocks, const LabelDesc &D, uint32_t *parent, uint32_t *chunk_roots, uint32_t *chunk_fg) {
+    hipLaunchKernelGGL(label_flatten_kernel, dim3(blocks), dim3(kLabelThreads), 0, stream, D, parent, chunk_roots, chunk_fg);
+}
+void label_launch_scan(hipStream_t stream, uint32_t chunks, uint32_t *chunk_roots, const uint32_t *chunk_fg, unsigned long long *totals) {
+    hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(kLabelThreads), 0, stream, chunks, chunk_roots, chunk_fg, totals);
+}
+void label_launch_number(hipStream_t stream, uint32_t blocks, const LabelDesc &D, const uint32_t *parent, const uint32_t *chunk_offset, uint32_t *labels, const LabelRecords &R) {
+    hipLaunchKernelGGL(label_number_kernel, dim3(blocks), dim3(kLabelThreads), 0, stream, D, parent, chunk_offset, labels, R);
+}
+void label_launch_stats(hipStream_t stream, uint32_t blocks, const LabelDesc &D, const uint32_t *parent, uint32_t *labels, const LabelRecords &R) {
+    hipLaunchKernelGGL(label_stats_kernel, dim3(blocks), dim3(kLabelThreads), 0, stream, D, parent, labels, R);
 }
 
 extern "C" {

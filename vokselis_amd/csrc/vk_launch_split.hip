@@ -1,0 +1,318 @@
+// vk_launch_split.hip -- split touching objects (vk_split_components): S is eroded by a radius, what survives is
+// labelled as markers, the markers grow back over S round by round, what no marker reaches is labelled on its own, and S is cut where
+// two regions meet.  The request's validation, the states of the growth array and a voxel's step of a round are vk_split.hpp's, shared
+// with the host fuzz.  The distance kernels (vk_dist_launch.hpp) and the label pass's tile / seam / flatten / scan / number / stats
+// kernels (vk_label_launch.hpp) are borrowed as they are; the kernels here are the growth's and the cut's.
+//
+//   distance  D2(not S, .): the distance pass's first round.
+//   markers   tile (predicate: D2 > R2, from the word array), seam, flatten: every voxel of K holds its marker component's anchor.
+//   seed      the state array: K keeps its anchors, S \ K becomes kSplitUnreached, everything else stays kLabelBackground.
+//   grow      one launch per round, from one state array into the other: a voxel that is unreached takes the smallest anchor among its
+//             neighbours in the array the round before left, every other voxel is copied.  The host launches kSplitBatch rounds, reads
+//             how many voxels each labelled, and stops after the batch in which a round labelled none.
+//   residue   tile (predicate: state == kSplitUnreached), seam, flatten over what no marker reached.
+//   merge     a reached voxel's parent is its anchor, an unreached one's its residue root: one parent array in which a root is a
+//             region's anchor; roots and foreground voxels are counted per chunk for the scan.
+//   number, stats   the label pass's, over the merged array.
+//   cut       one kernel per volume kind: the label, the neighbours' labels, then the stored texel or the fill; n_cut as one partial sum
+//             per workgroup.
+// Phases and rounds are separated by kernel boundaries: no flags, tickets or grid barriers, no wave waits for another workgroup, and no
+// kernel here reads an address that another thread of the same launch writes.  Plain C++; no inline assembly.
+#include "vk_dist_launch.hpp"
+#include "vk_label_launch.hpp"
+#include "vk_split.hpp"
+#include "vk_texel.hpp"
+
+#include <utility>
+#include <vector>
+
+using namespace vk;
+
+constexpr uint32_t kSplitMaxPartials = 8192;  // the cut kernel's grid: one partial sum per workgroup
+
+struct SplitPlainLoad {
+    static __device__ __forceinline__ uint32_t load(const uint32_t *p, uint32_t i) { return p[i]; }
+};
+
+// the sum of v over a workgroup's threads, added to *slot (LDS, zeroed before): lanes are combined in registers, one LDS add per wave
+__device__ __forceinline__ void split_block_add(unsigned long long *slot, uint32_t v) {
+    unsigned long long s = v;
+    for (int d = warpSize / 2; d > 0; d >>= 1) s += __shfl_down(s, d);
+    if ((threadIdx.x & (warpSize - 1)) == 0 && s) atomicAdd(slot, s);
+}
+
+// state is the markers' flattened parent array on entry: an anchor on K, kLabelBackground elsewhere.  d2 != 0 exactly on S.
+__global__ __launch_bounds__(kLabelThreads) void split_seed_kernel(const LabelDesc D, const uint32_t *__restrict__ d2, uint32_t *__restrict__ state) {
+    for (uint32_t chunk = blockIdx.x; chunk < D.chunks; chunk += gridDim.x) {
+        for (uint32_t k = 0; k < kLabelChunkPerThread; k++) {
+            const uint64_t i = (uint64_t)chunk * kLabelChunk + k * kLabelThreads + threadIdx.x;
+            if (i < D.n && state[i] == kLabelBackground && d2[i] != 0u) state[i] = kSplitUnreached;
+        }
+    }
+}
+
+// One round: out = in, but an unreached voxel takes the smallest anchor beside it in `in`.  *labelled: the voxels this round labelled.
+__global__ __launch_bounds__(kLabelThreads) void split_grow_kernel(const LabelDesc D, const uint32_t *__restrict__ in, uint32_t *__restrict__ out, unsigned long long *labelled) {
+    __shared__ unsigned long long s_n;
+    if (threadIdx.x == 0) s_n = 0ull;
+    __syncthreads();
+    uint32_t mine = 0u;
+    for (uint32_t chunk = blockIdx.x; chunk < D.chunks; chunk += gridDim.x) {
+        for (uint32_t k = 0; k < kLabelChunkPerThread; k++) {
+            const uint64_t i = (uint64_t)chunk * kLabelChunk + k * kLabelThreads + threadIdx.x;
+            if (i >= D.n) continue;
+            uint32_t s = in[i];
+            if (s == kSplitUnreached) {
+                uint32_t x, y, z;
+                label_coords((uint32_t)i, D.nx, D.ny, x, y, z);
+                s = split_grow_voxel<SplitPlainLoad>(in, x, y, z, D.nx, D.ny, D.nz, D.conn_sum);
+                mine += s != kSplitUnreached;
+            }
+            out[i] = s;
+        }
+    }
+    split_block_add(&s_n, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_n) atomicAdd(labelled, s_n);  // integers: the order of the adds does not show
+}
+
+// parent is the residue's flattened parent array on entry (a root on the unreached voxels, kLabelBackground elsewhere) and the merged one
+// on exit: a reached voxel holds its anchor.  A root of the merged array is a voxel that holds its own index.
+__global__ __launch_bounds__(kLabelThreads) void split_merge_kernel(const LabelDesc D, const uint32_t *__restrict__ state, uint32_t *__restrict__ parent, uint32_t *__restrict__ chunk_roots,
+                                                                    uint32_t *__restrict__ chunk_fg) {
+    __shared__ unsigned long long s_roots, s_fg;
+    for (uint32_t chunk = blockIdx.x; chunk < D.chunks; chunk += gridDim.x) {  // block-uniform
+        if (threadIdx.x == 0) { s_roots = 0ull; s_fg = 0ull; }
+        __syncthreads();
+        uint32_t roots = 0u, fg = 0u;
+        for (uint32_t k = 0; k < kLabelChunkPerThread; k++) {
+            const uint64_t i = (uint64_t)chunk * kLabelChunk + k * kLabelThreads + threadIdx.x;
+            if (i >= D.n) continue;
+            const uint32_t s = state[i];
+            const uint32_t p = s < kSplitUnreached ? s : parent[i];
+            if (s < kSplitUnreached) parent[i] = p;
+            fg += p != kLabelBackground;
+            roots += p == (uint32_t)i;
+        }
+        split_block_add(&s_roots, roots);
+        split_block_add(&s_fg, fg);
+        __syncthreads();
+        if (threadIdx.x == 0) { chunk_roots[chunk] = (uint32_t)s_roots; chunk_fg[chunk] = (uint32_t)s_fg; }
+        __syncthreads();
+    }
+}
+
+// out (may be NULL): the stored texel, or the fill where a neighbour in S carries a smaller id.  partial[b]: the cut voxels workgroup b saw.
+template <int VOL>
+__global__ __launch_bounds__(kLabelThreads) void split_cut_kernel(const VolumeDesc V, const LabelDesc D, const uint32_t *__restrict__ labels, void *__restrict__ out,
+                                                                  unsigned long long *__restrict__ partial) {
+    __shared__ unsigned long long s_n;
+    if (threadIdx.x == 0) s_n = 0ull;
+    __syncthreads();
+    uint32_t mine = 0u;
+    for (uint32_t chunk = blockIdx.x; chunk < D.chunks; chunk += gridDim.x) {
+        for (uint32_t k = 0; k < kLabelChunkPerThread; k++) {
+            const uint64_t i = (uint64_t)chunk * kLabelChunk + k * kLabelThreads + threadIdx.x;
+            if (i >= D.n) continue;
+            uint32_t x, y, z;
+            label_coords((uint32_t)i, D.nx, D.ny, x, y, z);
+            const uint32_t id = labels[i];
+            bool cut = false;
+            if (id > 1u) {  // region 1 has no smaller id beside it
+                for (uint32_t o = 0; o < kLabelOffsets; o++) {
+                    int dx, dy, dz;
+                    label_offset(o, dx, dy, dz);
+                    if (!label_adjacent(dx, dy, dz, D.conn_sum)) continue;
+                    const int64_t hx = (int64_t)x + dx, hy = (int64_t)y + dy, hz = (int64_t)z + dz;  // no wrap
+                    if (hx < 0 || hy < 0 || hz < 0 || hx >= (int64_t)D.nx || hy >= (int64_t)D.ny || hz >= (int64_t)D.nz) continue;
+                    const uint32_t other = labels[voxel_index((uint32_t)hx, (uint32_t)hy, (uint32_t)hz, D.nx, D.ny)];
+                    cut = cut || (other != 0u && other < id);
+                }
+            }
+            mine += cut;
+            if (!out) continue;
+            const uint32_t bits = cut ? D.fill_bits : voxel_texel_bits<VOL>(V, x, y, z);
+            if constexpr (texel_class(VOL) == TEXEL_U8) reinterpret_cast<uint8_t *>(out)[i] = (uint8_t)bits;
+            else reinterpret_cast<uint16_t *>(out)[i] = (uint16_t)bits;
+        }
+    }
+    split_block_add(&s_n, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = s_n;
+}
+
+extern "C" {
+
+int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel_box *box, uint32_t *labels_out, vk_component *components, uint64_t cap_components, void *dense_out,
+                        vk_split_result *result) {
+    static const char *const entry = "vk_split_components";
+    if (!ctx) return VK_ERR_INVALID;
+    if (const char *why = split_validate(req, labels_out != nullptr, components != nullptr, cap_components, dense_out != nullptr, result != nullptr))
+        return fail(ctx, VK_ERR_INVALID, std::string(entry) + ": " + why);
+    const bool install = (req->flags & VK_SPLIT_INSTALL) != 0u;
+    if (install && ctx->fif_open) return fail(ctx, VK_ERR_INVALID, std::string(entry) + ": VK_SPLIT_INSTALL while a frame is being recorded (call it outside vk_frame_begin / vk_frame_end)");
+    if (int rc = pass_needs(ctx, PASS_NEEDS_VOLUME, entry, "split")) return rc;
+    vk_voxel_box B;
+    if (int rc = pass_voxel_box(ctx, entry, "VK_SPLIT_CLIP_BOX", box, (req->flags & VK_SPLIT_CLIP_BOX) != 0u, B)) return rc;
+    if (int rc = pass_needs(ctx, PASS_NEEDS_SCALAR_KIND, entry, "split")) return rc;
+    const uint64_t n = (uint64_t)ctx->nx * ctx->ny * ctx->nz;
+    if (!label_volume_fits(ctx->nx, ctx->ny, ctx->nz)) return fail(ctx, VK_ERR_UNSUPPORTED, "split: a volume of more than 2^32 - 2 voxels (labels are 32-bit)");
+    if (!dist_d2_fits(req->spacing, ctx->nx, ctx->ny, ctx->nz))
+        return fail(ctx, VK_ERR_UNSUPPORTED, "split: sum_c (spacing[c] (n_c - 1))^2 exceeds 0xFFFFFFFE: a squared distance would not fit in 32 bits");
+    const float lo_k = label_scale_bound(req->lo, ctx->format), hi_k = label_scale_bound(req->hi, ctx->format);
+    if ((dense_out || install) && !split_fill_leaves_set(req->fill_out, ctx->format, lo_k, hi_k))
+        return fail(ctx, VK_ERR_INVALID, std::string(entry) + ": fill_out, once stored, lies inside [lo, hi]: the cut would cut nothing");
+
+    const int kind = ctx->vol_kind;
+    const FilterGrid G = filter_grid(ctx->nx, ctx->ny, ctx->nz, kLabelTile, ctx->label_max_blocks);
+    LabelDesc D{};
+    D.nx = ctx->nx; D.ny = ctx->ny; D.nz = ctx->nz;
+    D.conn_sum = label_conn_sum(req->connectivity);
+    D.box = B;
+    D.ntx = G.ntx; D.nty = G.nty; D.tiles = G.tiles;
+    D.n = n;
+    D.chunks = label_chunks(n);
+    D.lo_k = lo_k; D.hi_k = hi_k;
+    D.fill_bits = label_fill_bits(req->fill_out, ctx->format);
+    const uint32_t chunk_blocks = label_blocks(D.chunks, ctx->label_max_blocks);
+    const uint32_t cut_blocks = std::min(chunk_blocks, kSplitMaxPartials);
+    const uint64_t r2 = dist_r2(req->radius);  // <= VK_DIST_MAX_RADIUS^2 < VK_DIST_INF: r2 + 1 fits in a word
+
+    const VolumeDesc V = volume_desc(ctx);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipError_t e = hipSuccess;
+    auto alloc = [&](DeviceTemp &d, size_t bytes, const char *what) -> int {
+        e = hipMalloc(&d.p, bytes ? bytes : 1u);
+        if (e == hipSuccess) return VK_OK;
+        (void)hipGetLastError();
+        return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string(entry) + ": " + what + ": " + hipGetErrorString(e));
+    };
+    // (debug, vk_debug_set_param("split_timing", k): phase k alone between the context's timer events, read with vk_timer_elapsed_ms --
+    //  1 distance, 2 markers, 3 growth (every round, with the host's looks at the counts), 4 residue, 5 merge, 6 number and stats, 7 cut)
+    auto phase = [&](uint32_t k, auto &&launch) {
+        const bool timed = ctx->split_timing == k;
+        if (timed && e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+        if (e == hipSuccess) { launch(); if (e == hipSuccess) e = hipGetLastError(); }
+        if (timed && e == hipSuccess) {
+            e = hipEventRecord(ctx->ev1, ctx->stream);
+            ctx->timing_open = false;
+            ctx->timing_done = true;
+        }
+    };
+    auto hip_failed = [&]() { return fail(ctx, VK_ERR_HIP, std::string(entry) + ": " + hipGetErrorString(e)); };
+
+    DeviceTemp d_a, d_b, d_c, d_chunk_roots, d_chunk_fg, d_totals, d_counts, d_partial;
+    if (int rc = alloc(d_a, (size_t)n * 4u, "the distance array")) return rc;
+    if (int rc = alloc(d_b, (size_t)n * 4u, "the state array")) return rc;
+    if (int rc = alloc(d_c, (size_t)n * 4u, "the second state array")) return rc;
+    if (int rc = alloc(d_chunk_roots, (size_t)D.chunks * 4u, "the chunk counts")) return rc;
+    if (int rc = alloc(d_chunk_fg, (size_t)D.chunks * 4u, "the chunk counts")) return rc;
+    if (int rc = alloc(d_totals, 48u, "the totals")) return rc;
+    if (int rc = alloc(d_counts, (size_t)kSplitBatch * 8u, "the rounds' counts")) return rc;
+    if (int rc = alloc(d_partial, (size_t)cut_blocks * 8u, "the partial counts")) return rc;
+    uint32_t *a = (uint32_t *)d_a.p, *chunk_roots = (uint32_t *)d_chunk_roots.p, *chunk_fg = (uint32_t *)d_chunk_fg.p;
+    unsigned long long *d_tot = (unsigned long long *)d_totals.p, *counts = (unsigned long long *)d_counts.p;
+
+    // D2(not S, .) into a; the markers' parent array into b
+    phase(1u, [&] { dist_launch_inside(ctx, B, lo_k, hi_k, req->spacing, a, (uint32_t *)d_b.p, (uint32_t *)d_c.p); });
+    uint32_t *cur = (uint32_t *)d_b.p, *other = (uint32_t *)d_c.p;
+    phase(2u, [&] {
+        label_launch_tile_words(ctx->stream, G.blocks, D, LabelWords{a, (uint32_t)(r2 + 1u), 0xffffffffu}, cur);
+        label_launch_seam(ctx->stream, G.blocks, D, cur);
+        label_launch_flatten(ctx->stream, chunk_blocks, D, cur, chunk_roots, chunk_fg);
+        label_launch_scan(ctx->stream, D.chunks, chunk_roots, chunk_fg, d_tot);  // {marker components, |K|}
+        hipLaunchKernelGGL(split_seed_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, (const uint32_t *)a, cur);
+    });
+
+    // The growth.  Every batch but the last labels at least one voxel in each of its rounds, and S is finite: the loop ends.  A round that
+    // labels nothing copies the state, and so does every round after it: `cur` holds the fixed point when the batch is over.
+    uint32_t rounds = 0u;
+    phase(3u, [&] {
+        for (bool done = false; !done && e == hipSuccess;) {
+            unsigned long long got[kSplitBatch] = {};
+            e = hipMemsetAsync(counts, 0, sizeof got, ctx->stream);
+            for (uint32_t k = 0; k < kSplitBatch && e == hipSuccess; k++) {
+                hipLaunchKernelGGL(split_grow_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, (const uint32_t *)cur, other, counts + k);
+                e = hipGetLastError();
+                std::swap(cur, other);
+            }
+            if (e == hipSuccess) e = hipMemcpyAsync(got, counts, sizeof got, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            for (uint32_t k = 0; k < kSplitBatch && e == hipSuccess && !done; k++) {
+                if (got[k] == 0ull) done = true;
+                else rounds++;
+            }
+        }
+    });
+
+    // what no marker reached, labelled on its own into `other`; then the merged parent array, in place
+    phase(4u, [&] {
+        label_launch_tile_words(ctx->stream, G.blocks, D, LabelWords{cur, kSplitUnreached, kSplitUnreached}, other);
+        label_launch_seam(ctx->stream, G.blocks, D, other);
+        label_launch_flatten(ctx->stream, chunk_blocks, D, other, chunk_roots, chunk_fg);
+        label_launch_scan(ctx->stream, D.chunks, chunk_roots, chunk_fg, d_tot + 2);  // {residue regions, residue voxels}
+    });
+    uint32_t *parent = other, *labels = a;  // D2 is not needed any more
+    unsigned long long totals[6] = {};
+    phase(5u, [&] {
+        hipLaunchKernelGGL(split_merge_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, (const uint32_t *)cur, parent, chunk_roots, chunk_fg);
+        label_launch_scan(ctx->stream, D.chunks, chunk_roots, chunk_fg, d_tot + 4);  // {regions, |S|}
+    });
+    if (e == hipSuccess) e = hipMemcpyAsync(totals, d_tot, sizeof totals, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return hip_failed();
+    const uint64_t n_reg = totals[4];
+
+    DeviceTemp d_first, d_size, d_box;
+    if (int rc = alloc(d_first, (size_t)n_reg * 4u, "the region records")) return rc;
+    if (int rc = alloc(d_size, (size_t)n_reg * 4u, "the region records")) return rc;
+    if (int rc = alloc(d_box, (size_t)n_reg * 24u, "the region records")) return rc;
+    const LabelRecords R{(uint32_t *)d_first.p, (uint32_t *)d_size.p, (uint32_t *)d_box.p};
+    phase(6u, [&] {
+        if (n_reg) label_launch_number(ctx->stream, chunk_blocks, D, parent, chunk_roots, labels, R);
+        label_launch_stats(ctx->stream, chunk_blocks, D, parent, labels, R);
+    });
+
+    const size_t dense_bytes = (size_t)n * (ctx->format == VK_FMT_R8_UNORM ? 1u : 2u);
+    DeviceTemp d_out;
+    if (dense_out || install)
+        if (int rc = alloc(d_out, dense_bytes, "the output buffer")) return rc;
+    std::vector<unsigned long long> sums(cut_blocks);
+    if (dense_out || install || result) {
+        phase(7u, [&] {
+            with_scalar_kind(kind, [&](auto VOL) {
+                hipLaunchKernelGGL(split_cut_kernel<VOL()>, dim3(cut_blocks), dim3(kLabelThreads), 0, ctx->stream, V, D, (const uint32_t *)labels, d_out.p, (unsigned long long *)d_partial.p);
+            });
+        });
+        if (e == hipSuccess) e = hipMemcpyAsync(sums.data(), d_partial.p, sums.size() * 8u, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && dense_out) e = hipMemcpyAsync(dense_out, d_out.p, dense_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    if (e == hipSuccess && labels_out) e = hipMemcpyAsync(labels_out, labels, (size_t)n * 4u, hipMemcpyDeviceToHost, ctx->stream);
+    const uint64_t n_rec = components ? (n_reg < cap_components ? n_reg : cap_components) : 0u;
+    std::vector<uint32_t> firsts((size_t)n_rec), sizes((size_t)n_rec), boxes((size_t)n_rec * 6u);
+    if (e == hipSuccess && n_rec) e = hipMemcpyAsync(firsts.data(), R.first, (size_t)n_rec * 4u, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && n_rec) e = hipMemcpyAsync(sizes.data(), R.size, (size_t)n_rec * 4u, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && n_rec) e = hipMemcpyAsync(boxes.data(), R.box, (size_t)n_rec * 24u, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return hip_failed();
+    for (uint64_t c = 0; c < n_rec; c++) {
+        const uint32_t *b = boxes.data() + 6u * c;
+        components[c].n_voxels = sizes[c];
+        components[c].first = firsts[c];
+        components[c].box = vk_voxel_box{b[0], b[1], b[2], b[3] + 1u, b[4] + 1u, b[5] + 1u};
+    }
+    if (result) {
+        vk_split_result r{};
+        r.n_regions = n_reg; r.n_foreground = totals[5];
+        r.n_markers = totals[0]; r.n_marker_voxels = totals[1];
+        r.n_residue_regions = totals[2]; r.n_residue_voxels = totals[3];
+        for (unsigned long long s : sums) r.n_cut += s;
+        r.rounds = rounds;
+        *result = r;
+    }
+    if (!install) return VK_OK;
+    // the build runs on the same stream behind the kernel, adopts or frees d_out, and commits only when it stands: the old volume stays otherwise
+    return install_dense(ctx, d_out.release(), D.nx, D.ny, D.nz, ctx->format, ctx->layout);
+}
+
+}  // extern "C"

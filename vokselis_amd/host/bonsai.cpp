@@ -66,6 +66,11 @@
 //                                                            the range becomes the sample value IN (default: HI, or max(LO, 1) under an open range), one that
 //                                                            leaves it OUT (default 0).  Runs after --median / --smooth and before --components and the keep
 //                                                            flags, so close-then-keep-largest and open-then-label both work; --save-raw writes the result
+//          [--split RADIUS [CONN]]                          split touching objects of that range (vk_split_components): markers that survive an erosion by RADIUS
+//                                                            (in the units of --morph-spacing) grow back over the range, and a voxel beside a region of smaller id
+//                                                            becomes the sample value of --label-fill (default 0).  CONN: 6 (default), 18 or 26.  Runs after --morph
+//                                                            and before --components and the keep flags, so --split 6 --keep-pick PX PY isolates the one grain under
+//                                                            a pixel; prints the totals and the ten largest regions; --save-raw writes the cut volume
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -131,6 +136,9 @@ static std::vector<MorphOp> g_morph;                                            
 static uint32_t g_morph_spacing[3] = {1u, 1u, 1u};                               // --morph-spacing SX SY SZ
 static float g_morph_fill[2] = {0.0f, 0.0f};                                     // --morph-fill IN OUT
 static bool g_morph_spacing_on = false, g_morph_fill_on = false;
+static bool g_split_on = false;                                                  // --split RADIUS [CONN] (vk_split_components), on the same range
+static float g_split_radius = 0.0f;
+static uint32_t g_split_conn = 6;
 static bool label_ops() { return !g_keep_largest.empty() || !g_drop_islands.empty() || !g_keep_voxels.empty() || !g_remove_voxels.empty() || !g_keep_picks.empty(); }
 
 // the context of a run that replaces the render: 8 x 8, or the frame's size under the render's camera when --keep-pick casts rays through it
@@ -150,7 +158,7 @@ static void apply_morph(Context &ctx) {
     int fmt = 0;
     check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !label_ops()) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !label_ops() && !g_split_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     const float fill_in = g_morph_fill_on ? g_morph_fill[0] : (std::isfinite(g_label_hi) ? g_label_hi : (std::isfinite(g_label_lo) ? std::max(g_label_lo, 1.0f) : 1.0f));
     for (size_t k = 0; k < g_morph.size(); k++) {
         const MorphOp &op = g_morph[k];
@@ -162,9 +170,30 @@ static void apply_morph(Context &ctx) {
     if (!dense.empty()) write_dense(dense, "morphed");
 }
 
-// --morph, then --components, then the keep flags in their fixed order, after the filters and before anything else reads the volume; the last of them fills --save-raw's file
+// --split, after --morph and before --components and the keep flags; it fills --save-raw's file unless a keep flag follows
+static void apply_split(Context &ctx) {
+    if (!g_split_on) return;
+    uint32_t dims[3] = {0, 0, 0};
+    int fmt = 0;
+    check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
+    std::vector<unsigned char> dense;
+    if (!g_save_raw.empty() && !label_ops()) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    const Regions r = ctx.split_components(g_label_lo, g_label_hi, g_split_radius, g_morph_spacing, g_split_conn, nullptr, false, false, g_label_fill, true, dense.empty() ? nullptr : dense.data());
+    std::printf("split: [%g, %g] radius %g connectivity %u: %llu regions (%llu markers of %llu voxels, %llu unreached regions of %llu voxels), %llu foreground voxels, %llu cut, %u rounds\n",
+                g_label_lo, g_label_hi, g_split_radius, g_split_conn, (unsigned long long)r.totals.n_regions, (unsigned long long)r.totals.n_markers, (unsigned long long)r.totals.n_marker_voxels,
+                (unsigned long long)r.totals.n_residue_regions, (unsigned long long)r.totals.n_residue_voxels, (unsigned long long)r.totals.n_foreground, (unsigned long long)r.totals.n_cut, r.totals.rounds);
+    for (uint64_t id : r.largest(10)) {
+        const vk_component &k = r.table[id - 1];
+        std::printf("region %llu: %llu voxels, anchor %llu, box %u %u %u .. %u %u %u\n", (unsigned long long)id, (unsigned long long)k.n_voxels, (unsigned long long)k.first, k.box.x0, k.box.y0, k.box.z0,
+                    k.box.x1, k.box.y1, k.box.z1);
+    }
+    if (!dense.empty()) write_dense(dense, "split");
+}
+
+// --morph, then --split, then --components, then the keep flags in their fixed order, after the filters and before anything else reads the volume; the last of them fills --save-raw's file
 static void apply_labels(Context &ctx) {
     apply_morph(ctx);
+    apply_split(ctx);
     if (!g_components && !label_ops()) return;
     uint32_t dims[3] = {0, 0, 0};
     int fmt = 0;
@@ -220,7 +249,7 @@ static void apply_labels(Context &ctx) {
 static void apply_resample(Context &ctx) {
     if (g_resample.empty()) return;
     static const char *const fmt_name[] = {"R8_UNORM", "R16_FLOAT", "RGBA16F_PAIR", "R16_UNORM"};
-    const bool save = !g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty();
+    const bool save = !g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && !g_split_on;
     std::vector<unsigned char> dense;
     for (size_t k = 0; k < g_resample.size(); k++) {
         const ResampleOp &op = g_resample[k];
@@ -248,7 +277,7 @@ static void apply_filters(Context &ctx) {
     apply_resample(ctx);
     if (!g_median && !g_smooth) { apply_labels(ctx); return; }
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !label_ops() && g_morph.empty()) {
+    if (!g_save_raw.empty() && !label_ops() && g_morph.empty() && !g_split_on) {
         uint32_t dims[3] = {0, 0, 0};
         int fmt = 0;
         check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
@@ -763,6 +792,16 @@ int main(int argc, char **argv) {
             if (g_morph.size() >= 16u) { std::fprintf(stderr, "bonsai: --morph: at most 16 times\n"); return 2; }
             g_morph.push_back({found->op, found->name, radius});
         }
+        else if (a == "--split") {
+            g_split_on = true;
+            g_split_radius = (float)std::atof(next());
+            if (!std::isfinite(g_split_radius) || g_split_radius < 0.0f || g_split_radius > VK_DIST_MAX_RADIUS) { std::fprintf(stderr, "bonsai: --split RADIUS [CONN]: a finite RADIUS of 0 .. 65535\n"); return 2; }
+            if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) {
+                const int c = std::atoi(next());
+                if (c != 6 && c != 18 && c != 26) { std::fprintf(stderr, "bonsai: --split RADIUS [CONN]: CONN is 6, 18 or 26\n"); return 2; }
+                g_split_conn = (uint32_t)c;
+            }
+        }
         else if (a == "--morph-spacing") {
             g_morph_spacing_on = true;
             for (int k = 0; k < 3; k++) {
@@ -798,18 +837,20 @@ int main(int argc, char **argv) {
     if (!mesh_path.empty() && (sl.on || hist || gpus > 0 || g_auto_window)) { std::fprintf(stderr, "bonsai: --mesh replaces the render: no --slice, --slice-plane, --histogram, --gpus or --auto-window\n"); return 2; }
     if (label_ops() && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel and --keep-pick need a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
     if (!g_keep_picks.empty() && !g_iso_on) { std::fprintf(stderr, "bonsai: --keep-pick needs --iso (the ray stops at the isosurface)\n"); return 2; }
-    if (g_label_fill_on && !label_ops()) { std::fprintf(stderr, "bonsai: --label-fill needs a flag that drops voxels: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel or --keep-pick\n"); return 2; }
+    if (g_label_fill_on && !label_ops() && !g_split_on) { std::fprintf(stderr, "bonsai: --label-fill needs a flag that drops voxels: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel or --keep-pick\n"); return 2; }
     if (g_keep_voxels.size() + g_keep_picks.size() > 16u) { std::fprintf(stderr, "bonsai: --keep-voxel and --keep-pick: at most 16 seeds together\n"); return 2; }
     if ((g_components || label_ops()) && gpus > 0) { std::fprintf(stderr, "bonsai: --components and the keep flags run on one GPU\n"); return 2; }
     if (!g_morph.empty() && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --morph needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
-    if ((g_morph_spacing_on || g_morph_fill_on) && g_morph.empty()) { std::fprintf(stderr, "bonsai: %s needs --morph\n", g_morph_spacing_on ? "--morph-spacing" : "--morph-fill"); return 2; }
+    if (g_split_on && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --split needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
+    if (g_split_on && gpus > 0) { std::fprintf(stderr, "bonsai: --split runs on one GPU\n"); return 2; }
+    if (((g_morph_spacing_on && !g_split_on) || g_morph_fill_on) && g_morph.empty()) { std::fprintf(stderr, "bonsai: %s needs --morph\n", g_morph_spacing_on ? "--morph-spacing" : "--morph-fill"); return 2; }
     if (!g_morph.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --morph runs on one GPU\n"); return 2; }
-    if ((label_ops() || !g_morph.empty()) && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
+    if ((label_ops() || !g_morph.empty() || g_split_on) && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
     g_w = w; g_h = h;
     if (!g_resample.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --crop, --resample, --downsample, --isotropic, --to-u8 and --to-u16 run on one GPU\n"); return 2; }
     for (const ResampleOp &op : g_resample)
         if (op.kind == ResampleOp::CROP_CLIP && !g_clip_on) { std::fprintf(stderr, "bonsai: --crop clip needs --clip\n"); return 2; }
-    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && g_resample.empty()) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
+    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && g_resample.empty() && !g_split_on) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
     if ((g_median || g_smooth) && gpus > 0) { std::fprintf(stderr, "bonsai: --median and --smooth run on one GPU\n"); return 2; }
     if (hist) return run_histogram(hist_bins, hist_lo, hist_hi);
     if (!mesh_path.empty()) return run_mesh(mesh_path, mesh_obj, mesh_iso_on ? mesh_iso : g_iso.iso, mesh_scale);

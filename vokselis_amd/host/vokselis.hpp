@@ -198,6 +198,21 @@ struct Components {
         return ids;
     }
 };
+static_assert(sizeof(vk_split_request) == 40 && sizeof(vk_split_result) == 64, "vk_split_request is 40 bytes, vk_split_result 64 (vk_split_components)");
+// What Context::split_components returns: the regions in id order (`first` is a region's anchor), the totals, and the labels when asked for.
+struct Regions {
+    std::vector<vk_component> table;
+    vk_split_result totals{};
+    std::vector<uint32_t> labels;  // nx ny nz, x fastest, 0: off the set; empty unless asked for
+    // the ids of the min(k, table.size()) largest regions of the table: by size descending, then by anchor
+    std::vector<uint64_t> largest(size_t k) const {
+        std::vector<uint64_t> ids(table.size());
+        for (size_t i = 0; i < ids.size(); i++) ids[i] = i + 1;
+        std::stable_sort(ids.begin(), ids.end(), [&](uint64_t a, uint64_t b) { return table[a - 1].n_voxels > table[b - 1].n_voxels; });
+        ids.resize(std::min(k, ids.size()));
+        return ids;
+    }
+};
 // The voxel of a volume of nx x ny x nz that holds the unit-cube position pos (vk_hit.pos): min(floor(pos_c n_c), n_c - 1) per axis.
 inline std::array<uint32_t, 3> voxel_of(const float pos[3], uint32_t nx, uint32_t ny, uint32_t nz) {
     const uint32_t n[3] = {nx, ny, nz};
@@ -525,6 +540,33 @@ class Context {
         vk_distance_result res{};
         check(ctx_, vk_distance_transform(ctx_, &req, box, nullptr, dense_out, &res));
         return res;
+    }
+    // Split touching objects (vk_split_components; blocks): S = the voxels in [lo, hi] is eroded by `radius` (in the units of the integer pitch
+    // spacing, nullptr: 1 1 1), the markers that survive grow back over S, and a voxel beside a region of smaller id becomes fill_out (which
+    // must lie outside the range).  The table's `first` is a region's anchor.  install: the cut volume replaces the context's (outside
+    // frame_begin / frame_end); dense_out: nullptr, or host memory of nx ny nz elements of the volume's format.  One call with room for
+    // 4096 regions; a second, for the table alone, only when there are more and nothing was installed: after an install the context holds
+    // the cut volume, so the table then stays at its first 4096 regions and totals.n_regions tells how many there are.
+    Regions split_components(float lo, float hi, float radius, const uint32_t *spacing = nullptr, uint32_t connectivity = 6, const vk_voxel_box *box = nullptr, bool clip = false,
+                             bool want_labels = false, float fill_out = 0.0f, bool install = false, void *dense_out = nullptr) {
+        vk_split_request req{};
+        req.lo = lo; req.hi = hi; req.connectivity = connectivity; req.radius = radius; req.fill_out = fill_out;
+        req.flags = (clip ? (uint32_t)VK_SPLIT_CLIP_BOX : 0u) | (install ? (uint32_t)VK_SPLIT_INSTALL : 0u);
+        for (int c = 0; c < 3; c++) req.spacing[c] = spacing ? spacing[c] : 1u;
+        Regions r;
+        if (want_labels) {
+            uint32_t dims[3] = {0, 0, 0};
+            check(ctx_, vk_volume_info(ctx_, dims, nullptr, nullptr, nullptr));
+            r.labels.assign((size_t)dims[0] * dims[1] * dims[2], 0u);
+        }
+        r.table.resize(4096);
+        check(ctx_, vk_split_components(ctx_, &req, box, want_labels ? r.labels.data() : nullptr, r.table.data(), r.table.size(), dense_out, &r.totals));
+        if (r.totals.n_regions > r.table.size() && !install) {
+            r.table.resize((size_t)r.totals.n_regions);
+            check(ctx_, vk_split_components(ctx_, &req, box, nullptr, r.table.data(), r.table.size(), nullptr, &r.totals));
+        }
+        r.table.resize((size_t)std::min<uint64_t>(r.totals.n_regions, r.table.size()));
+        return r;
     }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
