@@ -469,18 +469,10 @@ class Context:
         and the statistics of the region, as a Histogram.  box: None -- the whole volume; "clip" -- the voxels whose centres lie in the clip
         box in force; ((x0, y0, z0), (x1, y1, z1)) -- the voxels [x0, x1) x [y0, y1) x [z0, z1).  Blocks; changes no state of the context."""
         from .histogram import Histogram
+        from .label import voxel_box
 
-        req = N.VkHistogram(float(domain[0]), float(domain[1]), int(bins), 0)
-        vb = None
-        if isinstance(box, str):
-            if box != "clip":
-                raise ValueError('box: None, "clip" or ((x0, y0, z0), (x1, y1, z1))')
-            req.flags = N.HIST_CLIP_BOX
-        elif box is not None:
-            lo, hi = (tuple(int(v) for v in c) for c in box)
-            if len(lo) != 3 or len(hi) != 3 or min(lo + hi) < 0:
-                raise ValueError("box: two triples of voxel indices >= 0")
-            vb = N.VkVoxelBox(*lo, *hi)
+        req = N.VkHistogram(float(domain[0]), float(domain[1]), int(bins), N.HIST_CLIP_BOX if isinstance(box, str) and box == "clip" else 0)
+        vb = voxel_box(box)
         counts = np.zeros(max(int(bins), 0), np.uint64)
         stats = N.VkVolumeStats()
         N.check(self._h, N.lib().vk_volume_histogram(self._h, C.byref(req), C.byref(vb) if vb is not None else None,
@@ -494,17 +486,10 @@ class Context:
         volume; "clip" -- the voxels whose centres lie in the clip box in force; ((x0, y0, z0), (x1, y1, z1)).  max_triangles: at most that
         many, the first ones in order.  A count call, then a fill call; blocks; changes no state of the context.  See V.weld, V.write_stl
         and V.write_obj."""
-        req = N.VkMeshRequest(float(iso), 0)
-        vb = None
-        if isinstance(box, str):
-            if box != "clip":
-                raise ValueError('box: None, "clip" or ((x0, y0, z0), (x1, y1, z1))')
-            req.flags = N.MESH_CLIP_BOX
-        elif box is not None:
-            lo, hi = (tuple(int(v) for v in c) for c in box)
-            if len(lo) != 3 or len(hi) != 3 or min(lo + hi) < 0:
-                raise ValueError("box: two triples of voxel indices >= 0")
-            vb = N.VkVoxelBox(*lo, *hi)
+        from .label import voxel_box
+
+        req = N.VkMeshRequest(float(iso), N.MESH_CLIP_BOX if isinstance(box, str) and box == "clip" else 0)
+        vb = voxel_box(box)
         if max_triangles is not None and int(max_triangles) < 0:
             raise ValueError("max_triangles: None or >= 0")
         bp = C.byref(vb) if vb is not None else None
@@ -526,13 +511,7 @@ class Context:
         from .filter import filter_request
 
         req = filter_request(weights, op, install)
-        dense = None
-        if out:
-            dims, fmt = (C.c_uint32 * 3)(), C.c_int()
-            N.check(self._h, N.lib().vk_volume_info(self._h, dims, C.byref(fmt), None, None))
-            dtype = {N.FMT_R8_UNORM: np.uint8, N.FMT_R16_UNORM: np.uint16, N.FMT_R16_FLOAT: np.float16}.get(fmt.value)
-            # (RGBA16F_PAIR: the library refuses before it writes)
-            dense = np.zeros((dims[2], dims[1], dims[0]) if dtype is not None else (1, 1, 1), dtype or np.uint8)
+        dense = self._dense_out() if out else None
         N.check(self._h, N.lib().vk_volume_filter(self._h, C.byref(req), dense.ctypes.data if dense is not None else None))
         return dense
 
@@ -622,6 +601,11 @@ class Context:
         N.check(self._h, N.lib().vk_volume_info(self._h, dims, C.byref(fmt), None, None))
         return tuple(dims), {N.FMT_R8_UNORM: np.uint8, N.FMT_R16_UNORM: np.uint16, N.FMT_R16_FLOAT: np.float16}.get(fmt.value)
 
+    def _dense_out(self):
+        """A dense array [nz, ny, nx] of the volume's dtype for a pass to write; RGBA16F_PAIR: a stand-in, the library refuses before it writes."""
+        dims, dtype = self._volume_dtype()
+        return np.zeros((dims[2], dims[1], dims[0]) if dtype is not None else (1, 1, 1), dtype or np.uint8)
+
     def label_components(self, lo, hi=float("inf"), connectivity: int = 6, box=None, labels: bool = False):
         """vk_label_components: the connected components of the voxels whose stored texel lies in [lo, hi] (sample values, like
         set_isosurface's), as a Components -- .n, .sizes, .first, .boxes in id order (ids 1 .. n by first voxel in raster order),
@@ -658,10 +642,7 @@ class Context:
         req, vb = label_request(lo, hi, connectivity=connectivity, box=box, keep=keep, count=count, seeds=seeds, invert=invert, fill=fill, install=install), voxel_box(box)
         if not (install or out):
             raise ValueError("keep_components: needs install or out")
-        dense = None
-        if out:
-            dims, dtype = self._volume_dtype()
-            dense = np.zeros((dims[2], dims[1], dims[0]) if dtype is not None else (1, 1, 1), dtype or np.uint8)
+        dense = self._dense_out() if out else None
         res = N.VkLabelResult()
         N.check(self._h, N.lib().vk_label_components(self._h, C.byref(req), C.byref(vb) if vb is not None else None, None, None, 0,
                                                      dense.ctypes.data if dense is not None else None, C.byref(res)))
@@ -697,10 +678,7 @@ class Context:
         if op not in MORPH_OPS:
             raise ValueError('op: "close", "open", "dilate" or "erode"')
         req, vb = distance_request(lo, hi, op=op, radius=radius, spacing=spacing, fill_in=fill_in, fill_out=fill_out, install=install, box=box), voxel_box(box)
-        dense = None
-        if out:
-            dims, dtype = self._volume_dtype()
-            dense = np.zeros((dims[2], dims[1], dims[0]) if dtype is not None else (1, 1, 1), dtype or np.uint8)
+        dense = self._dense_out() if out else None
         res = N.VkDistanceResult()
         N.check(self._h, N.lib().vk_distance_transform(self._h, C.byref(req), C.byref(vb) if vb is not None else None, None, dense.ctypes.data if dense is not None else None,
                                                        C.byref(res)))
@@ -724,9 +702,9 @@ class Context:
         req, vb = split_request(lo, hi, radius=radius, spacing=spacing, connectivity=connectivity, box=box, fill_out=fill_out, install=install), voxel_box(box)
         bp = C.byref(vb) if vb is not None else None
         res = N.VkSplitResult()
-        dims, dtype = self._volume_dtype()
+        dims, _ = self._volume_dtype()
         lab = np.zeros((dims[2], dims[1], dims[0]), np.uint32) if labels else None
-        dense = np.zeros((dims[2], dims[1], dims[0]) if dtype is not None else (1, 1, 1), dtype or np.uint8) if out else None
+        dense = self._dense_out() if out else None
         room = 4096
         table = (N.VkComponent * room)()
         N.check(self._h, N.lib().vk_split_components(self._h, C.byref(req), bp, lab.ctypes.data if lab is not None else None, table, room,

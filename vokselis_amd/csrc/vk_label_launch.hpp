@@ -7,6 +7,8 @@
 #include "vk_launch.hpp"
 #include "vk_label.hpp"
 
+#include <vector>
+
 struct LabelDesc {
     uint32_t nx, ny, nz, conn_sum;
     vk_voxel_box box;
@@ -22,6 +24,26 @@ struct LabelDesc {
 struct LabelRecords {
     uint32_t *first, *size, *box;  // box: 6 words per component -- the smallest x, y, z, then the largest
 };
+
+// The first n_rec records into `components`, the call's last download: the arrays' copies, the call's last wait, then the records, a box's
+// upper corner made exclusive.  sizes: the host's copy of R.size where the caller holds one (it is not downloaded again), else NULL.
+inline int label_download_components(vk::PassCall &call, const LabelRecords &R, const uint32_t *sizes, uint64_t n_rec, vk_component *components) {
+    std::vector<uint32_t> firsts((size_t)n_rec), own(sizes ? (size_t)0u : (size_t)n_rec), boxes((size_t)n_rec * 6u);
+    if (n_rec) {
+        call.download(firsts.data(), R.first, (size_t)n_rec * 4u);
+        if (!sizes) call.download(own.data(), R.size, (size_t)n_rec * 4u);
+        call.download(boxes.data(), R.box, (size_t)n_rec * 24u);
+    }
+    if (int rc = call.finish()) return rc;
+    if (!sizes) sizes = own.data();
+    for (uint64_t c = 0; c < n_rec; c++) {
+        const uint32_t *b = boxes.data() + 6u * c;
+        components[c].n_voxels = sizes[c];
+        components[c].first = firsts[c];
+        components[c].box = vk_voxel_box{b[0], b[1], b[2], b[3] + 1u, b[4] + 1u, b[5] + 1u};
+    }
+    return VK_OK;
+}
 
 // A predicate that comes from a word array: voxel i is foreground iff lo <= w[i] <= hi.  No box: the array holds what the box left.
 struct LabelWords {

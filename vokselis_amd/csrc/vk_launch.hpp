@@ -67,7 +67,7 @@ void with_table_layout(const vk_ctx *ctx, bool skip, bool safe, F &&f) {
     }
 }
 
-// ---- the passes that are not a march (slice, histogram, mesh, filter): kernels on the seven scalar kinds of has_table_layout ----------
+// ---- the passes that are not a march (slice, histogram, mesh, filter, label, distance, resample, split): kernels on the seven scalar kinds of has_table_layout ----------
 // f(VOL) over those kinds.  A caller whose kernel covers fewer of them says so with `if constexpr` in its lambda: nothing else is instantiated.
 template <class F>
 void with_scalar_kind(int kind, F &&f) {
@@ -102,6 +102,55 @@ inline int pass_voxel_box(vk_ctx *ctx, const char *entry, const char *flag, cons
     else B = vk_voxel_box{0u, 0u, 0u, ctx->nx, ctx->ny, ctx->nz};
     return VK_OK;
 }
+
+// ... and of a pass that can install its dense output as the volume: not while a frame is being recorded.  flag: the request flag's name.
+inline int pass_install_refused(vk_ctx *ctx, const char *prefix, const char *flag, bool install) {
+    if (!install || !ctx->fif_open) return VK_OK;
+    return fail(ctx, VK_ERR_INVALID, std::string(prefix) + ": " + flag + " while a frame is being recorded (call it outside vk_frame_begin / vk_frame_end)");
+}
+
+// the bytes of a dense array of n texels
+inline size_t pass_dense_bytes(int format, uint64_t n) { return (size_t)n * (format == VK_FMT_R8_UNORM ? 1u : 2u); }
+
+// The host frame of one call of such a pass, behind its refusals and hipSetDevice: one object per call.  It carries the first HIP error
+// of the call; every step but alloc is skipped once there is one, and finish reports it.  prefix: what the call's messages begin with.
+struct PassCall {
+    vk_ctx *ctx;
+    const char *prefix;
+    hipError_t e = hipSuccess;
+
+    // a temporary of the call (an empty one still gets a byte): VK_OK, or the error set.  what: the buffer, in the message's words
+    int alloc(DeviceTemp &d, size_t bytes, const char *what) {
+        e = hipMalloc(&d.p, bytes ? bytes : 1u);
+        if (e == hipSuccess) return VK_OK;
+        (void)hipGetLastError();
+        return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string(prefix) + ": " + what + ": " + hipGetErrorString(e));
+    }
+    // launch(): the kernels of one phase, between the context's timer events where timed (the pass's X_timing names this phase).  A
+    // launch that looks at HIP errors itself leaves the first in e.
+    template <class F>
+    void phase(bool timed, F &&launch) {
+        if (timed && e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
+        if (e == hipSuccess) { launch(); if (e == hipSuccess) e = hipGetLastError(); }
+        if (timed && e == hipSuccess) {
+            e = hipEventRecord(ctx->ev1, ctx->stream);
+            ctx->timing_open = false;
+            ctx->timing_done = true;
+        }
+    }
+    // an output the caller may not have asked for (dst NULL), behind the kernels on the stream
+    void download(void *dst, const void *src, size_t bytes) {
+        if (e == hipSuccess && dst) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    // the stream runs dry (sync), then VK_OK, or the call's first HIP error set
+    int finish(bool sync = true) {
+        if (sync && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        return e == hipSuccess ? VK_OK : fail(ctx, VK_ERR_HIP, std::string(prefix) + ": " + hipGetErrorString(e));
+    }
+    // d_out becomes the volume: the build runs on the same stream behind the kernel, adopts or frees d_out, and commits only when it
+    // stands: the old volume stays otherwise
+    int install(DeviceTemp &d_out, uint32_t nx, uint32_t ny, uint32_t nz, int format, int layout) { return install_dense(ctx, d_out.release(), nx, ny, nz, format, layout); }
+};
 
 // Dynamic LDS of a cell kernel (vk_march_kernel_body.hpp) -- the fast path of the cell layouts keeps its per-axis index tables there
 // (vk_march.hpp: load_cell_luts) -- and, for the variants without skipping, V.lut moved on to the byte-offset copy of the tables.

@@ -106,13 +106,6 @@ __global__ __launch_bounds__(kDistThreads) void dist_transpose_kernel(uint32_t n
     }
 }
 
-// the sum of v over a workgroup's threads, added to *slot (LDS, zeroed before): lanes are combined in registers, one LDS add per wave
-__device__ __forceinline__ void dist_block_add(unsigned long long *slot, uint32_t v) {
-    unsigned long long s = v;
-    for (int d = warpSize / 2; d > 0; d >>= 1) s += __shfl_down(s, d);
-    if ((threadIdx.x & (warpSize - 1)) == 0 && s) atomicAdd(slot, s);
-}
-
 constexpr uint32_t kDistStatsWords = 2, kDistMaskWords = 4;
 
 // partial[2 b]: the zeros workgroup b saw; partial[2 b + 1]: the largest value that is not INF (0: none)
@@ -127,7 +120,7 @@ __global__ __launch_bounds__(kDistThreads) void dist_stats_kernel(const DistDesc
         zeros += v == 0u;
         if (v != kDistInf && v > top) top = v;
     }
-    dist_block_add(&s_zeros, zeros);
+    block_add(&s_zeros, zeros);
     for (int d = warpSize / 2; d > 0; d >>= 1) { const uint32_t o = (uint32_t)__shfl_down((int)top, d); top = o > top ? o : top; }
     if ((threadIdx.x & (warpSize - 1)) == 0 && top) atomicMax(&s_max, top);
     __syncthreads();
@@ -149,10 +142,9 @@ __global__ __launch_bounds__(kDistThreads) void dist_mask_kernel(const DistVolum
         n_s += in_s; n_m += in_m; n_add += in_m && !in_s; n_rem += in_s && !in_m;
         if (!out) continue;
         const uint32_t bits = in_m == in_s ? voxel_texel_bits<VOL>(S.V, x, y, z) : (in_m ? D.fill_in_bits : D.fill_out_bits);
-        if constexpr (texel_class(VOL) == TEXEL_U8) reinterpret_cast<uint8_t *>(out)[i] = (uint8_t)bits;
-        else reinterpret_cast<uint16_t *>(out)[i] = (uint16_t)bits;
+        store_texel_bits<texel_class(VOL)>(out, i, bits);
     }
-    dist_block_add(&s_n[0], n_s); dist_block_add(&s_n[1], n_m); dist_block_add(&s_n[2], n_add); dist_block_add(&s_n[3], n_rem);
+    block_add(&s_n[0], n_s); block_add(&s_n[1], n_m); block_add(&s_n[2], n_add); block_add(&s_n[3], n_rem);
     __syncthreads();
     if (threadIdx.x < kDistMaskWords) partial[(size_t)kDistMaskWords * blockIdx.x + threadIdx.x] = s_n[threadIdx.x];
 }
@@ -213,7 +205,7 @@ int vk_distance_transform(vk_ctx *ctx, const vk_distance_request *req, const vk_
     if (!ctx) return VK_ERR_INVALID;
     if (const char *why = dist_validate(req, d2_out != nullptr, dense_out != nullptr, result != nullptr)) return fail(ctx, VK_ERR_INVALID, std::string(entry) + ": " + why);
     const bool install = (req->flags & VK_DIST_INSTALL) != 0u;
-    if (install && ctx->fif_open) return fail(ctx, VK_ERR_INVALID, std::string(entry) + ": VK_DIST_INSTALL while a frame is being recorded (call it outside vk_frame_begin / vk_frame_end)");
+    if (int rc = pass_install_refused(ctx, entry, "VK_DIST_INSTALL", install)) return rc;
     if (int rc = pass_needs(ctx, PASS_NEEDS_VOLUME, entry, "distance")) return rc;
     vk_voxel_box B;
     if (int rc = pass_voxel_box(ctx, entry, "VK_DIST_CLIP_BOX", box, (req->flags & VK_DIST_CLIP_BOX) != 0u, B)) return rc;
@@ -242,51 +234,35 @@ int vk_distance_transform(vk_ctx *ctx, const vk_distance_request *req, const vk_
 
     const VolumeDesc V = volume_desc(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipError_t e = hipSuccess;
-    auto alloc = [&](DeviceTemp &d, size_t bytes, const char *what) -> int {
-        e = hipMalloc(&d.p, bytes ? bytes : 1u);
-        if (e == hipSuccess) return VK_OK;
-        (void)hipGetLastError();
-        return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string(entry) + ": " + what + ": " + hipGetErrorString(e));
-    };
+    PassCall call{ctx, entry};
     // (debug, vk_debug_set_param("dist_timing", k): phase k alone between the context's timer events, read with vk_timer_elapsed_ms --
     //  1 column, 2 line y, 3 line x of the first round, 4 .. 6 of the second, 7 stats or mask)
-    auto phase = [&](uint32_t k, auto &&launch) {
-        const bool timed = ctx->dist_timing == k;
-        if (timed && e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
-        if (e == hipSuccess) { launch(); e = hipGetLastError(); }
-        if (timed && e == hipSuccess) {
-            e = hipEventRecord(ctx->ev1, ctx->stream);
-            ctx->timing_open = false;
-            ctx->timing_done = true;
-        }
-    };
-    auto hip_failed = [&]() { return fail(ctx, VK_ERR_HIP, std::string(entry) + ": " + hipGetErrorString(e)); };
+    const uint32_t timing = ctx->dist_timing;
 
     const uint32_t words = morph ? kDistMaskWords : kDistStatsWords;
-    const size_t dense_bytes = (size_t)n * (ctx->format == VK_FMT_R8_UNORM ? 1u : 2u);
+    const size_t dense_bytes = pass_dense_bytes(ctx->format, n);
     DeviceTemp d_a, d_b, d_stack, d_partial, d_out;
-    if (int rc = alloc(d_a, (size_t)n * 4u, "the distance array")) return rc;
-    if (int rc = alloc(d_b, (size_t)n * 4u, "the second distance array")) return rc;
-    if (int rc = alloc(d_stack, (size_t)n * 4u, "the envelope stacks")) return rc;
-    if (int rc = alloc(d_partial, (size_t)voxel_blocks * words * 8u, "the partial counts")) return rc;
+    if (int rc = call.alloc(d_a, (size_t)n * 4u, "the distance array")) return rc;
+    if (int rc = call.alloc(d_b, (size_t)n * 4u, "the second distance array")) return rc;
+    if (int rc = call.alloc(d_stack, (size_t)n * 4u, "the envelope stacks")) return rc;
+    if (int rc = call.alloc(d_partial, (size_t)voxel_blocks * words * 8u, "the partial counts")) return rc;
     if (dense_out || install)
-        if (int rc = alloc(d_out, dense_bytes, "the output buffer")) return rc;
+        if (int rc = call.alloc(d_out, dense_bytes, "the output buffer")) return rc;
     uint32_t *a = (uint32_t *)d_a.p, *b = (uint32_t *)d_b.p, *stack = (uint32_t *)d_stack.p;
     unsigned long long *partial = (unsigned long long *)d_partial.p;
 
     // a round: the columns of the target into a, then a -> b along y and b -> a along x
     auto lines = [&](uint32_t k) {
-        phase(k + 1u, [&] { dist_launch_line_y(ctx, D, G, a, b, stack); });
-        phase(k + 2u, [&] { dist_launch_line_x(ctx, D, G, a, b, stack); });
+        call.phase(timing == k + 1u, [&] { dist_launch_line_y(ctx, D, G, a, b, stack); });
+        call.phase(timing == k + 2u, [&] { dist_launch_line_x(ctx, D, G, a, b, stack); });
     };
-    phase(1u, [&] { dist_launch_column(ctx, V, D, G, a); });
+    call.phase(timing == 1u, [&] { dist_launch_column(ctx, V, D, G, a); });
     lines(1u);
     if (dist_two_rounds(req->op)) {
-        phase(4u, [&] { hipLaunchKernelGGL(dist_column_kernel<DistAboveTarget>, dim3(column_blocks), dim3(kDistThreads), 0, ctx->stream, DistAboveTarget{a}, D, a); });
+        call.phase(timing == 4u, [&] { hipLaunchKernelGGL(dist_column_kernel<DistAboveTarget>, dim3(column_blocks), dim3(kDistThreads), 0, ctx->stream, DistAboveTarget{a}, D, a); });
         lines(4u);
     }
-    phase(7u, [&] {
+    call.phase(timing == 7u, [&] {
         if (!morph) hipLaunchKernelGGL(dist_stats_kernel, dim3(voxel_blocks), dim3(kDistThreads), 0, ctx->stream, D, (const uint32_t *)a, partial);
         else
             with_scalar_kind(kind, [&](auto VOL) {
@@ -295,11 +271,10 @@ int vk_distance_transform(vk_ctx *ctx, const vk_distance_request *req, const vk_
     });
 
     std::vector<unsigned long long> sums((size_t)voxel_blocks * words);
-    if (e == hipSuccess) e = hipMemcpyAsync(sums.data(), partial, sums.size() * 8u, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && d2_out) e = hipMemcpyAsync(d2_out, a, (size_t)n * 4u, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && dense_out) e = hipMemcpyAsync(dense_out, d_out.p, dense_bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_failed();
+    call.download(sums.data(), partial, sums.size() * 8u);
+    call.download(d2_out, a, (size_t)n * 4u);
+    call.download(dense_out, d_out.p, dense_bytes);
+    if (int rc = call.finish()) return rc;
     if (result) {
         vk_distance_result r{};
         if (morph) {
@@ -311,9 +286,7 @@ int vk_distance_transform(vk_ctx *ctx, const vk_distance_request *req, const vk_
         }
         *result = r;
     }
-    if (!install) return VK_OK;
-    // the build runs on the same stream behind the kernel, adopts or frees d_out, and commits only when it stands: the old volume stays otherwise
-    return install_dense(ctx, d_out.release(), D.nx, D.ny, D.nz, ctx->format, ctx->layout);
+    return install ? call.install(d_out, D.nx, D.ny, D.nz, ctx->format, ctx->layout) : VK_OK;
 }
 
 }  // extern "C"

@@ -34,11 +34,6 @@ struct FilterDesc {
 static_assert(sizeof(FilterDesc) % 8 == 0 && pass_kernargs_fit<FilterDesc>, "filter kernels: VolumeDesc + FilterDesc");
 
 template <int FMT>
-__device__ __forceinline__ void filter_store_bits(void *__restrict__ out, uint64_t i, uint32_t bits) {
-    if constexpr (FMT == TEXEL_U8) reinterpret_cast<uint8_t *>(out)[i] = (uint8_t)bits;
-    else reinterpret_cast<uint16_t *>(out)[i] = (uint16_t)bits;
-}
-template <int FMT>
 __device__ __forceinline__ uint32_t filter_store_rule(float v) {
     if constexpr (FMT == TEXEL_U8) return filter_store_unorm(v, 255.0f);
     else if constexpr (FMT == TEXEL_U16) return filter_store_unorm(v, 65535.0f);
@@ -126,7 +121,7 @@ __global__ __launch_bounds__(kFilterThreads, 2) void filter_convolve_kernel(cons
             const float *t = lds + filter_lds_index(T, lx + rx, ly + ry, lz);
             const float v = rz ? filter_taps(D.w[2], t, rz, PX * PY) : t[0];
             const uint32_t gx = x0 + lx, gy = y0 + ly, gz = z0 + lz;
-            if (gx < D.nx && gy < D.ny && gz < D.nz) filter_store_bits<FMT>(out, filter_voxel_offset(gx, gy, gz, D.nx, D.ny), filter_store_rule<FMT>(v));
+            if (gx < D.nx && gy < D.ny && gz < D.nz) store_texel_bits<FMT>(out, filter_voxel_offset(gx, gy, gz, D.nx, D.ny), filter_store_rule<FMT>(v));
         }
         __syncthreads();  // the next tile's load overwrites what the z pass reads
     }
@@ -166,7 +161,7 @@ __global__ __launch_bounds__(kFilterThreads) void filter_median_kernel(const Vol
                     for (uint32_t a = 0; a < 3u; a++) v[a + 3u * b + 9u * c] = lds[filter_lds_index(T, lx + a, ly + b, lz + c)];
             const uint32_t m = filter_median27(v);
             const uint32_t gx = x0 + lx, gy = y0 + ly, gz = z0 + lz;
-            if (gx < D.nx && gy < D.ny && gz < D.nz) filter_store_bits<FMT>(out, filter_voxel_offset(gx, gy, gz, D.nx, D.ny), FMT == TEXEL_F16 ? filter_f16_unkey(m) : m);
+            if (gx < D.nx && gy < D.ny && gz < D.nz) store_texel_bits<FMT>(out, filter_voxel_offset(gx, gy, gz, D.nx, D.ny), FMT == TEXEL_F16 ? filter_f16_unkey(m) : m);
         }
         __syncthreads();  // the next tile's load overwrites the keys
     }
@@ -187,7 +182,7 @@ int vk_volume_filter(vk_ctx *ctx, const struct vk_volume_filter *f, void *dense_
     if (!ctx) return VK_ERR_INVALID;
     if (const char *why = filter_validate(f, dense_out != nullptr)) return fail(ctx, VK_ERR_INVALID, std::string("vk_volume_filter: ") + why);
     const bool install = (f->flags & VK_FILTER_INSTALL) != 0u;
-    if (install && ctx->fif_open) return fail(ctx, VK_ERR_INVALID, "vk_volume_filter: VK_FILTER_INSTALL while a frame is being recorded (call it outside vk_frame_begin / vk_frame_end)");
+    if (int rc = pass_install_refused(ctx, "vk_volume_filter", "VK_FILTER_INSTALL", install)) return rc;
     if (int rc = pass_needs(ctx, PASS_NEEDS_VOLUME, "vk_volume_filter", "filter")) return rc;
     if (int rc = pass_needs(ctx, PASS_NEEDS_SCALAR_KIND, "vk_volume_filter", "filter")) return rc;
 
@@ -209,31 +204,20 @@ int vk_volume_filter(vk_ctx *ctx, const struct vk_volume_filter *f, void *dense_
 
     const VolumeDesc V = volume_desc(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)D.nx * D.ny * D.nz * (ctx->format == VK_FMT_R8_UNORM ? 1u : 2u);
+    PassCall call{ctx, "vk_volume_filter"};
+    const size_t bytes = pass_dense_bytes(ctx->format, (uint64_t)D.nx * D.ny * D.nz);
     DeviceTemp d_out;
-    hipError_t e = hipMalloc(&d_out.p, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("vk_volume_filter: the output buffer: ") + hipGetErrorString(e));
-    }
+    if (int rc = call.alloc(d_out, bytes, "the output buffer")) return rc;
     // (debug, vk_debug_set_param("filter_timing", 1): the kernel alone between the context's timer events, read with vk_timer_elapsed_ms)
-    if (ctx->filter_timing) e = hipEventRecord(ctx->ev0, ctx->stream);
-    with_scalar_kind(kind, [&](auto VOL) {
-        if (median) hipLaunchKernelGGL(filter_median_kernel<VOL()>, dim3(G.blocks), dim3(kFilterThreads), 0, ctx->stream, V, D, d_out.p);
-        else filter_launch_convolve<VOL()>(ctx, cls, G.blocks, V, D, d_out.p);
+    call.phase(ctx->filter_timing != 0u, [&] {
+        with_scalar_kind(kind, [&](auto VOL) {
+            if (median) hipLaunchKernelGGL(filter_median_kernel<VOL()>, dim3(G.blocks), dim3(kFilterThreads), 0, ctx->stream, V, D, d_out.p);
+            else filter_launch_convolve<VOL()>(ctx, cls, G.blocks, V, D, d_out.p);
+        });
     });
-    if (e == hipSuccess) e = hipGetLastError();
-    if (ctx->filter_timing && e == hipSuccess) {
-        e = hipEventRecord(ctx->ev1, ctx->stream);
-        ctx->timing_open = false;
-        ctx->timing_done = true;
-    }
-    if (e == hipSuccess && dense_out) e = hipMemcpyAsync(dense_out, d_out.p, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && (dense_out || !install)) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(ctx, VK_ERR_HIP, std::string("vk_volume_filter: ") + hipGetErrorString(e));
-    if (!install) return VK_OK;
-    // the build runs on the same stream behind the kernel, adopts or frees d_out, and commits only when it stands: the old volume stays otherwise
-    return install_dense(ctx, d_out.release(), D.nx, D.ny, D.nz, ctx->format, ctx->layout);
+    call.download(dense_out, d_out.p, bytes);
+    if (int rc = call.finish(dense_out || !install)) return rc;  // an install alone is not waited for
+    return install ? call.install(d_out, D.nx, D.ny, D.nz, ctx->format, ctx->layout) : VK_OK;
 }
 
 int vk_filter_gaussian(double sigma_voxels, uint32_t radius, float *weights) {

@@ -354,16 +354,16 @@ int vk_volume_histogram(vk_ctx *ctx, const vk_histogram *hist, const vk_voxel_bo
         DeviceTemp d;
         HIP_TRY(ctx, hipMalloc(&d.p, words * sizeof(unsigned long long)));
         D.out = reinterpret_cast<unsigned long long *>(d.p);
-        hipError_t e = hipMemsetAsync(d.p, 0, words * sizeof(unsigned long long), ctx->stream);
-        if (e != hipSuccess) return fail(ctx, VK_ERR_HIP, std::string("vk_volume_histogram: ") + hipGetErrorString(e));
-        with_scalar_kind(kind, [&](auto VOL) {
-            if constexpr (is_cell_layout(VOL())) hipLaunchKernelGGL(hist_cells_kernel<VOL()>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, volume_desc(ctx), D);
-            else hipLaunchKernelGGL(hist_linear_kernel<VOL()>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, (const void *)ctx->vol, D);
+        PassCall call{ctx, "vk_volume_histogram"};
+        call.e = hipMemsetAsync(d.p, 0, words * sizeof(unsigned long long), ctx->stream);
+        call.phase(false, [&] {
+            with_scalar_kind(kind, [&](auto VOL) {
+                if constexpr (is_cell_layout(VOL())) hipLaunchKernelGGL(hist_cells_kernel<VOL()>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, volume_desc(ctx), D);
+                else hipLaunchKernelGGL(hist_linear_kernel<VOL()>, dim3(grid), dim3(kHistThreads), 0, ctx->stream, (const void *)ctx->vol, D);
+            });
         });
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(ctx, VK_ERR_HIP, std::string("vk_volume_histogram: ") + hipGetErrorString(e));
+        call.download(h.data(), d.p, words * sizeof(unsigned long long));
+        if (int rc = call.finish()) return rc;
     }
     if (counts)
         for (uint32_t i = 0; i < K.bins; i++) counts[i] = h[i];

@@ -301,8 +301,7 @@ __global__ __launch_bounds__(kLabelThreads) void label_mask_kernel(const VolumeD
             label_coords((uint32_t)i, D.nx, D.ny, x, y, z);
             const uint32_t m = keep[labels[i]];  // keep[0] == 0: background is never selected
             const uint32_t bits = (m != 0u) != (D.invert != 0u) ? voxel_texel_bits<VOL>(V, x, y, z) : D.fill_bits;
-            if constexpr (texel_class(VOL) == TEXEL_U8) reinterpret_cast<uint8_t *>(out)[i] = (uint8_t)bits;
-            else reinterpret_cast<uint16_t *>(out)[i] = (uint16_t)bits;
+            store_texel_bits<texel_class(VOL)>(out, i, bits);
         }
     }
 }
@@ -336,7 +335,7 @@ int vk_label_components(vk_ctx *ctx, const vk_label_request *req, const vk_voxel
     if (const char *why = label_validate(req, labels_out != nullptr, components != nullptr, cap_components, dense_out != nullptr, result != nullptr))
         return fail(ctx, VK_ERR_INVALID, std::string(entry) + ": " + why);
     const bool install = (req->flags & VK_LABEL_INSTALL) != 0u;
-    if (install && ctx->fif_open) return fail(ctx, VK_ERR_INVALID, std::string(entry) + ": VK_LABEL_INSTALL while a frame is being recorded (call it outside vk_frame_begin / vk_frame_end)");
+    if (int rc = pass_install_refused(ctx, entry, "VK_LABEL_INSTALL", install)) return rc;
     if (int rc = pass_needs(ctx, PASS_NEEDS_VOLUME, entry, "label")) return rc;
     if (!label_seeds_inside(req, ctx->nx, ctx->ny, ctx->nz)) return fail(ctx, VK_ERR_INVALID, std::string(entry) + ": a seed lies outside the volume");
     vk_voxel_box B;
@@ -362,95 +361,64 @@ int vk_label_components(vk_ctx *ctx, const vk_label_request *req, const vk_voxel
 
     const VolumeDesc V = volume_desc(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipError_t e = hipSuccess;
-    auto alloc = [&](DeviceTemp &d, size_t bytes, const char *what) -> int {
-        e = hipMalloc(&d.p, bytes ? bytes : 1u);
-        if (e == hipSuccess) return VK_OK;
-        (void)hipGetLastError();
-        return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string(entry) + ": " + what + ": " + hipGetErrorString(e));
-    };
+    PassCall call{ctx, entry};
     // (debug, vk_debug_set_param("label_timing", k): phase k alone between the context's timer events, read with vk_timer_elapsed_ms --
     //  1 tile, 2 seam, 3 flatten, 4 scan, 5 number, 6 label, 7 mask)
-    auto phase = [&](uint32_t k, auto &&launch) {
-        const bool timed = ctx->label_timing == k;
-        if (timed && e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
-        if (e == hipSuccess) { launch(); e = hipGetLastError(); }
-        if (timed && e == hipSuccess) {
-            e = hipEventRecord(ctx->ev1, ctx->stream);
-            ctx->timing_open = false;
-            ctx->timing_done = true;
-        }
-    };
-    auto hip_failed = [&]() { return fail(ctx, VK_ERR_HIP, std::string(entry) + ": " + hipGetErrorString(e)); };
+    const uint32_t timing = ctx->label_timing;
 
     DeviceTemp d_parent, d_labels, d_chunk_roots, d_chunk_fg, d_totals;
-    if (int rc = alloc(d_parent, (size_t)n * 4u, "the parent array")) return rc;
-    if (int rc = alloc(d_labels, (size_t)n * 4u, "the label array")) return rc;
-    if (int rc = alloc(d_chunk_roots, (size_t)D.chunks * 4u, "the chunk counts")) return rc;
-    if (int rc = alloc(d_chunk_fg, (size_t)D.chunks * 4u, "the chunk counts")) return rc;
-    if (int rc = alloc(d_totals, 16u, "the totals")) return rc;
+    if (int rc = call.alloc(d_parent, (size_t)n * 4u, "the parent array")) return rc;
+    if (int rc = call.alloc(d_labels, (size_t)n * 4u, "the label array")) return rc;
+    if (int rc = call.alloc(d_chunk_roots, (size_t)D.chunks * 4u, "the chunk counts")) return rc;
+    if (int rc = call.alloc(d_chunk_fg, (size_t)D.chunks * 4u, "the chunk counts")) return rc;
+    if (int rc = call.alloc(d_totals, 16u, "the totals")) return rc;
     uint32_t *parent = (uint32_t *)d_parent.p, *labels = (uint32_t *)d_labels.p, *chunk_roots = (uint32_t *)d_chunk_roots.p, *chunk_fg = (uint32_t *)d_chunk_fg.p;
 
-    phase(1u, [&] { with_scalar_kind(kind, [&](auto VOL) { hipLaunchKernelGGL(label_tile_kernel<VOL()>, dim3(G.blocks), dim3(kLabelThreads), 0, ctx->stream, V, D, parent); }); });
-    phase(2u, [&] { hipLaunchKernelGGL(label_seam_kernel, dim3(G.blocks), dim3(kLabelThreads), 0, ctx->stream, D, parent); });
-    phase(3u, [&] { hipLaunchKernelGGL(label_flatten_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, parent, chunk_roots, chunk_fg); });
-    phase(4u, [&] { hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(kLabelThreads), 0, ctx->stream, D.chunks, chunk_roots, chunk_fg, (unsigned long long *)d_totals.p); });
+    call.phase(timing == 1u, [&] { with_scalar_kind(kind, [&](auto VOL) { hipLaunchKernelGGL(label_tile_kernel<VOL()>, dim3(G.blocks), dim3(kLabelThreads), 0, ctx->stream, V, D, parent); }); });
+    call.phase(timing == 2u, [&] { hipLaunchKernelGGL(label_seam_kernel, dim3(G.blocks), dim3(kLabelThreads), 0, ctx->stream, D, parent); });
+    call.phase(timing == 3u, [&] { hipLaunchKernelGGL(label_flatten_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, parent, chunk_roots, chunk_fg); });
+    call.phase(timing == 4u, [&] { hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(kLabelThreads), 0, ctx->stream, D.chunks, chunk_roots, chunk_fg, (unsigned long long *)d_totals.p); });
     unsigned long long totals[2] = {0ull, 0ull};
-    if (e == hipSuccess) e = hipMemcpyAsync(totals, d_totals.p, sizeof totals, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_failed();
+    call.download(totals, d_totals.p, sizeof totals);
+    if (int rc = call.finish()) return rc;
     const uint64_t n_comp = totals[0], n_fg = totals[1];
 
     DeviceTemp d_first, d_size, d_box;
-    if (int rc = alloc(d_first, (size_t)n_comp * 4u, "the component records")) return rc;
-    if (int rc = alloc(d_size, (size_t)n_comp * 4u, "the component records")) return rc;
-    if (int rc = alloc(d_box, (size_t)n_comp * 24u, "the component records")) return rc;
+    if (int rc = call.alloc(d_first, (size_t)n_comp * 4u, "the component records")) return rc;
+    if (int rc = call.alloc(d_size, (size_t)n_comp * 4u, "the component records")) return rc;
+    if (int rc = call.alloc(d_box, (size_t)n_comp * 24u, "the component records")) return rc;
     const LabelRecords R{(uint32_t *)d_first.p, (uint32_t *)d_size.p, (uint32_t *)d_box.p};
-    if (n_comp) phase(5u, [&] { hipLaunchKernelGGL(label_number_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, parent, chunk_roots, labels, R); });
-    phase(6u, [&] { hipLaunchKernelGGL(label_stats_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, parent, labels, R); });
+    if (n_comp) call.phase(timing == 5u, [&] { hipLaunchKernelGGL(label_number_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, parent, chunk_roots, labels, R); });
+    call.phase(timing == 6u, [&] { hipLaunchKernelGGL(label_stats_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, parent, labels, R); });
 
     // the selection: host arithmetic over the sizes; the seeds' labels are a sixteen-word download
     std::vector<uint32_t> sizes((size_t)n_comp);
     uint32_t seed_labels[VK_LABEL_MAX_SEEDS] = {};
-    if (e == hipSuccess && n_comp) e = hipMemcpyAsync(sizes.data(), R.size, (size_t)n_comp * 4u, hipMemcpyDeviceToHost, ctx->stream);
-    for (uint32_t s = 0; s < req->n_seeds && e == hipSuccess; s++)
-        e = hipMemcpyAsync(seed_labels + s, labels + voxel_index(req->seeds[s][0], req->seeds[s][1], req->seeds[s][2], D.nx, D.ny), 4u, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_failed();
+    if (n_comp) call.download(sizes.data(), R.size, (size_t)n_comp * 4u);
+    for (uint32_t s = 0; s < req->n_seeds; s++) call.download(seed_labels + s, labels + voxel_index(req->seeds[s][0], req->seeds[s][1], req->seeds[s][2], D.nx, D.ny), 4u);
+    if (int rc = call.finish()) return rc;
     std::vector<uint8_t> keep;
     uint64_t kept_voxels = 0;
     const uint64_t kept_comps = label_select(*req, sizes.data(), n_comp, seed_labels, keep, &kept_voxels);
 
-    const size_t dense_bytes = (size_t)n * (ctx->format == VK_FMT_R8_UNORM ? 1u : 2u);
+    const size_t dense_bytes = pass_dense_bytes(ctx->format, n);
     DeviceTemp d_keep, d_out;
     if (dense_out || install) {
-        if (int rc = alloc(d_keep, keep.size(), "the keep bytes")) return rc;
-        if (int rc = alloc(d_out, dense_bytes, "the output buffer")) return rc;
-        e = hipMemcpyAsync(d_keep.p, keep.data(), keep.size(), hipMemcpyHostToDevice, ctx->stream);
-        phase(7u, [&] {
+        if (int rc = call.alloc(d_keep, keep.size(), "the keep bytes")) return rc;
+        if (int rc = call.alloc(d_out, dense_bytes, "the output buffer")) return rc;
+        call.e = hipMemcpyAsync(d_keep.p, keep.data(), keep.size(), hipMemcpyHostToDevice, ctx->stream);
+        call.phase(timing == 7u, [&] {
             with_scalar_kind(kind, [&](auto VOL) {
                 hipLaunchKernelGGL(label_mask_kernel<VOL()>, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, V, D, labels, (const uint8_t *)d_keep.p, d_out.p);
             });
         });
-        if (e == hipSuccess && dense_out) e = hipMemcpyAsync(dense_out, d_out.p, dense_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        call.download(dense_out, d_out.p, dense_bytes);
     }
-    if (e == hipSuccess && labels_out) e = hipMemcpyAsync(labels_out, labels, (size_t)n * 4u, hipMemcpyDeviceToHost, ctx->stream);
+    call.download(labels_out, labels, (size_t)n * 4u);
     const uint64_t n_rec = components ? (n_comp < cap_components ? n_comp : cap_components) : 0u;
-    std::vector<uint32_t> firsts((size_t)n_rec), boxes((size_t)n_rec * 6u);
-    if (e == hipSuccess && n_rec) e = hipMemcpyAsync(firsts.data(), R.first, (size_t)n_rec * 4u, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && n_rec) e = hipMemcpyAsync(boxes.data(), R.box, (size_t)n_rec * 24u, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_failed();
-    for (uint64_t c = 0; c < n_rec; c++) {
-        const uint32_t *b = boxes.data() + 6u * c;
-        components[c].n_voxels = sizes[c];
-        components[c].first = firsts[c];
-        components[c].box = vk_voxel_box{b[0], b[1], b[2], b[3] + 1u, b[4] + 1u, b[5] + 1u};
-    }
+    if (int rc = label_download_components(call, R, sizes.data(), n_rec, components)) return rc;
     if (result) *result = vk_label_result{n_comp, n_fg, kept_comps, kept_voxels};
-    if (!install) return VK_OK;
-    // the build runs on the same stream behind the kernel, adopts or frees d_out, and commits only when it stands: the old volume stays otherwise
-    return install_dense(ctx, d_out.release(), D.nx, D.ny, D.nz, ctx->format, ctx->layout);
+    return install ? call.install(d_out, D.nx, D.ny, D.nz, ctx->format, ctx->layout) : VK_OK;
 }
 
 }  // extern "C"

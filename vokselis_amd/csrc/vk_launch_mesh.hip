@@ -291,36 +291,30 @@ int vk_extract_isosurface(vk_ctx *ctx, const vk_mesh_request *req, const vk_voxe
     MeshScanHeader *d_hdr = reinterpret_cast<MeshScanHeader *>(work.p);
     MeshActive *d_act = reinterpret_cast<MeshActive *>(d_hdr + 1);
     uint32_t *d_totals = reinterpret_cast<uint32_t *>(d_act + D.n_chunks);
-    with_scalar_kind(kind, [&](auto VOL) {
-        hipLaunchKernelGGL(mesh_count_kernel<VOL()>, dim3(mesh_grid(D.n_chunks, cus, ctx->mesh_max_blocks)), dim3(kMeshThreads), 0, ctx->stream, V, D, d_totals);
+    PassCall call{ctx, "vk_extract_isosurface"};
+    call.phase(false, [&] {
+        with_scalar_kind(kind, [&](auto VOL) {
+            hipLaunchKernelGGL(mesh_count_kernel<VOL()>, dim3(mesh_grid(D.n_chunks, cus, ctx->mesh_max_blocks)), dim3(kMeshThreads), 0, ctx->stream, V, D, d_totals);
+        });
     });
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(kMeshScanThreads), 0, ctx->stream, (const uint32_t *)d_totals, D.n_chunks, d_act, d_hdr);
-        e = hipGetLastError();
-    }
+    call.phase(false, [&] { hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(kMeshScanThreads), 0, ctx->stream, (const uint32_t *)d_totals, D.n_chunks, d_act, d_hdr); });
     MeshScanHeader hdr{};
-    if (e == hipSuccess) e = hipMemcpyAsync(&hdr, d_hdr, sizeof(hdr), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return fail(ctx, VK_ERR_HIP, std::string("vk_extract_isosurface: ") + hipGetErrorString(e));
+    call.download(&hdr, d_hdr, sizeof(hdr));
+    if (int rc = call.finish()) return rc;
 
     const uint64_t n_write = hdr.n_triangles < cap_triangles ? hdr.n_triangles : cap_triangles;
     if (triangles && n_write) {  // (no triangle to write: no emit launch)
         const size_t out_bytes = (size_t)n_write * 9u * sizeof(float);
         DeviceTemp d_out;
-        e = hipMalloc(&d_out.p, out_bytes);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("vk_extract_isosurface: the output buffer: ") + hipGetErrorString(e));
-        }
-        with_scalar_kind(kind, [&](auto VOL) {
-            hipLaunchKernelGGL(mesh_emit_kernel<VOL()>, dim3(mesh_grid(hdr.n_active, cus, ctx->mesh_max_blocks)), dim3(kMeshThreads), 0, ctx->stream, V, D, (const MeshActive *)d_act,
-                               hdr.n_active, reinterpret_cast<float *>(d_out.p), n_write);
+        if (int rc = call.alloc(d_out, out_bytes, "the output buffer")) return rc;
+        call.phase(false, [&] {
+            with_scalar_kind(kind, [&](auto VOL) {
+                hipLaunchKernelGGL(mesh_emit_kernel<VOL()>, dim3(mesh_grid(hdr.n_active, cus, ctx->mesh_max_blocks)), dim3(kMeshThreads), 0, ctx->stream, V, D, (const MeshActive *)d_act,
+                                   hdr.n_active, reinterpret_cast<float *>(d_out.p), n_write);
+            });
         });
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(triangles, d_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return fail(ctx, VK_ERR_HIP, std::string("vk_extract_isosurface: ") + hipGetErrorString(e));
+        call.download(triangles, d_out.p, out_bytes);
+        if (int rc = call.finish()) return rc;
     }
     *n_triangles = hdr.n_triangles;
     return VK_OK;

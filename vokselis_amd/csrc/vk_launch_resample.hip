@@ -206,8 +206,7 @@ static void resample_launch(vk_ctx *ctx, int mode, uint32_t taps, dim3 grid, con
 // Every refusal of a call, in the header's order, before anything is launched or written: VK_OK with the box and the plan, or the error set.
 static int resample_prepare(vk_ctx *ctx, const vk_resample_request *req, const vk_voxel_box *box, bool have_out, vk_voxel_box &B, ResamplePlan &P) {
     if (const char *why = resample_validate(req, have_out)) return fail(ctx, VK_ERR_INVALID, std::string("resample: ") + why);
-    if ((req->flags & VK_RESAMPLE_INSTALL) && ctx->fif_open)
-        return fail(ctx, VK_ERR_INVALID, "resample: VK_RESAMPLE_INSTALL while a frame is being recorded (call it outside vk_frame_begin / vk_frame_end)");
+    if (int rc = pass_install_refused(ctx, "resample", "VK_RESAMPLE_INSTALL", (req->flags & VK_RESAMPLE_INSTALL) != 0u)) return rc;
     if (int rc = pass_needs(ctx, PASS_NEEDS_VOLUME, "resample", "resample")) return rc;
     if (int rc = pass_needs(ctx, PASS_NEEDS_SCALAR_KIND, "resample", "resample")) return rc;
     if (int rc = pass_voxel_box(ctx, "resample", "VK_RESAMPLE_CLIP_BOX", box, (req->flags & VK_RESAMPLE_CLIP_BOX) != 0u, B)) return rc;
@@ -259,30 +258,25 @@ int vk_volume_resample(vk_ctx *ctx, const vk_resample_request *req, const vk_vox
     const int kind = ctx->vol_kind;
     const VolumeDesc V = volume_desc(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)D.nx * D.ny * D.nz * (P.format == VK_FMT_R8_UNORM ? 1u : 2u);
+    PassCall call{ctx, "resample"};
+    const size_t bytes = pass_dense_bytes(P.format, (uint64_t)D.nx * D.ny * D.nz);
     DeviceTemp d_tab, d_out;
-    hipError_t e = hipMalloc(&d_tab.p, (size_t)words * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&d_out.p, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("resample: the output buffer: ") + hipGetErrorString(e));
-    }
-    e = hipMemcpy(d_tab.p, table.data(), (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice);  // blocking: the tables stand before the launch
+    if (int rc = call.alloc(d_tab, (size_t)words * sizeof(uint32_t), "the output buffer")) return rc;
+    if (int rc = call.alloc(d_out, bytes, "the output buffer")) return rc;
+    call.e = hipMemcpy(d_tab.p, table.data(), (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice);  // blocking: the tables stand before the launch
     const bool passes = req->mode == VK_RESAMPLE_AREA && ctx->resample_area_passes != 0u;
     DeviceTemp d_t1, d_t2;  // the separate passes' intermediates: the x sums of the box's rows, the y sums of those
-    if (e == hipSuccess && passes) {
-        e = hipMalloc(&d_t1.p, (size_t)P.n[0] * P.nb[1] * P.nb[2] * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&d_t2.p, (size_t)P.n[0] * P.n[1] * P.nb[2] * sizeof(float));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("resample: the intermediates of the separate passes: ") + hipGetErrorString(e));
-        }
+    if (call.e == hipSuccess && passes) {
+        if (int rc = call.alloc(d_t1, (size_t)P.n[0] * P.nb[1] * P.nb[2] * sizeof(float), "the intermediates of the separate passes")) return rc;
+        if (int rc = call.alloc(d_t2, (size_t)P.n[0] * P.n[1] * P.nb[2] * sizeof(float), "the intermediates of the separate passes")) return rc;
     }
+    const uint32_t *tab = static_cast<const uint32_t *>(d_tab.p);
     // (debug, vk_debug_set_param("resample_timing", 1): the kernels alone, behind every allocation, between the context's timer events, read with vk_timer_elapsed_ms)
-    const bool timing = ctx->resample_timing == 1u;
-    if (e == hipSuccess && timing) e = hipEventRecord(ctx->ev0, ctx->stream);
-    if (e == hipSuccess && passes) {
-        const uint32_t *tab = static_cast<const uint32_t *>(d_tab.p);
+    call.phase(ctx->resample_timing == 1u, [&] {
+        if (!passes) {
+            with_scalar_kind(kind, [&](auto VOL) { resample_launch<VOL()>(ctx, req->mode, taps, resample_dim3(G), V, D, tab, d_out.p); });
+            return;
+        }
         for (uint32_t axis = 0; axis < 3u; axis++) {
             ResampleAxisDesc A{};
             A.x0 = B.x0; A.y0 = B.y0; A.z0 = B.z0;
@@ -298,24 +292,12 @@ int vk_volume_resample(vk_ctx *ctx, const vk_resample_request *req, const vk_vox
             if (axis == 0u) with_scalar_kind(kind, [&](auto VOL) { hipLaunchKernelGGL(resample_area_axis_kernel<VOL()>, resample_dim3(GA), dim3(kResampleThreads), 0, ctx->stream, V, A, tab, in, dst); });
             else hipLaunchKernelGGL(resample_area_axis_kernel<-1>, resample_dim3(GA), dim3(kResampleThreads), 0, ctx->stream, V, A, tab, in, dst);
         }
-        e = hipGetLastError();
-    } else if (e == hipSuccess) {
-        with_scalar_kind(kind, [&](auto VOL) { resample_launch<VOL()>(ctx, req->mode, taps, resample_dim3(G), V, D, static_cast<const uint32_t *>(d_tab.p), d_out.p); });
-        e = hipGetLastError();
-    }
-    if (timing && e == hipSuccess) {
-        e = hipEventRecord(ctx->ev1, ctx->stream);
-        ctx->timing_open = false;
-        ctx->timing_done = true;
-    }
-    if (e == hipSuccess && dense_out) e = hipMemcpyAsync(dense_out, d_out.p, bytes, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the call blocks; the tables are freed on return
-    if (e != hipSuccess) return fail(ctx, VK_ERR_HIP, std::string("resample: ") + hipGetErrorString(e));
-    if (install) {
-        // the build adopts or frees d_out and commits only when it stands: the old volume stays otherwise
-        if (int rc = install_dense(ctx, d_out.release(), D.nx, D.ny, D.nz, P.format, P.layout)) return rc;
-    }
-    if (result) {
+    });
+    call.download(dense_out, d_out.p, bytes);
+    if (int rc = call.finish()) return rc;  // the call blocks; the tables are freed on return
+    if (install)
+        if (int rc = call.install(d_out, D.nx, D.ny, D.nz, P.format, P.layout)) return rc;
+    if (result) {  // behind the install: the layout is the one the volume took
         result->dims[0] = D.nx; result->dims[1] = D.ny; result->dims[2] = D.nz;
         result->format = P.format;
         result->layout = install ? ctx->layout : 0;

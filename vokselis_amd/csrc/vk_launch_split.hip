@@ -34,13 +34,6 @@ struct SplitPlainLoad {
     static __device__ __forceinline__ uint32_t load(const uint32_t *p, uint32_t i) { return p[i]; }
 };
 
-// the sum of v over a workgroup's threads, added to *slot (LDS, zeroed before): lanes are combined in registers, one LDS add per wave
-__device__ __forceinline__ void split_block_add(unsigned long long *slot, uint32_t v) {
-    unsigned long long s = v;
-    for (int d = warpSize / 2; d > 0; d >>= 1) s += __shfl_down(s, d);
-    if ((threadIdx.x & (warpSize - 1)) == 0 && s) atomicAdd(slot, s);
-}
-
 // state is the markers' flattened parent array on entry: an anchor on K, kLabelBackground elsewhere.  d2 != 0 exactly on S.
 __global__ __launch_bounds__(kLabelThreads) void split_seed_kernel(const LabelDesc D, const uint32_t *__restrict__ d2, uint32_t *__restrict__ state) {
     for (uint32_t chunk = blockIdx.x; chunk < D.chunks; chunk += gridDim.x) {
@@ -71,7 +64,7 @@ __global__ __launch_bounds__(kLabelThreads) void split_grow_kernel(const LabelDe
             out[i] = s;
         }
     }
-    split_block_add(&s_n, mine);
+    block_add(&s_n, mine);
     __syncthreads();
     if (threadIdx.x == 0 && s_n) atomicAdd(labelled, s_n);  // integers: the order of the adds does not show
 }
@@ -94,8 +87,8 @@ __global__ __launch_bounds__(kLabelThreads) void split_merge_kernel(const LabelD
             fg += p != kLabelBackground;
             roots += p == (uint32_t)i;
         }
-        split_block_add(&s_roots, roots);
-        split_block_add(&s_fg, fg);
+        block_add(&s_roots, roots);
+        block_add(&s_fg, fg);
         __syncthreads();
         if (threadIdx.x == 0) { chunk_roots[chunk] = (uint32_t)s_roots; chunk_fg[chunk] = (uint32_t)s_fg; }
         __syncthreads();
@@ -132,11 +125,10 @@ __global__ __launch_bounds__(kLabelThreads) void split_cut_kernel(const VolumeDe
             mine += cut;
             if (!out) continue;
             const uint32_t bits = cut ? D.fill_bits : voxel_texel_bits<VOL>(V, x, y, z);
-            if constexpr (texel_class(VOL) == TEXEL_U8) reinterpret_cast<uint8_t *>(out)[i] = (uint8_t)bits;
-            else reinterpret_cast<uint16_t *>(out)[i] = (uint16_t)bits;
+            store_texel_bits<texel_class(VOL)>(out, i, bits);
         }
     }
-    split_block_add(&s_n, mine);
+    block_add(&s_n, mine);
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = s_n;
 }
@@ -150,7 +142,7 @@ int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel
     if (const char *why = split_validate(req, labels_out != nullptr, components != nullptr, cap_components, dense_out != nullptr, result != nullptr))
         return fail(ctx, VK_ERR_INVALID, std::string(entry) + ": " + why);
     const bool install = (req->flags & VK_SPLIT_INSTALL) != 0u;
-    if (install && ctx->fif_open) return fail(ctx, VK_ERR_INVALID, std::string(entry) + ": VK_SPLIT_INSTALL while a frame is being recorded (call it outside vk_frame_begin / vk_frame_end)");
+    if (int rc = pass_install_refused(ctx, entry, "VK_SPLIT_INSTALL", install)) return rc;
     if (int rc = pass_needs(ctx, PASS_NEEDS_VOLUME, entry, "split")) return rc;
     vk_voxel_box B;
     if (int rc = pass_voxel_box(ctx, entry, "VK_SPLIT_CLIP_BOX", box, (req->flags & VK_SPLIT_CLIP_BOX) != 0u, B)) return rc;
@@ -180,43 +172,28 @@ int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel
 
     const VolumeDesc V = volume_desc(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipError_t e = hipSuccess;
-    auto alloc = [&](DeviceTemp &d, size_t bytes, const char *what) -> int {
-        e = hipMalloc(&d.p, bytes ? bytes : 1u);
-        if (e == hipSuccess) return VK_OK;
-        (void)hipGetLastError();
-        return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string(entry) + ": " + what + ": " + hipGetErrorString(e));
-    };
+    PassCall call{ctx, entry};
+    hipError_t &e = call.e;  // the growth loop looks at its launches itself
     // (debug, vk_debug_set_param("split_timing", k): phase k alone between the context's timer events, read with vk_timer_elapsed_ms --
     //  1 distance, 2 markers, 3 growth (every round, with the host's looks at the counts), 4 residue, 5 merge, 6 number and stats, 7 cut)
-    auto phase = [&](uint32_t k, auto &&launch) {
-        const bool timed = ctx->split_timing == k;
-        if (timed && e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
-        if (e == hipSuccess) { launch(); if (e == hipSuccess) e = hipGetLastError(); }
-        if (timed && e == hipSuccess) {
-            e = hipEventRecord(ctx->ev1, ctx->stream);
-            ctx->timing_open = false;
-            ctx->timing_done = true;
-        }
-    };
-    auto hip_failed = [&]() { return fail(ctx, VK_ERR_HIP, std::string(entry) + ": " + hipGetErrorString(e)); };
+    const uint32_t timing = ctx->split_timing;
 
     DeviceTemp d_a, d_b, d_c, d_chunk_roots, d_chunk_fg, d_totals, d_counts, d_partial;
-    if (int rc = alloc(d_a, (size_t)n * 4u, "the distance array")) return rc;
-    if (int rc = alloc(d_b, (size_t)n * 4u, "the state array")) return rc;
-    if (int rc = alloc(d_c, (size_t)n * 4u, "the second state array")) return rc;
-    if (int rc = alloc(d_chunk_roots, (size_t)D.chunks * 4u, "the chunk counts")) return rc;
-    if (int rc = alloc(d_chunk_fg, (size_t)D.chunks * 4u, "the chunk counts")) return rc;
-    if (int rc = alloc(d_totals, 48u, "the totals")) return rc;
-    if (int rc = alloc(d_counts, (size_t)kSplitBatch * 8u, "the rounds' counts")) return rc;
-    if (int rc = alloc(d_partial, (size_t)cut_blocks * 8u, "the partial counts")) return rc;
+    if (int rc = call.alloc(d_a, (size_t)n * 4u, "the distance array")) return rc;
+    if (int rc = call.alloc(d_b, (size_t)n * 4u, "the state array")) return rc;
+    if (int rc = call.alloc(d_c, (size_t)n * 4u, "the second state array")) return rc;
+    if (int rc = call.alloc(d_chunk_roots, (size_t)D.chunks * 4u, "the chunk counts")) return rc;
+    if (int rc = call.alloc(d_chunk_fg, (size_t)D.chunks * 4u, "the chunk counts")) return rc;
+    if (int rc = call.alloc(d_totals, 48u, "the totals")) return rc;
+    if (int rc = call.alloc(d_counts, (size_t)kSplitBatch * 8u, "the rounds' counts")) return rc;
+    if (int rc = call.alloc(d_partial, (size_t)cut_blocks * 8u, "the partial counts")) return rc;
     uint32_t *a = (uint32_t *)d_a.p, *chunk_roots = (uint32_t *)d_chunk_roots.p, *chunk_fg = (uint32_t *)d_chunk_fg.p;
     unsigned long long *d_tot = (unsigned long long *)d_totals.p, *counts = (unsigned long long *)d_counts.p;
 
     // D2(not S, .) into a; the markers' parent array into b
-    phase(1u, [&] { dist_launch_inside(ctx, B, lo_k, hi_k, req->spacing, a, (uint32_t *)d_b.p, (uint32_t *)d_c.p); });
+    call.phase(timing == 1u, [&] { dist_launch_inside(ctx, B, lo_k, hi_k, req->spacing, a, (uint32_t *)d_b.p, (uint32_t *)d_c.p); });
     uint32_t *cur = (uint32_t *)d_b.p, *other = (uint32_t *)d_c.p;
-    phase(2u, [&] {
+    call.phase(timing == 2u, [&] {
         label_launch_tile_words(ctx->stream, G.blocks, D, LabelWords{a, (uint32_t)(r2 + 1u), 0xffffffffu}, cur);
         label_launch_seam(ctx->stream, G.blocks, D, cur);
         label_launch_flatten(ctx->stream, chunk_blocks, D, cur, chunk_roots, chunk_fg);
@@ -227,7 +204,7 @@ int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel
     // The growth.  Every batch but the last labels at least one voxel in each of its rounds, and S is finite: the loop ends.  A round that
     // labels nothing copies the state, and so does every round after it: `cur` holds the fixed point when the batch is over.
     uint32_t rounds = 0u;
-    phase(3u, [&] {
+    call.phase(timing == 3u, [&] {
         for (bool done = false; !done && e == hipSuccess;) {
             unsigned long long got[kSplitBatch] = {};
             e = hipMemsetAsync(counts, 0, sizeof got, ctx->stream);
@@ -246,7 +223,7 @@ int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel
     });
 
     // what no marker reached, labelled on its own into `other`; then the merged parent array, in place
-    phase(4u, [&] {
+    call.phase(timing == 4u, [&] {
         label_launch_tile_words(ctx->stream, G.blocks, D, LabelWords{cur, kSplitUnreached, kSplitUnreached}, other);
         label_launch_seam(ctx->stream, G.blocks, D, other);
         label_launch_flatten(ctx->stream, chunk_blocks, D, other, chunk_roots, chunk_fg);
@@ -254,53 +231,41 @@ int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel
     });
     uint32_t *parent = other, *labels = a;  // D2 is not needed any more
     unsigned long long totals[6] = {};
-    phase(5u, [&] {
+    call.phase(timing == 5u, [&] {
         hipLaunchKernelGGL(split_merge_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, (const uint32_t *)cur, parent, chunk_roots, chunk_fg);
         label_launch_scan(ctx->stream, D.chunks, chunk_roots, chunk_fg, d_tot + 4);  // {regions, |S|}
     });
-    if (e == hipSuccess) e = hipMemcpyAsync(totals, d_tot, sizeof totals, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_failed();
+    call.download(totals, d_tot, sizeof totals);
+    if (int rc = call.finish()) return rc;
     const uint64_t n_reg = totals[4];
 
     DeviceTemp d_first, d_size, d_box;
-    if (int rc = alloc(d_first, (size_t)n_reg * 4u, "the region records")) return rc;
-    if (int rc = alloc(d_size, (size_t)n_reg * 4u, "the region records")) return rc;
-    if (int rc = alloc(d_box, (size_t)n_reg * 24u, "the region records")) return rc;
+    if (int rc = call.alloc(d_first, (size_t)n_reg * 4u, "the region records")) return rc;
+    if (int rc = call.alloc(d_size, (size_t)n_reg * 4u, "the region records")) return rc;
+    if (int rc = call.alloc(d_box, (size_t)n_reg * 24u, "the region records")) return rc;
     const LabelRecords R{(uint32_t *)d_first.p, (uint32_t *)d_size.p, (uint32_t *)d_box.p};
-    phase(6u, [&] {
+    call.phase(timing == 6u, [&] {
         if (n_reg) label_launch_number(ctx->stream, chunk_blocks, D, parent, chunk_roots, labels, R);
         label_launch_stats(ctx->stream, chunk_blocks, D, parent, labels, R);
     });
 
-    const size_t dense_bytes = (size_t)n * (ctx->format == VK_FMT_R8_UNORM ? 1u : 2u);
+    const size_t dense_bytes = pass_dense_bytes(ctx->format, n);
     DeviceTemp d_out;
     if (dense_out || install)
-        if (int rc = alloc(d_out, dense_bytes, "the output buffer")) return rc;
+        if (int rc = call.alloc(d_out, dense_bytes, "the output buffer")) return rc;
     std::vector<unsigned long long> sums(cut_blocks);
     if (dense_out || install || result) {
-        phase(7u, [&] {
+        call.phase(timing == 7u, [&] {
             with_scalar_kind(kind, [&](auto VOL) {
                 hipLaunchKernelGGL(split_cut_kernel<VOL()>, dim3(cut_blocks), dim3(kLabelThreads), 0, ctx->stream, V, D, (const uint32_t *)labels, d_out.p, (unsigned long long *)d_partial.p);
             });
         });
-        if (e == hipSuccess) e = hipMemcpyAsync(sums.data(), d_partial.p, sums.size() * 8u, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && dense_out) e = hipMemcpyAsync(dense_out, d_out.p, dense_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        call.download(sums.data(), d_partial.p, sums.size() * 8u);
+        call.download(dense_out, d_out.p, dense_bytes);
     }
-    if (e == hipSuccess && labels_out) e = hipMemcpyAsync(labels_out, labels, (size_t)n * 4u, hipMemcpyDeviceToHost, ctx->stream);
+    call.download(labels_out, labels, (size_t)n * 4u);
     const uint64_t n_rec = components ? (n_reg < cap_components ? n_reg : cap_components) : 0u;
-    std::vector<uint32_t> firsts((size_t)n_rec), sizes((size_t)n_rec), boxes((size_t)n_rec * 6u);
-    if (e == hipSuccess && n_rec) e = hipMemcpyAsync(firsts.data(), R.first, (size_t)n_rec * 4u, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && n_rec) e = hipMemcpyAsync(sizes.data(), R.size, (size_t)n_rec * 4u, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && n_rec) e = hipMemcpyAsync(boxes.data(), R.box, (size_t)n_rec * 24u, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_failed();
-    for (uint64_t c = 0; c < n_rec; c++) {
-        const uint32_t *b = boxes.data() + 6u * c;
-        components[c].n_voxels = sizes[c];
-        components[c].first = firsts[c];
-        components[c].box = vk_voxel_box{b[0], b[1], b[2], b[3] + 1u, b[4] + 1u, b[5] + 1u};
-    }
+    if (int rc = label_download_components(call, R, nullptr, n_rec, components)) return rc;
     if (result) {
         vk_split_result r{};
         r.n_regions = n_reg; r.n_foreground = totals[5];
@@ -310,9 +275,7 @@ int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel
         r.rounds = rounds;
         *result = r;
     }
-    if (!install) return VK_OK;
-    // the build runs on the same stream behind the kernel, adopts or frees d_out, and commits only when it stands: the old volume stays otherwise
-    return install_dense(ctx, d_out.release(), D.nx, D.ny, D.nz, ctx->format, ctx->layout);
+    return install ? call.install(d_out, D.nx, D.ny, D.nz, ctx->format, ctx->layout) : VK_OK;
 }
 
 }  // extern "C"

@@ -97,4 +97,18 @@ __device__ __forceinline__ uint32_t voxel_texel_bits(const VolumeDesc &V, uint32
     } else return linear_texel_bits<VOL>(V.data, voxel_index(x, y, z, V.nx, V.ny));
 }
 
+// bits as texel i of a dense array of class CLASS (texel_class): a u8, or a u16 / half
+template <int CLASS>
+__device__ __forceinline__ void store_texel_bits(void *__restrict__ out, uint64_t i, uint32_t bits) {
+    if constexpr (CLASS == TEXEL_U8) reinterpret_cast<uint8_t *>(out)[i] = (uint8_t)bits;
+    else reinterpret_cast<uint16_t *>(out)[i] = (uint16_t)bits;
+}
+
+// the sum of v over a workgroup's threads, added to *slot (LDS, zeroed before): lanes are combined in registers, one LDS add per wave
+__device__ __forceinline__ void block_add(unsigned long long *slot, uint32_t v) {
+    unsigned long long s = v;
+    for (int d = warpSize / 2; d > 0; d >>= 1) s += __shfl_down(s, d);
+    if ((threadIdx.x & (warpSize - 1)) == 0 && s) atomicAdd(slot, s);
+}
+
 }  // namespace vk
