@@ -778,6 +778,70 @@ _Static_assert(sizeof(vk_split_request) == 40 && sizeof(vk_split_result) == 64, 
 int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel_box *box, uint32_t *labels_out, vk_component *components,
                         uint64_t cap_components, void *dense_out, vk_split_result *result);
 
+/* Measure labelled regions: the volume and a label array are reduced into one exact integer record per region --
+ * voxel count, first voxel, box, the sums of the voxel indices and of their products, the sums of the stored texel and of its square,
+ * its extremes, and the exposed voxel faces per axis.  Every field is an integer; the hosts derive centroid, covariance, principal
+ * axes, mean, deviation, volume and surface from it.
+ * Labels.  labels_in == NULL: the regions are vk_label_components' components of [lo, hi] under `connectivity` inside the voxel box
+ * (`box`, the clip box under VK_MEASURE_CLIP_BOX, or NULL for the whole volume), numbered as there; the label array stays on the
+ * device.  After a VK_SPLIT_INSTALL these are the split regions, since the cut separates them.  labels_in != NULL: a host array of
+ * nx ny nz uint32, x fastest, 0 background -- vk_label_components' or vk_split_components' labels_out, or a caller's segmentation;
+ * the regions are the ids 1 .. max_label; lo, hi and connectivity must be 0, box NULL and VK_MEASURE_CLIP_BOX clear.  An id above
+ * max_label is found on the device after the upload and refused (VK_ERR_INVALID, outputs untouched).  An id no voxel carries gives a
+ * record with n_voxels = 0, first = UINT64_MAX, a box of zeros, q_min = INT64_MAX, q_max = INT64_MIN and zero sums.
+ * q.  q(v) is the stored texel of voxel v on an integer scale: R8 and R16_UNORM the stored integer, R16F t 2^24 (every finite half is a
+ * multiple of 2^-24; |q| < 2^40; -0 gives 0), PACKED_PAIRS the value tap.  result->scale is the divisor from q to the sample value:
+ * 255, 65535 or 16777216.
+ * The record.  n_voxels, first (the smallest linear index x + nx (y + ny z)) and box (tight, half-open) as vk_component.  sum_x ..
+ * sum_yz: the sums over the region's voxels of x, y, z, x x, y y, z z, x y, x z, y z.  n_nonfinite: the voxels whose texel is NaN or
+ * +-inf (R16F; 0 otherwise); they are left out of q_min, q_max, sum_q and sum_qq.  sum_q = sum_q_hi 2^64 + sum_q_lo is a signed
+ * 128-bit two's complement sum of q, sum_qq = sum_qq_hi 2^64 + sum_qq_lo the unsigned 128-bit sum of q q: both exact.  faces[a]: for
+ * each voxel of the region and each of its two neighbours along axis a (x, y, z), one when the neighbour lies outside the volume or
+ * carries another label (background and everything outside the box are label 0); a face between two regions counts once for each.
+ * Outputs.  regions (may be NULL): the first min(n_regions, cap_regions) records in id order.  result (may be NULL): n_regions (the
+ * components found, or max_label), n_foreground (the voxels with a label), records_written, scale.  No context state changes: the
+ * call is allowed while a frame is being recorded.  It blocks, runs on the context's current stream and frees its buffers.  The
+ * records depend on no launch shape, schedule or layout.
+ * VK_ERR_INVALID, decided before any launch, outputs untouched ("vk_measure_components: ..."): a NULL request; lo or hi NaN, lo > hi;
+ * without labels_in a connectivity other than 6, 18, 26; an unknown flag; pad != 0; regions != NULL with cap_regions == 0; neither
+ * regions nor result requested; with labels_in a nonzero lo, hi or connectivity, a box or VK_MEASURE_CLIP_BOX, max_label == 0;
+ * without labels_in max_label != 0; no volume; a box that is inverted or leaves the volume, a box together with
+ * VK_MEASURE_CLIP_BOX; max_label above the voxel count.  VK_ERR_UNSUPPORTED ("measure: ..."): a BRICKED / QUADS / STAGED or
+ * RGBA16F_PAIR volume; a volume of more than 2^32 - 2 voxels; a volume whose n (max dimension - 1)^2 does not fit 64 bits (an index
+ * sum could overflow).  VK_ERR_OOM: a buffer cannot be allocated. */
+enum { VK_MEASURE_CLIP_BOX = 1 };
+typedef struct vk_measure_request {
+    float    lo, hi;         /* the value range, formed exactly as vk_label_components forms lo_k, hi_k; 0 with labels_in */
+    uint32_t connectivity;   /* 6, 18 or 26; 0 with labels_in */
+    uint32_t flags;          /* VK_MEASURE_CLIP_BOX */
+    uint32_t max_label;      /* with labels_in: the regions are 1 .. max_label; otherwise 0 */
+    uint32_t pad;            /* 0 */
+} vk_measure_request;        /* 24 bytes */
+typedef struct vk_region {
+    uint64_t n_voxels, first;
+    vk_voxel_box box;        /* tight, half-open; zeros for an empty region */
+    uint64_t sum_x, sum_y, sum_z;
+    uint64_t sum_xx, sum_yy, sum_zz, sum_xy, sum_xz, sum_yz;
+    uint64_t n_nonfinite;
+    int64_t  q_min, q_max;   /* over the finite voxels; INT64_MAX / INT64_MIN when there are none */
+    int64_t  sum_q_hi;       /* signed 128-bit: sum_q_hi 2^64 + sum_q_lo */
+    uint64_t sum_q_lo;
+    uint64_t sum_qq_hi, sum_qq_lo;  /* unsigned 128-bit */
+    uint64_t faces[3];       /* exposed voxel faces across x, y, z */
+} vk_region;                 /* 192 bytes */
+typedef struct vk_measure_result {
+    uint64_t n_regions, n_foreground, records_written;
+    uint32_t scale;          /* 255, 65535 or 16777216 */
+    uint32_t pad;
+} vk_measure_result;         /* 32 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(vk_measure_request) == 24 && sizeof(vk_region) == 192 && sizeof(vk_measure_result) == 32, "vk_measure_request: 24 bytes, vk_region: 192, vk_measure_result: 32");
+#else
+_Static_assert(sizeof(vk_measure_request) == 24 && sizeof(vk_region) == 192 && sizeof(vk_measure_result) == 32, "vk_measure_request: 24 bytes, vk_region: 192, vk_measure_result: 32");
+#endif
+int vk_measure_components(vk_ctx *ctx, const vk_measure_request *req, const vk_voxel_box *box, const uint32_t *labels_in, vk_region *regions,
+                          uint64_t cap_regions, vk_measure_result *result);
+
 /* The resample pass: a voxel box of the volume the context holds into a volume of caller-chosen dimensions, by
  * one of three rules, optionally mapped into another scalar format -- crop, resize, make isotropic, window 16-bit data into u8 --
  * without a trip through the host.  Every f32 operation below is rounded once; fmaf is fused where written and nowhere else.

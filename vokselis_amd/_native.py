@@ -215,6 +215,32 @@ class VkSplitResult(C.Structure):
 assert C.sizeof(VkSplitRequest) == 40 and C.sizeof(VkSplitResult) == 64
 
 
+MEASURE_CLIP_BOX = 1
+
+
+class VkMeasureRequest(C.Structure):
+    """vk_measure_request (24 bytes): the request of vk_measure_components -- the value range, the connectivity and the flags where the
+    library labels the regions itself; max_label where the caller brings the labels (everything else is 0 then)."""
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("connectivity", C.c_uint32), ("flags", C.c_uint32), ("max_label", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class VkRegion(C.Structure):
+    """vk_region (192 bytes): a region's exact integer record -- voxels, first voxel, box, the sums of the voxel indices and of their
+    products, the texel's extremes and 128-bit sums on the integer scale q, the exposed faces per axis."""
+    _fields_ = [("n_voxels", C.c_uint64), ("first", C.c_uint64), ("box", VkVoxelBox), ("sum_x", C.c_uint64), ("sum_y", C.c_uint64), ("sum_z", C.c_uint64),
+                ("sum_xx", C.c_uint64), ("sum_yy", C.c_uint64), ("sum_zz", C.c_uint64), ("sum_xy", C.c_uint64), ("sum_xz", C.c_uint64), ("sum_yz", C.c_uint64),
+                ("n_nonfinite", C.c_uint64), ("q_min", C.c_int64), ("q_max", C.c_int64), ("sum_q_hi", C.c_int64), ("sum_q_lo", C.c_uint64),
+                ("sum_qq_hi", C.c_uint64), ("sum_qq_lo", C.c_uint64), ("faces", C.c_uint64 * 3)]
+
+
+class VkMeasureResult(C.Structure):
+    """vk_measure_result (32 bytes): the totals of vk_measure_components and the divisor from q to the sample value."""
+    _fields_ = [("n_regions", C.c_uint64), ("n_foreground", C.c_uint64), ("records_written", C.c_uint64), ("scale", C.c_uint32), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(VkMeasureRequest) == 24 and C.sizeof(VkRegion) == 192 and C.sizeof(VkMeasureResult) == 32
+
+
 RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_AREA = 0, 1, 2
 RESAMPLE_INSTALL, RESAMPLE_CLIP_BOX, RESAMPLE_WINDOW = 1, 2, 4
 RESAMPLE_KEEP_FORMAT = -1
@@ -296,6 +322,7 @@ SYMBOLS = {
     "vk_label_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp]),  # const vk_label_request *, const vk_voxel_box *, labels_out, vk_component *, cap, dense_out, vk_label_result *
     "vk_distance_transform": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_distance_request *, const vk_voxel_box *, d2_out, dense_out, vk_distance_result *
     "vk_split_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp]),  # const vk_split_request *, const vk_voxel_box *, labels_out, vk_component *, cap, dense_out, vk_split_result *
+    "vk_measure_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),  # const vk_measure_request *, const vk_voxel_box *, labels_in (NULL: label the range), vk_region *, cap, vk_measure_result *
     "vk_volume_resample": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, dense_out, vk_resample_result *
     "vk_resample_output": (C.c_int, [_vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, vk_resample_result *: the output's extents, format, layout and box, nothing launched
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),

@@ -715,6 +715,41 @@ class Context:
             N.check(self._h, N.lib().vk_split_components(self._h, C.byref(req), bp, None, table, n, None, C.byref(res)))
         return Regions(table, res, lab, dense)
 
+    # -- measure labelled regions: one exact integer record per region (vk_measure_components)
+    def measure_components(self, lo=None, hi=float("inf"), connectivity: int = 6, box=None, labels=None, max_label=None):
+        """vk_measure_components: a Measurements -- per region the voxel count, first voxel, box, centroid, covariance and principal axes,
+        mean / std / min / max of the stored texels, and the exposed voxel faces.  labels None: the regions are label_components' components
+        of [lo, hi] under `connectivity` inside `box` (after split_components(install=True): the split regions), and the label array never
+        leaves the device.  labels: a uint32 array [nz, ny, nx] (label_components' or split_components' .labels, or your own; 0:
+        background); the regions are 1 .. max_label (default labels.max()), and lo, hi, connectivity and box are not used.  One call with
+        room for 4096 regions, a second only when there are more; blocks; changes no state of the context."""
+        from .label import voxel_box
+        from .measure import Measurements, measure_request
+
+        dims, _ = self._volume_dtype()
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, np.uint32)
+            if labels.shape != (dims[2], dims[1], dims[0]):
+                raise ValueError("labels: a uint32 array [nz, ny, nx] of the volume's dimensions")
+            if max_label is None:
+                max_label = max(int(labels.max()), 1) if labels.size else 1
+            req, vb = measure_request(box=box, max_label=max_label), None
+        else:
+            if max_label is not None or lo is None:
+                raise ValueError("measure_components: a range (lo, hi) without labels, max_label only with labels")
+            req, vb = measure_request(lo, hi, connectivity=connectivity, box=box), voxel_box(box)
+        bp = C.byref(vb) if vb is not None else None
+        lp = labels.ctypes.data if labels is not None else None
+        res = N.VkMeasureResult()
+        room = 4096
+        table = (N.VkRegion * room)()
+        N.check(self._h, N.lib().vk_measure_components(self._h, C.byref(req), bp, lp, table, room, C.byref(res)))
+        n = int(res.n_regions)
+        if n > room:  # more regions than the table had room for: once more
+            table = (N.VkRegion * n)()
+            N.check(self._h, N.lib().vk_measure_components(self._h, C.byref(req), bp, lp, table, n, C.byref(res)))
+        return Measurements(table, int(res.records_written), res, dims)
+
     def set_root_skip(self, k: int):
         """vk_partition_root_skip: rank 0 sits out every k-th round of the tile deal (0: never)."""
         N.check(self._h, N.lib().vk_partition_root_skip(self._h, int(k)))

@@ -52,6 +52,8 @@ struct LabelWords {
 };
 
 // One launch each, on `stream`; the caller looks at hipGetLastError.  blocks: of the tile grid (tile, seam) or of the chunk grid.
+// kind: the volume's scalar kind (with_scalar_kind): the predicate is the volume's stored texel against [D.lo_k, D.hi_k] inside D.box
+void label_launch_tile(hipStream_t stream, uint32_t blocks, int kind, const vk::VolumeDesc &V, const LabelDesc &D, uint32_t *parent);
 void label_launch_tile_words(hipStream_t stream, uint32_t blocks, const LabelDesc &D, const LabelWords &W, uint32_t *parent);
 void label_launch_seam(hipStream_t stream, uint32_t blocks, const LabelDesc &D, uint32_t *parent);
 void label_launch_flatten(hipStream_t stream, uint32_t blocks, const LabelDesc &D, uint32_t *parent, uint32_t *chunk_roots, uint32_t *chunk_fg);

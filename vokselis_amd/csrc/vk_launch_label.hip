@@ -307,6 +307,9 @@ __global__ __launch_bounds__(kLabelThreads) void label_mask_kernel(const VolumeD
 }
 
 // ---- the kernels as another pass launches them (vk_label_launch.hpp) ----------------------------------------------------------------
+void label_launch_tile(hipStream_t stream, uint32_t blocks, int kind, const VolumeDesc &V, const LabelDesc &D, uint32_t *parent) {
+    with_scalar_kind(kind, [&](auto VOL) { hipLaunchKernelGGL(label_tile_kernel<VOL()>, dim3(blocks), dim3(kLabelThreads), 0, stream, V, D, parent); });
+}
 void label_launch_tile_words(hipStream_t stream, uint32_t blocks, const LabelDesc &D, const LabelWords &W, uint32_t *parent) {
     hipLaunchKernelGGL(label_tile_words_kernel, dim3(blocks), dim3(kLabelThreads), 0, stream, W, D, parent);
 }

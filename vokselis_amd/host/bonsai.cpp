@@ -71,6 +71,11 @@
 //                                                            becomes the sample value of --label-fill (default 0).  CONN: 6 (default), 18 or 26.  Runs after --morph
 //                                                            and before --components and the keep flags, so --split 6 --keep-pick PX PY isolates the one grain under
 //                                                            a pixel; prints the totals and the ten largest regions; --save-raw writes the cut volume
+//          [--measure [FILE.csv]]                           measure the regions of that range (vk_measure_components): the components of [LO, HI] (--components, or
+//                                                            --iso V for [V, inf) at connectivity 6) on the volume that --morph, --split and the keep flags left -- after
+//                                                            --split, the split regions.  Prints the totals and the ten largest regions: id, voxels, centroid,
+//                                                            equivalent diameter, principal lengths, mean +- std, surface, in the units of --morph-spacing; FILE.csv
+//                                                            takes one line per region
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -139,6 +144,8 @@ static bool g_morph_spacing_on = false, g_morph_fill_on = false;
 static bool g_split_on = false;                                                  // --split RADIUS [CONN] (vk_split_components), on the same range
 static float g_split_radius = 0.0f;
 static uint32_t g_split_conn = 6;
+static bool g_measure_on = false;                                                // --measure [FILE.csv] (vk_measure_components), on the same range
+static std::string g_measure_csv;
 static bool label_ops() { return !g_keep_largest.empty() || !g_drop_islands.empty() || !g_keep_voxels.empty() || !g_remove_voxels.empty() || !g_keep_picks.empty(); }
 
 // the context of a run that replaces the render: 8 x 8, or the frame's size under the render's camera when --keep-pick casts rays through it
@@ -244,6 +251,25 @@ static void apply_labels(Context &ctx) {
     if (!dense.empty()) write_dense(dense, "cleaned");
 }
 
+// --measure, after --morph, --split, --components and the keep flags, on the volume they left
+static void apply_measure(Context &ctx) {
+    if (!g_measure_on) return;
+    const Measurements m = ctx.measure_components(g_label_lo, g_label_hi, g_label_conn);
+    const double sp[3] = {(double)g_morph_spacing[0], (double)g_morph_spacing[1], (double)g_morph_spacing[2]};
+    std::printf("measure: [%g, %g] connectivity %u: %llu regions, %llu foreground voxels of %llu, spacing %g %g %g\n", g_label_lo, g_label_hi, g_label_conn, (unsigned long long)m.totals.n_regions,
+                (unsigned long long)m.totals.n_foreground, (unsigned long long)m.dims[0] * m.dims[1] * m.dims[2], sp[0], sp[1], sp[2]);
+    for (uint64_t id : m.largest(10)) {
+        const size_t k = (size_t)id - 1;
+        const std::array<double, 3> c = m.centroid(k), l = m.principal_lengths(k, sp);
+        std::printf("region %llu: %llu voxels, centroid %.3f %.3f %.3f, diameter %.3f, lengths %.3f %.3f %.3f, mean %.6g +- %.6g, surface %.6g\n", (unsigned long long)id,
+                    (unsigned long long)m.table[k].n_voxels, c[0], c[1], c[2], m.equivalent_diameter(k, sp), l[0], l[1], l[2], m.mean(k), m.stddev(k), m.surface_area(k, sp));
+    }
+    if (!g_measure_csv.empty()) {
+        m.to_csv(g_measure_csv, sp);
+        std::printf("measure: %zu regions -> %s\n", m.table.size(), g_measure_csv.c_str());
+    }
+}
+
 // --crop, --resample, --downsample, --isotropic, --to-u8, --to-u16 in the order given, right after the volume is loaded; the last of them fills --save-raw's
 // file unless a filter, a --morph or a keep flag follows
 static void apply_resample(Context &ctx) {
@@ -275,7 +301,7 @@ static void apply_resample(Context &ctx) {
 // --median, then --smooth, once the volume is there and before anything reads it; the last of them also fills --save-raw's file (unless a keep flag follows)
 static void apply_filters(Context &ctx) {
     apply_resample(ctx);
-    if (!g_median && !g_smooth) { apply_labels(ctx); return; }
+    if (!g_median && !g_smooth) { apply_labels(ctx); apply_measure(ctx); return; }
     std::vector<unsigned char> dense;
     if (!g_save_raw.empty() && !label_ops() && g_morph.empty() && !g_split_on) {
         uint32_t dims[3] = {0, 0, 0};
@@ -288,6 +314,7 @@ static void apply_filters(Context &ctx) {
     std::printf("filter:%s%s\n", g_median ? " median 3x3x3" : "", g_smooth ? (" gaussian sigma " + std::to_string(g_sigma[0]) + " " + std::to_string(g_sigma[1]) + " " + std::to_string(g_sigma[2])).c_str() : "");
     if (!dense.empty()) write_dense(dense, "filtered");
     apply_labels(ctx);
+    apply_measure(ctx);
 }
 
 // --tf PATH: the whole file as little-endian f32 RGBA rows (the library checks n, finiteness and alpha)
@@ -802,6 +829,10 @@ int main(int argc, char **argv) {
                 g_split_conn = (uint32_t)c;
             }
         }
+        else if (a == "--measure") {
+            g_measure_on = true;
+            if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) g_measure_csv = next();
+        }
         else if (a == "--morph-spacing") {
             g_morph_spacing_on = true;
             for (int k = 0; k < 3; k++) {
@@ -843,9 +874,11 @@ int main(int argc, char **argv) {
     if (!g_morph.empty() && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --morph needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
     if (g_split_on && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --split needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
     if (g_split_on && gpus > 0) { std::fprintf(stderr, "bonsai: --split runs on one GPU\n"); return 2; }
-    if (((g_morph_spacing_on && !g_split_on) || g_morph_fill_on) && g_morph.empty()) { std::fprintf(stderr, "bonsai: %s needs --morph\n", g_morph_spacing_on ? "--morph-spacing" : "--morph-fill"); return 2; }
+    if (g_measure_on && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --measure needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
+    if (g_measure_on && gpus > 0) { std::fprintf(stderr, "bonsai: --measure runs on one GPU\n"); return 2; }
+    if (((g_morph_spacing_on && !g_split_on && !g_measure_on) || g_morph_fill_on) && g_morph.empty()) { std::fprintf(stderr, "bonsai: %s needs --morph\n", g_morph_spacing_on ? "--morph-spacing" : "--morph-fill"); return 2; }
     if (!g_morph.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --morph runs on one GPU\n"); return 2; }
-    if ((label_ops() || !g_morph.empty() || g_split_on) && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
+    if ((label_ops() || !g_morph.empty() || g_split_on || g_measure_on) && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
     g_w = w; g_h = h;
     if (!g_resample.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --crop, --resample, --downsample, --isotropic, --to-u8 and --to-u16 run on one GPU\n"); return 2; }
     for (const ResampleOp &op : g_resample)

@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <memory>
@@ -211,6 +212,125 @@ struct Regions {
         std::stable_sort(ids.begin(), ids.end(), [&](uint64_t a, uint64_t b) { return table[a - 1].n_voxels > table[b - 1].n_voxels; });
         ids.resize(std::min(k, ids.size()));
         return ids;
+    }
+};
+static_assert(sizeof(vk_measure_request) == 24 && sizeof(vk_region) == 192 && sizeof(vk_measure_result) == 32, "vk_measure_request is 24 bytes, vk_region 192, vk_measure_result 32 (vk_measure_components)");
+// What Context::measure_components returns: the regions' exact integer records in id order (id k + 1 at index k), the totals, the volume's
+// dimensions, and the quantities derived from a record in double: the 128-bit fields are joined in __int128, a quotient is taken once.
+// An empty region (an id no voxel carries) gives NaN wherever a quotient has no meaning.  k below is an index into `table`: id - 1.
+struct Measurements {
+    std::vector<vk_region> table;
+    vk_measure_result totals{};
+    uint32_t dims[3] = {0, 0, 0};
+    std::vector<uint64_t> largest(size_t k) const {
+        std::vector<uint64_t> ids(table.size());
+        for (size_t i = 0; i < ids.size(); i++) ids[i] = i + 1;
+        std::stable_sort(ids.begin(), ids.end(), [&](uint64_t a, uint64_t b) { return table[a - 1].n_voxels > table[b - 1].n_voxels; });
+        ids.resize(std::min(k, ids.size()));
+        return ids;
+    }
+    // the mean voxel index (x, y, z); centroid_unit: (c + 0.5) / dims, the unit-cube convention of the mesh and of vk_hit.pos
+    std::array<double, 3> centroid(size_t k) const {
+        const vk_region &r = table[k];
+        const double n = (double)r.n_voxels;
+        return {r.n_voxels ? (double)r.sum_x / n : NAN, r.n_voxels ? (double)r.sum_y / n : NAN, r.n_voxels ? (double)r.sum_z / n : NAN};
+    }
+    std::array<double, 3> centroid_unit(size_t k) const {
+        const std::array<double, 3> c = centroid(k);
+        return {(c[0] + 0.5) / dims[0], (c[1] + 0.5) / dims[1], (c[2] + 0.5) / dims[2]};
+    }
+    // the covariance of the voxel positions (population form) in the units of spacing (nullptr: 1 1 1): (n S_ab - S_a S_b) / n^2 with the
+    // numerator exact in __int128 (it fits whenever n times the largest dimension stays below 2^63: every volume that fits a device)
+    std::array<std::array<double, 3>, 3> covariance(size_t k, const double *spacing = nullptr) const {
+        const vk_region &r = table[k];
+        const uint64_t s[3] = {r.sum_x, r.sum_y, r.sum_z}, p[3][3] = {{r.sum_xx, r.sum_xy, r.sum_xz}, {r.sum_xy, r.sum_yy, r.sum_yz}, {r.sum_xz, r.sum_yz, r.sum_zz}};
+        std::array<std::array<double, 3>, 3> c{};
+        for (int a = 0; a < 3; a++)
+            for (int b = 0; b < 3; b++) {
+                const __int128 num = (__int128)r.n_voxels * p[a][b] - (__int128)s[a] * s[b];
+                c[a][b] = r.n_voxels ? (double)num / ((double)r.n_voxels * (double)r.n_voxels) * (spacing ? spacing[a] * spacing[b] : 1.0) : NAN;
+            }
+        return c;
+    }
+    // the covariance's eigenvalues, descending, and their unit eigenvectors (vectors[j] belongs to values[j]): cyclic Jacobi sweeps of the 3 x 3 matrix
+    void principal_axes(size_t k, const double *spacing, double values[3], double vectors[3][3]) const {
+        std::array<std::array<double, 3>, 3> a = covariance(k, spacing);
+        double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+        for (int sweep = 0; sweep < 32 && std::isfinite(a[0][0]); sweep++) {
+            const double off = std::fabs(a[0][1]) + std::fabs(a[0][2]) + std::fabs(a[1][2]);
+            if (off <= 1e-300 || off <= 1e-17 * (std::fabs(a[0][0]) + std::fabs(a[1][1]) + std::fabs(a[2][2]))) break;
+            for (int p = 0; p < 2; p++)
+                for (int q = p + 1; q < 3; q++) {
+                    if (a[p][q] == 0.0) continue;
+                    const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
+                    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0)), c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+                    for (int i = 0; i < 3; i++) { const double x = a[i][p], y = a[i][q]; a[i][p] = c * x - sn * y; a[i][q] = sn * x + c * y; }
+                    for (int i = 0; i < 3; i++) { const double x = a[p][i], y = a[q][i]; a[p][i] = c * x - sn * y; a[q][i] = sn * x + c * y; }
+                    for (int i = 0; i < 3; i++) { const double x = v[i][p], y = v[i][q]; v[i][p] = c * x - sn * y; v[i][q] = sn * x + c * y; }
+                }
+        }
+        int order[3] = {0, 1, 2};
+        std::sort(order, order + 3, [&](int x, int y) { return a[x][x] > a[y][y]; });
+        for (int j = 0; j < 3; j++) {
+            values[j] = a[order[j]][order[j]];
+            for (int i = 0; i < 3; i++) vectors[j][i] = std::isfinite(values[j]) ? v[i][order[j]] : NAN;
+        }
+    }
+    // the full axes, longest first, of the uniform ellipsoid that has the region's covariance: 2 sqrt(5 lambda)
+    std::array<double, 3> principal_lengths(size_t k, const double *spacing = nullptr) const {
+        double w[3], v[3][3];
+        principal_axes(k, spacing, w, v);
+        return {2.0 * std::sqrt(5.0 * std::max(w[0], 0.0)), 2.0 * std::sqrt(5.0 * std::max(w[1], 0.0)), 2.0 * std::sqrt(5.0 * std::max(w[2], 0.0))};
+    }
+    double volume(size_t k, const double *spacing = nullptr) const { return (double)table[k].n_voxels * (spacing ? spacing[0] * spacing[1] * spacing[2] : 1.0); }
+    double equivalent_diameter(size_t k, const double *spacing = nullptr) const { return std::cbrt(6.0 * volume(k, spacing) / 3.14159265358979323846); }
+    // the area of the exposed voxel faces, faces . (sy sz, sx sz, sx sy): the voxel staircase's surface, an overestimate for a smooth shape
+    double surface_area(size_t k, const double *spacing = nullptr) const {
+        const vk_region &r = table[k];
+        const double sx = spacing ? spacing[0] : 1.0, sy = spacing ? spacing[1] : 1.0, sz = spacing ? spacing[2] : 1.0;
+        return (double)r.faces[0] * sy * sz + (double)r.faces[1] * sx * sz + (double)r.faces[2] * sx * sy;
+    }
+    bool touches_border(size_t k) const {
+        const vk_region &r = table[k];
+        return r.n_voxels && (r.box.x0 == 0 || r.box.y0 == 0 || r.box.z0 == 0 || r.box.x1 == dims[0] || r.box.y1 == dims[1] || r.box.z1 == dims[2]);
+    }
+    // intensity in sample values (q / scale), over the finite voxels
+    uint64_t n_finite(size_t k) const { return table[k].n_voxels - table[k].n_nonfinite; }
+    double mean(size_t k) const {
+        const vk_region &r = table[k];
+        const __int128 q = ((__int128)r.sum_q_hi << 64) + (__int128)r.sum_q_lo;
+        return n_finite(k) ? (double)q / ((double)n_finite(k) * (double)totals.scale) : NAN;
+    }
+    // (m sum q^2 - (sum q)^2) / (m scale)^2, exact in 128 bits where the products fit (always for the integer formats), else in long double
+    double variance(size_t k) const {
+        const vk_region &r = table[k];
+        const uint64_t m = n_finite(k);
+        if (!m) return NAN;
+        const __int128 q = ((__int128)r.sum_q_hi << 64) + (__int128)r.sum_q_lo;
+        const unsigned __int128 qq = ((unsigned __int128)r.sum_qq_hi << 64) + r.sum_qq_lo, aq = (unsigned __int128)(q < 0 ? -q : q);
+        unsigned __int128 left, right;
+        const double den = ((double)m * (double)totals.scale) * ((double)m * (double)totals.scale);
+        if (!__builtin_mul_overflow(qq, (unsigned __int128)m, &left) && !__builtin_mul_overflow(aq, aq, &right)) return (double)(left - right) / den;  // left >= right (Cauchy-Schwarz)
+        const long double mean_q = (long double)q / (long double)m, ms = (long double)qq / (long double)m - mean_q * mean_q;
+        return (double)(ms > 0 ? ms : 0) / ((double)totals.scale * (double)totals.scale);
+    }
+    double stddev(size_t k) const { return std::sqrt(variance(k)); }
+    double min(size_t k) const { return n_finite(k) ? (double)table[k].q_min / (double)totals.scale : NAN; }
+    double max(size_t k) const { return n_finite(k) ? (double)table[k].q_max / (double)totals.scale : NAN; }
+    // one line per region: id, voxels, first, box, centroid, volume, equivalent diameter, principal lengths, mean, std, min, max, nonfinite voxels, faces, area, border
+    void to_csv(const std::string &path, const double *spacing = nullptr) const {
+        std::FILE *f = std::fopen(path.c_str(), "w");
+        if (!f) throw std::runtime_error("cannot write " + path);
+        std::fprintf(f, "id,n_voxels,first,x0,y0,z0,x1,y1,z1,cx,cy,cz,volume,equivalent_diameter,length_1,length_2,length_3,mean,std,min,max,n_nonfinite,faces_x,faces_y,faces_z,surface_area,touches_border\n");
+        for (size_t k = 0; k < table.size(); k++) {
+            const vk_region &r = table[k];
+            const std::array<double, 3> c = centroid(k), l = principal_lengths(k, spacing);
+            std::fprintf(f, "%zu,%llu,%llu,%u,%u,%u,%u,%u,%u,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%llu,%llu,%llu,%llu,%.17g,%d\n", k + 1, (unsigned long long)r.n_voxels,
+                         (unsigned long long)r.first, r.box.x0, r.box.y0, r.box.z0, r.box.x1, r.box.y1, r.box.z1, c[0], c[1], c[2], volume(k, spacing), equivalent_diameter(k, spacing), l[0], l[1], l[2],
+                         mean(k), stddev(k), min(k), max(k), (unsigned long long)r.n_nonfinite, (unsigned long long)r.faces[0], (unsigned long long)r.faces[1], (unsigned long long)r.faces[2],
+                         surface_area(k, spacing), touches_border(k) ? 1 : 0);
+        }
+        if (std::fclose(f) != 0) throw std::runtime_error("cannot write " + path);
     }
 };
 // The voxel of a volume of nx x ny x nz that holds the unit-cube position pos (vk_hit.pos): min(floor(pos_c n_c), n_c - 1) per axis.
@@ -567,6 +687,27 @@ class Context {
         }
         r.table.resize((size_t)std::min<uint64_t>(r.totals.n_regions, r.table.size()));
         return r;
+    }
+    // Measure labelled regions (vk_measure_components; blocks; changes no state): one exact integer record per region and what derives from
+    // it (Measurements).  labels nullptr: the regions are label_components' components of [lo, hi] under `connectivity` inside box / the
+    // clip box -- after split_components(install) the split regions; the label array stays on the device.  labels: nx ny nz ids, x fastest,
+    // 0 background (label_components' or split_components' labels, or the caller's own); the regions are 1 .. max_label and lo, hi,
+    // connectivity and box are not used.  One call with room for 4096 regions, a second only when there are more.
+    Measurements measure_components(float lo, float hi = INFINITY, uint32_t connectivity = 6, const vk_voxel_box *box = nullptr, bool clip = false, const uint32_t *labels = nullptr,
+                                    uint32_t max_label = 0) {
+        vk_measure_request req{};
+        if (labels) req.max_label = max_label;
+        else { req.lo = lo; req.hi = hi; req.connectivity = connectivity; req.flags = clip ? (uint32_t)VK_MEASURE_CLIP_BOX : 0u; }
+        Measurements m;
+        check(ctx_, vk_volume_info(ctx_, m.dims, nullptr, nullptr, nullptr));
+        m.table.resize(4096);
+        check(ctx_, vk_measure_components(ctx_, &req, labels ? nullptr : box, labels, m.table.data(), m.table.size(), &m.totals));
+        if (m.totals.n_regions > m.table.size()) {
+            m.table.resize((size_t)m.totals.n_regions);
+            check(ctx_, vk_measure_components(ctx_, &req, labels ? nullptr : box, labels, m.table.data(), m.table.size(), &m.totals));
+        }
+        m.table.resize((size_t)m.totals.records_written);
+        return m;
     }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
