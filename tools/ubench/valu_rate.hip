@@ -77,6 +77,12 @@ DEFINE_KERNEL(k_med3_i32, OP3("v_med3_i32"))
 // the 32-bit integer multiplies of an unsigned division by a launch constant (the block map before its reciprocals: profiles/block_map_scalar.txt)
 DEFINE_KERNEL(k_mul_lo_u32, OP2("v_mul_lo_u32"))
 DEFINE_KERNEL(k_mul_hi_u32, OP2("v_mul_hi_u32"))
+// the three instructions of the compiler's f32 division that are not fma / mul / rcp (profiles/ray_setup_divisions.txt): the scaling (writes VCC),
+// the last fma (reads VCC, never written in the loop) and the fix-up
+DEFINE_KERNEL_C(k_div_scale, "v_div_scale_f32 %0, vcc, %0, %8, %0\nv_div_scale_f32 %1, vcc, %1, %8, %1\nv_div_scale_f32 %2, vcc, %2, %8, %2\nv_div_scale_f32 %3, vcc, %3, %8, %3\n"
+                             "v_div_scale_f32 %4, vcc, %4, %8, %4\nv_div_scale_f32 %5, vcc, %5, %8, %5\nv_div_scale_f32 %6, vcc, %6, %8, %6\nv_div_scale_f32 %7, vcc, %7, %8, %7\n", "vcc")
+DEFINE_KERNEL(k_div_fmas, OP3("v_div_fmas_f32"))
+DEFINE_KERNEL(k_div_fixup, OP3("v_div_fixup_f32"))
 DEFINE_KERNEL(k_fma_mix, "v_fma_mix_f32 %0, %0, %8, %9 op_sel_hi:[0,1,1]\nv_fma_mix_f32 %1, %1, %8, %9 op_sel_hi:[0,1,1]\nv_fma_mix_f32 %2, %2, %8, %9 op_sel_hi:[0,1,1]\n"
                          "v_fma_mix_f32 %3, %3, %8, %9 op_sel_hi:[0,1,1]\nv_fma_mix_f32 %4, %4, %8, %9 op_sel_hi:[0,1,1]\nv_fma_mix_f32 %5, %5, %8, %9 op_sel_hi:[0,1,1]\n"
                          "v_fma_mix_f32 %6, %6, %8, %9 op_sel_hi:[0,1,1]\nv_fma_mix_f32 %7, %7, %8, %9 op_sel_hi:[0,1,1]\n")
@@ -225,6 +231,7 @@ int main(int argc, char **argv) {
     hipEvent_t e0, e1; CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
     std::vector<Entry> ks = {{"v_fma_f32", k_fma, 16}, {"v_fma_f32 dependent", k_fma_dep, 16}, {"v_fma_f32 2 chains", k_fma_dep2, 16}, {"v_add_f32", k_add, 16}, {"v_mul_f32", k_mul, 16}, {"v_min_f32", k_min, 16},
         {"v_pk_fma_f32", k_pk_fma, 16}, {"v_fma_f64", k_fma_f64, 16}, {"v_fma_mix_f32", k_fma_mix, 16}, {"v_cos_f32", k_cos, 16}, {"v_exp_f32", k_exp, 16}, {"v_rcp_f32", k_rcp, 16},
+        {"v_div_scale_f32", k_div_scale, 16}, {"v_div_fmas_f32", k_div_fmas, 16}, {"v_div_fixup_f32", k_div_fixup, 16},
         {"v_fract_f32", k_fract, 16}, {"v_cvt_flr_i32_f32", k_cvt_flr, 16}, {"v_cvt_f32_i32", k_cvt_f32_i32, 16}, {"v_cvt_f32_ubyte0", k_cvt_ub0, 16},
         {"v_min_i32", k_min_i32, 16}, {"v_add_u32", k_add_u32, 16}, {"v_lshlrev_b32", k_lshl, 16}, {"v_lshl_add_u32", k_lshl_add, 16}, {"v_add3_u32", k_add3, 16}, {"v_mad_i32_i24", k_mad_i24, 16},
         {"v_med3_i32", k_med3_i32, 16}, {"v_mul_lo_u32", k_mul_lo_u32, 16}, {"v_mul_hi_u32", k_mul_hi_u32, 16}, {"v_fmac_f32 (VOP2)", k_fmac, 16}, {"v_add_f32_e64 (VOP3)", k_add_e64, 16}, {"v_max_f32", k_max, 16}, {"v_mov_b32", k_mov, 16}, {"v_and_b32", k_and, 16},

@@ -129,6 +129,9 @@ struct LaunchDesc {
     // the reciprocals of the block map's divisors -- ts / 8 and its square, n_frames, tiles_x, the deal's root_skip (vk_hostmath.hpp:
     // block_map_make, called where the fields above are filled): a wave maps its block without a division
     BlockMapDesc bm;
+    // ... and RN(1 / W), RN(1 / H) for the two divisions of a ray's NDC coordinates (vk_exactdiv.hpp: div_const), filled in the same place
+    // (vk_render.hip: dispatch_march)
+    float rcp_w, rcp_h;
     // LF_ORDER_INLINE: the tile order rides in the kernel arguments (single-frame launches of up to kOrderInline tiles): no table upload
     // in the frame's stream.  Last member: launches that do not use it never touch these bytes.
     uint16_t order_inline[1024];
@@ -148,6 +151,7 @@ enum LaunchFlag : uint32_t {
     LF_FRAME_RUNS = 32u,          // batched launches: every XCD marches a run of consecutive frames of a tile position
     LF_PROBE_AHEAD = 128u,        // skip kernels, fast path: the next position's distance byte is requested under this trip's sample (vk_march.hpp: AHEAD)
     LF_ORDER_INLINE = 256u,       // map_pixel reads the tile order from LaunchDesc::order_inline (kernel arguments) instead of the device table
+    LF_SETUP_GENERIC = 512u,      // cell march: every wave takes the ray set-up with the generic divisions (vk_debug_set_param "setup_generic": A/B runs, tests)
     LF_TRIP_LOG = 64u,            // COUNT builds: `trace` holds per-trip logs of trip_log_cap entries per wave (docs/archive/tools/repack_census.py)
 };
 
@@ -410,6 +414,18 @@ __device__ __forceinline__ void intersect_box(const float o[3], const float d[3]
     for (int i = 0; i < 3; i++) {
         float inv = 1.0f / d[i];
         float a = (lo[i] - o[i]) * inv, b = (hi[i] - o[i]) * inv;
+        tmin[i] = fminf(a, b);
+        tmax[i] = fmaxf(a, b);
+    }
+    t0 = fmaxf(tmin[0], fmaxf(tmin[1], tmin[2]));
+    t1 = fminf(tmax[0], fminf(tmax[1], tmax[2]));
+}
+// ... and with the reciprocals 1 / d[i] already taken (the short ray set-up of the cell march, vk_exactdiv.hpp): the operations behind the division
+__device__ __forceinline__ void intersect_box_inv(const float o[3], const float inv[3], const float lo[3], const float hi[3], float &t0, float &t1) {
+    float tmin[3], tmax[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        float a = (lo[i] - o[i]) * inv[i], b = (hi[i] - o[i]) * inv[i];
         tmin[i] = fminf(a, b);
         tmax[i] = fmaxf(a, b);
     }

@@ -526,6 +526,7 @@ int vk_debug_set_param(vk_ctx *ctx, const char *name, double value) {
     else if (n == "wave_prio") ctx->wave_prio = (uint32_t)value;
     else if (n == "fif_concurrent") ctx->fif_concurrent = (uint32_t)value;  // frames in flight: how many of the ring's frames may execute at once (0: all)
     else if (n == "order_never_inline") ctx->order_never_inline = (uint32_t)value;  // A/B: the tile order through the device table for every launch
+    else if (n == "setup_generic") ctx->setup_generic = (uint32_t)value;            // A/B, tests: the cell march's ray set-up with the generic divisions (vk_exactdiv.hpp)
     else if (n == "walk_cap") ctx->walk_cap = (uint32_t)value;
     else if (n == "walk_cap_all") ctx->walk_cap_all = (uint32_t)value;
     else if (n == "render_tile") ctx->render_tile = ((uint32_t)value & ~7u);

@@ -160,6 +160,7 @@ struct vk_ctx {
     uint32_t order_rays = 3;     // estimate rays per tile edge of the heaviest-first order (single-frame launches)
     uint32_t order_rays_batch = 1;  // ... of launches spanning >= 4 frames
     uint32_t order_never_inline = 0;  // debug / A-B: single-frame launches read the tile order from the device table as before round 6
+    uint32_t setup_generic = 0;  // debug / A-B: the cell march's ray set-up with the generic divisions in every wave (LF_SETUP_GENERIC)
     uint32_t wave_prio = 1;      // issue priority by ray length (set_wave_priority); 0 for A/B measurements
     uint32_t naive_lds_pad = 0;  // debug: extra dynamic LDS per workgroup of the cell kernels (caps the waves per SIMD)
     uint32_t root_skip = 0;  // dealing: rank 0 sits out every root_skip-th round (vk_partition_root_skip)

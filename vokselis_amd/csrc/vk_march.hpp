@@ -7,6 +7,7 @@
 #pragma once
 
 #include "vk_common.hpp"
+#include "vk_exactdiv.hpp"
 #include "vk_march_parts.hpp"
 #include "vk_iso.hpp"
 #include "vk_light.hpp"

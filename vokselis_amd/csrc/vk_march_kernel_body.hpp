@@ -67,18 +67,47 @@
     if (!pm.valid) return;
 
     // --- ray: SURVEY A.1 step 1 (replaces vs_main + rasteriser) ---
-    float fxp = (float)pm.x + 0.5f, fyp = (float)pm.y + 0.5f;
-    float ndcx = (2.0f * fxp) / (float)L.W - 1.0f;
-    float ndcy = 1.0f - (2.0f * fyp) / (float)L.H;
-    float q[4];
-    mat4_mul_vec4(fv.inv_proj, ndcx, ndcy, 1.0f, 1.0f, q);
+    // The set-up's 14 divisions come in two texts.  The short one (vk_exactdiv.hpp) runs first: the compiler's own division chain without its
+    // scaling and fix-up instructions -- the same bits while every operand is in range --, the refinement of a divisor shared by its three
+    // quotients, and the launch's reciprocals for the two divisions by the image size.  One predicate per lane holds every operand to
+    // [kDivLo, kDivHi]: the clip-space point, the far point's offset from the eye (a zero or tiny direction component fails it: 1 / 0 = inf is the
+    // reference's, and the generic division's) and its length.  If a single lane fails, or the launch asks for it (LF_SETUP_GENERIC), the
+    // whole wave takes the generic text below -- the set-up as it always was -- and nothing of the short one is used.
+    const float fxp = (float)pm.x + 0.5f, fyp = (float)pm.y + 0.5f;
     const float eye[3] = {fv.eye[0], fv.eye[1], fv.eye[2]};
-    float dir[3] = {q[0] / q[3] - eye[0], q[1] / q[3] - eye[1], q[2] / q[3] - eye[2]};
-    normalize3(dir[0], dir[1], dir[2]);
-
-    float t0, t1;
-    if constexpr (CLIP) intersect_box(eye, dir, clp->lo, clp->hi, t0, t1);  // the clip box (vk_set_clip_box): the family's kernels of their own
-    else intersect_box(eye, dir, 0.0f, 1.0f, t0, t1);
+    float dir[3], t0, t1;
+    [[maybe_unused]] float inv[3];  // short set-up: 1 / dir[i], which dt takes again below
+    bool short_setup = !(L.flags & LF_SETUP_GENERIC) && L.W <= kDivConstMax && L.H <= kDivConstMax;  // wave-uniform
+    if (short_setup) {
+        const float ndcx = div_const(2.0f * fxp, (float)L.W, L.rcp_w) - 1.0f;
+        const float ndcy = 1.0f - div_const(2.0f * fyp, (float)L.H, L.rcp_h);
+        float q[4];
+        mat4_mul_vec4(fv.inv_proj, ndcx, ndcy, 1.0f, 1.0f, q);
+        const Recip rq = recip_refine(q[3]);
+        const float ex = div_by(q[0], rq) - eye[0], ey = div_by(q[1], rq) - eye[1], ez = div_by(q[2], rq) - eye[2];
+        const float len = sqrtf((ex * ex + ey * ey) + ez * ez);
+        const Recip rl = recip_refine(len);
+        dir[0] = div_by(ex, rl); dir[1] = div_by(ey, rl); dir[2] = div_by(ez, rl);
+#pragma unroll
+        for (int i = 0; i < 3; i++) inv[i] = div_inrange(1.0f, dir[i]);
+        float blo[3] = {0.0f, 0.0f, 0.0f}, bhi[3] = {1.0f, 1.0f, 1.0f};
+        if constexpr (CLIP) { for (int i = 0; i < 3; i++) { blo[i] = clp->lo[i]; bhi[i] = clp->hi[i]; } }
+        intersect_box_inv(eye, inv, blo, bhi, t0, t1);
+        // (len >= every |e|: it bounds them from above, and it is a NaN if anything before it is -- fminf / fmaxf drop a NaN, its own compare does not)
+        const float lo = fminf(fminf(fminf(fabsf(q[0]), fabsf(q[1])), fabsf(q[2])), fminf(fminf(fabsf(ex), fabsf(ey)), fminf(fabsf(ez), fabsf(q[3]))));
+        const float hi = fmaxf(fmaxf(fabsf(q[0]), fabsf(q[1])), fmaxf(fabsf(q[2]), fabsf(q[3])));
+        if (__ballot(!(lo >= kDivLo && hi <= kDivHi && len <= kDivHi)) != 0ull) short_setup = false;
+    }
+    if (!short_setup) {
+        float ndcx = (2.0f * fxp) / (float)L.W - 1.0f;
+        float ndcy = 1.0f - (2.0f * fyp) / (float)L.H;
+        float q[4];
+        mat4_mul_vec4(fv.inv_proj, ndcx, ndcy, 1.0f, 1.0f, q);
+        dir[0] = q[0] / q[3] - eye[0]; dir[1] = q[1] / q[3] - eye[1]; dir[2] = q[2] / q[3] - eye[2];
+        normalize3(dir[0], dir[1], dir[2]);
+        if constexpr (CLIP) intersect_box(eye, dir, clp->lo, clp->hi, t0, t1);  // the clip box (vk_set_clip_box): the family's kernels of their own
+        else intersect_box(eye, dir, 0.0f, 1.0f, t0, t1);
+    }
     Census cs;
     const bool trip_log = COUNT && L.trace && (L.flags & LF_TRIP_LOG);
     if (trip_log) {  // (the loops of the maximum projection keep no log: such a launch writes neither a log nor stamps)
@@ -93,9 +122,17 @@
     if (!(t0 > t1)) {  // :91-93
         t0 = fmaxf(t0, 0.0f);  // :94
         const float fnx = (float)V.nx, fny = (float)V.ny, fnz = (float)V.nz;
-        float dtx = 1.0f / (fnx * fabsf(dir[0]));
-        float dty = 1.0f / (fny * fabsf(dir[1]));
-        float dtz = 1.0f / (fnz * fabsf(dir[2]));
+        float dtx, dty, dtz;
+        if (short_setup) {
+            // a power-of-two dimension (wave-uniform, on the scalar unit): 1 / (fn |d|) is |1 / d| (1 / fn) exactly, and 1 / d is at hand
+            dtx = is_pow2(V.nx) ? fabsf(inv[0]) * pow2_recip(fnx) : div_inrange(1.0f, fnx * fabsf(dir[0]));
+            dty = is_pow2(V.ny) ? fabsf(inv[1]) * pow2_recip(fny) : div_inrange(1.0f, fny * fabsf(dir[1]));
+            dtz = is_pow2(V.nz) ? fabsf(inv[2]) * pow2_recip(fnz) : div_inrange(1.0f, fnz * fabsf(dir[2]));
+        } else {
+            dtx = 1.0f / (fnx * fabsf(dir[0]));
+            dty = 1.0f / (fny * fabsf(dir[1]));
+            dtz = 1.0f / (fnz * fabsf(dir[2]));
+        }
         const float dt = L.dt_scale * fminf(dtx, fminf(dty, dtz));  // :97-99
         float px = eye[0] + t0 * dir[0], py = eye[1] + t0 * dir[1], pz = eye[2] + t0 * dir[2];  // :100
         const float sx = dir[0] * dt, sy = dir[1] * dt, sz = dir[2] * dt;  // :118

@@ -22,6 +22,7 @@ uint32_t launch_flags(const vk_ctx *ctx, uint32_t render_flags, bool batch) {
     if (render_flags & VK_RENDER_DEBUG_FALLBACK) f |= LF_STEPS_ARE_FALLBACKS;
     if (!(render_flags & VK_RENDER_PROBE_ALWAYS)) f |= LF_ADAPTIVE_PROBING;
     if (ctx->wave_prio) f |= LF_WAVE_PRIORITY;
+    if (ctx->setup_generic) f |= LF_SETUP_GENERIC;
     if (batch && ctx->frame_runs) f |= LF_FRAME_RUNS;
     // probe ahead pays where a frame's waves run against their own dependent chains -- a lone single-frame launch (-11 %) -- and costs where the
     // machine is full (+6-8 % in batches).  A frame of a ring in which three frames execute at once (k = 4) is in the second case: C2 0.0768 ->
@@ -76,6 +77,9 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
     // the block map's reciprocals (vk_hostmath.hpp): exact for every block index below n_blocks, or the launch is refused
     if (!block_map_make(L.ts, L.tiles_x, L.tiles_y, L.frames ? L.n_frames : 1u, L.nranks, L.root_skip, n_blocks, L.bm))
         return fail(ctx, VK_ERR_UNSUPPORTED, "launch too large for the block map: a smaller image, larger tiles or fewer frames per batch");
+    // ... and the reciprocals of the image size for the rays' NDC coordinates
+    L.rcp_w = 1.0f / (float)L.W;
+    L.rcp_h = 1.0f / (float)L.H;
     // a runtime transfer function (vk_set_transfer_function) has kernels on the LINEAR / PACKED / PACKED_PAIRS layouts, walking with the loop
     // a first-hit isosurface (vk_set_isosurface): kernels of its own with the table kernels' coverage; table and projection are ignored under it, lighting is honoured
     const bool iso = mode == VK_MODE_NAIVE_TRILINEAR && ctx->iso_on;
