@@ -842,6 +842,62 @@ _Static_assert(sizeof(vk_measure_request) == 24 && sizeof(vk_region) == 192 && s
 int vk_measure_components(vk_ctx *ctx, const vk_measure_request *req, const vk_voxel_box *box, const uint32_t *labels_in, vk_region *regions,
                           uint64_t cap_regions, vk_measure_result *result);
 
+/* Local thickness of a value range: for every voxel of the set S, the squared radius of the largest ball that
+ * fits inside S and contains the voxel -- trabecular thickness, strut thickness, pore size.  Every result is an integer but the dense
+ * value, whose three roundings are written out below.
+ * The set.  S, t, lo_k, hi_k, the box (`box`, the clip box under VK_THICK_CLIP_BOX, or NULL for the whole volume) and the integer
+ * `spacing` are exactly vk_distance_transform's.  The box restricts S only.
+ * Distances.  d2(u, v) = sum_c (spacing[c] * (u_c - v_c))^2.  D(u) = D2(not S, u) as VK_DIST_INSIDE defines it: 0 off S, and
+ * VK_DIST_INF on S when S is the whole volume -- nothing outside the volume is background.
+ * The cap.  C = (uint64_t)floor((double)max_radius * (double)max_radius); Dc(u) = min(D(u), C).  The cap bounds the reach of every
+ * ball and with it the work of a launch, and it saturates the result: a structure thicker than max_radius reports C.  VK_DIST_INF
+ * never appears in an output.
+ * Thickness.  For v in S: T2(v) = max { Dc(u) : u in S, d2(u, v) < Dc(u) }.  For v not in S: T2(v) = 0.  The ball is open: the set of
+ * w with d2(u, w) < D(u) is the largest ball about u that holds no background voxel.  u = v always qualifies, so T2 >= Dc > 0 on S.
+ * The thickness a user reads is 2 sqrt(T2), in the units of spacing; the hosts derive it.
+ * Outputs.  t2_out (may be NULL): nx ny nz uint32, x fastest, over the whole volume.  The dense value of v in S is
+ * w(v) = sqrtf((float)T2(v)) * gain: the conversion (exact: T2 <= 2^22), the correctly rounded square root and the product are each
+ * rounded once, nothing is fused; it is stored through vk_label_components' fill rule F.  A voxel outside S stores F(fill_out).
+ * gain == 0 asks for the automatic gain 1.0f / sqrtf((float)max_t2), or 0 when max_t2 is 0: the thickest place stores full scale.
+ * dense_out (may be NULL; host memory of nx ny nz elements of the volume's format) and VK_THICK_INSTALL behave exactly as
+ * vk_distance_transform's dense_out and VK_DIST_INSTALL: the same re-layout, the table, projection, isosurface, lighting and clip box
+ * stay in force, the old volume stays on any failure.  Without VK_THICK_INSTALL no context state changes.  The call blocks, runs on
+ * the context's current stream and allocates and frees its own buffers.
+ * result (may be NULL).  n_foreground = |S|; max_t2 = the largest T2 (0: S is empty); n_saturated = the voxels with T2 == C; sum_t2
+ * = the sum of T2 over S; gain = the gain used.  sum_t2 cannot overflow: C <= (VK_THICK_MAX_REACH * VK_DIST_MAX_SPACING)^2 = 2^22 and
+ * |S| < 2^32, so the sum stays below 2^54.
+ * VK_ERR_INVALID, decided before any launch, outputs untouched ("vk_local_thickness: ..."), in this order: a NULL request; lo or hi
+ * NaN; lo > hi; an unknown flag; a spacing of 0 or above VK_DIST_MAX_SPACING; a max_radius that is not finite or lies below 1;
+ * max_radius / min_c spacing[c] > VK_THICK_MAX_REACH (the largest ball then reaches no further than 32 voxels along any axis, which
+ * keeps the window a tile of 8^3 voxels gathers from at (8 + 64)^3 voxels); a gain that is negative or not finite; a fill_out that
+ * is not finite; none of t2_out, dense_out, VK_THICK_INSTALL and result requested; then VK_THICK_INSTALL while a frame is being
+ * recorded; no volume; a box that is inverted or leaves the volume, a box together with VK_THICK_CLIP_BOX.  VK_ERR_UNSUPPORTED
+ * ("thickness: ..."): a BRICKED / QUADS / STAGED or RGBA16F_PAIR volume; a volume of more than 2^32 - 2 voxels;
+ * sum_c (spacing[c] * (n_c - 1))^2 > 0xFFFFFFFE.  VK_ERR_OOM: a buffer cannot be allocated.  A call that fails later may have written
+ * its outputs already; the context's volume is the old one whenever the call does not return VK_OK. */
+#define VK_THICK_MAX_REACH 32
+enum { VK_THICK_CLIP_BOX = 1, VK_THICK_INSTALL = 2 };
+typedef struct vk_thickness_request {
+    float    lo, hi;         /* the value range, formed exactly as vk_label_components forms lo_k, hi_k */
+    uint32_t flags;          /* VK_THICK_CLIP_BOX | VK_THICK_INSTALL */
+    uint32_t spacing[3];     /* integer voxel pitch per axis x, y, z: 1 .. VK_DIST_MAX_SPACING */
+    float    max_radius;     /* the cap, in the units of spacing: >= 1, at most VK_THICK_MAX_REACH times the smallest spacing */
+    float    gain;           /* the dense value is sqrtf(T2) * gain; 0: 1 / sqrtf(max_t2) */
+    float    fill_out;       /* sample value of a voxel outside S; finite */
+} vk_thickness_request;      /* 36 bytes */
+typedef struct vk_thickness_result {
+    uint64_t n_foreground, n_saturated, sum_t2;
+    uint32_t max_t2;         /* the largest T2 (0: S is empty) */
+    float    gain;           /* the gain used */
+} vk_thickness_result;       /* 32 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(vk_thickness_request) == 36 && sizeof(vk_thickness_result) == 32, "vk_thickness_request: 36 bytes, vk_thickness_result: 32 bytes");
+#else
+_Static_assert(sizeof(vk_thickness_request) == 36 && sizeof(vk_thickness_result) == 32, "vk_thickness_request: 36 bytes, vk_thickness_result: 32 bytes");
+#endif
+int vk_local_thickness(vk_ctx *ctx, const vk_thickness_request *req, const vk_voxel_box *box, uint32_t *t2_out, void *dense_out,
+                       vk_thickness_result *result);
+
 /* The resample pass: a voxel box of the volume the context holds into a volume of caller-chosen dimensions, by
  * one of three rules, optionally mapped into another scalar format -- crop, resize, make isotropic, window 16-bit data into u8 --
  * without a trip through the host.  Every f32 operation below is rounded once; fmaf is fused where written and nowhere else.

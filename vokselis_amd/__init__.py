@@ -14,6 +14,7 @@ Only the raycast hot path and the host surface that drives it live here (SURVEY.
   distance   distance_request, default_fill_in: the request of Context.distance_transform / morph_volume
   split      Regions, split_request: the result and the request of Context.split_components
   measure    Measurements, measure_request: the result and the request of Context.measure_components
+  thickness  Thickness, thickness_request: the result and the request of Context.local_thickness
   resample   resample_request: the request of Context.resample_volume / crop_volume / downsample_volume / isotropic_volume
   dist       tile-parallel multi-GPU frame (one process per GPU, RCCL gather over xGMI)
 """
@@ -31,6 +32,7 @@ from ._native import (FMT_R8_UNORM, FMT_R16_FLOAT, FMT_RGBA16F_PAIR, FMT_R16_UNO
                       VkDistanceRequest, VkDistanceResult,
                       SPLIT_CLIP_BOX, SPLIT_INSTALL, VkSplitRequest, VkSplitResult,
                       MEASURE_CLIP_BOX, VkMeasureRequest, VkRegion, VkMeasureResult,
+                      THICK_MAX_REACH, THICK_CLIP_BOX, THICK_INSTALL, VkThicknessRequest, VkThicknessResult,
                       RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_AREA, RESAMPLE_INSTALL, RESAMPLE_CLIP_BOX, RESAMPLE_WINDOW, RESAMPLE_KEEP_FORMAT, RESAMPLE_MAX_RATIO,
                       VkResampleRequest, VkResampleResult)
 from .camera import Camera
@@ -42,6 +44,7 @@ from .label import Components, voxel_of
 from .distance import distance_request
 from .split import Regions, split_request
 from .measure import Measurements, measure_request
+from .thickness import Thickness, thickness_request
 from .resample import resample_request
 from .context import (Context, Demo, FrameCounter, HdrBackBuffer, Hit, ImageDimentions, RaycastPipeline, Uniform,
                       VolumeTexture, dispatch_optimal, partition_slots, render_batch, run_headless, transfer_table, untile_batch)
@@ -62,6 +65,7 @@ __all__ = [
     "VkDistanceRequest", "VkDistanceResult", "distance_request",
     "SPLIT_CLIP_BOX", "SPLIT_INSTALL", "VkSplitRequest", "VkSplitResult", "Regions", "split_request",
     "MEASURE_CLIP_BOX", "VkMeasureRequest", "VkRegion", "VkMeasureResult", "Measurements", "measure_request",
+    "THICK_MAX_REACH", "THICK_CLIP_BOX", "THICK_INSTALL", "VkThicknessRequest", "VkThicknessResult", "Thickness", "thickness_request",
     "RESAMPLE_NEAREST", "RESAMPLE_LINEAR", "RESAMPLE_AREA", "RESAMPLE_INSTALL", "RESAMPLE_CLIP_BOX", "RESAMPLE_WINDOW", "RESAMPLE_KEEP_FORMAT", "RESAMPLE_MAX_RATIO",
     "VkResampleRequest", "VkResampleResult", "resample_request",
 ]

@@ -241,6 +241,25 @@ class VkMeasureResult(C.Structure):
 assert C.sizeof(VkMeasureRequest) == 24 and C.sizeof(VkRegion) == 192 and C.sizeof(VkMeasureResult) == 32
 
 
+THICK_MAX_REACH = 32
+THICK_CLIP_BOX, THICK_INSTALL = 1, 2
+
+
+class VkThicknessRequest(C.Structure):
+    """vk_thickness_request (36 bytes): the request of vk_local_thickness -- the value range, the flags, the integer spacing per axis
+    (x, y, z), the cap of the radius, the gain of the dense value (0: automatic) and the fill of a voxel outside the set."""
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("flags", C.c_uint32), ("spacing", C.c_uint32 * 3), ("max_radius", C.c_float), ("gain", C.c_float),
+                ("fill_out", C.c_float)]
+
+
+class VkThicknessResult(C.Structure):
+    """vk_thickness_result (32 bytes): the totals of vk_local_thickness and the gain it used."""
+    _fields_ = [("n_foreground", C.c_uint64), ("n_saturated", C.c_uint64), ("sum_t2", C.c_uint64), ("max_t2", C.c_uint32), ("gain", C.c_float)]
+
+
+assert C.sizeof(VkThicknessRequest) == 36 and C.sizeof(VkThicknessResult) == 32
+
+
 RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_AREA = 0, 1, 2
 RESAMPLE_INSTALL, RESAMPLE_CLIP_BOX, RESAMPLE_WINDOW = 1, 2, 4
 RESAMPLE_KEEP_FORMAT = -1
@@ -323,6 +342,7 @@ SYMBOLS = {
     "vk_distance_transform": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_distance_request *, const vk_voxel_box *, d2_out, dense_out, vk_distance_result *
     "vk_split_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp]),  # const vk_split_request *, const vk_voxel_box *, labels_out, vk_component *, cap, dense_out, vk_split_result *
     "vk_measure_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),  # const vk_measure_request *, const vk_voxel_box *, labels_in (NULL: label the range), vk_region *, cap, vk_measure_result *
+    "vk_local_thickness": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_thickness_request *, const vk_voxel_box *, t2_out, dense_out, vk_thickness_result *
     "vk_volume_resample": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, dense_out, vk_resample_result *
     "vk_resample_output": (C.c_int, [_vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, vk_resample_result *: the output's extents, format, layout and box, nothing launched
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),

@@ -750,6 +750,28 @@ class Context:
             N.check(self._h, N.lib().vk_measure_components(self._h, C.byref(req), bp, lp, table, n, C.byref(res)))
         return Measurements(table, int(res.records_written), res, dims)
 
+    # -- local thickness of a value range: the largest inscribed ball per voxel (vk_local_thickness)
+    def local_thickness(self, lo, hi=float("inf"), max_radius: float = 16.0, spacing=(1, 1, 1), box=None, gain=None, fill_out: float = 0.0, install: bool = False,
+                        out: bool = False, t2: bool = False):
+        """vk_local_thickness: for every voxel of the set S of voxels whose stored texel lies in [lo, hi], the squared radius T2 of the
+        largest ball that fits inside S and holds the voxel, over the integer voxel pitch `spacing`, capped at max_radius^2 (a thicker
+        place reports the cap).  The dense map stores sqrt(T2) * gain on S (gain None: automatic, the thickest place stores full scale)
+        and fill_out elsewhere; install: it replaces the context's volume (outside frame_begin / frame_end), so that the table march
+        colours the set by thickness, volume_histogram gives the distribution and measure_components(labels=...) the mean per region.
+        Returns a Thickness: n_foreground, max_t2, n_saturated, sum_t2, gain, max_thickness (2 sqrt(max_t2)), mean_t2, with t2=True .t2
+        (uint32 [nz, ny, nx]) and with out=True .dense [nz, ny, nx].  Blocks."""
+        from .label import voxel_box
+        from .thickness import Thickness, thickness_request
+
+        req, vb = thickness_request(lo, hi, max_radius=max_radius, spacing=spacing, box=box, gain=gain, fill_out=fill_out, install=install), voxel_box(box)
+        dims, _ = self._volume_dtype()
+        arr = np.zeros((dims[2], dims[1], dims[0]), np.uint32) if t2 else None
+        dense = self._dense_out() if out else None
+        res = N.VkThicknessResult()
+        N.check(self._h, N.lib().vk_local_thickness(self._h, C.byref(req), C.byref(vb) if vb is not None else None, arr.ctypes.data if arr is not None else None,
+                                                    dense.ctypes.data if dense is not None else None, C.byref(res)))
+        return Thickness(res, arr, dense)
+
     def set_root_skip(self, k: int):
         """vk_partition_root_skip: rank 0 sits out every k-th round of the tile deal (0: never)."""
         N.check(self._h, N.lib().vk_partition_root_skip(self._h, int(k)))

@@ -76,6 +76,12 @@
 //                                                            --split, the split regions.  Prints the totals and the ten largest regions: id, voxels, centroid,
 //                                                            equivalent diameter, principal lengths, mean +- std, surface, in the units of --morph-spacing; FILE.csv
 //                                                            takes one line per region
+//          [--thickness MAX_RADIUS [GAIN]]                  local thickness of that range (vk_local_thickness): every voxel of the range takes the radius of the largest
+//                                                            ball that fits inside the range and holds it, capped at MAX_RADIUS (in the units of --morph-spacing), stored
+//                                                            as radius * GAIN (default: the thickest place stores full scale); every other voxel becomes the sample value
+//                                                            of --label-fill (default 0).  Runs after --measure, as the last step that replaces the volume, so
+//                                                            --thickness 16 --histogram 64 prints the thickness distribution and --thickness 16 --tf table.f32 renders
+//                                                            the range coloured by thickness; prints the totals; --save-raw writes the thickness map
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -146,6 +152,8 @@ static float g_split_radius = 0.0f;
 static uint32_t g_split_conn = 6;
 static bool g_measure_on = false;                                                // --measure [FILE.csv] (vk_measure_components), on the same range
 static std::string g_measure_csv;
+static bool g_thick_on = false;                                                  // --thickness MAX_RADIUS [GAIN] (vk_local_thickness), on the same range
+static float g_thick_radius = 16.0f, g_thick_gain = 0.0f;                        // (gain 0: automatic)
 static bool label_ops() { return !g_keep_largest.empty() || !g_drop_islands.empty() || !g_keep_voxels.empty() || !g_remove_voxels.empty() || !g_keep_picks.empty(); }
 
 // the context of a run that replaces the render: 8 x 8, or the frame's size under the render's camera when --keep-pick casts rays through it
@@ -165,7 +173,7 @@ static void apply_morph(Context &ctx) {
     int fmt = 0;
     check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !label_ops() && !g_split_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !label_ops() && !g_split_on && !g_thick_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     const float fill_in = g_morph_fill_on ? g_morph_fill[0] : (std::isfinite(g_label_hi) ? g_label_hi : (std::isfinite(g_label_lo) ? std::max(g_label_lo, 1.0f) : 1.0f));
     for (size_t k = 0; k < g_morph.size(); k++) {
         const MorphOp &op = g_morph[k];
@@ -184,7 +192,7 @@ static void apply_split(Context &ctx) {
     int fmt = 0;
     check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !label_ops()) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !label_ops() && !g_thick_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     const Regions r = ctx.split_components(g_label_lo, g_label_hi, g_split_radius, g_morph_spacing, g_split_conn, nullptr, false, false, g_label_fill, true, dense.empty() ? nullptr : dense.data());
     std::printf("split: [%g, %g] radius %g connectivity %u: %llu regions (%llu markers of %llu voxels, %llu unreached regions of %llu voxels), %llu foreground voxels, %llu cut, %u rounds\n",
                 g_label_lo, g_label_hi, g_split_radius, g_split_conn, (unsigned long long)r.totals.n_regions, (unsigned long long)r.totals.n_markers, (unsigned long long)r.totals.n_marker_voxels,
@@ -240,7 +248,7 @@ static void apply_labels(Context &ctx) {
     for (uint64_t n : g_drop_islands) ops.push_back({"drop-islands", VK_LABEL_KEEP_MIN_SIZE, n, &none, false});
     for (uint64_t k : g_keep_largest) ops.push_back({"keep-largest", VK_LABEL_KEEP_LARGEST, k, &none, false});
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty()) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !g_thick_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     for (size_t k = 0; k < ops.size(); k++) {
         const Op &op = ops[k];
         const vk_label_result r = ctx.keep_components(g_label_lo, g_label_hi, op.keep, op.count, *op.seeds, op.invert, g_label_fill, g_label_conn, nullptr, false, true,
@@ -270,12 +278,26 @@ static void apply_measure(Context &ctx) {
     }
 }
 
+// --thickness, after --measure: the last step that replaces the volume; it takes over --save-raw's file
+static void apply_thickness(Context &ctx) {
+    if (!g_thick_on) return;
+    uint32_t dims[3] = {0, 0, 0};
+    int fmt = 0;
+    check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
+    std::vector<unsigned char> dense;
+    if (!g_save_raw.empty()) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    const vk_thickness_result r = ctx.local_thickness(g_label_lo, g_label_hi, g_thick_radius, g_morph_spacing, nullptr, false, g_thick_gain, g_label_fill, true, dense.empty() ? nullptr : dense.data());
+    std::printf("thickness: [%g, %g] cap %g spacing %u %u %u: %llu foreground voxels, largest thickness %.6g, %llu saturated voxels, gain %.9g\n", g_label_lo, g_label_hi, g_thick_radius,
+                g_morph_spacing[0], g_morph_spacing[1], g_morph_spacing[2], (unsigned long long)r.n_foreground, Context::thickness_of(r.max_t2), (unsigned long long)r.n_saturated, r.gain);
+    if (!dense.empty()) write_dense(dense, "thickness");
+}
+
 // --crop, --resample, --downsample, --isotropic, --to-u8, --to-u16 in the order given, right after the volume is loaded; the last of them fills --save-raw's
 // file unless a filter, a --morph or a keep flag follows
 static void apply_resample(Context &ctx) {
     if (g_resample.empty()) return;
     static const char *const fmt_name[] = {"R8_UNORM", "R16_FLOAT", "RGBA16F_PAIR", "R16_UNORM"};
-    const bool save = !g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && !g_split_on;
+    const bool save = !g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && !g_split_on && !g_thick_on;
     std::vector<unsigned char> dense;
     for (size_t k = 0; k < g_resample.size(); k++) {
         const ResampleOp &op = g_resample[k];
@@ -301,9 +323,9 @@ static void apply_resample(Context &ctx) {
 // --median, then --smooth, once the volume is there and before anything reads it; the last of them also fills --save-raw's file (unless a keep flag follows)
 static void apply_filters(Context &ctx) {
     apply_resample(ctx);
-    if (!g_median && !g_smooth) { apply_labels(ctx); apply_measure(ctx); return; }
+    if (!g_median && !g_smooth) { apply_labels(ctx); apply_measure(ctx); apply_thickness(ctx); return; }
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !label_ops() && g_morph.empty() && !g_split_on) {
+    if (!g_save_raw.empty() && !label_ops() && g_morph.empty() && !g_split_on && !g_thick_on) {
         uint32_t dims[3] = {0, 0, 0};
         int fmt = 0;
         check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
@@ -315,6 +337,7 @@ static void apply_filters(Context &ctx) {
     if (!dense.empty()) write_dense(dense, "filtered");
     apply_labels(ctx);
     apply_measure(ctx);
+    apply_thickness(ctx);
 }
 
 // --tf PATH: the whole file as little-endian f32 RGBA rows (the library checks n, finiteness and alpha)
@@ -829,6 +852,16 @@ int main(int argc, char **argv) {
                 g_split_conn = (uint32_t)c;
             }
         }
+        else if (a == "--thickness") {
+            if (g_thick_on) { std::fprintf(stderr, "bonsai: --thickness: at most once\n"); return 2; }
+            g_thick_on = true;
+            g_thick_radius = (float)std::atof(next());
+            if (!std::isfinite(g_thick_radius) || g_thick_radius < 1.0f) { std::fprintf(stderr, "bonsai: --thickness MAX_RADIUS [GAIN]: a finite MAX_RADIUS of at least 1\n"); return 2; }
+            if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) {
+                g_thick_gain = (float)std::atof(next());
+                if (!std::isfinite(g_thick_gain) || !(g_thick_gain > 0.0f)) { std::fprintf(stderr, "bonsai: --thickness MAX_RADIUS [GAIN]: a finite GAIN above 0\n"); return 2; }
+            }
+        }
         else if (a == "--measure") {
             g_measure_on = true;
             if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) g_measure_csv = next();
@@ -868,7 +901,7 @@ int main(int argc, char **argv) {
     if (!mesh_path.empty() && (sl.on || hist || gpus > 0 || g_auto_window)) { std::fprintf(stderr, "bonsai: --mesh replaces the render: no --slice, --slice-plane, --histogram, --gpus or --auto-window\n"); return 2; }
     if (label_ops() && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel and --keep-pick need a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
     if (!g_keep_picks.empty() && !g_iso_on) { std::fprintf(stderr, "bonsai: --keep-pick needs --iso (the ray stops at the isosurface)\n"); return 2; }
-    if (g_label_fill_on && !label_ops() && !g_split_on) { std::fprintf(stderr, "bonsai: --label-fill needs a flag that drops voxels: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel or --keep-pick\n"); return 2; }
+    if (g_label_fill_on && !label_ops() && !g_split_on && !g_thick_on) { std::fprintf(stderr, "bonsai: --label-fill needs a flag that drops voxels: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel or --keep-pick\n"); return 2; }
     if (g_keep_voxels.size() + g_keep_picks.size() > 16u) { std::fprintf(stderr, "bonsai: --keep-voxel and --keep-pick: at most 16 seeds together\n"); return 2; }
     if ((g_components || label_ops()) && gpus > 0) { std::fprintf(stderr, "bonsai: --components and the keep flags run on one GPU\n"); return 2; }
     if (!g_morph.empty() && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --morph needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
@@ -876,14 +909,19 @@ int main(int argc, char **argv) {
     if (g_split_on && gpus > 0) { std::fprintf(stderr, "bonsai: --split runs on one GPU\n"); return 2; }
     if (g_measure_on && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --measure needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
     if (g_measure_on && gpus > 0) { std::fprintf(stderr, "bonsai: --measure runs on one GPU\n"); return 2; }
-    if (((g_morph_spacing_on && !g_split_on && !g_measure_on) || g_morph_fill_on) && g_morph.empty()) { std::fprintf(stderr, "bonsai: %s needs --morph\n", g_morph_spacing_on ? "--morph-spacing" : "--morph-fill"); return 2; }
+    if (g_thick_on && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --thickness needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
+    if (g_thick_on && g_thick_radius / (float)std::min({g_morph_spacing[0], g_morph_spacing[1], g_morph_spacing[2]}) > (float)VK_THICK_MAX_REACH) {
+        std::fprintf(stderr, "bonsai: --thickness MAX_RADIUS [GAIN]: MAX_RADIUS reaches further than 32 voxels of the smallest spacing\n"); return 2;
+    }
+    if (g_thick_on && gpus > 0) { std::fprintf(stderr, "bonsai: --thickness runs on one GPU\n"); return 2; }
+    if (((g_morph_spacing_on && !g_split_on && !g_measure_on && !g_thick_on) || g_morph_fill_on) && g_morph.empty()) { std::fprintf(stderr, "bonsai: %s needs --morph\n", g_morph_spacing_on ? "--morph-spacing" : "--morph-fill"); return 2; }
     if (!g_morph.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --morph runs on one GPU\n"); return 2; }
-    if ((label_ops() || !g_morph.empty() || g_split_on || g_measure_on) && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
+    if ((label_ops() || !g_morph.empty() || g_split_on || g_measure_on || g_thick_on) && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
     g_w = w; g_h = h;
     if (!g_resample.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --crop, --resample, --downsample, --isotropic, --to-u8 and --to-u16 run on one GPU\n"); return 2; }
     for (const ResampleOp &op : g_resample)
         if (op.kind == ResampleOp::CROP_CLIP && !g_clip_on) { std::fprintf(stderr, "bonsai: --crop clip needs --clip\n"); return 2; }
-    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && g_resample.empty() && !g_split_on) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
+    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && g_resample.empty() && !g_split_on && !g_thick_on) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
     if ((g_median || g_smooth) && gpus > 0) { std::fprintf(stderr, "bonsai: --median and --smooth run on one GPU\n"); return 2; }
     if (hist) return run_histogram(hist_bins, hist_lo, hist_hi);
     if (!mesh_path.empty()) return run_mesh(mesh_path, mesh_obj, mesh_iso_on ? mesh_iso : g_iso.iso, mesh_scale);

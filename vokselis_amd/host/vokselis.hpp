@@ -709,6 +709,22 @@ class Context {
         m.table.resize((size_t)m.totals.records_written);
         return m;
     }
+    // Local thickness (vk_local_thickness; blocks): for every voxel of S = the voxels in [lo, hi], the squared radius T2 of the largest ball
+    // that fits inside S and holds the voxel, over the integer pitch spacing (nullptr: 1 1 1), capped at max_radius^2.  The dense map stores
+    // sqrtf(T2) * gain on S (gain 0: automatic, the thickest place stores full scale) and fill_out elsewhere.  install: it replaces the
+    // context's volume (outside frame_begin / frame_end); dense_out: nullptr, or host memory of nx ny nz elements of the volume's format;
+    // t2_out: nullptr, or nx ny nz uint32.  The thickness a user reads is 2 sqrt(T2): thickness_of.
+    vk_thickness_result local_thickness(float lo, float hi = INFINITY, float max_radius = 16.0f, const uint32_t *spacing = nullptr, const vk_voxel_box *box = nullptr, bool clip = false,
+                                        float gain = 0.0f, float fill_out = 0.0f, bool install = false, void *dense_out = nullptr, uint32_t *t2_out = nullptr) {
+        vk_thickness_request req{};
+        req.lo = lo; req.hi = hi; req.max_radius = max_radius; req.gain = gain; req.fill_out = fill_out;
+        req.flags = (clip ? (uint32_t)VK_THICK_CLIP_BOX : 0u) | (install ? (uint32_t)VK_THICK_INSTALL : 0u);
+        for (int c = 0; c < 3; c++) req.spacing[c] = spacing ? spacing[c] : 1u;
+        vk_thickness_result res{};
+        check(ctx_, vk_local_thickness(ctx_, &req, box, t2_out, dense_out, &res));
+        return res;
+    }
+    static double thickness_of(uint32_t t2) { return 2.0 * std::sqrt((double)t2); }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
     void frames_in_flight(uint32_t k) { check(ctx_, vk_ctx_frames_in_flight(ctx_, k)); }
