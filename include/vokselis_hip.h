@@ -898,6 +898,74 @@ _Static_assert(sizeof(vk_thickness_request) == 36 && sizeof(vk_thickness_result)
 int vk_local_thickness(vk_ctx *ctx, const vk_thickness_request *req, const vk_voxel_box *box, uint32_t *t2_out, void *dense_out,
                        vk_thickness_result *result);
 
+/* Geodesic distance through a value range: for every voxel of the set S, the length of the shortest path that
+ * stays inside S, from a face of the box or from picked voxels -- percolation, tortuosity, the reachable fraction.  Every result is
+ * an integer but the dense value, whose two roundings are written out below.
+ * The set.  S, t, lo_k, hi_k and the integer `spacing` are exactly vk_distance_transform's.  The box B is `box`, the clip box under
+ * VK_GEO_CLIP_BOX, or the whole volume (NULL).  A voxel is in S iff it lies in B and t >= lo_k && t <= hi_k.  B restricts S; the
+ * outputs cover the whole volume.
+ * Adjacency.  connectivity is 6, 18 or 26, exactly as in vk_label_components: no wrap, no clamping.
+ * Step cost.  For an adjacent pair with index difference d: q(d) = sum_c (spacing[c] * d_c)^2, 1 <= q <= 12288, and w(d) is the
+ * largest integer r with r * r <= q * 65536 -- the floor of 256 sqrt(q), computed in integers.  At spacing (1,1,1) the costs are 256,
+ * 362 and 443, at (64,64,64) 16384, 23170 and 28377, at (1,2,3) {256, 512, 572, 768, 809, 923, 957}.  One unit (VK_GEO_UNIT) is 1/256
+ * of a spacing unit.
+ * Sources.  source_faces is a mask of six bits: 1 x-, 2 x+, 4 y-, 8 y+, 16 z-, 32 z+.  A voxel of S lies on a face when its
+ * coordinate equals B's first or last index on that axis.  seeds[0 .. n_seeds) are voxel indices inside the volume.  The source set
+ * is A = S n (faces u seeds); a seed off S contributes nothing, as in VK_LABEL_KEEP_SEEDS.
+ * Distance.  g(v) = 0 on A.  For other v in S, g(v) = min(L(v), VK_GEO_FAR), L(v) the least sum of step costs over paths
+ * v0 in A, ..., vk = v whose every voxel lies in S and whose consecutive voxels are adjacent.  g(v) = VK_GEO_INF where there is no
+ * such path, and off S.  Every relaxation is the saturating min(a + w, VK_GEO_FAR) of a finite a: saturation is monotone and
+ * commutes with min, so g is the unique fixed point and depends on no order, launch shape or layout.
+ * Targets.  target_faces is a second face mask and may be 0.  target_min is the least g over the voxels of S on those faces,
+ * VK_GEO_INF when no such voxel is reached or the mask is 0; n_target_reached counts the reached voxels among them.
+ * Outputs.  g_out (may be NULL): nx ny nz uint32, x fastest.  The dense value of a reached voxel of S is (float)g(v) * gain: the
+ * conversion rounds once to nearest even, the product rounds once, nothing is fused; an unreached voxel of S stores fill_unreached,
+ * a voxel off S fill_out; all three go through vk_label_components' fill rule F.  gain == 0 asks for 1.0f / (float)max_g, or 0 when
+ * max_g == 0.  dense_out (may be NULL; host memory of nx ny nz elements of the volume's format) and VK_GEO_INSTALL behave exactly as
+ * vk_local_thickness' dense_out and VK_THICK_INSTALL: the same re-layout, the table, projection, isosurface, lighting and clip box
+ * stay in force, the old volume stays on any failure.  Without VK_GEO_INSTALL no context state changes.  The call blocks, runs on
+ * the context's current stream and allocates and frees its own buffers.
+ * result (may be NULL).  n_foreground = |S|; n_sources = |A|; n_reached = the voxels of S with finite g, sources included;
+ * n_saturated = those with g == VK_GEO_FAR; n_target_reached; sum_g = the sum of g over the reached voxels (below 2^64: fewer than
+ * 2^32 voxels of less than 2^32 each); max_g = the largest finite g, 0 if none; target_min; gain = the gain used.  No field depends
+ * on how many rounds the implementation took.
+ * VK_ERR_INVALID, decided before any launch, outputs untouched ("vk_geodesic_distance: ..."), in this order: a NULL request; lo or
+ * hi NaN; lo > hi; a connectivity other than 6, 18, 26; an unknown flag; pad != 0; a spacing of 0 or above VK_DIST_MAX_SPACING; a
+ * face mask with a bit above 32; n_seeds > VK_GEO_MAX_SEEDS; source_faces == 0 && n_seeds == 0; a gain that is negative or not
+ * finite; a fill_out or fill_unreached that is not finite; none of g_out, dense_out, VK_GEO_INSTALL and result requested; then
+ * VK_GEO_INSTALL while a frame is being recorded; no volume; a seed outside the volume; a box that is inverted or leaves the volume,
+ * a box together with VK_GEO_CLIP_BOX.  VK_ERR_UNSUPPORTED ("geodesic: ..."): a BRICKED / QUADS / STAGED or RGBA16F_PAIR volume; a
+ * volume of more than 2^32 - 2 voxels.  VK_ERR_OOM: a buffer cannot be allocated.  A call that fails later may have written its
+ * outputs already; the context's volume is the old one whenever the call does not return VK_OK. */
+#define VK_GEO_INF 0xFFFFFFFFu
+#define VK_GEO_FAR 0xFFFFFFFEu
+#define VK_GEO_UNIT 256u
+#define VK_GEO_MAX_SEEDS 16
+enum { VK_GEO_CLIP_BOX = 1, VK_GEO_INSTALL = 2 };
+enum { VK_GEO_FACE_X0 = 1, VK_GEO_FACE_X1 = 2, VK_GEO_FACE_Y0 = 4, VK_GEO_FACE_Y1 = 8, VK_GEO_FACE_Z0 = 16, VK_GEO_FACE_Z1 = 32 };
+typedef struct vk_geodesic_request {
+    float    lo, hi;                               /* the value range, formed exactly as vk_label_components forms lo_k, hi_k */
+    uint32_t connectivity, flags;                  /* 6, 18 or 26; VK_GEO_CLIP_BOX | VK_GEO_INSTALL */
+    uint32_t spacing[3];                           /* integer voxel pitch per axis x, y, z: 1 .. VK_DIST_MAX_SPACING */
+    uint32_t source_faces, target_faces, n_seeds;  /* VK_GEO_FACE_* masks; the seeds in use */
+    float    gain, fill_out, fill_unreached;       /* the dense value is (float)g * gain (0: 1 / max_g); the sample values off S and of an unreached voxel of S */
+    uint32_t pad;                                  /* 0 */
+    uint32_t seeds[VK_GEO_MAX_SEEDS][3];           /* voxel indices x, y, z */
+} vk_geodesic_request;                             /* 248 bytes */
+typedef struct vk_geodesic_result {
+    uint64_t n_foreground, n_sources, n_reached, n_saturated, n_target_reached, sum_g;
+    uint32_t max_g, target_min;
+    float    gain;
+    uint32_t pad;
+} vk_geodesic_result;                              /* 64 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(vk_geodesic_request) == 248 && sizeof(vk_geodesic_result) == 64, "vk_geodesic_request: 248 bytes, vk_geodesic_result: 64 bytes");
+#else
+_Static_assert(sizeof(vk_geodesic_request) == 248 && sizeof(vk_geodesic_result) == 64, "vk_geodesic_request: 248 bytes, vk_geodesic_result: 64 bytes");
+#endif
+int vk_geodesic_distance(vk_ctx *ctx, const vk_geodesic_request *req, const vk_voxel_box *box, uint32_t *g_out, void *dense_out,
+                         vk_geodesic_result *result);
+
 /* The resample pass: a voxel box of the volume the context holds into a volume of caller-chosen dimensions, by
  * one of three rules, optionally mapped into another scalar format -- crop, resize, make isotropic, window 16-bit data into u8 --
  * without a trip through the host.  Every f32 operation below is rounded once; fmaf is fused where written and nowhere else.

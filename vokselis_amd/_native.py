@@ -260,6 +260,29 @@ class VkThicknessResult(C.Structure):
 assert C.sizeof(VkThicknessRequest) == 36 and C.sizeof(VkThicknessResult) == 32
 
 
+GEO_INF, GEO_FAR, GEO_UNIT, GEO_MAX_SEEDS = 0xFFFFFFFF, 0xFFFFFFFE, 256, 16
+GEO_CLIP_BOX, GEO_INSTALL = 1, 2
+GEO_FACE_X0, GEO_FACE_X1, GEO_FACE_Y0, GEO_FACE_Y1, GEO_FACE_Z0, GEO_FACE_Z1 = 1, 2, 4, 8, 16, 32
+
+
+class VkGeodesicRequest(C.Structure):
+    """vk_geodesic_request (248 bytes): the request of vk_geodesic_distance -- the value range, the connectivity, the flags, the integer
+    spacing per axis (x, y, z), the source and target face masks, the seeds in use, the gain of the dense value (0: automatic), the fills
+    of a voxel outside the set and of an unreached voxel of it, and the seeds as voxel indices (x, y, z)."""
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("connectivity", C.c_uint32), ("flags", C.c_uint32), ("spacing", C.c_uint32 * 3), ("source_faces", C.c_uint32),
+                ("target_faces", C.c_uint32), ("n_seeds", C.c_uint32), ("gain", C.c_float), ("fill_out", C.c_float), ("fill_unreached", C.c_float), ("pad", C.c_uint32),
+                ("seeds", (C.c_uint32 * 3) * GEO_MAX_SEEDS)]
+
+
+class VkGeodesicResult(C.Structure):
+    """vk_geodesic_result (64 bytes): the totals of vk_geodesic_distance and the gain it used."""
+    _fields_ = [("n_foreground", C.c_uint64), ("n_sources", C.c_uint64), ("n_reached", C.c_uint64), ("n_saturated", C.c_uint64), ("n_target_reached", C.c_uint64),
+                ("sum_g", C.c_uint64), ("max_g", C.c_uint32), ("target_min", C.c_uint32), ("gain", C.c_float), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(VkGeodesicRequest) == 248 and C.sizeof(VkGeodesicResult) == 64
+
+
 RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_AREA = 0, 1, 2
 RESAMPLE_INSTALL, RESAMPLE_CLIP_BOX, RESAMPLE_WINDOW = 1, 2, 4
 RESAMPLE_KEEP_FORMAT = -1
@@ -343,6 +366,7 @@ SYMBOLS = {
     "vk_split_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp]),  # const vk_split_request *, const vk_voxel_box *, labels_out, vk_component *, cap, dense_out, vk_split_result *
     "vk_measure_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),  # const vk_measure_request *, const vk_voxel_box *, labels_in (NULL: label the range), vk_region *, cap, vk_measure_result *
     "vk_local_thickness": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_thickness_request *, const vk_voxel_box *, t2_out, dense_out, vk_thickness_result *
+    "vk_geodesic_distance": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_geodesic_request *, const vk_voxel_box *, g_out, dense_out, vk_geodesic_result *
     "vk_volume_resample": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, dense_out, vk_resample_result *
     "vk_resample_output": (C.c_int, [_vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, vk_resample_result *: the output's extents, format, layout and box, nothing launched
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),

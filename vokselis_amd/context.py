@@ -772,6 +772,38 @@ class Context:
                                                     dense.ctypes.data if dense is not None else None, C.byref(res)))
         return Thickness(res, arr, dense)
 
+    # -- geodesic distance through a value range: sources, targets, tortuosity (vk_geodesic_distance)
+    def geodesic_distance(self, lo, hi=float("inf"), sources=("x-",), seeds=(), targets=(), connectivity: int = 26, spacing=(1, 1, 1), gain: float = 0.0, fill_out: float = 0.0,
+                          fill_unreached: float = 0.0, box=None, install: bool = True, out: bool = False, g: bool = False):
+        """vk_geodesic_distance: for every voxel of the set S of voxels whose stored texel lies in [lo, hi] (inside box: None, "clip" or
+        ((x0, y0, z0), (x1, y1, z1))), the length of the shortest path inside S from the source set -- the voxels of S on the box's faces
+        `sources` ("x-", "x+", "y-", "y+", "z-", "z+") and the `seeds` (x, y, z) that lie in S -- in units of 1/256 of the integer voxel
+        pitch `spacing`, over steps to the 6, 18 or 26 neighbours.  targets: the faces whose nearest reached voxel gives target_min.  The
+        dense map stores g * gain on a reached voxel (gain 0: automatic, the farthest stores full scale), fill_unreached on the rest of S
+        and fill_out elsewhere; install: it replaces the context's volume (outside frame_begin / frame_end), so that the table march
+        colours the set by its distance from the inlet.  Returns a Geodesic: the totals, n_unreached, reached_fraction, percolates,
+        max_distance, mean_distance, target_distance, tortuosity(axis), with g=True .g (uint32 [nz, ny, nx]) and .distance, with out=True
+        .dense [nz, ny, nx].  Blocks."""
+        from .geodesic import Geodesic, geodesic_request
+        from .label import voxel_box
+
+        req = geodesic_request(lo, hi, sources=sources, seeds=seeds, targets=targets, connectivity=connectivity, spacing=spacing, gain=gain, fill_out=fill_out,
+                               fill_unreached=fill_unreached, box=box, install=install)
+        vb = voxel_box(box)
+        dims, _ = self._volume_dtype()
+        extent = dims
+        if vb is not None:
+            extent = (vb.x1 - vb.x0, vb.y1 - vb.y0, vb.z1 - vb.z0)
+        elif box == "clip" and self.clip_box is not None:  # the voxels whose centre lies in the clip box, as the library counts them
+            cl, ch = self.clip_box
+            extent = tuple(sum(1 for i in range(n) if float(np.float32(l)) <= (i + 0.5) / n <= float(np.float32(h))) for l, h, n in zip(cl, ch, dims))
+        arr = np.zeros((dims[2], dims[1], dims[0]), np.uint32) if g else None
+        dense = self._dense_out() if out else None
+        res = N.VkGeodesicResult()
+        N.check(self._h, N.lib().vk_geodesic_distance(self._h, C.byref(req), C.byref(vb) if vb is not None else None, arr.ctypes.data if arr is not None else None,
+                                                      dense.ctypes.data if dense is not None else None, C.byref(res)))
+        return Geodesic(res, spacing, extent, arr, dense)
+
     def set_root_skip(self, k: int):
         """vk_partition_root_skip: rank 0 sits out every k-th round of the tile deal (0: never)."""
         N.check(self._h, N.lib().vk_partition_root_skip(self._h, int(k)))

@@ -725,6 +725,28 @@ class Context {
         return res;
     }
     static double thickness_of(uint32_t t2) { return 2.0 * std::sqrt((double)t2); }
+    // Geodesic distance (vk_geodesic_distance; blocks): for every voxel of S = the voxels in [lo, hi], the length g of the shortest path inside S
+    // from the source set -- the voxels of S on the faces of source_faces (VK_GEO_FACE_*) and the seeds that lie in S -- in units of 1 / VK_GEO_UNIT
+    // of the integer pitch spacing (nullptr: 1 1 1), over steps to the 6, 18 or 26 neighbours.  target_faces: the faces whose nearest reached voxel
+    // gives target_min (VK_GEO_INF: S does not percolate).  The dense map stores (float)g * gain on a reached voxel (gain 0: automatic, the farthest
+    // stores full scale), fill_unreached on the rest of S and fill_out elsewhere.  install: it replaces the context's volume (outside frame_begin /
+    // frame_end); dense_out: nullptr, or host memory of nx ny nz elements of the volume's format; g_out: nullptr, or nx ny nz uint32.
+    vk_geodesic_result geodesic_distance(float lo, float hi = INFINITY, uint32_t source_faces = VK_GEO_FACE_X0, uint32_t target_faces = 0u, const std::vector<std::array<uint32_t, 3>> &seeds = {},
+                                         uint32_t connectivity = 26u, const uint32_t *spacing = nullptr, const vk_voxel_box *box = nullptr, bool clip = false, float gain = 0.0f,
+                                         float fill_out = 0.0f, float fill_unreached = 0.0f, bool install = true, void *dense_out = nullptr, uint32_t *g_out = nullptr) {
+        if (seeds.size() > (size_t)VK_GEO_MAX_SEEDS) throw std::runtime_error("geodesic_distance: at most VK_GEO_MAX_SEEDS seeds");
+        vk_geodesic_request req{};
+        req.lo = lo; req.hi = hi; req.connectivity = connectivity; req.gain = gain; req.fill_out = fill_out; req.fill_unreached = fill_unreached;
+        req.flags = (clip ? (uint32_t)VK_GEO_CLIP_BOX : 0u) | (install ? (uint32_t)VK_GEO_INSTALL : 0u);
+        for (int c = 0; c < 3; c++) req.spacing[c] = spacing ? spacing[c] : 1u;
+        req.source_faces = source_faces; req.target_faces = target_faces; req.n_seeds = (uint32_t)seeds.size();
+        for (size_t s = 0; s < seeds.size(); s++)
+            for (int c = 0; c < 3; c++) req.seeds[s][c] = seeds[s][c];
+        vk_geodesic_result res{};
+        check(ctx_, vk_geodesic_distance(ctx_, &req, box, g_out, dense_out, &res));
+        return res;
+    }
+    static double geodesic_units(uint32_t g) { return (double)g / (double)VK_GEO_UNIT; }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
     void frames_in_flight(uint32_t k) { check(ctx_, vk_ctx_frames_in_flight(ctx_, k)); }
