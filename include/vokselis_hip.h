@@ -966,6 +966,71 @@ _Static_assert(sizeof(vk_geodesic_request) == 248 && sizeof(vk_geodesic_result) 
 int vk_geodesic_distance(vk_ctx *ctx, const vk_geodesic_request *req, const vk_voxel_box *box, uint32_t *g_out, void *dense_out,
                          vk_geodesic_result *result);
 
+/* Skeleton of a value range: the set S thinned to a one-voxel-wide set K with the same pieces, tunnels and
+ * cavities -- centre lines, from which follow free ends, branch points and centre-line length.  Every result is an integer.
+ * The set.  S, t, lo_k, hi_k and the box B (`box`, the clip box under VK_SKEL_CLIP_BOX, or the whole volume) are exactly
+ * vk_geodesic_distance's.  Everything not in S is background: voxels outside B, voxels outside the volume.  No wrap, no clamp.
+ * Connectivity.  The set is 26-connected and the background 6-connected.  There is no other pairing.
+ * Neighbourhood mask.  For a voxel v of the current set K, m(v) has bit k set iff the neighbour at offset o(k) is in K, with the
+ * offsets numbered as vk_label_components numbers them, d = (o % 3 - 1, o / 3 % 3 - 1, o / 9 - 1), the centre (o = 13) skipped:
+ * o(k) = k for k < 13 and k + 1 for k >= 13 -- 26 bits.
+ * Simple point (Malandain and Bertrand).  skel_simple(m) is true iff both hold: (a) the set bits of m, joined by 26-adjacency among
+ * the 26 positions, form exactly one component (zero components: not simple); (b) the clear bits among the 18 positions with
+ * |d|_1 <= 2, joined by 6-adjacency among those 18 positions, have exactly one component that contains one of the 6 face positions.
+ * Line end.  popcount(m) == 1.
+ * Subfields.  sf(v) = (x & 1) | (y & 1) << 1 | (z & 1) << 2 on absolute voxel indices, not box-relative.  Two voxels of one subfield
+ * are never 26-adjacent.
+ * Iteration i = 1, 2, ...  Let K_i be the set at the iteration's start, K_1 = S.  The candidates C_i are the voxels of K_i with at
+ * least one of the 6 face neighbours not in K_i; volume faces and B's faces therefore peel.  Then come eight sub-passes s = 0 .. 7 in
+ * that order.  Sub-pass s looks at every voxel v with sf(v) == s, v in C_i, v still in K; in VK_SKEL_CURVE mode it also requires
+ * that m(v) on the current K is not a line end; it deletes all such v with skel_simple(m(v)) at once.  The pass ends after the first
+ * iteration that deletes nothing, or after max_iterations iterations if that is not 0.
+ * Modes.  VK_SKEL_CURVE keeps line ends and gives centre lines.  VK_SKEL_KERNEL has no end condition and gives the ultimate homotopic
+ * kernel: a blob becomes a voxel, a ring a closed curve, and a shell stays a closed surface.
+ * Why the result depends on no launch shape, order or layout.  Within a sub-pass no deleted voxel lies in another deleted voxel's
+ * N26: the simultaneous deletion equals a sequential one in any order, and each deletion is of a simple point.
+ * Outputs.  class_out (may be NULL): nx ny nz bytes, x fastest: 0 off K, 1 isolated (0 neighbours in K), 2 end (1), 3 regular (2),
+ * 4 junction (>= 3).  Dense value: a voxel of K keeps its stored bits (a PACKED_PAIRS voxel the u8 value tap + delta, as in
+ * vk_morph_volume), or stores F(fill_in) under VK_SKEL_FILL_IN; every other voxel stores F(fill_out); F is vk_label_components' fill
+ * rule.  dense_out (may be NULL) and VK_SKEL_INSTALL behave exactly as vk_geodesic_distance's dense_out and VK_GEO_INSTALL.  Without
+ * VK_SKEL_INSTALL no context state changes.  The call blocks, runs on the context's current stream and allocates and frees its own
+ * buffers.
+ * result (may be NULL).  n_foreground = |S|; n_skeleton = |K|; n_isolated, n_end, n_regular, n_junction = the voxels of K per class;
+ * links[j], j = 0 .. 12: the unordered 26-adjacent pairs of K whose offset is o = 14 + j (the offsets above the centre), so that the
+ * hosts derive the length sum_j links[j] sqrt(q_j), q_j = sum_c (spacing[c] d_c)^2, for any spacing -- it counts every adjacent pair,
+ * so it over-counts inside junction clumps, where voxels are adjacent to more than two others; iterations = the iterations that
+ * deleted something; converged = 1 iff an iteration that deleted nothing ran (0: max_iterations stopped the pass first).
+ * VK_ERR_INVALID, decided before any launch, outputs untouched ("vk_skeletonize: ..."), in this order: a NULL request; lo or hi NaN;
+ * lo > hi; an unknown mode; an unknown flag; pad != 0; a fill_out that is not finite, or a fill_in that is not finite under
+ * VK_SKEL_FILL_IN; none of class_out, dense_out, VK_SKEL_INSTALL and result requested; then VK_SKEL_INSTALL while a frame is being
+ * recorded; no volume; a box that is inverted or leaves the volume, a box together with VK_SKEL_CLIP_BOX.  VK_ERR_UNSUPPORTED
+ * ("skeleton: ..."): a BRICKED / QUADS / STAGED or RGBA16F_PAIR volume; a volume of more than 2^32 - 2 voxels.  VK_ERR_OOM: a buffer
+ * cannot be allocated.  A call that fails later may have written its outputs already; the context's volume is the old one whenever
+ * the call does not return VK_OK. */
+enum { VK_SKEL_CURVE = 0, VK_SKEL_KERNEL = 1 };
+enum { VK_SKEL_CLIP_BOX = 1, VK_SKEL_INSTALL = 2, VK_SKEL_FILL_IN = 4 };
+enum { VK_SKEL_OFF = 0, VK_SKEL_ISOLATED = 1, VK_SKEL_END = 2, VK_SKEL_REGULAR = 3, VK_SKEL_JUNCTION = 4 };
+#define VK_SKEL_LINKS 13
+typedef struct vk_skeleton_request {
+    float    lo, hi;                       /* the value range, formed exactly as vk_label_components forms lo_k, hi_k */
+    uint32_t mode, flags;                  /* VK_SKEL_CURVE or VK_SKEL_KERNEL; VK_SKEL_CLIP_BOX | VK_SKEL_INSTALL | VK_SKEL_FILL_IN */
+    uint32_t max_iterations;               /* 0: until an iteration deletes nothing */
+    float    fill_in, fill_out;            /* the sample values of a voxel of K under VK_SKEL_FILL_IN, and of every other voxel */
+    uint32_t pad;                          /* 0 */
+} vk_skeleton_request;                     /* 32 bytes */
+typedef struct vk_skeleton_result {
+    uint64_t n_foreground, n_skeleton, n_isolated, n_end, n_regular, n_junction;
+    uint64_t links[VK_SKEL_LINKS];
+    uint32_t iterations, converged;
+} vk_skeleton_result;                      /* 160 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(vk_skeleton_request) == 32 && sizeof(vk_skeleton_result) == 160, "vk_skeleton_request: 32 bytes, vk_skeleton_result: 160 bytes");
+#else
+_Static_assert(sizeof(vk_skeleton_request) == 32 && sizeof(vk_skeleton_result) == 160, "vk_skeleton_request: 32 bytes, vk_skeleton_result: 160 bytes");
+#endif
+int vk_skeletonize(vk_ctx *ctx, const vk_skeleton_request *req, const vk_voxel_box *box, uint8_t *class_out, void *dense_out,
+                   vk_skeleton_result *result);
+
 /* The resample pass: a voxel box of the volume the context holds into a volume of caller-chosen dimensions, by
  * one of three rules, optionally mapped into another scalar format -- crop, resize, make isotropic, window 16-bit data into u8 --
  * without a trip through the host.  Every f32 operation below is rounded once; fmaf is fused where written and nowhere else.

@@ -16,6 +16,7 @@ Only the raycast hot path and the host surface that drives it live here (SURVEY.
   measure    Measurements, measure_request: the result and the request of Context.measure_components
   thickness  Thickness, thickness_request: the result and the request of Context.local_thickness
   geodesic   Geodesic, geodesic_request, geodesic_path: the result and the request of Context.geodesic_distance, and the path back to a source
+  skeleton   Skeleton, skeleton_request: the result and the request of Context.skeletonize
   resample   resample_request: the request of Context.resample_volume / crop_volume / downsample_volume / isotropic_volume
   dist       tile-parallel multi-GPU frame (one process per GPU, RCCL gather over xGMI)
 """
@@ -36,6 +37,8 @@ from ._native import (FMT_R8_UNORM, FMT_R16_FLOAT, FMT_RGBA16F_PAIR, FMT_R16_UNO
                       THICK_MAX_REACH, THICK_CLIP_BOX, THICK_INSTALL, VkThicknessRequest, VkThicknessResult,
                       GEO_INF, GEO_FAR, GEO_UNIT, GEO_MAX_SEEDS, GEO_CLIP_BOX, GEO_INSTALL, GEO_FACE_X0, GEO_FACE_X1, GEO_FACE_Y0, GEO_FACE_Y1, GEO_FACE_Z0, GEO_FACE_Z1,
                       VkGeodesicRequest, VkGeodesicResult,
+                      SKEL_CURVE, SKEL_KERNEL, SKEL_CLIP_BOX, SKEL_INSTALL, SKEL_FILL_IN, SKEL_OFF, SKEL_ISOLATED, SKEL_END, SKEL_REGULAR, SKEL_JUNCTION, SKEL_LINKS,
+                      VkSkeletonRequest, VkSkeletonResult,
                       RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_AREA, RESAMPLE_INSTALL, RESAMPLE_CLIP_BOX, RESAMPLE_WINDOW, RESAMPLE_KEEP_FORMAT, RESAMPLE_MAX_RATIO,
                       VkResampleRequest, VkResampleResult)
 from .camera import Camera
@@ -49,6 +52,7 @@ from .split import Regions, split_request
 from .measure import Measurements, measure_request
 from .thickness import Thickness, thickness_request
 from .geodesic import Geodesic, geodesic_path, geodesic_request
+from .skeleton import Skeleton, skeleton_request
 from .resample import resample_request
 from .context import (Context, Demo, FrameCounter, HdrBackBuffer, Hit, ImageDimentions, RaycastPipeline, Uniform,
                       VolumeTexture, dispatch_optimal, partition_slots, render_batch, run_headless, transfer_table, untile_batch)
@@ -72,6 +76,8 @@ __all__ = [
     "THICK_MAX_REACH", "THICK_CLIP_BOX", "THICK_INSTALL", "VkThicknessRequest", "VkThicknessResult", "Thickness", "thickness_request",
     "GEO_INF", "GEO_FAR", "GEO_UNIT", "GEO_MAX_SEEDS", "GEO_CLIP_BOX", "GEO_INSTALL", "GEO_FACE_X0", "GEO_FACE_X1", "GEO_FACE_Y0", "GEO_FACE_Y1", "GEO_FACE_Z0", "GEO_FACE_Z1",
     "VkGeodesicRequest", "VkGeodesicResult", "Geodesic", "geodesic_request", "geodesic_path",
+    "SKEL_CURVE", "SKEL_KERNEL", "SKEL_CLIP_BOX", "SKEL_INSTALL", "SKEL_FILL_IN", "SKEL_OFF", "SKEL_ISOLATED", "SKEL_END", "SKEL_REGULAR", "SKEL_JUNCTION", "SKEL_LINKS",
+    "VkSkeletonRequest", "VkSkeletonResult", "Skeleton", "skeleton_request",
     "RESAMPLE_NEAREST", "RESAMPLE_LINEAR", "RESAMPLE_AREA", "RESAMPLE_INSTALL", "RESAMPLE_CLIP_BOX", "RESAMPLE_WINDOW", "RESAMPLE_KEEP_FORMAT", "RESAMPLE_MAX_RATIO",
     "VkResampleRequest", "VkResampleResult", "resample_request",
 ]

@@ -283,6 +283,28 @@ class VkGeodesicResult(C.Structure):
 assert C.sizeof(VkGeodesicRequest) == 248 and C.sizeof(VkGeodesicResult) == 64
 
 
+SKEL_CURVE, SKEL_KERNEL = 0, 1
+SKEL_CLIP_BOX, SKEL_INSTALL, SKEL_FILL_IN = 1, 2, 4
+SKEL_OFF, SKEL_ISOLATED, SKEL_END, SKEL_REGULAR, SKEL_JUNCTION = 0, 1, 2, 3, 4
+SKEL_LINKS = 13
+
+
+class VkSkeletonRequest(C.Structure):
+    """vk_skeleton_request (32 bytes): the request of vk_skeletonize -- the value range, the mode, the flags, the cap of the iterations
+    (0: none), the sample value of a skeleton voxel under SKEL_FILL_IN and of every other voxel."""
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("mode", C.c_uint32), ("flags", C.c_uint32), ("max_iterations", C.c_uint32), ("fill_in", C.c_float), ("fill_out", C.c_float),
+                ("pad", C.c_uint32)]
+
+
+class VkSkeletonResult(C.Structure):
+    """vk_skeleton_result (160 bytes): the totals of vk_skeletonize."""
+    _fields_ = [("n_foreground", C.c_uint64), ("n_skeleton", C.c_uint64), ("n_isolated", C.c_uint64), ("n_end", C.c_uint64), ("n_regular", C.c_uint64), ("n_junction", C.c_uint64),
+                ("links", C.c_uint64 * SKEL_LINKS), ("iterations", C.c_uint32), ("converged", C.c_uint32)]
+
+
+assert C.sizeof(VkSkeletonRequest) == 32 and C.sizeof(VkSkeletonResult) == 160
+
+
 RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_AREA = 0, 1, 2
 RESAMPLE_INSTALL, RESAMPLE_CLIP_BOX, RESAMPLE_WINDOW = 1, 2, 4
 RESAMPLE_KEEP_FORMAT = -1
@@ -367,6 +389,7 @@ SYMBOLS = {
     "vk_measure_components": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),  # const vk_measure_request *, const vk_voxel_box *, labels_in (NULL: label the range), vk_region *, cap, vk_measure_result *
     "vk_local_thickness": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_thickness_request *, const vk_voxel_box *, t2_out, dense_out, vk_thickness_result *
     "vk_geodesic_distance": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_geodesic_request *, const vk_voxel_box *, g_out, dense_out, vk_geodesic_result *
+    "vk_skeletonize": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_skeleton_request *, const vk_voxel_box *, class_out, dense_out, vk_skeleton_result *
     "vk_volume_resample": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, dense_out, vk_resample_result *
     "vk_resample_output": (C.c_int, [_vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, vk_resample_result *: the output's extents, format, layout and box, nothing launched
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),

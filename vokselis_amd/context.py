@@ -804,6 +804,30 @@ class Context:
                                                       dense.ctypes.data if dense is not None else None, C.byref(res)))
         return Geodesic(res, spacing, extent, arr, dense)
 
+    # -- skeleton of a value range: topology-preserving thinning to centre lines (vk_skeletonize)
+    def skeletonize(self, lo, hi=float("inf"), mode: str = "curve", max_iterations: int = 0, fill_in=None, fill_out: float = 0.0, box=None, install: bool = True, classes: bool = False,
+                    out: bool = False):
+        """vk_skeletonize: the set S of voxels whose stored texel lies in [lo, hi] (inside box: None, "clip" or ((x0, y0, z0), (x1, y1, z1)))
+        thinned to a one-voxel-wide skeleton with the same pieces, tunnels and cavities (the set 26-connected, the background 6-connected).
+        mode: "curve" keeps line ends and gives centre lines, "kernel" thins to the ultimate homotopic kernel; max_iterations: 0 thins
+        until nothing more can go.  The dense volume keeps the stored value on the skeleton (fill_in: a sample value stored there instead)
+        and stores fill_out elsewhere; install: it replaces the context's volume (outside frame_begin / frame_end) -- after
+        local_thickness(install=True) the skeleton carries the radius along each centre line.  Returns a Skeleton: n_foreground,
+        n_skeleton, n_isolated, n_end, n_regular, n_junction, links, length(spacing), iterations, converged, with classes=True .classes
+        (uint8 [nz, ny, nx]), with out=True .dense [nz, ny, nx].  Blocks."""
+        from .label import voxel_box
+        from .skeleton import Skeleton, skeleton_request
+
+        req = skeleton_request(lo, hi, mode=mode, max_iterations=max_iterations, fill_in=fill_in, fill_out=fill_out, box=box, install=install)
+        vb = voxel_box(box)
+        dims, _ = self._volume_dtype()
+        cls = np.zeros((dims[2], dims[1], dims[0]), np.uint8) if classes else None
+        dense = self._dense_out() if out else None
+        res = N.VkSkeletonResult()
+        N.check(self._h, N.lib().vk_skeletonize(self._h, C.byref(req), C.byref(vb) if vb is not None else None, cls.ctypes.data if cls is not None else None,
+                                                dense.ctypes.data if dense is not None else None, C.byref(res)))
+        return Skeleton(res, cls, dense)
+
     def set_root_skip(self, k: int):
         """vk_partition_root_skip: rank 0 sits out every k-th round of the tile deal (0: never)."""
         N.check(self._h, N.lib().vk_partition_root_skip(self._h, int(k)))

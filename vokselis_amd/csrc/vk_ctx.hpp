@@ -181,6 +181,8 @@ struct vk_ctx {
     uint32_t thick_timing = 0;       // ... k (measurements): the call brackets its k-th phase with the timer's events (vk_launch_thick.hip)
     uint32_t geo_max_blocks = 0;     // vk_geodesic_distance: cap of its grids (0: none) -- lets a small volume drive the grid-stride loops over tiles and voxels
     uint32_t geo_timing = 0;         // ... k (measurements): the call brackets its k-th phase with the timer's events; 9: it leaves its round counts as the last message (vk_launch_geo.hip)
+    uint32_t skel_max_blocks = 0;    // vk_skeletonize: cap of its grids (0: none) -- lets a small volume drive the grid-stride loops over tiles and voxels
+    uint32_t skel_timing = 0;        // ... k (measurements): the call brackets its k-th phase with the timer's events; 9: it leaves its iteration counts as the last message (vk_launch_skel.hip)
     uint32_t resample_max_blocks = 0;  // vk_volume_resample: cap of the grid (0: none) -- lets a small volume drive the loop over tiles
     uint32_t resample_area_passes = 0; // ... 1 (measurements, tests): AREA as three axis passes through f32 intermediates instead of the fused footprint loop
     uint32_t resample_area_unroll = 1; // ... 0 (measurements, tests): AREA by an integer ratio of 2 .. 4 runs the table-driven footprint loops, not the unrolled ones

@@ -90,6 +90,13 @@
 //                                                            after --thickness, as the last step that replaces the volume; prints foreground, sources, reached,
 //                                                            unreached, largest and mean distance, and with TARGET_FACE "percolates yes|no", the target distance and
 //                                                            the tortuosity along that face's axis; --save-raw writes the distance map
+//          [--skeleton [curve|kernel] [MAX_ITER]]           skeleton of that range (vk_skeletonize): the range thinned to a one-voxel-wide set with the same pieces, tunnels
+//                                                            and cavities; curve (the default) keeps line ends and gives centre lines, kernel thins to the ultimate
+//                                                            homotopic kernel; MAX_ITER stops after that many iterations (default 0: until nothing more can go).  The
+//                                                            skeleton keeps its stored values -- after --thickness the radius along each centre line --, every other
+//                                                            voxel takes the sample value of --label-fill (default 0).  Runs after --geodesic, as the last step that
+//                                                            replaces the volume; prints foreground, skeleton voxels, ends, junctions, isolated voxels and the length in
+//                                                            the units of --morph-spacing; --save-raw writes the skeleton
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -167,6 +174,8 @@ static bool g_geo_face_on = false, g_label_conn_on = false;                     
 static uint32_t g_geo_sources = 0, g_geo_targets = 0;
 static int g_geo_axis = 0;                                                       // the target face's axis
 static std::vector<std::array<uint32_t, 3>> g_geo_seeds;
+static bool g_skel_on = false;                                                   // --skeleton [curve|kernel] [MAX_ITER] (vk_skeletonize), on the same range
+static uint32_t g_skel_mode = VK_SKEL_CURVE, g_skel_max_iter = 0;
 static bool label_ops() { return !g_keep_largest.empty() || !g_drop_islands.empty() || !g_keep_voxels.empty() || !g_remove_voxels.empty() || !g_keep_picks.empty(); }
 
 // the context of a run that replaces the render: 8 x 8, or the frame's size under the render's camera when --keep-pick casts rays through it
@@ -186,7 +195,7 @@ static void apply_morph(Context &ctx) {
     int fmt = 0;
     check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !label_ops() && !g_split_on && !g_thick_on && !g_geo_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !label_ops() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     const float fill_in = g_morph_fill_on ? g_morph_fill[0] : (std::isfinite(g_label_hi) ? g_label_hi : (std::isfinite(g_label_lo) ? std::max(g_label_lo, 1.0f) : 1.0f));
     for (size_t k = 0; k < g_morph.size(); k++) {
         const MorphOp &op = g_morph[k];
@@ -205,7 +214,7 @@ static void apply_split(Context &ctx) {
     int fmt = 0;
     check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !label_ops() && !g_thick_on && !g_geo_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !label_ops() && !g_thick_on && !g_geo_on && !g_skel_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     const Regions r = ctx.split_components(g_label_lo, g_label_hi, g_split_radius, g_morph_spacing, g_split_conn, nullptr, false, false, g_label_fill, true, dense.empty() ? nullptr : dense.data());
     std::printf("split: [%g, %g] radius %g connectivity %u: %llu regions (%llu markers of %llu voxels, %llu unreached regions of %llu voxels), %llu foreground voxels, %llu cut, %u rounds\n",
                 g_label_lo, g_label_hi, g_split_radius, g_split_conn, (unsigned long long)r.totals.n_regions, (unsigned long long)r.totals.n_markers, (unsigned long long)r.totals.n_marker_voxels,
@@ -261,7 +270,7 @@ static void apply_labels(Context &ctx) {
     for (uint64_t n : g_drop_islands) ops.push_back({"drop-islands", VK_LABEL_KEEP_MIN_SIZE, n, &none, false});
     for (uint64_t k : g_keep_largest) ops.push_back({"keep-largest", VK_LABEL_KEEP_LARGEST, k, &none, false});
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !g_thick_on && !g_geo_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !g_thick_on && !g_geo_on && !g_skel_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     for (size_t k = 0; k < ops.size(); k++) {
         const Op &op = ops[k];
         const vk_label_result r = ctx.keep_components(g_label_lo, g_label_hi, op.keep, op.count, *op.seeds, op.invert, g_label_fill, g_label_conn, nullptr, false, true,
@@ -298,7 +307,7 @@ static void apply_thickness(Context &ctx) {
     int fmt = 0;
     check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !g_geo_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !g_geo_on && !g_skel_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     const vk_thickness_result r = ctx.local_thickness(g_label_lo, g_label_hi, g_thick_radius, g_morph_spacing, nullptr, false, g_thick_gain, g_label_fill, true, dense.empty() ? nullptr : dense.data());
     std::printf("thickness: [%g, %g] cap %g spacing %u %u %u: %llu foreground voxels, largest thickness %.6g, %llu saturated voxels, gain %.9g\n", g_label_lo, g_label_hi, g_thick_radius,
                 g_morph_spacing[0], g_morph_spacing[1], g_morph_spacing[2], (unsigned long long)r.n_foreground, Context::thickness_of(r.max_t2), (unsigned long long)r.n_saturated, r.gain);
@@ -312,7 +321,7 @@ static void apply_geodesic(Context &ctx) {
     int fmt = 0;
     check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty()) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !g_skel_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     const uint32_t conn = g_label_conn_on ? g_label_conn : 26u;
     const vk_geodesic_result r = ctx.geodesic_distance(g_label_lo, g_label_hi, g_geo_sources, g_geo_targets, g_geo_seeds, conn, g_morph_spacing, nullptr, false, 0.0f, g_label_fill, g_label_fill, true,
                                                        dense.empty() ? nullptr : dense.data());
@@ -331,12 +340,28 @@ static void apply_geodesic(Context &ctx) {
     if (!dense.empty()) write_dense(dense, "geodesic");
 }
 
+// --skeleton, after --geodesic: the last step that replaces the volume; it takes over --save-raw's file
+static void apply_skeleton(Context &ctx) {
+    if (!g_skel_on) return;
+    uint32_t dims[3] = {0, 0, 0};
+    int fmt = 0;
+    check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
+    std::vector<unsigned char> dense;
+    if (!g_save_raw.empty()) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    const vk_skeleton_result r = ctx.skeletonize(g_label_lo, g_label_hi, g_skel_mode, g_skel_max_iter, nullptr, false, nullptr, g_label_fill, true, dense.empty() ? nullptr : dense.data());
+    std::printf("skeleton: [%g, %g] %s spacing %u %u %u: %llu foreground voxels, %llu skeleton voxels, %llu ends, %llu junctions, %llu isolated voxels, length %.6g, %u iterations%s\n", g_label_lo,
+                g_label_hi, g_skel_mode == VK_SKEL_KERNEL ? "kernel" : "curve", g_morph_spacing[0], g_morph_spacing[1], g_morph_spacing[2], (unsigned long long)r.n_foreground,
+                (unsigned long long)r.n_skeleton, (unsigned long long)r.n_end, (unsigned long long)r.n_junction, (unsigned long long)r.n_isolated, Context::skeleton_length(r, g_morph_spacing),
+                r.iterations, r.converged ? "" : " (stopped by MAX_ITER)");
+    if (!dense.empty()) write_dense(dense, "skeleton");
+}
+
 // --crop, --resample, --downsample, --isotropic, --to-u8, --to-u16 in the order given, right after the volume is loaded; the last of them fills --save-raw's
 // file unless a filter, a --morph or a keep flag follows
 static void apply_resample(Context &ctx) {
     if (g_resample.empty()) return;
     static const char *const fmt_name[] = {"R8_UNORM", "R16_FLOAT", "RGBA16F_PAIR", "R16_UNORM"};
-    const bool save = !g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && !g_split_on && !g_thick_on && !g_geo_on;
+    const bool save = !g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on;
     std::vector<unsigned char> dense;
     for (size_t k = 0; k < g_resample.size(); k++) {
         const ResampleOp &op = g_resample[k];
@@ -362,9 +387,9 @@ static void apply_resample(Context &ctx) {
 // --median, then --smooth, once the volume is there and before anything reads it; the last of them also fills --save-raw's file (unless a keep flag follows)
 static void apply_filters(Context &ctx) {
     apply_resample(ctx);
-    if (!g_median && !g_smooth) { apply_labels(ctx); apply_measure(ctx); apply_thickness(ctx); apply_geodesic(ctx); return; }
+    if (!g_median && !g_smooth) { apply_labels(ctx); apply_measure(ctx); apply_thickness(ctx); apply_geodesic(ctx); apply_skeleton(ctx); return; }
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !label_ops() && g_morph.empty() && !g_split_on && !g_thick_on && !g_geo_on) {
+    if (!g_save_raw.empty() && !label_ops() && g_morph.empty() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on) {
         uint32_t dims[3] = {0, 0, 0};
         int fmt = 0;
         check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
@@ -378,6 +403,7 @@ static void apply_filters(Context &ctx) {
     apply_measure(ctx);
     apply_thickness(ctx);
     apply_geodesic(ctx);
+    apply_skeleton(ctx);
 }
 
 // --tf PATH: the whole file as little-endian f32 RGBA rows (the library checks n, finiteness and alpha)
@@ -927,6 +953,22 @@ int main(int argc, char **argv) {
             if (g_geo_seeds.size() >= (size_t)VK_GEO_MAX_SEEDS) { std::fprintf(stderr, "bonsai: --geodesic-voxel: at most 16 seeds\n"); return 2; }
             g_geo_seeds.push_back({(uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2]});
         }
+        else if (a == "--skeleton") {
+            if (g_skel_on) { std::fprintf(stderr, "bonsai: --skeleton: at most once\n"); return 2; }
+            g_skel_on = true;
+            if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0 && !std::isdigit((unsigned char)argv[i + 1][0]) && argv[i + 1][0] != '-') {
+                const std::string mode = next();
+                if (mode == "kernel") g_skel_mode = VK_SKEL_KERNEL;
+                else if (mode != "curve") { std::fprintf(stderr, "bonsai: --skeleton [curve|kernel] [MAX_ITER]: the mode is curve or kernel\n"); return 2; }
+            }
+            if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) {
+                const char *v = next();
+                char *end = nullptr;
+                const long long k = std::strtoll(v, &end, 10);
+                if (end == v || *end != '\0' || k < 0 || k > 0xffffffffll) { std::fprintf(stderr, "bonsai: --skeleton [curve|kernel] [MAX_ITER]: MAX_ITER is an integer >= 0\n"); return 2; }
+                g_skel_max_iter = (uint32_t)k;
+            }
+        }
         else if (a == "--measure") {
             g_measure_on = true;
             if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) g_measure_csv = next();
@@ -966,7 +1008,7 @@ int main(int argc, char **argv) {
     if (!mesh_path.empty() && (sl.on || hist || gpus > 0 || g_auto_window)) { std::fprintf(stderr, "bonsai: --mesh replaces the render: no --slice, --slice-plane, --histogram, --gpus or --auto-window\n"); return 2; }
     if (label_ops() && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel and --keep-pick need a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
     if (!g_keep_picks.empty() && !g_iso_on) { std::fprintf(stderr, "bonsai: --keep-pick needs --iso (the ray stops at the isosurface)\n"); return 2; }
-    if (g_label_fill_on && !label_ops() && !g_split_on && !g_thick_on && !g_geo_on) { std::fprintf(stderr, "bonsai: --label-fill needs a flag that drops voxels: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel or --keep-pick\n"); return 2; }
+    if (g_label_fill_on && !label_ops() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on) { std::fprintf(stderr, "bonsai: --label-fill needs a flag that drops voxels: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel or --keep-pick\n"); return 2; }
     if (g_keep_voxels.size() + g_keep_picks.size() > 16u) { std::fprintf(stderr, "bonsai: --keep-voxel and --keep-pick: at most 16 seeds together\n"); return 2; }
     if ((g_components || label_ops()) && gpus > 0) { std::fprintf(stderr, "bonsai: --components and the keep flags run on one GPU\n"); return 2; }
     if (!g_morph.empty() && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --morph needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
@@ -981,14 +1023,16 @@ int main(int argc, char **argv) {
     if (g_thick_on && gpus > 0) { std::fprintf(stderr, "bonsai: --thickness runs on one GPU\n"); return 2; }
     if (g_geo_on && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --geodesic and --geodesic-voxel need a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
     if (g_geo_on && gpus > 0) { std::fprintf(stderr, "bonsai: --geodesic runs on one GPU\n"); return 2; }
-    if (((g_morph_spacing_on && !g_split_on && !g_measure_on && !g_thick_on && !g_geo_on) || g_morph_fill_on) && g_morph.empty()) { std::fprintf(stderr, "bonsai: %s needs --morph\n", g_morph_spacing_on ? "--morph-spacing" : "--morph-fill"); return 2; }
+    if (g_skel_on && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --skeleton needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
+    if (g_skel_on && gpus > 0) { std::fprintf(stderr, "bonsai: --skeleton runs on one GPU\n"); return 2; }
+    if (((g_morph_spacing_on && !g_split_on && !g_measure_on && !g_thick_on && !g_geo_on && !g_skel_on) || g_morph_fill_on) && g_morph.empty()) { std::fprintf(stderr, "bonsai: %s needs --morph\n", g_morph_spacing_on ? "--morph-spacing" : "--morph-fill"); return 2; }
     if (!g_morph.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --morph runs on one GPU\n"); return 2; }
-    if ((label_ops() || !g_morph.empty() || g_split_on || g_measure_on || g_thick_on || g_geo_on) && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
+    if ((label_ops() || !g_morph.empty() || g_split_on || g_measure_on || g_thick_on || g_geo_on || g_skel_on) && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
     g_w = w; g_h = h;
     if (!g_resample.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --crop, --resample, --downsample, --isotropic, --to-u8 and --to-u16 run on one GPU\n"); return 2; }
     for (const ResampleOp &op : g_resample)
         if (op.kind == ResampleOp::CROP_CLIP && !g_clip_on) { std::fprintf(stderr, "bonsai: --crop clip needs --clip\n"); return 2; }
-    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && g_resample.empty() && !g_split_on && !g_thick_on && !g_geo_on) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
+    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && g_resample.empty() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
     if ((g_median || g_smooth) && gpus > 0) { std::fprintf(stderr, "bonsai: --median and --smooth run on one GPU\n"); return 2; }
     if (hist) return run_histogram(hist_bins, hist_lo, hist_hi);
     if (!mesh_path.empty()) return run_mesh(mesh_path, mesh_obj, mesh_iso_on ? mesh_iso : g_iso.iso, mesh_scale);

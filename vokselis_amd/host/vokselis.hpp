@@ -747,6 +747,32 @@ class Context {
         return res;
     }
     static double geodesic_units(uint32_t g) { return (double)g / (double)VK_GEO_UNIT; }
+    // Skeleton (vk_skeletonize; blocks): S = the voxels in [lo, hi] thinned to a one-voxel-wide set with the same pieces, tunnels and cavities, the set
+    // 26-connected and the background 6-connected.  mode: VK_SKEL_CURVE keeps line ends (centre lines), VK_SKEL_KERNEL does not (the ultimate homotopic
+    // kernel); max_iterations: 0 thins until an iteration deletes nothing.  The dense volume keeps the stored value on the skeleton -- fill_in: nullptr, or
+    // the sample value stored there instead -- and stores fill_out elsewhere.  install: it replaces the context's volume (outside frame_begin / frame_end);
+    // dense_out: nullptr, or host memory of nx ny nz elements of the volume's format; class_out: nullptr, or nx ny nz bytes (VK_SKEL_OFF .. VK_SKEL_JUNCTION).
+    vk_skeleton_result skeletonize(float lo, float hi = INFINITY, uint32_t mode = VK_SKEL_CURVE, uint32_t max_iterations = 0u, const vk_voxel_box *box = nullptr, bool clip = false,
+                                   const float *fill_in = nullptr, float fill_out = 0.0f, bool install = true, void *dense_out = nullptr, uint8_t *class_out = nullptr) {
+        vk_skeleton_request req{};
+        req.lo = lo; req.hi = hi; req.mode = mode; req.max_iterations = max_iterations; req.fill_in = fill_in ? *fill_in : 0.0f; req.fill_out = fill_out;
+        req.flags = (clip ? (uint32_t)VK_SKEL_CLIP_BOX : 0u) | (install ? (uint32_t)VK_SKEL_INSTALL : 0u) | (fill_in ? (uint32_t)VK_SKEL_FILL_IN : 0u);
+        vk_skeleton_result res{};
+        check(ctx_, vk_skeletonize(ctx_, &req, box, class_out, dense_out, &res));
+        return res;
+    }
+    // sum_j links[j] sqrt(sum_c (spacing[c] d_c)^2) over the 13 offsets above the centre: the centre-line length in the units of the spacing (nullptr: 1 1 1).
+    // Every adjacent pair counts, so the sum over-counts inside junction clumps.
+    static double skeleton_length(const vk_skeleton_result &r, const uint32_t *spacing = nullptr) {
+        double sum = 0.0;
+        for (int j = 0; j < VK_SKEL_LINKS; j++) {
+            const int o = 14 + j, d[3] = {o % 3 - 1, o / 3 % 3 - 1, o / 9 - 1};
+            double q = 0.0;
+            for (int c = 0; c < 3; c++) { const double e = (spacing ? (double)spacing[c] : 1.0) * d[c]; q += e * e; }
+            sum += (double)r.links[j] * std::sqrt(q);
+        }
+        return sum;
+    }
     // Frames in flight: the reference's queue runs ahead of the GPU (src/lib.rs:178-194), bounded by the swapchain
     // (get_current_texture, src/context.rs:252).  k surfaces, each on a stream of its own; 1 = one surface (the default).
     void frames_in_flight(uint32_t k) { check(ctx_, vk_ctx_frames_in_flight(ctx_, k)); }
