@@ -1358,6 +1358,13 @@ int vk_debug_wave_trace(vk_ctx *ctx, int enable, uint64_t *out, size_t n_blocks)
  * "stage_slab_cells" (a round is a slab of at most that many cells along the wave's major axis, default 8), "stage_copies_mask" (bit k: build the brick copy
  * whose slow axis is k; applies to the next upload, default 7). */
 int vk_debug_set_param(vk_ctx *ctx, const char *name, double value);
+/* Debug: which build of the cell march vk_render(ctx, VK_MODE_NAIVE_TRILINEAR, ..., dt_scale, flags) would launch now, for the context's
+ * volume and camera: *fast = 1 the unclamped build (index tables in LDS, 32-bit offsets), 0 the clamped one (VK_RENDER_SAFE's).  The
+ * answer of the function the launch itself asks (the cell array under 4 GiB, the tables within their LDS budget, and camera distance and
+ * ray length -- max(dims) / dt_scale trips -- small enough that f32 drift keeps every index inside the tables); 0 on the layouts that are
+ * always clamped (LINEAR, BRICKED, QUADS, STAGED).  Frames are the same bits on either build.  No volume, no camera, fast == NULL or a
+ * dt_scale that is not finite and > 0: VK_ERR_INVALID.  Host code only. */
+int vk_debug_march_path(vk_ctx *ctx, float dt_scale, uint32_t flags, int *fast);
 /* Per-pixel executed loop iterations of the last VK_RENDER_COUNT launch ([height][width] u32). */
 int vk_readback_steps(vk_ctx *ctx, uint32_t *dst);
 

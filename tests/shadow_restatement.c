@@ -34,6 +34,11 @@ typedef struct {
     int format;
 } volume_t;
 
+/* Audit hook (tests/fastpath_fuzz.cpp): called with every position whose voxel indices a march looks up, and the indices as the kernels
+ * form them before any clamp.  ahead = 1: the position one step past a ray's last sample, which the probe-ahead trip of the kernels has
+ * located by then.  NULL (the default): nothing is called. */
+void (*shr_lookup_hook)(const float p[3], int ix, int iy, int iz, int ahead) = 0;
+
 static int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 static int sat_i32(float f) { return (f != f) ? 0 : (f < -2147483648.0f ? INT32_MIN : (f >= 2147483648.0f ? INT32_MAX : (int)f)); }
 
@@ -47,6 +52,7 @@ static float sample_at(const volume_t *V, const float p[3], float g[3], int *bad
     if (fy >= 1.0f) fy = 0x1.fffffep-1f;
     if (fz >= 1.0f) fz = 0x1.fffffep-1f;
     const int ix = sat_i32(flx), iy = sat_i32(fly), iz = sat_i32(flz);
+    if (shr_lookup_hook) shr_lookup_hook(p, ix, iy, iz, 0);
     const int x0 = clampi(ix, 0, (int)nx - 1), x1 = clampi(ix < INT32_MAX ? ix + 1 : ix, 0, (int)nx - 1);
     const int y0 = clampi(iy, 0, (int)ny - 1), y1 = clampi(iy < INT32_MAX ? iy + 1 : iy, 0, (int)ny - 1);
     const int z0 = clampi(iz, 0, (int)nz - 1), z1 = clampi(iz < INT32_MAX ? iz + 1 : iz, 0, (int)nz - 1);
@@ -98,6 +104,46 @@ static float step_of(const volume_t *V, const float d[3], float dt_scale) {
     return dt_scale * fminf(dtx, fminf(dty, dtz));
 }
 
+/* the hook's call for the position a ray stands on when its loop has ended without a hit */
+static void looked_ahead(const volume_t *V, const float p[3]) {
+    if (!shr_lookup_hook) return;
+    const float ux = fmaf(p[0], (float)V->nx, -0.5f), uy = fmaf(p[1], (float)V->ny, -0.5f), uz = fmaf(p[2], (float)V->nz, -0.5f);
+    shr_lookup_hook(p, sat_i32(floorf(ux)), sat_i32(floorf(uy)), sat_i32(floorf(uz)), 1);
+}
+
+/* The shadow ray of the point q towards Lr (a unit vector): whether it hits; *n: its iterations executed; *flags gains SHR_MISS, SHR_ZERO,
+ * SHR_NAN_SEEN, SHR_PINF_HIT. */
+static int shadow_walk(const volume_t *V, const float q[3], const float Lr[3], float dt_scale, float bias, float iso_k, const float *box,
+                       uint32_t *n_out, uint32_t *flags, int *bad) {
+    const float dts = step_of(V, Lr, dt_scale);
+    float tb[2];
+    intersect(q, Lr, box, tb);
+    int shadowed = 0;
+    uint32_t n = 0;
+    if (tb[0] > tb[1]) {
+        *flags |= SHR_MISS;
+    } else {
+        const float ts0 = fmaxf(fmaxf(tb[0], 0.0f), bias * dts);
+        float ps[3] = {fmaf(ts0, Lr[0], q[0]), fmaf(ts0, Lr[1], q[1]), fmaf(ts0, Lr[2], q[2])};
+        const float ss[3] = {Lr[0] * dts, Lr[1] * dts, Lr[2] * dts};
+        for (float t = ts0; t < tb[1]; t = t + dts) {
+            const float v = sample_at(V, ps, NULL, bad);
+            n++;
+            if (v != v) *flags |= SHR_NAN_SEEN;
+            if (v >= iso_k) {
+                shadowed = 1;
+                if (v == INFINITY) *flags |= SHR_PINF_HIT;
+                break;
+            }
+            ps[0] = ps[0] + ss[0]; ps[1] = ps[1] + ss[1]; ps[2] = ps[2] + ss[2];
+        }
+        if (n == 0) *flags |= SHR_ZERO;
+        if (!shadowed && n != 0) looked_ahead(V, ps); /* (a ray without an iteration looks nothing up) */
+    }
+    *n_out = n;
+    return shadowed;
+}
+
 typedef struct {
     float *rgba;
     uint32_t *steps, *flags, *sh_iters;
@@ -130,6 +176,7 @@ static int pixel(const vo_camera_uniform *cam, const volume_t *V, uint32_t W, ui
         j = j + 1;
     }
     *o.steps = it;
+    if (!hit && it != 0) looked_ahead(V, p);
     if (bad) return -2;
     if (!hit) return 0;
     *o.flags |= SHR_HIT;
@@ -165,30 +212,8 @@ static int pixel(const vo_camera_uniform *cam, const volume_t *V, uint32_t W, ui
         float kf = 1.0f;
         if (shadows && !head) {
             *o.flags |= SHR_CAST;
-            const float dts = step_of(V, Lr, dt_scale);
-            float tb[2];
-            intersect(q, Lr, box, tb);
-            int shadowed = 0;
             uint32_t n = 0;
-            if (tb[0] > tb[1]) {
-                *o.flags |= SHR_MISS;
-            } else {
-                const float ts0 = fmaxf(fmaxf(tb[0], 0.0f), shadows[1] * dts);
-                float ps[3] = {fmaf(ts0, Lr[0], q[0]), fmaf(ts0, Lr[1], q[1]), fmaf(ts0, Lr[2], q[2])};
-                const float ss[3] = {Lr[0] * dts, Lr[1] * dts, Lr[2] * dts};
-                for (float t = ts0; t < tb[1]; t = t + dts) {
-                    const float v = sample_at(V, ps, NULL, &bad);
-                    n++;
-                    if (v != v) *o.flags |= SHR_NAN_SEEN;
-                    if (v >= iso_k) {
-                        shadowed = 1;
-                        if (v == INFINITY) *o.flags |= SHR_PINF_HIT;
-                        break;
-                    }
-                    ps[0] = ps[0] + ss[0]; ps[1] = ps[1] + ss[1]; ps[2] = ps[2] + ss[2];
-                }
-                if (n == 0) *o.flags |= SHR_ZERO;
-            }
+            const int shadowed = shadow_walk(V, q, Lr, dt_scale, shadows[1], iso_k, box, &n, o.flags, &bad);
             *o.sh_iters = n;
             if (shadowed) {
                 *o.flags |= SHR_SHADOWED;
@@ -220,6 +245,17 @@ static int pixel(const vo_camera_uniform *cam, const volume_t *V, uint32_t W, ui
     if (bad) return -2;
     for (int k = 0; k < 3; k++) o.rgba[k] = vo_linear_to_srgb(c[k]);
     return 0;
+}
+
+/* One shadow ray on its own (the audit's secondary rays): from q towards the unit vector L, bias in steps, the unit cube.  Returns whether it
+ * hit, -2 as shr_render; *n_out: its iterations executed. */
+int shr_shadow_ray(const void *vol, uint32_t nx, uint32_t ny, uint32_t nz, int format, const float q[3], const float L[3], float dt_scale,
+                   float bias, float iso_k, uint32_t *n_out) {
+    const volume_t V = {vol, nx, ny, nz, format};
+    uint32_t flags = 0;
+    int bad = 0;
+    const int shadowed = shadow_walk(&V, q, L, dt_scale, bias, iso_k, NULL, n_out, &flags, &bad);
+    return bad ? -2 : shadowed;
 }
 
 /* The tile [tx, tx + tw) x [ty, ty + th) of a W x H frame.  format: 0 R8, 1 R16F, 3 R16_UNORM; iso_k on the kernel's scale; light: 8 floats

@@ -37,3 +37,18 @@ def test_hostmath_header_is_what_the_library_compiles():
     assert "vk::tile_order(" in order and "hull_separates" not in order.replace("vk_hostmath", "")
     batch = open(os.path.join(csrc, "vk_batch.hip")).read()
     assert "batch_table_bytes(" in batch and "batch_order_offset(" in batch
+    # the cell march's dispatch rule, the index tables' entries and the clamped offset: one statement each, in the header tests/fastpath_fuzz.cpp includes
+    hostmath = open(os.path.join(csrc, "vk_hostmath.hpp")).read()
+    for name in ("inline bool cell_march_fast(", "VK_HD uint32_t cell_lut_entry(", "VK_HD int64_t cell_offset_clamped(", "inline CellAddr cell_addr_make(",
+                 "VK_HD uint32_t cell_lut_entries("):
+        assert hostmath.count(name) == 1, name
+    render = open(os.path.join(csrc, "vk_render.hip")).read()
+    assert render.count("cell_march_fast(") == 2 and "nextafter" not in render.split("int dispatch_march(")[1].split("static int render_common(")[0]
+    assert "dispatch_march(" in batch and "cell_march_fast" not in batch  # vk_render_batch and the geometry pass go through dispatch_march
+    assert "cell_lut_entries(uint32_t" not in common and "cell_lut_bytes(uint32_t" not in common
+    kernels = open(os.path.join(csrc, "vk_volume_kernels.hpp")).read()
+    assert "cell_lut_entry(e, nx, ny, nz, nbx, nby)" in kernels and "brick_mul * ((c + 3u) >> 2)" not in kernels
+    parts = open(os.path.join(csrc, "vk_march_parts.hpp")).read()
+    assert "return cell_offset_clamped(V.kz, V.c0, V.max_off, V.kx, V.ky, V.sh_x, V.sh_y, V.sh_z, ix, iy, iz);" in parts and "(int)V.ky" not in parts
+    volume = open(os.path.join(csrc, "vk_volume.hip")).read()
+    assert "cell_addr_make(nb.nbx, nb.nby, nb.nbz" in volume and "64 * bxyn" not in volume

@@ -303,3 +303,25 @@ def test_reshaping_a_context_again_and_again_does_not_leak_device_memory(V):
         finally:
             c.close()
     assert before - free_bytes() < (8 << 20)
+
+
+def test_debug_march_path_answers_for_the_volume_and_camera_in_place(V):
+    lib, W, H = V.native.lib(), 32, 16
+    fast = C.c_int(-1)
+    ctx = V.Context(W, H, backbuffer=(W, H), out_format=V.OUT_RGBA32F)
+    try:
+        assert lib.vk_debug_march_path(ctx.handle, 1.0, 0, C.byref(fast)) != 0 and fast.value == -1  # no volume
+        V.VolumeTexture(ctx, _fog(32), layout=V.LAYOUT_PACKED)
+        ctx.set_camera_blob(_camera(V, W, H))
+        assert lib.vk_debug_march_path(ctx.handle, 1.0, 0, None) != 0
+        assert lib.vk_debug_march_path(ctx.handle, 0.0, 0, C.byref(fast)) != 0
+        assert lib.vk_debug_march_path(ctx.handle, float("nan"), 0, C.byref(fast)) != 0 and fast.value == -1
+        V.native.check(ctx.handle, lib.vk_debug_march_path(ctx.handle, 1.0, 0, C.byref(fast)))
+        assert fast.value == 1 and ctx.march_path_fast(1.0)                              # 32^3 from nearby: the unclamped build
+        V.native.check(ctx.handle, lib.vk_debug_march_path(ctx.handle, 1.0, V.RENDER_SAFE, C.byref(fast)))
+        assert fast.value == 0                                                           # the caller forces the clamped one
+        assert not ctx.march_path_fast(0.0005)                                           # 64 000 trips per ray: too long to run unclamped
+        V.VolumeTexture(ctx, _fog(32), layout=V.LAYOUT_LINEAR)
+        assert not ctx.march_path_fast(1.0)                                              # LINEAR is always clamped
+    finally:
+        ctx.close()

@@ -449,6 +449,7 @@ SYMBOLS = {
     "vk_debug_set_tile_order": (C.c_int, [_vp, C.POINTER(_u32), _u32]),
     "vk_debug_read_skip_maps": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_sz), _vp, _sz]),
     "vk_debug_set_param": (C.c_int, [_vp, C.c_char_p, C.c_double]),
+    "vk_debug_march_path": (C.c_int, [_vp, C.c_float, _u32, C.POINTER(C.c_int)]),
     "vk_debug_wave_trace": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint64), _sz]),
     "vk_readback_steps": (C.c_int, [_vp, _vp]),
     "vk_timer_begin": (C.c_int, [_vp]),

@@ -847,6 +847,13 @@ class Context:
         """Debug / tuning knob of the library (vk_debug_set_param)."""
         N.check(self._h, N.lib().vk_debug_set_param(self._h, name.encode(), float(value)))
 
+    def march_path_fast(self, dt_scale: float = 1.0, flags: int = 0) -> bool:
+        """Debug (vk_debug_march_path): whether a NAIVE_TRILINEAR render of the current volume from the current camera would launch the
+        unclamped build of the cell march (False: the clamped one, RENDER_SAFE's).  The frame is the same either way."""
+        fast = C.c_int(-1)
+        N.check(self._h, N.lib().vk_debug_march_path(self._h, float(dt_scale), int(flags), C.byref(fast)))
+        return bool(fast.value)
+
     def read_skip_maps(self):
         """Debug (vk_debug_read_skip_maps): (grid, maps) of the current volume -- grid = (cells in x, y, z), maps uint8 [n_maps, cells] as
         stored (bricked order); n_maps is 0 for a layout without maps, 1 for the isotropic map, 8 for the octant maps.  Blocks."""

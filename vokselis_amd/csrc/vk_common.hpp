@@ -514,8 +514,8 @@ __device__ __forceinline__ bool wave_leader() {
 // neighbours (clamp), so a position one step outside the box -- the prefetch of march_stream --
 // still reads a real entry.  The three tables are stored back to back.  `shift` pre-scales the
 // entries to byte offsets when no per-cell side table is read.
-__host__ __device__ __forceinline__ uint32_t cell_lut_entries(uint32_t nx, uint32_t ny, uint32_t nz) { return (nx + ny + nz + 9u + 3u) & ~3u; }  // padded to whole uint4
-__host__ __device__ __forceinline__ uint32_t cell_lut_bytes(uint32_t nx, uint32_t ny, uint32_t nz) { return cell_lut_entries(nx, ny, nz) * 4u; }
+// cell_lut_entries, cell_lut_bytes, cell_lut_entry (an entry's value) and cell_march_fast (the host's rule for reading the tables
+// unclamped) are vk_hostmath.hpp's, where a CPU program can include them.
 // behind the tables in LDS, in the built-in skip kernels that decode lone-speckle codes (vk_march.hpp): 8 corners x (o_y, o_z, o_x, 0) f32, o_i = 1 - (corner bit i);
 // a code's bits 6..4 are the corner, so `code & 0x70` is the entry's byte offset
 constexpr uint32_t kSpeckleLutBytes = 128u;

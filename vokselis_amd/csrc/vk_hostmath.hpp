@@ -215,6 +215,104 @@ VK_HD uint64_t untile_blocks(uint32_t ts, uint32_t n_tiles, uint32_t n_frames) {
 VK_HD size_t batch_table_bytes(uint32_t n_frames, size_t n_tiles, size_t frame_desc_bytes) { return (size_t)n_frames * (frame_desc_bytes + 2u * n_tiles * sizeof(uint32_t)); }
 VK_HD size_t batch_order_offset(uint32_t n_frames, size_t frame_desc_bytes) { return (size_t)n_frames * frame_desc_bytes; }  // bytes; pos follows at + n_frames * n_tiles words
 
+// ---- the cell layouts (PACKED, PACKED_PAIRS): addressing constants, index tables, and the rule that lets a march read them unclamped --------
+// The cell with low-corner voxel i (i in [-1, n - 1] per axis) lives in physical brick (i >> 2) + 1 at in-brick position i & 3; a brick
+// holds 64 cells.  CellAddr carries the constants of the byte offset's closed form
+//   c0 + bx*kx + by*ky + bz*kz + (ix << sh_x) + (iy << sh_y) + (iz << sh_z),  b = i >> 2
+// as the upload computes them (VolumeDesc holds the same fields).  tests/fastpath_fuzz.cpp holds cell_offset_clamped to the plain 64-bit
+// form for every shape the upload accepts, under UBSan.
+struct CellAddr {
+    int64_t kz, c0, max_off;
+    int32_t kx, ky;
+    uint32_t sh_x, sh_y, sh_z;
+};
+inline uint32_t cell_bricks(uint32_t n_vox) { return ((n_vox - 1u) >> 2) + 2u; }
+inline CellAddr cell_addr_make(uint32_t nbx, uint32_t nby, uint32_t nbz, uint32_t cell_bytes) {
+    CellAddr A;
+    const int64_t cb = (int64_t)cell_bytes, bxn = nbx, bxyn = (int64_t)nbx * nby;
+    const uint64_t n_cells = (uint64_t)nbx * nby * nbz * 64u;
+    A.sh_x = cell_bytes == 8 ? 3 : 4;
+    A.sh_y = A.sh_x + 2;
+    A.sh_z = A.sh_x + 4;
+    A.kx = (int32_t)(60 * cb);
+    A.ky = (int32_t)((64 * bxn - 16) * cb);
+    A.kz = (64 * bxyn - 64) * cb;
+    A.c0 = (64 * bxyn + 64 * bxn + 64) * cb;
+    A.max_off = (int64_t)(n_cells - 1) * cb;
+    return A;
+}
+// The clamped march's offset (vk_march_parts.hpp: safe_cell_offset): the closed form in 64 bits, clamped into the cell array whatever
+// the indices are.  by * ky passes 2^31 on flat volumes of 4 GiB and more (5800 x 5800 x 4 u16: 1450 * 1485568), so that product is
+// formed in 64 bits; bx * kx (<= 2049 * 960) and the shifts (<= 8191 << 8) stay far inside 32.
+VK_HD int64_t cell_offset_clamped(int64_t kz, int64_t c0, int64_t max_off, int32_t kx, int32_t ky, uint32_t sh_x, uint32_t sh_y, uint32_t sh_z, int ix, int iy, int iz) {
+    const int bx = ix >> 2, by = iy >> 2, bz = iz >> 2;
+    int64_t off = (int64_t)bz * kz + ((int64_t)by * (int64_t)ky + (int64_t)(bx * kx)) +
+                  (int64_t)(int32_t)(((uint32_t)iz << sh_z) + ((uint32_t)iy << sh_y) + ((uint32_t)ix << sh_x)) + c0;  // (shifts of i = -1: on unsigned words)
+    return off < 0 ? 0 : (off > max_off ? max_off : off);
+}
+
+// Per-axis cell-index tables of the unclamped march (LDS):
+//   Tx[i] = 64*((i>>2)+1) + (i&3),  Ty[i] = 64*nbx*((i>>2)+1) + 4*(i&3),  Tz[i] = 64*nbx*nby*((i>>2)+1) + 16*(i&3)
+// Each table has n + 3 entries, entry e = i + 2 for i in [-2, n]; the two outer entries repeat their neighbours (clamp), so a position
+// up to 1.5 cells outside the box still reads a real cell's entry.  The three tables are stored back to back, padded to whole uint4.
+// NOTHING clamps the index itself: cell_march_fast below is what keeps it in [-2, n].
+VK_HD uint32_t cell_lut_entries(uint32_t nx, uint32_t ny, uint32_t nz) { return (nx + ny + nz + 9u + 3u) & ~3u; }  // padded to whole uint4
+VK_HD uint32_t cell_lut_bytes(uint32_t nx, uint32_t ny, uint32_t nz) { return cell_lut_entries(nx, ny, nz) * 4u; }
+// entry e of the back-to-back tables, in cell units (0 in the padding)
+VK_HD uint32_t cell_lut_entry(uint32_t e, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t nbx, uint32_t nby) {
+    const uint32_t n0 = nx + 3u, n1 = ny + 3u, n2 = nz + 3u;
+    if (e >= n0 + n1 + n2) return 0u;
+    uint32_t j = e, n = n0, brick_mul = 64u, cell_mul = 1u;
+    if (e >= n0 + n1) { j = e - n0 - n1; n = n2; brick_mul = 64u * nbx * nby; cell_mul = 16u; }
+    else if (e >= n0) { j = e - n0; n = n1; brick_mul = 64u * nbx; cell_mul = 4u; }
+    const uint32_t lo = j > 1u ? j : 1u;
+    const uint32_t c = (lo < n - 2u ? lo : n - 2u) - 1u;  // cell coordinate i + 1 in [0, n_vox]
+    return brick_mul * ((c + 3u) >> 2) + cell_mul * ((c + 3u) & 3u);
+}
+
+constexpr uint32_t kRenderSafeFlag = 4u;       // == VK_RENDER_SAFE (include/vokselis_hip.h; vk_render.hip asserts it)
+constexpr uint32_t kCellLutBudget = 16384u;    // bytes of LDS the three tables may take
+// May a NAIVE_TRILINEAR march on a cell layout take the unclamped build (SAFE = false: index tables, 32-bit offsets, a plain load of
+// the distance byte at the tables' sum)?  One pure function of what the host knows at launch: the array's last offset, the dims, the eye
+// (the farthest of a batch), dt_scale and the caller's VK_RENDER_* flags.  It must guarantee that EVERY index a ray looks up -- on every
+// trip its f32 loop makes, and (dt_scale <= 1.25) the probe-ahead position one step ahead of each -- lies in [-2, n] on its axis: the
+// skip kernels read the distance byte with a plain global load at the tables' sum.  (The request one step ahead in the loops without a
+// skip map goes through a bounds-checked load at any dt_scale and is not covered: vk_march.hpp.)
+//
+// In exact arithmetic a sampled position lies in the box: u = p*n - 0.5 in [-0.5, n - 0.5], floor(u) in [-1, n - 1].  The tables reach
+// 1.5 cells further on either side.  The probe-ahead trip looks one step ahead, at most dt_scale <= 1.25 cells (the host drops
+// LF_PROBE_AHEAD above that): 0.25 cells are left for everything f32 does to the position, on the worst axis (n <= nmax):
+//   set-up    p0 = eye + t0*d, t0 and t1 from the slab test: a few ulp(reach) each, reach = |eye| + 4 >= every t and |eye_i|; 64 ulp(reach).
+//   p drift   p += s rounds by <= ulp(2)/2 per trip while |p| < 4; s = fl(d*dt) itself is off by 2^-24 relative, which over a
+//             whole ray (<= nmax cells) is nmax * 2^-24 cells and is covered by the factor of two in ulp(2) against ulp(1).
+//   t drift   t += dt rounds by <= ulp(reach)/2 per trip, and inside a binade always the same way: after k trips the loop variable is
+//             off by up to k*ulp(reach)/2, the loop ends that much late (or early), and the ray has moved on by <= that much on any
+//             axis (|d_i| <= 1).
+// So k trips move a looked-up position at most 64 ulp(reach) + k*(ulp(reach)/2 + ulp(2)/2) outside the box.  k: the loop makes trip
+// k only while t_k < t1, t_k >= t0 + k*(dt - ulp(reach)/2); dt >= dt_scale/nmax, required below to be >= 8 ulp(reach), so
+// k < (16/15)*(t1 - t0)/dt, and (t1 - t0)/dt <= nmax/dt_scale because a ray crosses at most n_i cells on the axis that sets dt.
+// max_trips = 1.125*nmax/dt_scale + 4 takes the slack.  In double: none of this rounds at a size that matters.
+// tests/fastpath_fuzz.cpp replays the f32 loop (primary rays with the probe-ahead position, shadow rays) and holds this rule to it.
+inline double cell_march_drift_cells(uint32_t nx, uint32_t ny, uint32_t nz, const float eye[3], float dt_scale) {
+    const float reach = std::sqrt(eye[0] * eye[0] + eye[1] * eye[1] + eye[2] * eye[2]) + 4.0f;
+    const double nmax = (double)std::max(nx, std::max(ny, nz));
+    const double ulp_reach = (double)(std::nextafter(reach, 2.0f * reach) - reach), ulp_2 = (double)(std::nextafter(2.0f, 4.0f) - 2.0f);
+    const double max_trips = 1.125 * nmax / (double)dt_scale + 4.0;
+    return nmax * (64.0 * ulp_reach + max_trips * (0.5 * ulp_reach + 0.5 * ulp_2));
+}
+inline bool cell_march_fast(int64_t max_off, uint32_t nx, uint32_t ny, uint32_t nz, const float eye[3], float dt_scale, uint32_t render_flags) {
+    if (render_flags & kRenderSafeFlag) return false;
+    if (!(max_off + 16 < (1ll << 32))) return false;                    // 32-bit byte offsets
+    if (!(cell_lut_bytes(nx, ny, nz) <= kCellLutBudget)) return false;  // the tables' LDS budget
+    if (!(dt_scale > 0.0f) || !std::isfinite(dt_scale)) return false;
+    const float reach = std::sqrt(eye[0] * eye[0] + eye[1] * eye[1] + eye[2] * eye[2]) + 4.0f;
+    if (!std::isfinite(reach)) return false;
+    const double nmax = (double)std::max(nx, std::max(ny, nz));
+    const double ulp_reach = (double)(std::nextafter(reach, 2.0f * reach) - reach);
+    if (!((double)dt_scale / nmax >= 8.0 * ulp_reach)) return false;    // (check_render's guard: the bound on the trips leans on it)
+    return cell_march_drift_cells(nx, ny, nz, eye, dt_scale) < 0.25;
+}
+
 // ---- host-side geometry of a frame (plain host functions) ---------------------------------------------------------------
 constexpr int kModeNaive = 0;  // == VK_MODE_NAIVE_TRILINEAR (include/vokselis_hip.h); the other modes march the [-1, 1]^3 box from the near plane
 

@@ -67,8 +67,19 @@ static_assert(sizeof(RayState) == 64, "RayState is one 64-byte record");
 // idx = Tx[ix] + Ty[iy] + Tz[iz] with three small per-axis tables in LDS (`lut`, filled by the kernel:
 // see load_cell_luts).  Three ds_read_b32 (not VALU) + one v_add3 replace the 14 integer VALU
 // instructions of the closed form -- the loop is VALU-issue bound.  Every table entry is a valid
-// non-negative partial index and LDS reads outside the allocation return 0, so any combination stays
-// inside the cell array: no clamp.
+// non-negative partial index, so any combination of entries stays inside the cell array: no clamp.
+// The tables hold voxels [-2, n] and NOTHING here keeps an index inside them: an index beyond reads
+// the next axis' table, the padding or whatever follows in LDS, and the skip kernels read the distance
+// byte with a plain global load at that sum.  What keeps the indices inside is the host's rule for
+// launching this build at all -- cell_march_fast (vk_hostmath.hpp) bounds the camera distance AND the
+// length of the ray, because the f32 loop drifts by half an ulp of t and of p per trip and a long ray
+// keeps stepping after it has left the box -- and tests/fastpath_fuzz.cpp holds that rule to a replay of
+// the loop.  The guarantee is needed for, and audited for, that plain load of the distance byte: every
+// sampled position at any dt_scale, and the probe-ahead position for dt_scale <= 1.25.  The pipelined
+// loops without a skip map (march_stream and its iso / MAX twins) request the cell one step past the
+// ray's end at ANY dt_scale, up to dt_scale cells past the box: above 1.5 cells that index is outside
+// the tables, and harmless only because an LDS read outside the allocation returns 0, the cell comes
+// through a bounds-checked buffer load, and the value is never used.
 //
 // WALK: how a run of k exactly transparent steps advances the reference's position (p += s, k times: raycast_naive.wgsl:118; the loop
 // variable of :101 is the integer `left`, see RayState: left -= k).
@@ -135,10 +146,13 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
         const float ux = fmaf(qx, fnx, -0.5f), uy = fmaf(qy, fny, -0.5f), uz = fmaf(qz, fnz, -0.5f);
         a_fx = __builtin_amdgcn_fractf(ux); a_fy = __builtin_amdgcn_fractf(uy); a_fz = __builtin_amdgcn_fractf(uz);
         a_idx = lut[cvt_floor_i32(ux) + 2] + luty[cvt_floor_i32(uy) + 2] + lutz[cvt_floor_i32(uz) + 2];
-        // A request made for a ray that turns out to have ended looks at most one step past the box: <= dt_scale cells on any axis.  The tables carry
-        // one clamped entry beyond i = -1 and i = n - 1, which covers 1.5 cells; the host sets LF_PROBE_AHEAD only for dt_scale <= 1.25
-        // (vk_render.hip), so the index is always a real cell's and the map is read inside its allocation.  (No branch around the request, and a
-        // plain global load: an exec-masked region, or a bounds-checked buffer load, gives most of the gain back.)
+        // A request made for a ray that turns out to have ended looks one step past the ray's last sample: <= dt_scale cells further on any axis.
+        // The tables carry one clamped entry beyond i = -1 and i = n - 1, which covers 1.5 cells past the box; the host sets LF_PROBE_AHEAD only for
+        // dt_scale <= 1.25 (vk_render.hip), which leaves 0.25 cells for how far the f32 loop itself has carried the last sample out of the box --
+        // set-up rounding plus half an ulp of t and of p per trip.  The host launches this build only where that stays below 0.25 cells
+        // (vk_hostmath.hpp: cell_march_fast, which counts the trips of the longest ray), so the index is a table entry and the map is read inside
+        // its allocation.  (No branch around the request, and a plain global load: an exec-masked region, or a bounds-checked buffer load, gives
+        // most of the gain back.)
         a_d = dist_at(a_idx + doff);
     };
     if (AHEAD) locate(px, py, pz);
@@ -325,7 +339,8 @@ __device__ __forceinline__ bool march(const VolumeDesc &V, RayState &r, const ui
 // evaluated, so the fetch latency overlaps the ~40 VALU instructions of a sample instead of adding
 // to them -- it is the lone heavy waves at the tail of a frame that set the frame time.  The f32
 // operations on p, A and the colour sums are those of march(), in the same order per variable.
-// The request one step past the ray's end reads a real (clamped) table entry and is never used.
+// The request one step past the ray's end is never used.  It reads a real (clamped) table entry while that step is at most 1.5 cells;
+// a longer one (dt_scale > 1.5) indexes past the tables, and then only the bounds-checked buffer load keeps the request harmless.
 // CELL_LUT: the tables hold cell indices (the skip kernels' copy) instead of byte offsets; `budget` bounds the trips
 // (0xffffffff: none) so that the skip kernels can run stretches of it between probing windows.
 template <int VOL, bool COUNT, bool CELL_LUT = false, bool TF = false, bool LIT = false>

@@ -102,12 +102,11 @@ __device__ __forceinline__ CellBits<VOL> load_cell(__amdgpu_buffer_rsrc_t rs, ui
 
 // SAFE (no index tables): the byte offset of voxel (ix, iy, iz)'s cell, the 64-bit closed form of the tables' sum, clamped into
 // the cell array whatever the indices are; the cell at that offset comes through a plain pointer (vk_texel.hpp: load_cell, and cell_offset,
-// this function's twin on uint32_t indices in 64-bit arithmetic)
+// this function's twin on uint32_t indices in 64-bit arithmetic).  The arithmetic is vk_hostmath.hpp's cell_offset_clamped, which
+// tests/fastpath_fuzz.cpp runs under UBSan on every shape the upload accepts (by * ky is a 64-bit product: it passes 2^31 on flat
+// volumes of 4 GiB and more).
 __device__ __forceinline__ int64_t safe_cell_offset(const VolumeDesc &V, int ix, int iy, int iz) {
-    const int bx = ix >> 2, by = iy >> 2, bz = iz >> 2;
-    int64_t off = (int64_t)bz * (int64_t)V.kz + (int64_t)(by * (int)V.ky + bx * (int)V.kx) +
-                  (int64_t)((iz << V.sh_z) + (iy << V.sh_y) + (ix << V.sh_x)) + (int64_t)V.c0;
-    return off < 0 ? 0 : (off > (int64_t)V.max_off ? (int64_t)V.max_off : off);
+    return cell_offset_clamped(V.kz, V.c0, V.max_off, V.kx, V.ky, V.sh_x, V.sh_y, V.sh_z, ix, iy, iz);
 }
 
 // Where voxel (ix, iy, iz)'s cell is, and under DIST its distance byte in the ray's map (`doff`: the octant's offset).  SAFE: the clamped

@@ -155,18 +155,12 @@ int dispatch_march(vk_ctx *ctx, int mode, const LaunchDesc &L_in, uint32_t flags
         const bool skip = !(flags & VK_RENDER_NO_SKIP) && (forced || ctx->empty_fraction >= 0.45);
         if (skip && !forced && ctx->empty_fraction >= 0.55) L.flags &= ~(uint32_t)LF_ADAPTIVE_PROBING;
         if (skip && ctx->empty_fraction < 0.05) L.flags |= LF_LONG_STRETCHES;  // forced on (almost) solid material: long dense stretches from the start
-        // SAFE=false (no per-axis clamps, 32-bit offsets, index tables in LDS) only when provably
-        // harmless: the cell array is < 4 GiB, the tables fit a modest LDS budget, and the camera is
-        // near enough that the accumulated position stays within 0.5/n of the box
-        // (|p error| <= ~64 ulp(reach) << 0.5/n).
-        bool safe = true;
-        {
-            const float *e = reach_cam;
-            float reach = std::sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) + 4.0f;
-            float nmax = (float)std::max(ctx->nx, std::max(ctx->ny, ctx->nz));
-            float ulp = std::nextafter(reach, 2.0f * reach) - reach;
-            if (V.max_off + 16 < (1ll << 32) && cell_lut_bytes(ctx->nx, ctx->ny, ctx->nz) <= 16384u && 64.0f * ulp < 0.25f / nmax && !(flags & VK_RENDER_SAFE)) safe = false;
-        }
+        // SAFE=false (no per-axis clamps, 32-bit offsets, index tables in LDS) only where cell_march_fast (vk_hostmath.hpp, with the
+        // derivation) allows it: the cell array is < 4 GiB, the tables fit their LDS budget, and the camera's distance AND the length of the
+        // longest ray (nmax / dt_scale trips: the f32 loop drifts by half an ulp of t and of p per trip, and runs on while its t says so)
+        // keep every looked-up index inside the tables.  Frames are the same bits either way; vk_debug_march_path asks the same function.
+        static_assert(kRenderSafeFlag == (uint32_t)VK_RENDER_SAFE, "vk_hostmath.hpp restates VK_RENDER_SAFE");
+        const bool safe = !cell_march_fast(V.max_off, ctx->nx, ctx->ny, ctx->nz, reach_cam, L.dt_scale, flags);
         if (ctx->vol_kind == VOL_S8U8 || ctx->vol_kind == VOL_S8F16) launch_staged(ctx, L, V, grid, count, reach_cam);
         else if (is_u16_kind(ctx->vol_kind)) {  // an R16_UNORM volume: the same families, kernels of their own units (vk_march_u16.hpp)
             if (flags & VK_RENDER_FAST_WALK) return fail(ctx, VK_ERR_UNSUPPORTED, "R16_UNORM: VK_RENDER_FAST_WALK has no u16 kernels (the walks take the loop)");
@@ -457,6 +451,18 @@ int vk_slice_probe(vk_ctx *ctx, const vk_slice *slice, uint32_t x, uint32_t y, v
     out->inside = rec[1] != 0.0f ? 1 : 0;
     for (int i = 0; i < 3; i++) out->pos[i] = slice_position(slice->origin[i], slice->du[i], slice->dv[i], x, y);
     out->value = rec[0];
+    return VK_OK;
+}
+
+// Debug: the build vk_render(ctx, VK_MODE_NAIVE_TRILINEAR, ..., dt_scale, flags) would launch now -- dispatch_march's own question, asked
+// of the same function.  0 on the layouts that are always clamped.
+int vk_debug_march_path(vk_ctx *ctx, float dt_scale, uint32_t flags, int *fast) {
+    if (!ctx) return VK_ERR_INVALID;
+    if (!fast) return fail(ctx, VK_ERR_INVALID, "vk_debug_march_path: fast is NULL");
+    if (ctx->format < 0) return fail(ctx, VK_ERR_INVALID, "vk_debug_march_path: no volume uploaded");
+    if (!ctx->have_camera) return fail(ctx, VK_ERR_INVALID, "vk_debug_march_path: no camera (vk_set_camera)");
+    if (!(dt_scale > 0.0f) || !std::isfinite(dt_scale)) return fail(ctx, VK_ERR_INVALID, "dt_scale must be finite and > 0");
+    *fast = is_cell_layout(ctx->vol_kind) && cell_march_fast(volume_desc(ctx).max_off, ctx->nx, ctx->ny, ctx->nz, ctx->camera, dt_scale, flags) ? 1 : 0;
     return VK_OK;
 }
 

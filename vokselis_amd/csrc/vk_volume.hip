@@ -408,9 +408,9 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
     if (f16 && layout == VK_LAYOUT_PACKED_PAIRS)
         return fail(ctx, VK_ERR_UNSUPPORTED, "PACKED_PAIRS stores exact u8 differences; f16 volumes use PACKED");
     const int kind = f16 ? VOL_PF16 : (format == VK_FMT_R16_UNORM ? VOL_PU16 : (layout == VK_LAYOUT_PACKED_PAIRS ? VOL_P16 : VOL_P8));
-    nb.nbx = ((nx - 1) >> 2) + 2;
-    nb.nby = ((ny - 1) >> 2) + 2;
-    nb.nbz = ((nz - 1) >> 2) + 2;
+    nb.nbx = cell_bricks(nx);
+    nb.nby = cell_bricks(ny);
+    nb.nbz = cell_bricks(nz);
     const uint64_t n_bricks = (uint64_t)nb.nbx * nb.nby * nb.nbz;
     const uint64_t n_cells = n_bricks * kBrickCells;
     const size_t cell_bytes = kind == VOL_P8 ? 8 : 16;
@@ -453,15 +453,11 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
     }
     // addressing constants (vk_kernels.hpp: VolumeDesc)
     VolumeDesc &V = nb.vdesc;
-    const int64_t cb = (int64_t)cell_bytes, bxn = nb.nbx, bxyn = (int64_t)nb.nbx * nb.nby;
-    V.sh_x = cell_bytes == 8 ? 3 : 4;
-    V.sh_y = V.sh_x + 2;
-    V.sh_z = V.sh_x + 4;
-    V.kx = (int32_t)(60 * cb);
-    V.ky = (int32_t)((64 * bxn - 16) * cb);
-    V.kz = (64 * bxyn - 64) * cb;
-    V.c0 = (64 * bxyn + 64 * bxn + 64) * cb;
-    V.max_off = (int64_t)(n_cells - 1) * cb;
+    const CellAddr A = cell_addr_make(nb.nbx, nb.nby, nb.nbz, (uint32_t)cell_bytes);  // (vk_hostmath.hpp)
+    V.sh_x = A.sh_x; V.sh_y = A.sh_y; V.sh_z = A.sh_z;
+    V.kx = A.kx; V.ky = A.ky; V.kz = A.kz;
+    V.c0 = A.c0;
+    V.max_off = A.max_off;
     return commit_volume(ctx, nb);
 }
 

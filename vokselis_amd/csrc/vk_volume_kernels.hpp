@@ -13,16 +13,9 @@ namespace vk {
 // Built once per volume (two copies back to back: cell units, then byte offsets) ...
 __global__ __launch_bounds__(256) void build_cell_luts_kernel(uint32_t *__restrict__ out, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t nbx,
                                                                uint32_t nby, uint32_t byte_shift) {
-    const uint32_t n0 = nx + 3u, n1 = ny + 3u, n2 = nz + 3u, total = n0 + n1 + n2, padded = cell_lut_entries(nx, ny, nz);
+    const uint32_t padded = cell_lut_entries(nx, ny, nz);
     for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < padded; e += gridDim.x * blockDim.x) {
-        uint32_t v = 0;
-        if (e < total) {
-            uint32_t j = e, n = n0, brick_mul = 64u, cell_mul = 1u;
-            if (e >= n0 + n1) { j = e - n0 - n1; n = n2; brick_mul = 64u * nbx * nby; cell_mul = 16u; }
-            else if (e >= n0) { j = e - n0; n = n1; brick_mul = 64u * nbx; cell_mul = 4u; }
-            const uint32_t c = min(max(j, 1u), n - 2u) - 1u;  // cell coordinate i + 1 in [0, n_vox]
-            v = brick_mul * ((c + 3u) >> 2) + cell_mul * ((c + 3u) & 3u);
-        }
+        const uint32_t v = cell_lut_entry(e, nx, ny, nz, nbx, nby);  // (vk_hostmath.hpp: the entry's value, held to the march's indices on the CPU)
         out[e] = v;
         out[padded + e] = v << byte_shift;
     }
