@@ -188,14 +188,14 @@ static void fuzz_gather() {
     std::vector<uint32_t> tile_max(tiles, 0u);
     for (uint32_t t = 0; t < tiles; t++) {
         uint32_t tx, ty, tz;
-        thick_tile_coords(t, V.nt[0], V.nt[1], tx, ty, tz);
+        tile_coords(t, V.nt[0], V.nt[1], tx, ty, tz);
         CHECK(thick_tile_index(tx, ty, tz, V.nt[0], V.nt[1]) == t, "tile numbering");
         for_box(thick_tile_box(tx, ty, tz, V.n[0], V.n[1], V.n[2]), [&](const uint32_t v[3]) { tile_max[t] = std::max(tile_max[t], dc[V.index(v)]); });
     }
     uint64_t written = 0;
     for (uint32_t t = 0; t < tiles; t++) {
         uint32_t tx, ty, tz;
-        thick_tile_coords(t, V.nt[0], V.nt[1], tx, ty, tz);
+        tile_coords(t, V.nt[0], V.nt[1], tx, ty, tz);
         const ThickBox out = thick_tile_box(tx, ty, tz, V.n[0], V.n[1], V.n[2]);
         std::vector<uint32_t> mine;  // the tile's voxels
         for_box(out, [&](const uint32_t v[3]) { mine.push_back(V.index(v)); });
@@ -219,7 +219,7 @@ static void fuzz_gather() {
             for (uint32_t s : walk) {
                 if (lowest >= C) break;
                 uint32_t sx, sy, sz;
-                thick_tile_coords(s, V.nt[0], V.nt[1], sx, sy, sz);
+                tile_coords(s, V.nt[0], V.nt[1], sx, sy, sz);
                 const ThickBox src = thick_tile_box(sx, sy, sz, V.n[0], V.n[1], V.n[2]);
                 if (thick_tile_skipped(tile_max[s], thick_box_box_d2(src, out, V.w), lowest)) continue;
                 struct Entry { int32_t p[3]; uint32_t dc; };

@@ -23,7 +23,7 @@ extern "C" uint64_t thick_count(const uint32_t *d2, const uint32_t *t2, uint32_t
 #pragma omp parallel for schedule(dynamic, 64)
     for (int64_t t = 0; t < (int64_t)tiles; t++) {
         uint32_t tx, ty, tz;
-        thick_tile_coords((uint32_t)t, ntx, nty, tx, ty, tz);
+        tile_coords((uint32_t)t, ntx, nty, tx, ty, tz);
         const ThickBox b = thick_tile_box(tx, ty, tz, nx, ny, nz);
         uint32_t top = 0u;
         for (uint32_t z = b.lo[2]; z <= b.hi[2]; z++) for (uint32_t y = b.lo[1]; y <= b.hi[1]; y++) for (uint32_t x = b.lo[0]; x <= b.hi[0]; x++) top = std::max(top, dc_at(x, y, z));
@@ -33,7 +33,7 @@ extern "C" uint64_t thick_count(const uint32_t *d2, const uint32_t *t2, uint32_t
 #pragma omp parallel for schedule(dynamic, 16) reduction(+ : tested, accepted, entries, walking, wrong)
     for (int64_t t = 0; t < (int64_t)tiles; t++) {
         uint32_t tx, ty, tz;
-        thick_tile_coords((uint32_t)t, ntx, nty, tx, ty, tz);
+        tile_coords((uint32_t)t, ntx, nty, tx, ty, tz);
         const ThickBox out = thick_tile_box(tx, ty, tz, nx, ny, nz);
         struct Voxel { int32_t q[3]; uint32_t best; bool fg; uint64_t at; };
         std::vector<Voxel> mine;

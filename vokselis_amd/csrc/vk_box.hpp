@@ -1,5 +1,6 @@
 // vk_box.hpp -- a voxel box against a volume, for every pass that works on one (the histogram, the mesh extraction): whether a caller's
-// box is valid, its voxel count, the clip box as a voxel box; and the index of a voxel in a dense x-fastest array.  Host and device,
+// box is valid, its voxel count, the clip box as a voxel box; the index of a voxel in a dense x-fastest array, and a tile's coordinates
+// from its number (the thickness, geodesic and skeleton passes, and tests/thick_fuzz.cpp and tools/thick_evals.cpp).  Host and device,
 // no HIP in the host part: shared with the host fuzzes (tests/hist_fuzz.cpp, tests/mesh_fuzz.cpp, plain g++ under ASan / UBSan).
 #pragma once
 
@@ -19,6 +20,14 @@ namespace vk {
 
 // voxel (x, y, z) of a dense array of nx x ny x nz, x fastest: the LINEAR layouts, and every dense output
 VK_BOX_HD uint64_t voxel_index(uint32_t x, uint32_t y, uint32_t z, uint32_t nx, uint32_t ny) { return (uint64_t)x + (uint64_t)nx * ((uint64_t)y + (uint64_t)ny * (uint64_t)z); }
+// ... and back, for a pass that cuts the volume into tiles: tile number t of ntx x nty x ... tiles, x fastest, as its three (the counts by
+// reference: a kernel that keeps them in its descriptor reads them where the divisions stand, as if they were written there)
+VK_BOX_HD void tile_coords(uint32_t t, const uint32_t &ntx, const uint32_t &nty, uint32_t &tx, uint32_t &ty, uint32_t &tz) {
+    const uint32_t row = t / ntx;
+    tx = t - row * ntx;
+    tz = row / nty;
+    ty = row - tz * nty;
+}
 
 // A box against the volume: not inverted, inside.
 inline bool voxel_box_ok(const vk_voxel_box &b, uint32_t nx, uint32_t ny, uint32_t nz) {

@@ -8,7 +8,9 @@
 #include "vk_box.hpp"
 #include "vk_ctx.hpp"
 
+#include <algorithm>
 #include <type_traits>
+#include <vector>
 
 namespace vk {
 
@@ -67,7 +69,8 @@ void with_table_layout(const vk_ctx *ctx, bool skip, bool safe, F &&f) {
     }
 }
 
-// ---- the passes that are not a march (slice, histogram, mesh, filter, label, distance, resample, split): kernels on the seven scalar kinds of has_table_layout ----------
+// ---- the passes that are not a march (slice, histogram, mesh, filter, label, distance, resample, split, measure, thickness, geodesic,
+// skeleton): kernels on the seven scalar kinds of has_table_layout ----------
 // f(VOL) over those kinds.  A caller whose kernel covers fewer of them says so with `if constexpr` in its lambda: nothing else is instantiated.
 template <class F>
 void with_scalar_kind(int kind, F &&f) {
@@ -131,12 +134,40 @@ struct PassCall {
     template <class F>
     void phase(bool timed, F &&launch) {
         if (timed && e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
-        if (e == hipSuccess) { launch(); if (e == hipSuccess) e = hipGetLastError(); }
+        enqueue(launch);
         if (timed && e == hipSuccess) {
             e = hipEventRecord(ctx->ev1, ctx->stream);
             ctx->timing_open = false;
             ctx->timing_done = true;
         }
+    }
+    // launch() and the look at its HIP error, skipped once the call has one
+    template <class F>
+    void enqueue(F &&launch) {
+        if (e == hipSuccess) { launch(); if (e == hipSuccess) e = hipGetLastError(); }
+    }
+    // The batched fixed-point loop of a pass whose rounds run until one changes nothing, the one place where such a pass waits for the
+    // device in the middle of a call: B rounds are enqueued blind, then the host reads the W counts each left and stops at the first
+    // that says it was the last; the pass sees to it that the rounds behind that one in its batch found nothing to do.  counts: B * W
+    // words on the device.  round(r, slot): the launches of round r = 0, 1, ... (each behind enqueue where there are several), which add
+    // to slot[0 .. W).  last(c): takes one round's counts into the caller's totals and says whether it was the last; called in the rounds'
+    // order, never for a round behind the last.  budget: 0, or the most rounds to run -- the only thing that cuts a batch short.  The
+    // loop is a phase of the call (timed).
+    template <uint32_t B, uint32_t W, class R, class L>
+    void iterate(bool timed, unsigned long long *counts, uint32_t budget, R &&round, L &&last) {
+        phase(timed, [&] {
+            uint32_t r = 0u;
+            for (bool done = false; !done && e == hipSuccess;) {
+                const uint32_t batch = budget ? std::min<uint32_t>(B, budget - r) : B;
+                if (batch == 0u) break;
+                unsigned long long got[B * W] = {};
+                e = hipMemsetAsync(counts, 0, sizeof got, ctx->stream);
+                for (uint32_t k = 0; k < batch; k++, r++) enqueue([&] { round(r, counts + (size_t)k * W); });
+                download(got, counts, sizeof got);
+                if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+                for (uint32_t k = 0; k < batch && e == hipSuccess && !done; k++) done = last(got + (size_t)k * W);
+            }
+        });
     }
     // an output the caller may not have asked for (dst NULL), behind the kernels on the stream
     void download(void *dst, const void *src, size_t bytes) {
@@ -150,6 +181,27 @@ struct PassCall {
     // d_out becomes the volume: the build runs on the same stream behind the kernel, adopts or frees d_out, and commits only when it
     // stands: the old volume stays otherwise
     int install(DeviceTemp &d_out, uint32_t nx, uint32_t ny, uint32_t nz, int format, int layout) { return install_dense(ctx, d_out.release(), nx, ny, nz, format, layout); }
+};
+
+// Partial totals per workgroup (the kernels' half: vk_pass_blocks.hpp): a counting kernel runs at most kPassMaxPartials workgroups, each
+// writes a row of `words` 64-bit words, and the host folds the rows.  One object per counting kernel: the bytes of its device buffer, the
+// download behind the kernel and, once finish has run the stream dry, column k's total.
+constexpr uint32_t kPassMaxPartials = 8192;
+struct PassPartials {
+    typedef unsigned long long word;
+    uint32_t rows, words;  // rows: the counting kernel's workgroups
+    std::vector<word> v;
+    PassPartials(uint32_t rows, uint32_t words) : rows(rows), words(words), v((size_t)rows * words) {}
+    size_t bytes() const { return v.size() * 8u; }
+    void download(PassCall &call, const void *src) { call.download(v.data(), src, bytes()); }
+    template <class OP>
+    word fold(uint32_t k, word s, OP op) const {
+        for (uint32_t b = 0; b < rows; b++) s = op(s, v[(size_t)words * b + k]);
+        return s;
+    }
+    word sum(uint32_t k) const { return fold(k, 0ull, [](word a, word b) { return a + b; }); }
+    word max(uint32_t k) const { return fold(k, 0ull, [](word a, word b) { return std::max(a, b); }); }
+    word min(uint32_t k) const { return fold(k, ~0ull, [](word a, word b) { return std::min(a, b); }); }
 };
 
 // Dynamic LDS of a cell kernel (vk_march_kernel_body.hpp) -- the fast path of the cell layouts keeps its per-axis index tables there

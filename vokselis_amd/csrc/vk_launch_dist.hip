@@ -18,9 +18,8 @@
 // 2 n and n (vk_dist.hpp).  The counts reach memory as per-workgroup partial results that the host adds: no global atomics at all.
 #include "vk_dist_launch.hpp"
 #include "vk_label.hpp"
+#include "vk_pass_blocks.hpp"
 #include "vk_texel.hpp"
-
-#include <vector>
 
 using namespace vk;
 
@@ -121,7 +120,7 @@ __global__ __launch_bounds__(kDistThreads) void dist_stats_kernel(const DistDesc
         if (v != kDistInf && v > top) top = v;
     }
     block_add(&s_zeros, zeros);
-    for (int d = warpSize / 2; d > 0; d >>= 1) { const uint32_t o = (uint32_t)__shfl_down((int)top, d); top = o > top ? o : top; }
+    top = wave_reduce(top, WaveMax());
     if ((threadIdx.x & (warpSize - 1)) == 0 && top) atomicMax(&s_max, top);
     __syncthreads();
     if (threadIdx.x == 0) { partial[2u * blockIdx.x] = s_zeros; partial[2u * blockIdx.x + 1u] = s_max; }
@@ -145,8 +144,7 @@ __global__ __launch_bounds__(kDistThreads) void dist_mask_kernel(const DistVolum
         store_texel_bits<texel_class(VOL)>(out, i, bits);
     }
     block_add(&s_n[0], n_s); block_add(&s_n[1], n_m); block_add(&s_n[2], n_add); block_add(&s_n[3], n_rem);
-    __syncthreads();
-    if (threadIdx.x < kDistMaskWords) partial[(size_t)kDistMaskWords * blockIdx.x + threadIdx.x] = s_n[threadIdx.x];
+    publish_partials<kDistMaskWords>(partial, s_n);
 }
 
 // ---- a round's launches, written once: vk_distance_transform brackets them with its timing phases, dist_launch_inside (vk_dist_launch.hpp)
@@ -157,7 +155,7 @@ static DistGrids dist_grids(const vk_ctx *ctx, const DistDesc &D) {
     DistGrids G;
     G.column = blocks_for(D.slice); G.y = blocks_for((uint64_t)D.nx * D.nz); G.x = blocks_for((uint64_t)D.ny * D.nz);
     G.tile = label_blocks((uint64_t)((D.nx + kDistTile - 1u) / kDistTile) * ((D.ny + kDistTile - 1u) / kDistTile) * D.nz, ctx->dist_max_blocks);
-    G.voxel = std::min<uint32_t>(blocks_for(D.n), 8192u);  // the counting kernels: a partial result per workgroup
+    G.voxel = std::min<uint32_t>(blocks_for(D.n), kPassMaxPartials);  // the counting kernels: a partial result per workgroup
     return G;
 }
 // the columns of the volume's predicate into a
@@ -239,13 +237,13 @@ int vk_distance_transform(vk_ctx *ctx, const vk_distance_request *req, const vk_
     //  1 column, 2 line y, 3 line x of the first round, 4 .. 6 of the second, 7 stats or mask)
     const uint32_t timing = ctx->dist_timing;
 
-    const uint32_t words = morph ? kDistMaskWords : kDistStatsWords;
     const size_t dense_bytes = pass_dense_bytes(ctx->format, n);
     DeviceTemp d_a, d_b, d_stack, d_partial, d_out;
     if (int rc = call.alloc(d_a, (size_t)n * 4u, "the distance array")) return rc;
     if (int rc = call.alloc(d_b, (size_t)n * 4u, "the second distance array")) return rc;
     if (int rc = call.alloc(d_stack, (size_t)n * 4u, "the envelope stacks")) return rc;
-    if (int rc = call.alloc(d_partial, (size_t)voxel_blocks * words * 8u, "the partial counts")) return rc;
+    PassPartials sums(voxel_blocks, morph ? kDistMaskWords : kDistStatsWords);
+    if (int rc = call.alloc(d_partial, sums.bytes(), "the partial counts")) return rc;
     if (dense_out || install)
         if (int rc = call.alloc(d_out, dense_bytes, "the output buffer")) return rc;
     uint32_t *a = (uint32_t *)d_a.p, *b = (uint32_t *)d_b.p, *stack = (uint32_t *)d_stack.p;
@@ -270,18 +268,17 @@ int vk_distance_transform(vk_ctx *ctx, const vk_distance_request *req, const vk_
             });
     });
 
-    std::vector<unsigned long long> sums((size_t)voxel_blocks * words);
-    call.download(sums.data(), partial, sums.size() * 8u);
+    sums.download(call, partial);
     call.download(d2_out, a, (size_t)n * 4u);
     call.download(dense_out, d_out.p, dense_bytes);
     if (int rc = call.finish()) return rc;
     if (result) {
         vk_distance_result r{};
         if (morph) {
-            for (uint32_t k = 0; k < voxel_blocks; k++) { r.n_foreground += sums[4u * k]; r.n_result += sums[4u * k + 1u]; r.n_added += sums[4u * k + 2u]; r.n_removed += sums[4u * k + 3u]; }
+            r.n_foreground = sums.sum(0u); r.n_result = sums.sum(1u); r.n_added = sums.sum(2u); r.n_removed = sums.sum(3u);
         } else {
-            uint64_t zeros = 0;
-            for (uint32_t k = 0; k < voxel_blocks; k++) { zeros += sums[2u * k]; r.max_d2 = std::max(r.max_d2, (uint32_t)sums[2u * k + 1u]); }
+            const uint64_t zeros = sums.sum(0u);
+            r.max_d2 = (uint32_t)sums.max(1u);
             r.n_foreground = r.n_result = D.complement ? n - zeros : zeros;  // D2 is 0 exactly on the target
         }
         *result = r;

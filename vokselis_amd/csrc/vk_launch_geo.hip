@@ -27,13 +27,12 @@
 // geo_relax_kernel's registers, LDS and occupancy, from hipcc -S for gfx950: the kernel's comment.
 #include "vk_geo.hpp"
 #include "vk_launch.hpp"
+#include "vk_pass_blocks.hpp"
 #include "vk_texel.hpp"
-
-#include <vector>
 
 using namespace vk;
 
-constexpr uint32_t kGeoVoxelThreads = 256, kGeoStatsWords = 6, kGeoSeedWords = 2, kGeoMaxPartials = 8192;
+constexpr uint32_t kGeoVoxelThreads = 256, kGeoStatsWords = 6, kGeoSeedWords = 2;
 
 struct GeoDesc {
     uint32_t nx, ny, nz, conn_sum;
@@ -57,16 +56,6 @@ struct GeoLds {
     static __device__ __forceinline__ void store(uint32_t *p, uint32_t i, uint32_t v) { __hip_atomic_store(p + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 };
 
-__device__ __forceinline__ uint32_t geo_wave_or(uint32_t v) {
-    for (int d = warpSize / 2; d > 0; d >>= 1) v |= (uint32_t)__shfl_down((int)v, d);
-    return v;
-}
-__device__ __forceinline__ void geo_tile_coords(const GeoDesc &G, uint32_t t, uint32_t &tx, uint32_t &ty, uint32_t &tz) {
-    const uint32_t row = t / G.ntx;
-    tx = t - row * G.ntx;
-    tz = row / G.nty;
-    ty = row - tz * G.nty;
-}
 // the directions of s_dirs, by the first 27 threads: the tiles that exist take `stamp`.  Returns, in thread 0, how many were marked.
 __device__ __forceinline__ uint32_t geo_mark_tiles(const GeoDesc &G, uint32_t tx, uint32_t ty, uint32_t tz, uint32_t dirs, uint32_t *__restrict__ marks, uint32_t stamp) {
     bool marked = false;
@@ -89,7 +78,7 @@ __global__ __launch_bounds__(kLabelThreads) void geo_seed_kernel(const VolumeDes
         if (threadIdx.x == 0) s_dirs = 0u;
         __syncthreads();
         uint32_t tx, ty, tz;
-        geo_tile_coords(G, t, tx, ty, tz);
+        tile_coords(t, G.ntx, G.nty, tx, ty, tz);
         const uint32_t x0 = tx * kLabelTile.tx, y0 = ty * kLabelTile.ty, z0 = tz * kLabelTile.tz;
         uint32_t dirs = 0u;
         for (uint32_t k = 0; k < kLabelPerThread; k++) {
@@ -106,15 +95,14 @@ __global__ __launch_bounds__(kLabelThreads) void geo_seed_kernel(const VolumeDes
             n_fg += in_s; n_src += source;
             if (source) dirs |= geo_wake_mask(lx, ly, lz, G.conn_sum) | (1u << kLabelCentre);
         }
-        dirs = geo_wave_or(dirs);
+        dirs = wave_reduce(dirs, WaveOr());
         if ((threadIdx.x & (warpSize - 1)) == 0 && dirs) atomicOr(&s_dirs, dirs);
         __syncthreads();
         (void)geo_mark_tiles(G, tx, ty, tz, s_dirs, marks, 1u);
         __syncthreads();  // the next tile's reset
     }
     block_add(&s_n[0], n_fg); block_add(&s_n[1], n_src);
-    __syncthreads();
-    if (threadIdx.x < kGeoSeedWords) partial[(size_t)kGeoSeedWords * blockIdx.x + threadIdx.x] = s_n[threadIdx.x];
+    publish_partials<kGeoSeedWords>(partial, s_n);
 }
 
 // One round (G.round).  marks_cur: the tiles of this round; marks_next: those of the next.  counts[0 .. 4): the tiles this round woke,
@@ -134,7 +122,7 @@ __global__ __launch_bounds__(kLabelThreads) void geo_relax_kernel(const GeoDesc 
     for (uint32_t t = blockIdx.x; t < G.tiles; t += gridDim.x) {  // block-uniform
         if (marks_cur[t] != G.round) continue;                     // block-uniform: nobody writes marks_cur in this launch
         uint32_t tx, ty, tz;
-        geo_tile_coords(G, t, tx, ty, tz);
+        tile_coords(t, G.ntx, G.nty, tx, ty, tz);
         const uint32_t x0 = tx * kLabelTile.tx, y0 = ty * kLabelTile.ty, z0 = tz * kLabelTile.tz;
         // the window: the tile's words and the halo's, VK_GEO_INF outside the volume.  A halo word may be the value of before its owner's
         // store in this launch.
@@ -189,7 +177,7 @@ __global__ __launch_bounds__(kLabelThreads) void geo_relax_kernel(const GeoDesc 
             dirs |= geo_wake_mask(lx, ly, lz, CONN_SUM);
             stored++;
         }
-        dirs = geo_wave_or(dirs);
+        dirs = wave_reduce(dirs, WaveOr());
         if ((threadIdx.x & (warpSize - 1)) == 0 && dirs) atomicOr(&s_dirs, dirs);
         block_add(&s_written, stored);
         __syncthreads();
@@ -204,10 +192,6 @@ __global__ __launch_bounds__(kLabelThreads) void geo_relax_kernel(const GeoDesc 
     }
 }
 
-__device__ __forceinline__ void geo_block_add(unsigned long long *slot, unsigned long long s) {
-    for (int d = warpSize / 2; d > 0; d >>= 1) s += __shfl_down(s, d);
-    if ((threadIdx.x & (warpSize - 1)) == 0 && s) atomicAdd(slot, s);
-}
 // partial[6 b + ...]: n_reached, n_saturated, sum_g, max_g, target_min, n_target_reached over workgroup b's voxels
 __global__ __launch_bounds__(kGeoVoxelThreads) void geo_stats_kernel(const GeoDesc G, const uint32_t *__restrict__ state, const uint8_t *__restrict__ fg, unsigned long long *__restrict__ partial) {
     __shared__ unsigned long long s_n[4];
@@ -226,23 +210,15 @@ __global__ __launch_bounds__(kGeoVoxelThreads) void geo_stats_kernel(const GeoDe
         label_coords((uint32_t)i, G.nx, G.ny, x, y, z);
         if (geo_on_faces(x, y, z, G.box, G.target_faces)) { n_target++; low = g < low ? g : low; }
     }
-    geo_block_add(&s_n[0], n_reached); geo_block_add(&s_n[1], n_sat); geo_block_add(&s_n[2], sum); geo_block_add(&s_n[3], n_target);
+    block_add(&s_n[0], n_reached); block_add(&s_n[1], n_sat); block_add(&s_n[2], sum); block_add(&s_n[3], n_target);
     if (top) atomicMax(&s_max, top);
     if (low != kGeoInf) atomicMin(&s_min, low);
-    __syncthreads();
-    if (threadIdx.x < 3u) partial[(size_t)kGeoStatsWords * blockIdx.x + threadIdx.x] = s_n[threadIdx.x];
+    publish_partials<kGeoStatsWords, 3u>(partial, s_n);
     if (threadIdx.x == 3u) partial[(size_t)kGeoStatsWords * blockIdx.x + 3u] = s_max;
     if (threadIdx.x == 4u) partial[(size_t)kGeoStatsWords * blockIdx.x + 4u] = s_min;
     if (threadIdx.x == 5u) partial[(size_t)kGeoStatsWords * blockIdx.x + 5u] = s_n[3];
 }
 
-// F of a value, as label_fill_bits forms it
-template <int CLASS>
-__device__ __forceinline__ uint32_t geo_store_bits(float v) {
-    if constexpr (CLASS == TEXEL_U8) return filter_store_unorm(v * 255.0f, 255.0f);
-    else if constexpr (CLASS == TEXEL_U16) return filter_store_unorm(v * 65535.0f, 65535.0f);
-    else return filter_store_f16(v);
-}
 template <int CLASS>
 __global__ __launch_bounds__(kGeoVoxelThreads) void geo_dense_kernel(const GeoDesc G, const uint32_t *__restrict__ state, const uint8_t *__restrict__ fg, void *__restrict__ out) {
     for (uint64_t i = (uint64_t)blockIdx.x * kGeoVoxelThreads + threadIdx.x; i < G.n; i += (uint64_t)gridDim.x * kGeoVoxelThreads) {
@@ -251,7 +227,7 @@ __global__ __launch_bounds__(kGeoVoxelThreads) void geo_dense_kernel(const GeoDe
         if (fg[i] && g != kGeoInf) {
             const float f = (float)g;  // one rounding to nearest even
             const float w = f * G.gain;
-            bits = geo_store_bits<CLASS>(w);
+            bits = store_gained_bits<CLASS>(w);
         }
         store_texel_bits<CLASS>(out, i, bits);
     }
@@ -288,14 +264,14 @@ int vk_geodesic_distance(vk_ctx *ctx, const vk_geodesic_request *req, const vk_v
     G.n = n;
     G.W = geo_weights(req->spacing, G.conn_sum);
     const uint32_t tile_blocks = F.blocks;
-    const uint32_t seed_blocks = std::min<uint32_t>(tile_blocks, kGeoMaxPartials);  // a set of partial results per workgroup
-    const uint32_t voxel_blocks = std::min<uint32_t>(label_blocks((n + kGeoVoxelThreads - 1u) / kGeoVoxelThreads, ctx->geo_max_blocks), kGeoMaxPartials);
+    const uint32_t seed_blocks = std::min<uint32_t>(tile_blocks, kPassMaxPartials);  // a set of partial results per workgroup
+    const uint32_t voxel_blocks = std::min<uint32_t>(label_blocks((n + kGeoVoxelThreads - 1u) / kGeoVoxelThreads, ctx->geo_max_blocks), kPassMaxPartials);
 
     const int kind = ctx->vol_kind;
     const VolumeDesc V = volume_desc(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     PassCall call{ctx, entry};
-    hipError_t &e = call.e;  // the rounds' loop looks at its launches itself
+    hipError_t &e = call.e;
     // (debug, vk_debug_set_param("geo_timing", k): phase k alone between the context's timer events, read with vk_timer_elapsed_ms --
     //  1 seed, 2 relax (every round, with the host's looks at the counts), 3 stats, 4 dense; 9: nothing is timed, and a call that
     //  succeeds leaves "geodesic: rounds R launches L visits V passes P stored S" as the context's last message)
@@ -307,8 +283,9 @@ int vk_geodesic_distance(vk_ctx *ctx, const vk_geodesic_request *req, const vk_v
     if (int rc = call.alloc(d_fg, (size_t)n, "the foreground bytes")) return rc;
     if (int rc = call.alloc(d_marks, (size_t)G.tiles * 8u, "the tile marks")) return rc;
     if (int rc = call.alloc(d_counts, (size_t)kGeoBatch * kGeoRoundWords * 8u, "the rounds' counts")) return rc;
-    if (int rc = call.alloc(d_seed, (size_t)seed_blocks * kGeoSeedWords * 8u, "the partial totals")) return rc;
-    if (int rc = call.alloc(d_partial, (size_t)voxel_blocks * kGeoStatsWords * 8u, "the partial totals")) return rc;
+    PassPartials seeds(seed_blocks, kGeoSeedWords), sums(voxel_blocks, kGeoStatsWords);
+    if (int rc = call.alloc(d_seed, seeds.bytes(), "the partial totals")) return rc;
+    if (int rc = call.alloc(d_partial, sums.bytes(), "the partial totals")) return rc;
     if (dense_out || install)
         if (int rc = call.alloc(d_out, dense_bytes, "the output buffer")) return rc;
     uint32_t *state = (uint32_t *)d_state.p, *marks[2] = {(uint32_t *)d_marks.p, (uint32_t *)d_marks.p + G.tiles};
@@ -323,54 +300,38 @@ int vk_geodesic_distance(vk_ctx *ctx, const vk_geodesic_request *req, const vk_v
         });
     });
 
-    // The rounds.  Every batch but the last wakes a tile in each of its rounds; a round that wakes none leaves no active tile for the
-    // rounds behind it in the batch, which exit at once: the state holds the fixed point when the batch is over.
+    // The rounds (PassCall::iterate).  Every batch but the last wakes a tile in each of its rounds; a round that wakes none leaves no
+    // active tile for the rounds behind it in the batch, which exit at once: the state holds the fixed point when the batch is over.
     unsigned long long rounds = 0ull, launches = 0ull, visits = 0ull, passes = 0ull, stored = 0ull;
-    call.phase(timing == 2u, [&] {
-        uint32_t round = 1u;
-        for (bool done = false; !done && e == hipSuccess;) {
-            unsigned long long got[kGeoBatch * kGeoRoundWords] = {};
-            e = hipMemsetAsync(counts, 0, sizeof got, ctx->stream);
-            for (uint32_t k = 0; k < kGeoBatch && e == hipSuccess; k++, round++) {
-                G.round = round;
-                const uint32_t *cur = marks[round & 1u];
-                uint32_t *next = marks[(round + 1u) & 1u];
-                unsigned long long *slot = counts + (size_t)k * kGeoRoundWords;
-                if (G.conn_sum == 1u) hipLaunchKernelGGL(geo_relax_kernel<1u>, dim3(tile_blocks), dim3(kLabelThreads), 0, ctx->stream, G, state, (const uint8_t *)fg, cur, next, slot);
-                else if (G.conn_sum == 2u) hipLaunchKernelGGL(geo_relax_kernel<2u>, dim3(tile_blocks), dim3(kLabelThreads), 0, ctx->stream, G, state, (const uint8_t *)fg, cur, next, slot);
-                else hipLaunchKernelGGL(geo_relax_kernel<3u>, dim3(tile_blocks), dim3(kLabelThreads), 0, ctx->stream, G, state, (const uint8_t *)fg, cur, next, slot);
-                e = hipGetLastError();
-                launches++;
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(got, counts, sizeof got, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            for (uint32_t k = 0; k < kGeoBatch && e == hipSuccess && !done; k++) {
-                const unsigned long long *c = got + (size_t)k * kGeoRoundWords;
-                visits += c[1]; passes += c[2]; stored += c[3];
-                if (c[1]) rounds++;
-                if (c[0] == 0ull) done = true;
-            }
-        }
-    });
+    call.iterate<kGeoBatch, kGeoRoundWords>(timing == 2u, counts, 0u,
+        [&](uint32_t r, unsigned long long *slot) {
+            G.round = r + 1u;
+            const uint32_t *cur = marks[G.round & 1u];
+            uint32_t *next = marks[(G.round + 1u) & 1u];
+            if (G.conn_sum == 1u) hipLaunchKernelGGL(geo_relax_kernel<1u>, dim3(tile_blocks), dim3(kLabelThreads), 0, ctx->stream, G, state, (const uint8_t *)fg, cur, next, slot);
+            else if (G.conn_sum == 2u) hipLaunchKernelGGL(geo_relax_kernel<2u>, dim3(tile_blocks), dim3(kLabelThreads), 0, ctx->stream, G, state, (const uint8_t *)fg, cur, next, slot);
+            else hipLaunchKernelGGL(geo_relax_kernel<3u>, dim3(tile_blocks), dim3(kLabelThreads), 0, ctx->stream, G, state, (const uint8_t *)fg, cur, next, slot);
+            launches++;
+        },
+        [&](const unsigned long long *c) {
+            visits += c[1]; passes += c[2]; stored += c[3];
+            if (c[1]) rounds++;
+            return c[0] == 0ull;
+        });
 
     call.phase(timing == 3u, [&] {
         hipLaunchKernelGGL(geo_stats_kernel, dim3(voxel_blocks), dim3(kGeoVoxelThreads), 0, ctx->stream, G, (const uint32_t *)state, (const uint8_t *)fg, (unsigned long long *)d_partial.p);
     });
-    std::vector<unsigned long long> seeds((size_t)seed_blocks * kGeoSeedWords), sums((size_t)voxel_blocks * kGeoStatsWords);
-    call.download(seeds.data(), d_seed.p, seeds.size() * 8u);
-    call.download(sums.data(), d_partial.p, sums.size() * 8u);
+    seeds.download(call, d_seed.p);
+    sums.download(call, d_partial.p);
     call.download(g_out, state, (size_t)n * 4u);
     if (int rc = call.finish()) return rc;
 
     vk_geodesic_result r{};
-    r.target_min = kGeoInf;
-    for (uint32_t k = 0; k < seed_blocks; k++) { r.n_foreground += seeds[2u * k]; r.n_sources += seeds[2u * k + 1u]; }
-    for (uint32_t k = 0; k < voxel_blocks; k++) {
-        const unsigned long long *s = sums.data() + (size_t)kGeoStatsWords * k;
-        r.n_reached += s[0]; r.n_saturated += s[1]; r.sum_g += s[2]; r.n_target_reached += s[5];
-        r.max_g = std::max(r.max_g, (uint32_t)s[3]);
-        r.target_min = std::min(r.target_min, (uint32_t)s[4]);
-    }
+    r.n_foreground = seeds.sum(0u); r.n_sources = seeds.sum(1u);
+    r.n_reached = sums.sum(0u); r.n_saturated = sums.sum(1u); r.sum_g = sums.sum(2u); r.n_target_reached = sums.sum(5u);
+    r.max_g = (uint32_t)sums.max(3u);
+    r.target_min = (uint32_t)std::min<unsigned long long>(kGeoInf, sums.min(4u));
     r.gain = req->gain != 0.0f ? req->gain : geo_auto_gain(r.max_g);
     G.gain = r.gain;
     if (dense_out || install) {

@@ -23,6 +23,7 @@
 // launch shape.  Plain C++; no inline assembly.  wave64 is assumed in measure_kernel (the ballot is 64 bits wide).
 #include "vk_label_launch.hpp"
 #include "vk_measure.hpp"
+#include "vk_pass_blocks.hpp"
 #include "vk_texel.hpp"
 
 #include <vector>

@@ -24,14 +24,13 @@
 // the tile number and the tile's stamp (no workgroup of the launch writes the array it is read from).  Plain C++; no inline assembly.
 // skel_thin_kernel's registers, LDS and occupancy, from hipcc -S for gfx950: the kernel's comment and profiles/skel_pass_isa.txt.
 #include "vk_launch.hpp"
+#include "vk_pass_blocks.hpp"
 #include "vk_skel.hpp"
 #include "vk_texel.hpp"
 
-#include <vector>
-
 using namespace vk;
 
-constexpr uint32_t kSkelVoxelThreads = 256, kSkelStatsWords = 5u + VK_SKEL_LINKS, kSkelMaxPartials = 8192;
+constexpr uint32_t kSkelVoxelThreads = 256, kSkelStatsWords = 5u + VK_SKEL_LINKS;
 constexpr uint32_t kSkelWinBytes = (kGeoWindow + 3u) & ~3u;
 
 struct SkelDesc {
@@ -50,13 +49,6 @@ struct SkelLds {
     static __device__ __forceinline__ uint32_t load(const uint8_t *p, uint32_t i) { return p[i]; }
 };
 
-__device__ __forceinline__ void skel_tile_coords(const SkelDesc &G, uint32_t t, uint32_t &tx, uint32_t &ty, uint32_t &tz) {
-    const uint32_t row = t / G.ntx;
-    tx = t - row * G.ntx;
-    tz = row / G.nty;
-    ty = row - tz * G.nty;
-}
-
 // state: the whole volume.  marks: the array of iteration 1.  partial[b]: |S| over workgroup b's tiles.
 template <int VOL>
 __global__ __launch_bounds__(kLabelThreads) void skel_seed_kernel(const VolumeDesc V, const SkelDesc G, uint8_t *__restrict__ state, uint32_t *__restrict__ marks,
@@ -69,7 +61,7 @@ __global__ __launch_bounds__(kLabelThreads) void skel_seed_kernel(const VolumeDe
         if (threadIdx.x == 0) s_any = 0u;
         __syncthreads();
         uint32_t tx, ty, tz;
-        skel_tile_coords(G, t, tx, ty, tz);
+        tile_coords(t, G.ntx, G.nty, tx, ty, tz);
         const uint32_t x0 = tx * kLabelTile.tx, y0 = ty * kLabelTile.ty, z0 = tz * kLabelTile.tz;
         bool any = false;
         for (uint32_t k = 0; k < kLabelPerThread; k++) {
@@ -88,8 +80,7 @@ __global__ __launch_bounds__(kLabelThreads) void skel_seed_kernel(const VolumeDe
         __syncthreads();  // the next tile's reset
     }
     block_add(&s_n, n_fg);
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = s_n;
+    publish_partials<1u>(partial, &s_n);
 }
 
 // One sub-pass (G.subpass) of one iteration (G.iteration).  marks_cur: the tiles of this iteration; marks_next: those of the next.
@@ -103,7 +94,7 @@ __global__ __launch_bounds__(kLabelThreads) void skel_thin_kernel(const SkelDesc
     for (uint32_t t = blockIdx.x; t < G.tiles; t += gridDim.x) {  // block-uniform
         if (marks_cur[t] != G.iteration) continue;                 // block-uniform: nobody writes marks_cur in this launch
         uint32_t tx, ty, tz;
-        skel_tile_coords(G, t, tx, ty, tz);
+        tile_coords(t, G.ntx, G.nty, tx, ty, tz);
         const uint32_t x0 = tx * kLabelTile.tx, y0 = ty * kLabelTile.ty, z0 = tz * kLabelTile.tz;
         // the window: the tile's bytes and the halo's, 0 outside the volume.  A halo byte of this sub-pass's subfield may be the value of
         // before or after its owner's store in this launch; no voxel's visit reads a byte of its own subfield but its own.
@@ -176,8 +167,7 @@ __global__ __launch_bounds__(kSkelVoxelThreads) void skel_stats_kernel(const Ske
         for (uint32_t above = m27 >> (kLabelCentre + 1u), j = 0; above; above >>= 1, j++)
             if (above & 1u) atomicAdd(&s_n[5u + j], 1ull);
     }
-    __syncthreads();
-    if (threadIdx.x < kSkelStatsWords) partial[(size_t)kSkelStatsWords * blockIdx.x + threadIdx.x] = s_n[threadIdx.x];
+    publish_partials<kSkelStatsWords>(partial, s_n);
 }
 
 template <int VOL>
@@ -224,14 +214,14 @@ int vk_skeletonize(vk_ctx *ctx, const vk_skeleton_request *req, const vk_voxel_b
     G.fill_out_bits = label_fill_bits(req->fill_out, ctx->format);
     G.n = n;
     const uint32_t tile_blocks = F.blocks;
-    const uint32_t seed_blocks = std::min<uint32_t>(tile_blocks, kSkelMaxPartials);  // a partial result per workgroup
-    const uint32_t voxel_blocks = std::min<uint32_t>(label_blocks((n + kSkelVoxelThreads - 1u) / kSkelVoxelThreads, ctx->skel_max_blocks), kSkelMaxPartials);
+    const uint32_t seed_blocks = std::min<uint32_t>(tile_blocks, kPassMaxPartials);  // a partial result per workgroup
+    const uint32_t voxel_blocks = std::min<uint32_t>(label_blocks((n + kSkelVoxelThreads - 1u) / kSkelVoxelThreads, ctx->skel_max_blocks), kPassMaxPartials);
 
     const int kind = ctx->vol_kind;
     const VolumeDesc V = volume_desc(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     PassCall call{ctx, entry};
-    hipError_t &e = call.e;  // the iterations' loop looks at its launches itself
+    hipError_t &e = call.e;
     // (debug, vk_debug_set_param("skel_timing", k): phase k alone between the context's timer events, read with vk_timer_elapsed_ms --
     //  1 seed, 2 thin (every sub-pass of every iteration, with the host's looks at the counts), 3 stats (with the classes), 4 dense;
     //  9: nothing is timed, and a call that succeeds leaves "skeleton: iterations I launches L visits V deleted D" as the context's last
@@ -243,8 +233,9 @@ int vk_skeletonize(vk_ctx *ctx, const vk_skeleton_request *req, const vk_voxel_b
     if (int rc = call.alloc(d_state, (size_t)n, "the state bytes")) return rc;
     if (int rc = call.alloc(d_marks, (size_t)G.tiles * 8u, "the tile stamps")) return rc;
     if (int rc = call.alloc(d_counts, (size_t)kSkelBatch * kSkelIterWords * 8u, "the iterations' counts")) return rc;
-    if (int rc = call.alloc(d_seed, (size_t)seed_blocks * 8u, "the partial totals")) return rc;
-    if (int rc = call.alloc(d_partial, (size_t)voxel_blocks * kSkelStatsWords * 8u, "the partial totals")) return rc;
+    PassPartials seeds(seed_blocks, 1u), sums(voxel_blocks, kSkelStatsWords);
+    if (int rc = call.alloc(d_seed, seeds.bytes(), "the partial totals")) return rc;
+    if (int rc = call.alloc(d_partial, sums.bytes(), "the partial totals")) return rc;
     if (class_out)
         if (int rc = call.alloc(d_class, (size_t)n, "the classes")) return rc;
     if (dense_out || install)
@@ -261,45 +252,33 @@ int vk_skeletonize(vk_ctx *ctx, const vk_skeleton_request *req, const vk_voxel_b
         });
     });
 
-    // The iterations, whole ones in batches.  An iteration that deletes nothing stamps no tile, so the iterations behind it in its batch
-    // exit at once and the state is the fixed point when the batch is over.
+    // The iterations, whole ones in batches (PassCall::iterate), max_iterations of them at most.  An iteration that deletes nothing stamps
+    // no tile, so the iterations behind it in its batch exit at once and the state is the fixed point when the batch is over.
     unsigned long long iterations = 0ull, launches = 0ull, visits = 0ull, deleted = 0ull;
     uint32_t converged = 0u;
-    call.phase(timing == 2u, [&] {
-        uint32_t it = 1u;
-        for (bool done = false; !done && e == hipSuccess;) {
-            uint32_t batch = kSkelBatch;
-            if (req->max_iterations) batch = std::min<uint32_t>(batch, req->max_iterations - (it - 1u));
-            if (batch == 0u) break;
-            unsigned long long got[kSkelBatch * kSkelIterWords] = {};
-            e = hipMemsetAsync(counts, 0, sizeof got, ctx->stream);
-            for (uint32_t k = 0; k < batch && e == hipSuccess; k++, it++) {
-                G.iteration = it;
-                for (uint32_t s = 0; s < 8u && e == hipSuccess; s++) {
+    call.iterate<kSkelBatch, kSkelIterWords>(timing == 2u, counts, req->max_iterations,
+        [&](uint32_t r, unsigned long long *slot) {
+            const uint32_t it = r + 1u;
+            G.iteration = it;
+            for (uint32_t s = 0; s < 8u; s++)
+                call.enqueue([&] {
                     G.subpass = s;
-                    hipLaunchKernelGGL(skel_thin_kernel, dim3(tile_blocks), dim3(kLabelThreads), 0, ctx->stream, G, state, (const uint32_t *)marks[it & 1u], marks[(it + 1u) & 1u],
-                                       counts + (size_t)k * kSkelIterWords);
-                    e = hipGetLastError();
+                    hipLaunchKernelGGL(skel_thin_kernel, dim3(tile_blocks), dim3(kLabelThreads), 0, ctx->stream, G, state, (const uint32_t *)marks[it & 1u], marks[(it + 1u) & 1u], slot);
                     launches++;
-                }
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(got, counts, sizeof got, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            for (uint32_t k = 0; k < batch && e == hipSuccess && !done; k++) {
-                const unsigned long long *c = got + (size_t)k * kSkelIterWords;
-                visits += c[1]; deleted += c[0];
-                if (c[0]) iterations++;
-                else { converged = 1u; done = true; }
-            }
-        }
-    });
+                });
+        },
+        [&](const unsigned long long *c) {
+            visits += c[1]; deleted += c[0];
+            if (c[0]) iterations++;
+            else converged = 1u;
+            return c[0] == 0ull;
+        });
 
     call.phase(timing == 3u, [&] {
         hipLaunchKernelGGL(skel_stats_kernel, dim3(voxel_blocks), dim3(kSkelVoxelThreads), 0, ctx->stream, G, (const uint8_t *)state, (uint8_t *)d_class.p, (unsigned long long *)d_partial.p);
     });
-    std::vector<unsigned long long> seeds((size_t)seed_blocks), sums((size_t)voxel_blocks * kSkelStatsWords);
-    call.download(seeds.data(), d_seed.p, seeds.size() * 8u);
-    call.download(sums.data(), d_partial.p, sums.size() * 8u);
+    seeds.download(call, d_seed.p);
+    sums.download(call, d_partial.p);
     call.download(class_out, d_class.p, (size_t)n);
     if (dense_out || install) {
         call.phase(timing == 4u, [&] {
@@ -312,12 +291,9 @@ int vk_skeletonize(vk_ctx *ctx, const vk_skeleton_request *req, const vk_voxel_b
     if (int rc = call.finish()) return rc;
 
     vk_skeleton_result r{};
-    for (uint32_t k = 0; k < seed_blocks; k++) r.n_foreground += seeds[k];
-    for (uint32_t k = 0; k < voxel_blocks; k++) {
-        const unsigned long long *s = sums.data() + (size_t)kSkelStatsWords * k;
-        r.n_skeleton += s[0]; r.n_isolated += s[1]; r.n_end += s[2]; r.n_regular += s[3]; r.n_junction += s[4];
-        for (uint32_t j = 0; j < (uint32_t)VK_SKEL_LINKS; j++) r.links[j] += s[5u + j];
-    }
+    r.n_foreground = seeds.sum(0u);
+    r.n_skeleton = sums.sum(0u); r.n_isolated = sums.sum(1u); r.n_end = sums.sum(2u); r.n_regular = sums.sum(3u); r.n_junction = sums.sum(4u);
+    for (uint32_t j = 0; j < (uint32_t)VK_SKEL_LINKS; j++) r.links[j] = sums.sum(5u + j);
     r.iterations = (uint32_t)iterations;
     r.converged = converged;
     if (result) *result = r;

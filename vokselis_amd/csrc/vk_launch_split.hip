@@ -20,15 +20,13 @@
 // kernel here reads an address that another thread of the same launch writes.  Plain C++; no inline assembly.
 #include "vk_dist_launch.hpp"
 #include "vk_label_launch.hpp"
+#include "vk_pass_blocks.hpp"
 #include "vk_split.hpp"
 #include "vk_texel.hpp"
 
 #include <utility>
-#include <vector>
 
 using namespace vk;
-
-constexpr uint32_t kSplitMaxPartials = 8192;  // the cut kernel's grid: one partial sum per workgroup
 
 struct SplitPlainLoad {
     static __device__ __forceinline__ uint32_t load(const uint32_t *p, uint32_t i) { return p[i]; }
@@ -129,8 +127,7 @@ __global__ __launch_bounds__(kLabelThreads) void split_cut_kernel(const VolumeDe
         }
     }
     block_add(&s_n, mine);
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = s_n;
+    publish_partials<1u>(partial, &s_n);
 }
 
 extern "C" {
@@ -167,13 +164,12 @@ int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel
     D.lo_k = lo_k; D.hi_k = hi_k;
     D.fill_bits = label_fill_bits(req->fill_out, ctx->format);
     const uint32_t chunk_blocks = label_blocks(D.chunks, ctx->label_max_blocks);
-    const uint32_t cut_blocks = std::min(chunk_blocks, kSplitMaxPartials);
+    const uint32_t cut_blocks = std::min(chunk_blocks, kPassMaxPartials);  // the cut kernel's grid: one partial sum per workgroup
     const uint64_t r2 = dist_r2(req->radius);  // <= VK_DIST_MAX_RADIUS^2 < VK_DIST_INF: r2 + 1 fits in a word
 
     const VolumeDesc V = volume_desc(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     PassCall call{ctx, entry};
-    hipError_t &e = call.e;  // the growth loop looks at its launches itself
     // (debug, vk_debug_set_param("split_timing", k): phase k alone between the context's timer events, read with vk_timer_elapsed_ms --
     //  1 distance, 2 markers, 3 growth (every round, with the host's looks at the counts), 4 residue, 5 merge, 6 number and stats, 7 cut)
     const uint32_t timing = ctx->split_timing;
@@ -186,7 +182,8 @@ int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel
     if (int rc = call.alloc(d_chunk_fg, (size_t)D.chunks * 4u, "the chunk counts")) return rc;
     if (int rc = call.alloc(d_totals, 48u, "the totals")) return rc;
     if (int rc = call.alloc(d_counts, (size_t)kSplitBatch * 8u, "the rounds' counts")) return rc;
-    if (int rc = call.alloc(d_partial, (size_t)cut_blocks * 8u, "the partial counts")) return rc;
+    PassPartials sums(cut_blocks, 1u);
+    if (int rc = call.alloc(d_partial, sums.bytes(), "the partial counts")) return rc;
     uint32_t *a = (uint32_t *)d_a.p, *chunk_roots = (uint32_t *)d_chunk_roots.p, *chunk_fg = (uint32_t *)d_chunk_fg.p;
     unsigned long long *d_tot = (unsigned long long *)d_totals.p, *counts = (unsigned long long *)d_counts.p;
 
@@ -201,26 +198,18 @@ int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel
         hipLaunchKernelGGL(split_seed_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, (const uint32_t *)a, cur);
     });
 
-    // The growth.  Every batch but the last labels at least one voxel in each of its rounds, and S is finite: the loop ends.  A round that
-    // labels nothing copies the state, and so does every round after it: `cur` holds the fixed point when the batch is over.
+    // The growth (PassCall::iterate).  Every batch but the last labels at least one voxel in each of its rounds, and S is finite: the loop
+    // ends.  A round that labels nothing copies the state, and so does every round after it: `cur` holds the fixed point when the batch is over.
     uint32_t rounds = 0u;
-    call.phase(timing == 3u, [&] {
-        for (bool done = false; !done && e == hipSuccess;) {
-            unsigned long long got[kSplitBatch] = {};
-            e = hipMemsetAsync(counts, 0, sizeof got, ctx->stream);
-            for (uint32_t k = 0; k < kSplitBatch && e == hipSuccess; k++) {
-                hipLaunchKernelGGL(split_grow_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, (const uint32_t *)cur, other, counts + k);
-                e = hipGetLastError();
-                std::swap(cur, other);
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(got, counts, sizeof got, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            for (uint32_t k = 0; k < kSplitBatch && e == hipSuccess && !done; k++) {
-                if (got[k] == 0ull) done = true;
-                else rounds++;
-            }
-        }
-    });
+    call.iterate<kSplitBatch, 1u>(timing == 3u, counts, 0u,
+        [&](uint32_t, unsigned long long *slot) {
+            hipLaunchKernelGGL(split_grow_kernel, dim3(chunk_blocks), dim3(kLabelThreads), 0, ctx->stream, D, (const uint32_t *)cur, other, slot);
+            std::swap(cur, other);
+        },
+        [&](const unsigned long long *c) {
+            if (c[0]) rounds++;
+            return c[0] == 0ull;
+        });
 
     // what no marker reached, labelled on its own into `other`; then the merged parent array, in place
     call.phase(timing == 4u, [&] {
@@ -253,14 +242,13 @@ int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel
     DeviceTemp d_out;
     if (dense_out || install)
         if (int rc = call.alloc(d_out, dense_bytes, "the output buffer")) return rc;
-    std::vector<unsigned long long> sums(cut_blocks);
     if (dense_out || install || result) {
         call.phase(timing == 7u, [&] {
             with_scalar_kind(kind, [&](auto VOL) {
                 hipLaunchKernelGGL(split_cut_kernel<VOL()>, dim3(cut_blocks), dim3(kLabelThreads), 0, ctx->stream, V, D, (const uint32_t *)labels, d_out.p, (unsigned long long *)d_partial.p);
             });
         });
-        call.download(sums.data(), d_partial.p, sums.size() * 8u);
+        sums.download(call, d_partial.p);
         call.download(dense_out, d_out.p, dense_bytes);
     }
     call.download(labels_out, labels, (size_t)n * 4u);
@@ -271,7 +259,7 @@ int vk_split_components(vk_ctx *ctx, const vk_split_request *req, const vk_voxel
         r.n_regions = n_reg; r.n_foreground = totals[5];
         r.n_markers = totals[0]; r.n_marker_voxels = totals[1];
         r.n_residue_regions = totals[2]; r.n_residue_voxels = totals[3];
-        for (unsigned long long s : sums) r.n_cut += s;
+        r.n_cut = sums.sum(0u);
         r.rounds = rounds;
         *result = r;
     }

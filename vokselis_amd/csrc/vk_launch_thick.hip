@@ -18,10 +18,9 @@
 // LDS behind a barrier.  Plain C++; no inline assembly; the one per-thread array is the four list entries of a trip, unrolled into registers (ScratchSize 0).
 #include "vk_dist_launch.hpp"
 #include "vk_label.hpp"
+#include "vk_pass_blocks.hpp"
 #include "vk_texel.hpp"
 #include "vk_thick.hpp"
-
-#include <vector>
 
 using namespace vk;
 
@@ -39,15 +38,6 @@ struct ThickDesc {
 };
 static_assert(sizeof(ThickDesc) % 8 == 0 && pass_kernargs_fit<ThickDesc>, "thickness kernels: ThickDesc");
 
-// the smallest / largest v over a wave's lanes, in lane 0
-__device__ __forceinline__ uint32_t thick_wave_min(uint32_t v) {
-    for (int d = warpSize / 2; d > 0; d >>= 1) { const uint32_t o = (uint32_t)__shfl_down((int)v, d); v = o < v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ uint32_t thick_wave_max(uint32_t v) {
-    for (int d = warpSize / 2; d > 0; d >>= 1) { const uint32_t o = (uint32_t)__shfl_down((int)v, d); v = o > v ? o : v; }
-    return v;
-}
 // Dc of voxel (lx, ly, lz) of the tile whose box is b, or 0 where the tile's box ends before it.  a: D2(not S, .), 0 off S.
 __device__ __forceinline__ uint32_t thick_load_dc(const ThickDesc &T, const ThickBox &b, uint32_t lx, uint32_t ly, uint32_t lz, const uint32_t *__restrict__ a, uint64_t &i) {
     const uint32_t x = b.lo[0] + lx, y = b.lo[1] + ly, z = b.lo[2] + lz;
@@ -64,9 +54,9 @@ __global__ __launch_bounds__(kThickThreads) void thick_tile_max_kernel(const Thi
         if (threadIdx.x == 0) s_max = 0u;
         __syncthreads();
         uint32_t tx, ty, tz;
-        thick_tile_coords(t, T.ntx, T.nty, tx, ty, tz);
+        tile_coords(t, T.ntx, T.nty, tx, ty, tz);
         uint64_t i;
-        const uint32_t top = thick_wave_max(thick_load_dc(T, thick_tile_box(tx, ty, tz, T.nx, T.ny, T.nz), lx, ly, lz, a, i));
+        const uint32_t top = wave_reduce(thick_load_dc(T, thick_tile_box(tx, ty, tz, T.nx, T.ny, T.nz), lx, ly, lz, a, i), WaveMax());
         if ((threadIdx.x & (warpSize - 1)) == 0 && top) atomicMax(&s_max, top);
         __syncthreads();
         if (threadIdx.x == 0) tile_max[t] = s_max;
@@ -83,7 +73,7 @@ __global__ __launch_bounds__(kThickThreads) void thick_gather_kernel(const Thick
     const uint32_t wave = threadIdx.x / 64u, lane = threadIdx.x % 64u;
     for (uint32_t t = blockIdx.x; t < T.tiles; t += gridDim.x) {  // block-uniform
         uint32_t tx, ty, tz;
-        thick_tile_coords(t, T.ntx, T.nty, tx, ty, tz);
+        tile_coords(t, T.ntx, T.nty, tx, ty, tz);
         const ThickBox out = thick_tile_box(tx, ty, tz, T.nx, T.ny, T.nz);
         uint64_t at;
         uint32_t best = thick_load_dc(T, out, lx, ly, lz, a, at);
@@ -94,7 +84,7 @@ __global__ __launch_bounds__(kThickThreads) void thick_gather_kernel(const Thick
         if (threadIdx.x == 0) s_low = kThickNone;
         __syncthreads();
         {
-            const uint32_t low = thick_wave_min(fg ? best : kThickNone);
+            const uint32_t low = wave_reduce(fg ? best : kThickNone, WaveMin());
             if (lane == 0u && low != kThickNone) atomicMin(&s_low, low);
         }
         __syncthreads();
@@ -148,7 +138,7 @@ __global__ __launch_bounds__(kThickThreads) void thick_gather_kernel(const Thick
                     }
                 }
                 {
-                    const uint32_t low = thick_wave_min(fg ? best : kThickNone);
+                    const uint32_t low = wave_reduce(fg ? best : kThickNone, WaveMin());
                     if (lane == 0u) atomicMin(&s_low, low);
                 }
                 __syncthreads();
@@ -160,10 +150,6 @@ __global__ __launch_bounds__(kThickThreads) void thick_gather_kernel(const Thick
     }
 }
 
-__device__ __forceinline__ void thick_block_add(unsigned long long *slot, unsigned long long s) {
-    for (int d = warpSize / 2; d > 0; d >>= 1) s += __shfl_down(s, d);
-    if ((threadIdx.x & (warpSize - 1)) == 0 && s) atomicAdd(slot, s);
-}
 // partial[4 b + ...]: |S|, the voxels at C, the sum of T2 and the largest T2 over workgroup b's voxels
 __global__ __launch_bounds__(kThickVoxelThreads) void thick_stats_kernel(const ThickDesc T, const uint32_t *__restrict__ t2, unsigned long long *__restrict__ partial) {
     __shared__ unsigned long long s_n[kThickStatsWords];
@@ -178,22 +164,14 @@ __global__ __launch_bounds__(kThickVoxelThreads) void thick_stats_kernel(const T
         n_fg += v != 0u; n_sat += v == T.cap; sum += v;
         top = v > top ? v : top;
     }
-    thick_block_add(&s_n[0], n_fg); thick_block_add(&s_n[1], n_sat); thick_block_add(&s_n[2], sum);
-    top = thick_wave_max(top);
+    block_add(&s_n[0], n_fg); block_add(&s_n[1], n_sat); block_add(&s_n[2], sum);
+    top = wave_reduce(top, WaveMax());
     if ((threadIdx.x & (warpSize - 1)) == 0 && top) atomicMax(&s_max, top);
     __syncthreads();
     if (threadIdx.x == 0) s_n[3] = s_max;
-    __syncthreads();
-    if (threadIdx.x < kThickStatsWords) partial[(size_t)kThickStatsWords * blockIdx.x + threadIdx.x] = s_n[threadIdx.x];
+    publish_partials<kThickStatsWords>(partial, s_n);
 }
 
-// F of a value, as label_fill_bits forms it
-template <int CLASS>
-__device__ __forceinline__ uint32_t thick_store_bits(float v) {
-    if constexpr (CLASS == TEXEL_U8) return filter_store_unorm(v * 255.0f, 255.0f);
-    else if constexpr (CLASS == TEXEL_U16) return filter_store_unorm(v * 65535.0f, 65535.0f);
-    else return filter_store_f16(v);
-}
 template <int CLASS>
 __global__ __launch_bounds__(kThickVoxelThreads) void thick_dense_kernel(const ThickDesc T, const uint32_t *__restrict__ t2, void *__restrict__ out) {
     for (uint64_t i = (uint64_t)blockIdx.x * kThickVoxelThreads + threadIdx.x; i < T.n; i += (uint64_t)gridDim.x * kThickVoxelThreads) {
@@ -202,7 +180,7 @@ __global__ __launch_bounds__(kThickVoxelThreads) void thick_dense_kernel(const T
         if (v != 0u) {
             const float root = sqrtf((float)v);  // T2 <= 2^22: the conversion is exact
             const float w = root * T.gain;
-            bits = thick_store_bits<CLASS>(w);
+            bits = store_gained_bits<CLASS>(w);
         }
         store_texel_bits<CLASS>(out, i, bits);
     }
@@ -235,7 +213,7 @@ int vk_local_thickness(vk_ctx *ctx, const vk_thickness_request *req, const vk_vo
     T.n = n;
     T.fill_bits = label_fill_bits(req->fill_out, ctx->format);
     const uint32_t tile_blocks = label_blocks(T.tiles, ctx->thick_max_blocks);
-    const uint32_t voxel_blocks = std::min<uint32_t>(label_blocks((n + kThickVoxelThreads - 1u) / kThickVoxelThreads, ctx->thick_max_blocks), 8192u);  // a set of partial results per workgroup
+    const uint32_t voxel_blocks = std::min<uint32_t>(label_blocks((n + kThickVoxelThreads - 1u) / kThickVoxelThreads, ctx->thick_max_blocks), kPassMaxPartials);  // a set of partial results per workgroup
 
     const int kind = ctx->vol_kind;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -250,7 +228,8 @@ int vk_local_thickness(vk_ctx *ctx, const vk_thickness_request *req, const vk_vo
     if (int rc = call.alloc(d_b, (size_t)n * 4u, "the thickness array")) return rc;
     if (int rc = call.alloc(d_stack, (size_t)n * 4u, "the envelope stacks")) return rc;
     if (int rc = call.alloc(d_tile_max, (size_t)T.tiles * 4u, "the tile maxima")) return rc;
-    if (int rc = call.alloc(d_partial, (size_t)voxel_blocks * kThickStatsWords * 8u, "the partial totals")) return rc;
+    PassPartials sums(voxel_blocks, kThickStatsWords);
+    if (int rc = call.alloc(d_partial, sums.bytes(), "the partial totals")) return rc;
     if (dense_out || install)
         if (int rc = call.alloc(d_out, dense_bytes, "the output buffer")) return rc;
     uint32_t *a = (uint32_t *)d_a.p, *t2 = (uint32_t *)d_b.p, *tile_max = (uint32_t *)d_tile_max.p;
@@ -261,16 +240,13 @@ int vk_local_thickness(vk_ctx *ctx, const vk_thickness_request *req, const vk_vo
     call.phase(timing == 2u, [&] { hipLaunchKernelGGL(thick_tile_max_kernel, dim3(tile_blocks), dim3(kThickThreads), 0, ctx->stream, T, (const uint32_t *)a, tile_max); });
     call.phase(timing == 3u, [&] { hipLaunchKernelGGL(thick_gather_kernel, dim3(tile_blocks), dim3(kThickThreads), 0, ctx->stream, T, (const uint32_t *)a, (const uint32_t *)tile_max, t2); });
     call.phase(timing == 4u, [&] { hipLaunchKernelGGL(thick_stats_kernel, dim3(voxel_blocks), dim3(kThickVoxelThreads), 0, ctx->stream, T, (const uint32_t *)t2, partial); });
-    std::vector<unsigned long long> sums((size_t)voxel_blocks * kThickStatsWords);
-    call.download(sums.data(), partial, sums.size() * 8u);
+    sums.download(call, partial);
     call.download(t2_out, t2, (size_t)n * 4u);
     if (int rc = call.finish()) return rc;
 
     vk_thickness_result r{};
-    for (uint32_t k = 0; k < voxel_blocks; k++) {
-        r.n_foreground += sums[4u * k]; r.n_saturated += sums[4u * k + 1u]; r.sum_t2 += sums[4u * k + 2u];
-        r.max_t2 = std::max(r.max_t2, (uint32_t)sums[4u * k + 3u]);
-    }
+    r.n_foreground = sums.sum(0u); r.n_saturated = sums.sum(1u); r.sum_t2 = sums.sum(2u);
+    r.max_t2 = (uint32_t)sums.max(3u);
     r.gain = req->gain != 0.0f ? req->gain : thick_auto_gain(r.max_t2);
     T.gain = r.gain;
     if (dense_out || install) {

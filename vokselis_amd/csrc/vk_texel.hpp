@@ -104,11 +104,4 @@ __device__ __forceinline__ void store_texel_bits(void *__restrict__ out, uint64_
     else reinterpret_cast<uint16_t *>(out)[i] = (uint16_t)bits;
 }
 
-// the sum of v over a workgroup's threads, added to *slot (LDS, zeroed before): lanes are combined in registers, one LDS add per wave
-__device__ __forceinline__ void block_add(unsigned long long *slot, uint32_t v) {
-    unsigned long long s = v;
-    for (int d = warpSize / 2; d > 0; d >>= 1) s += __shfl_down(s, d);
-    if ((threadIdx.x & (warpSize - 1)) == 0 && s) atomicAdd(slot, s);
-}
-
 }  // namespace vk

@@ -12,6 +12,7 @@
 // the smallest running T2 of the output tile's foreground voxels can raise nothing either: max commutes, so the order of the walk is free.
 #pragma once
 
+#include "vk_box.hpp"
 #include "vk_dist.hpp"
 
 namespace vk {
@@ -113,14 +114,8 @@ VK_DIST_HD void thick_window(uint32_t t, uint32_t nt, uint32_t reach, uint32_t &
     const uint32_t end = (t * kThickTile + kThickTile - 1u + reach) / kThickTile;
     last = end < nt - 1u ? end : nt - 1u;
 }
-// a tile's number from its three, x fastest, and back
+// a tile's number from its three, x fastest (back: vk_box.hpp, tile_coords)
 VK_DIST_HD uint32_t thick_tile_index(uint32_t tx, uint32_t ty, uint32_t tz, uint32_t ntx, uint32_t nty) { return tx + ntx * (ty + nty * tz); }
-VK_DIST_HD void thick_tile_coords(uint32_t t, uint32_t ntx, uint32_t nty, uint32_t &tx, uint32_t &ty, uint32_t &tz) {
-    const uint32_t row = t / ntx;
-    tx = t - row * ntx;
-    tz = row / nty;
-    ty = row - tz * nty;
-}
 inline uint32_t thick_tiles_along(uint32_t n) { return (n + kThickTile - 1u) / kThickTile; }
 
 }  // namespace vk
