@@ -1113,6 +1113,9 @@ int vk_set_uniform(vk_ctx *ctx, const void *blob48);
 int vk_set_camera(vk_ctx *ctx, const void *blob144);
 
 /* ---- output surface: HdrBackBuffer::new, src/context/hdr_backbuffer.rs:41-87 ------------- */
+/* Every frame slot takes the new shape, cleared.  VK_ERR_OOM ("vk_backbuffer_resize: the backbuffer: ..."): a slot's backbuffer cannot
+ * be allocated; the context is then left without a backbuffer in any slot, at 0 x 0 -- vk_render, vk_present and vk_frame_begin refuse
+ * with "no backbuffer" -- until a resize succeeds. */
 int vk_backbuffer_resize(vk_ctx *ctx, uint32_t width, uint32_t height, int out_format);
 int vk_backbuffer_info(vk_ctx *ctx, uint32_t *width, uint32_t *height, int *out_format, void **device_ptr);
 /* Clear to the render pass's LoadOp::Clear(BLACK) = (0,0,0,1), examples/bonsai/main.rs:41. */
@@ -1356,7 +1359,11 @@ int vk_debug_read_skip_maps(vk_ctx *ctx, uint32_t grid[3], uint32_t *n_maps, siz
 int vk_debug_wave_trace(vk_ctx *ctx, int enable, uint64_t *out, size_t n_blocks);
 /* Debug / tuning knobs of the staged march: "stage_cap_bytes" (LDS window per wave; 0 = default: 8192 for u8, 10240 for f16),
  * "stage_slab_cells" (a round is a slab of at most that many cells along the wave's major axis, default 8), "stage_copies_mask" (bit k: build the brick copy
- * whose slow axis is k; applies to the next upload, default 7). */
+ * whose slow axis is k; applies to the next upload, default 7).
+ * Tests: "alloc_fail_at" k -- the k-th device or pinned-host allocation the library makes for this context from now on (k >= 1) fails as
+ * an allocation that does not fit fails (VK_ERR_OOM with the call's own message), once: the parameter then disarms itself.  0 disarms;
+ * setting it again restarts the count.  The allocation asks the runtime for 2^60 bytes in place of its size, so nothing is exhausted.
+ * What a failed call leaves behind is the documented contract of each entry point. */
 int vk_debug_set_param(vk_ctx *ctx, const char *name, double value);
 /* Debug: which build of the cell march vk_render(ctx, VK_MODE_NAIVE_TRILINEAR, ..., dt_scale, flags) would launch now, for the context's
  * volume and camera: *fast = 1 the unclamped build (index tables in LDS, 32-bit offsets), 0 the clamped one (VK_RENDER_SAFE's).  The

@@ -62,8 +62,9 @@ int vk_render_batch(vk_ctx *ctx, int mode, uint32_t n_frames, const void *camera
         const size_t floor256 = std::min<size_t>(batch_table_bytes(256u, n_tiles, sizeof(FrameDesc)), (size_t)4 << 20);
         const size_t want = std::max({bytes, 2 * B.cap, floor256});
         B.cap = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&B.d, want));
-        HIP_TRY(ctx, hipHostMalloc((void **)&B.h, want));
+        // (a failure leaves the slot at capacity 0: the next batch retires what stands and allocates both halves again)
+        if (hipError_t ae = ctx_alloc(ctx, (void **)&B.d, want)) return alloc_failed(ctx, ae, "vk_render_batch", "the batch tables");
+        if (hipError_t ae = ctx_alloc_host(ctx, (void **)&B.h, want)) return alloc_failed(ctx, ae, "vk_render_batch", "the batch tables' pinned staging");
         B.cap = want;
     }
     FrameDesc *fd = reinterpret_cast<FrameDesc *>(B.h);

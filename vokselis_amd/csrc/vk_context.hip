@@ -59,7 +59,7 @@ static void frame_slot_release(vk_ctx::FrameSlot &s, bool keep_stream) {  // a p
 }
 
 // (Re)allocate the CURRENT slot's backbuffer for the context's shape and clear it (HdrBackBuffer::new); its step image goes.
-static int surface_alloc_current(vk_ctx *ctx) {
+static int surface_alloc_current(vk_ctx *ctx, const char *who) {
     if (ctx->backbuffer) (void)hipFree(ctx->backbuffer);
     if (ctx->steps) (void)hipFree(ctx->steps);
     if (ctx->geom) (void)hipFree(ctx->geom);  // the geometry surface goes with the shape: the next geometry pass allocates it again
@@ -68,7 +68,7 @@ static int surface_alloc_current(vk_ctx *ctx) {
     ctx->geom = nullptr;
     if (ctx->slice_values) (void)hipFree(ctx->slice_values);  // ... and so does the slice pass's value surface
     ctx->slice_values = nullptr;
-    HIP_TRY(ctx, hipMalloc(&ctx->backbuffer, (size_t)ctx->width * ctx->height * px_bytes(ctx->out_format)));
+    if (hipError_t ae = ctx_alloc(ctx, &ctx->backbuffer, (size_t)ctx->width * ctx->height * px_bytes(ctx->out_format))) return alloc_failed(ctx, ae, who, "the backbuffer");
     return vk_backbuffer_clear(ctx);
 }
 
@@ -227,10 +227,27 @@ int vk_backbuffer_resize(vk_ctx *ctx, uint32_t width, uint32_t height, int out_f
     for (uint32_t i = 0; i < ctx->fif_k && rc == VK_OK; i++) {
         frame_slot_switch(ctx, i);
         ctx->fif[i].id = 0; ctx->fif[i].ended = false;
-        rc = surface_alloc_current(ctx);
+        rc = surface_alloc_current(ctx, "vk_backbuffer_resize");
     }
     frame_slot_switch(ctx, cur);
-    if (rc != VK_OK) { ctx->width = ctx->height = 0; return rc; }
+    if (rc != VK_OK) {
+        // no slot keeps a surface: the earlier ones have the new shape, the later ones the old, and width x height describes neither.
+        // Every pass then refuses with "no backbuffer" until a resize succeeds.  (The clears of the earlier slots may still run.)
+        const std::string why = ctx->err;
+        (void)frames_drain(ctx);
+        for (uint32_t i = 0; i < ctx->fif_k; i++) {
+            frame_slot_switch(ctx, i);
+            for (void **p : {&ctx->backbuffer, (void **)&ctx->steps, &ctx->geom, &ctx->slice_values, (void **)&ctx->rgba8, (void **)&ctx->bgra8}) {
+                if (*p) (void)hipFree(*p);
+                *p = nullptr;
+            }
+            ctx->present_w = ctx->present_h = 0;
+        }
+        frame_slot_switch(ctx, cur);
+        ctx->width = ctx->height = 0;
+        ctx->err = why;
+        return rc;
+    }
     return VK_OK;
 }
 
@@ -287,7 +304,7 @@ int vk_ctx_frames_in_flight(vk_ctx *ctx, uint32_t k) {
         for (uint32_t i = std::max(old_k, 1u); i < k && rc == VK_OK; i++) {
             if (!ctx->width) break;  // (no backbuffer yet: vk_backbuffer_resize sizes every slot)
             frame_slot_switch(ctx, i);  // a new slot takes the backbuffer's current shape, cleared
-            rc = surface_alloc_current(ctx);
+            rc = surface_alloc_current(ctx, "vk_ctx_frames_in_flight");
             frame_slot_switch(ctx, 0);
         }
     }
@@ -395,7 +412,7 @@ int vk_device_alloc(vk_ctx *ctx, size_t bytes, void **ptr) {
     if (!ctx || !ptr || bytes == 0) return fail(ctx, VK_ERR_INVALID, "vk_device_alloc: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     *ptr = nullptr;
-    hipError_t e = hipMalloc(ptr, bytes);
+    hipError_t e = ctx_alloc(ctx, ptr, bytes);
     if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("vk_device_alloc: ") + hipGetErrorString(e));
     return VK_OK;
 }
@@ -560,6 +577,10 @@ int vk_debug_set_param(vk_ctx *ctx, const char *name, double value) {
     else if (n == "resample_area_unroll") ctx->resample_area_unroll = (uint32_t)value;  // ... 0: no unrolled footprint at ratios 2 .. 4 (measurements, tests)
     else if (n == "resample_timing") ctx->resample_timing = (uint32_t)value;          // ... 1: the call times its kernel alone (vk_timer_elapsed_ms)
     else if (n == "stage_copies_mask") ctx->stage_copies_mask = (uint32_t)value; // which brick copies to build (next upload)
+    else if (n == "alloc_fail_at") {  // tests: the k-th allocation the context makes from now on fails, once (0 disarms; ctx_alloc, vk_ctx.hpp)
+        if (!(value >= 0.0 && value <= 4294967295.0)) return fail(ctx, VK_ERR_INVALID, "alloc_fail_at: 0 (disarm) or the number of the allocation to fail");
+        ctx->alloc_fail.arm((uint32_t)value);
+    }
     else return fail(ctx, VK_ERR_INVALID, "vk_debug_set_param: unknown parameter " + n);
     return VK_OK;
 }

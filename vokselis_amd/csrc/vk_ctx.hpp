@@ -27,6 +27,7 @@
 #pragma once
 
 #include "../../include/vokselis_hip.h"
+#include "vk_alloc_hook.hpp"
 #include "vk_common.hpp"
 #include "vk_geom.hpp"
 #include "vk_iso.hpp"
@@ -50,6 +51,7 @@ struct vk_ctx {
     hipStream_t stream = nullptr;
     std::string err;
     hipDeviceProp_t prop{};
+    vk::AllocFailHook alloc_fail;  // debug, tests: which of the context's next allocations fails (vk_debug_set_param "alloc_fail_at"; ctx_alloc below)
 
     // volume
     void *vol = nullptr, *vol2 = nullptr;  // cells / dense voxels / pair
@@ -240,6 +242,30 @@ inline int fail(vk_ctx *ctx, int code, const std::string &msg) {
                         std::string(#expr) + ": " + hipGetErrorString(e_));                    \
         }                                                                                      \
     } while (0)
+
+// ---- allocations ----------------------------------------------------------------------------------------
+// Every device and pinned-host allocation the library makes on behalf of a context goes through these two (the counters of vk_ctx_create,
+// made before there is a context, and vk_group_render's buffers, which belong to no context, do not).  On failure *p is NULL and HIP's
+// sticky last error is cleared -- the caller reports the code it gets, and no later look at hipGetLastError() behind a launch finds it --
+// and the call site keeps its own message and clean-up.  The allocation the debug hook picks (vk_alloc_hook.hpp) asks the runtime for
+// kAllocRefused bytes in place of its own size: more than any device holds, so the code and the runtime's state are those of a real refusal.
+constexpr size_t kAllocRefused = (size_t)1 << 60;
+inline hipError_t ctx_alloc(vk_ctx *ctx, void **p, size_t bytes) {
+    *p = nullptr;
+    const hipError_t e = hipMalloc(p, ctx->alloc_fail.fires() ? kAllocRefused : bytes);
+    if (e != hipSuccess) { *p = nullptr; (void)hipGetLastError(); }
+    return e;
+}
+inline hipError_t ctx_alloc_host(vk_ctx *ctx, void **p, size_t bytes) {
+    *p = nullptr;
+    const hipError_t e = hipHostMalloc(p, ctx->alloc_fail.fires() ? kAllocRefused : bytes);
+    if (e != hipSuccess) { *p = nullptr; (void)hipGetLastError(); }
+    return e;
+}
+// ... and what a failed one returns: "prefix: what: <HIP's text>", VK_ERR_OOM where the runtime says out of memory
+inline int alloc_failed(vk_ctx *ctx, hipError_t e, const std::string &prefix, const char *what) {
+    return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, prefix + ": " + what + ": " + hipGetErrorString(e));
+}
 
 // A hipMalloc'd temporary of one call: freed when the call returns, whichever way; release() hands the pointer on (install_dense).
 struct DeviceTemp {

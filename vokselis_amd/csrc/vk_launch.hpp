@@ -124,10 +124,9 @@ struct PassCall {
 
     // a temporary of the call (an empty one still gets a byte): VK_OK, or the error set.  what: the buffer, in the message's words
     int alloc(DeviceTemp &d, size_t bytes, const char *what) {
-        e = hipMalloc(&d.p, bytes ? bytes : 1u);
+        e = ctx_alloc(ctx, &d.p, bytes ? bytes : 1u);
         if (e == hipSuccess) return VK_OK;
-        (void)hipGetLastError();
-        return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string(prefix) + ": " + what + ": " + hipGetErrorString(e));
+        return alloc_failed(ctx, e, prefix, what);
     }
     // launch(): the kernels of one phase, between the context's timer events where timed (the pass's X_timing names this phase).  A
     // launch that looks at HIP errors itself leaves the first in e.

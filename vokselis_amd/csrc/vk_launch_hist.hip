@@ -352,9 +352,9 @@ int vk_volume_histogram(vk_ctx *ctx, const vk_histogram *hist, const vk_voxel_bo
     if (D.items) {
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         DeviceTemp d;
-        HIP_TRY(ctx, hipMalloc(&d.p, words * sizeof(unsigned long long)));
-        D.out = reinterpret_cast<unsigned long long *>(d.p);
         PassCall call{ctx, "vk_volume_histogram"};
+        if (int rc = call.alloc(d, words * sizeof(unsigned long long), "the counters")) return rc;
+        D.out = reinterpret_cast<unsigned long long *>(d.p);
         call.e = hipMemsetAsync(d.p, 0, words * sizeof(unsigned long long), ctx->stream);
         call.phase(false, [&] {
             with_scalar_kind(kind, [&](auto VOL) {

@@ -287,11 +287,11 @@ int vk_extract_isosurface(vk_ctx *ctx, const vk_mesh_request *req, const vk_voxe
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t work_bytes = sizeof(MeshScanHeader) + (size_t)D.n_chunks * sizeof(MeshActive) + (size_t)mesh_totals_padded(D.n_chunks) * sizeof(uint32_t);
     DeviceTemp work;
-    HIP_TRY(ctx, hipMalloc(&work.p, work_bytes));
+    PassCall call{ctx, "vk_extract_isosurface"};
+    if (int rc = call.alloc(work, work_bytes, "the work buffer")) return rc;
     MeshScanHeader *d_hdr = reinterpret_cast<MeshScanHeader *>(work.p);
     MeshActive *d_act = reinterpret_cast<MeshActive *>(d_hdr + 1);
     uint32_t *d_totals = reinterpret_cast<uint32_t *>(d_act + D.n_chunks);
-    PassCall call{ctx, "vk_extract_isosurface"};
     call.phase(false, [&] {
         with_scalar_kind(kind, [&](auto VOL) {
             hipLaunchKernelGGL(mesh_count_kernel<VOL()>, dim3(mesh_grid(D.n_chunks, cus, ctx->mesh_max_blocks)), dim3(kMeshThreads), 0, ctx->stream, V, D, d_totals);

@@ -261,7 +261,7 @@ int vk_volume_resample(vk_ctx *ctx, const vk_resample_request *req, const vk_vox
     PassCall call{ctx, "resample"};
     const size_t bytes = pass_dense_bytes(P.format, (uint64_t)D.nx * D.ny * D.nz);
     DeviceTemp d_tab, d_out;
-    if (int rc = call.alloc(d_tab, (size_t)words * sizeof(uint32_t), "the output buffer")) return rc;
+    if (int rc = call.alloc(d_tab, (size_t)words * sizeof(uint32_t), "the axis tables")) return rc;
     if (int rc = call.alloc(d_out, bytes, "the output buffer")) return rc;
     call.e = hipMemcpy(d_tab.p, table.data(), (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice);  // blocking: the tables stand before the launch
     const bool passes = req->mode == VK_RESAMPLE_AREA && ctx->resample_area_passes != 0u;

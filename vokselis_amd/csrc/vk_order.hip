@@ -89,8 +89,9 @@ int order_ensure_device(vk_ctx *ctx) {
         if (ctx->h_ring) (void)hipHostFree(ctx->h_ring);
         ctx->d_ring = ctx->h_ring = nullptr; ctx->d_order = ctx->d_order_pos = nullptr;
         ctx->d_order_cap = 0; ctx->ring_slot = -1;
-        HIP_TRY(ctx, hipMalloc(&ctx->d_ring, (size_t)kOrderRing * 2 * n * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipHostMalloc(&ctx->h_ring, (size_t)kOrderRing * 2 * n * sizeof(uint32_t)));
+        // (a failure leaves the ring at capacity 0: the next call frees what stands and allocates both halves again)
+        if (hipError_t ae = ctx_alloc(ctx, (void **)&ctx->d_ring, (size_t)kOrderRing * 2 * n * sizeof(uint32_t))) return alloc_failed(ctx, ae, "render", "the tile-order ring");
+        if (hipError_t ae = ctx_alloc_host(ctx, (void **)&ctx->h_ring, (size_t)kOrderRing * 2 * n * sizeof(uint32_t))) return alloc_failed(ctx, ae, "render", "the tile-order ring's pinned staging");
         ctx->d_order_cap = n;
     }
     const size_t cap = ctx->d_order_cap;

@@ -54,8 +54,14 @@ int present_targets(vk_ctx *ctx, uint32_t width, uint32_t height, bool also_bgra
     if (ctx->bgra8) (void)hipFree(ctx->bgra8);
     ctx->rgba8 = ctx->bgra8 = nullptr;
     ctx->present_w = ctx->present_h = 0;
-    HIP_TRY(ctx, hipMalloc(&ctx->rgba8, (size_t)width * height * 4));
-    if (also_bgra) HIP_TRY(ctx, hipMalloc(&ctx->bgra8, (size_t)width * height * 4));
+    // (a failure leaves the slot without present targets, at size 0 x 0: the next call allocates both again)
+    if (hipError_t ae = ctx_alloc(ctx, (void **)&ctx->rgba8, (size_t)width * height * 4)) return alloc_failed(ctx, ae, "vk_present", "the Rgba8 target");
+    if (also_bgra)
+        if (hipError_t ae = ctx_alloc(ctx, (void **)&ctx->bgra8, (size_t)width * height * 4)) {
+            (void)hipFree(ctx->rgba8);
+            ctx->rgba8 = nullptr;
+            return alloc_failed(ctx, ae, "vk_present", "the Bgra8 target");
+        }
     // (a tile-by-tile fused present fills it piecewise: what no tile covers reads as transparent black, never as stale memory)
     HIP_TRY(ctx, hipMemsetAsync(ctx->rgba8, 0, (size_t)width * height * 4, ctx->stream));
     if (also_bgra) HIP_TRY(ctx, hipMemsetAsync(ctx->bgra8, 0, (size_t)width * height * 4, ctx->stream));

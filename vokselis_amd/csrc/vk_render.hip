@@ -200,7 +200,7 @@ static int render_common(vk_ctx *ctx, int mode, int32_t ox, int32_t oy, uint32_t
     }
     const bool count = (flags & VK_RENDER_COUNT) != 0;
     if (count && !ctx->steps) {
-        HIP_TRY(ctx, hipMalloc(&ctx->steps, (size_t)ctx->width * ctx->height * sizeof(uint32_t)));
+        if (hipError_t ae = ctx_alloc(ctx, (void **)&ctx->steps, (size_t)ctx->width * ctx->height * sizeof(uint32_t))) return alloc_failed(ctx, ae, "render", "the step image");
         HIP_TRY(ctx, hipMemsetAsync(ctx->steps, 0, (size_t)ctx->width * ctx->height * sizeof(uint32_t), ctx->stream));
     }
     LaunchDesc L{};
@@ -267,7 +267,7 @@ static int render_common(vk_ctx *ctx, int mode, int32_t ox, int32_t oy, uint32_t
         if (ctx->trace_blocks < recs) {
             if (ctx->trace) (void)hipFree(ctx->trace);
             ctx->trace = nullptr; ctx->trace_blocks = 0;
-            HIP_TRY(ctx, hipMalloc(&ctx->trace, recs * 4 * sizeof(unsigned long long)));
+            if (hipError_t ae = ctx_alloc(ctx, (void **)&ctx->trace, recs * 4 * sizeof(unsigned long long))) return alloc_failed(ctx, ae, "render", "the wave trace");
             ctx->trace_blocks = recs;
         }
         // start = +inf (atomicMin), end = 0 (atomicMax): fill {0xff.., 0} pairs
@@ -379,7 +379,7 @@ int vk_render_geometry(vk_ctx *ctx, int32_t tile_x, int32_t tile_y, uint32_t til
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ctx->geom) {
         const size_t n = (size_t)ctx->width * ctx->height;
-        HIP_TRY(ctx, hipMalloc(&ctx->geom, geom_surface_bytes(ctx->width, ctx->height)));
+        if (hipError_t ae = ctx_alloc(ctx, &ctx->geom, geom_surface_bytes(ctx->width, ctx->height))) return alloc_failed(ctx, ae, "vk_render_geometry", "the geometry surface");
         hipLaunchKernelGGL(geom_fill_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, ctx->stream, reinterpret_cast<float4 *>(ctx->geom), n);
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -423,7 +423,7 @@ int vk_render_slice(vk_ctx *ctx, const vk_slice *slice, int32_t tile_x, int32_t 
     if ((S.y1 - S.y0 + 7u) / 8u > 65535u) return fail(ctx, VK_ERR_UNSUPPORTED, "slice: tile too tall for one launch");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((flags & VK_SLICE_VALUES) && !ctx->slice_values) {
-        HIP_TRY(ctx, hipMalloc(&ctx->slice_values, slice_surface_bytes(ctx->width, ctx->height)));
+        if (hipError_t ae = ctx_alloc(ctx, &ctx->slice_values, slice_surface_bytes(ctx->width, ctx->height))) return alloc_failed(ctx, ae, "vk_render_slice", "the value surface");
         HIP_TRY(ctx, hipMemsetAsync(ctx->slice_values, 0, slice_surface_bytes(ctx->width, ctx->height), ctx->stream));
     }
     for (int i = 0; i < 3; i++) { S.lo[i] = ctx->clip_on ? ctx->clip_lo[i] : 0.0f; S.hi[i] = ctx->clip_on ? ctx->clip_hi[i] : 1.0f; }

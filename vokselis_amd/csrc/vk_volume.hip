@@ -91,8 +91,8 @@ struct CellScratch {
 
 static int alloc_scratch(vk_ctx *ctx, CellScratch &sc, uint64_t n_cells) {
     for (uint8_t **p : {&sc.occ, &sc.tx, &sc.txy, &sc.code}) {
-        hipError_t e = hipMalloc((void **)p, n_cells);
-        if (e != hipSuccess) { *p = nullptr; return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("re-layout scratch allocation failed: ") + hipGetErrorString(e)); }
+        hipError_t e = ctx_alloc(ctx, (void **)p, n_cells);
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("re-layout scratch allocation failed: ") + hipGetErrorString(e));
     }
     return VK_OK;
 }
@@ -146,7 +146,7 @@ static int build_skip_maps(vk_ctx *ctx, CellScratch &sc, bool coded, uint32_t nb
     const bool octants = empty_fraction >= 0.30 && n_cells <= (1ull << 28);  // (the default policy skips from 45 %)
     const uint64_t bytes = octants ? 8 * n_cells : n_cells;
     uint8_t *d = nullptr;
-    hipError_t e = hipMalloc((void **)&d, bytes);
+    hipError_t e = ctx_alloc(ctx, (void **)&d, bytes);
     if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("distance map allocation failed: ") + hipGetErrorString(e));
     auto pass = [&](const uint8_t *in, uint8_t *out, int axis, int dir, int last) {
         hipLaunchKernelGGL(dist_pass_kernel, dim3(blocks), dim3(256), 0, ctx->stream, in, out, nbx, nby, nbz, axis, dir, last, (int)kDistRadius,
@@ -279,8 +279,8 @@ static int build_from_dense(vk_ctx *ctx, const void *d_src, const void *d_src2, 
         return VK_OK;
     };
     auto alloc = [&](void **p, size_t bytes, const char *what) -> int {
-        hipError_t e = hipMalloc(p, bytes);
-        if (e != hipSuccess) { *p = nullptr; return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string(what) + " allocation failed: " + hipGetErrorString(e)); }
+        hipError_t e = ctx_alloc(ctx, p, bytes);
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string(what) + " allocation failed: " + hipGetErrorString(e));
         return VK_OK;
     };
     int rc;
@@ -488,11 +488,13 @@ int vk_volume_upload(vk_ctx *ctx, const void *host, const void *host2, uint32_t 
     const size_t n_vox = (size_t)nx * ny * nz;
     const size_t bpv = format == VK_FMT_R8_UNORM ? 1 : (format == VK_FMT_R16_FLOAT || format == VK_FMT_R16_UNORM ? 2 : 8);
     void *d = nullptr, *d2 = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d, n_vox * bpv));
-    hipError_t e = hipMemcpy(d, host, n_vox * bpv, hipMemcpyHostToDevice);
+    hipError_t e = ctx_alloc(ctx, &d, n_vox * bpv);
+    if (e != hipSuccess) return alloc_failed(ctx, e, "volume upload", "dense source");
+    e = hipMemcpy(d, host, n_vox * bpv, hipMemcpyHostToDevice);
     if (e == hipSuccess && format == VK_FMT_RGBA16F_PAIR) {
-        e = hipMalloc(&d2, n_vox * bpv);
-        if (e == hipSuccess) e = hipMemcpy(d2, host2, n_vox * bpv, hipMemcpyHostToDevice);
+        e = ctx_alloc(ctx, &d2, n_vox * bpv);
+        if (e != hipSuccess) { (void)hipFree(d); return alloc_failed(ctx, e, "volume upload", "dense source (normals)"); }
+        e = hipMemcpy(d2, host2, n_vox * bpv, hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
         (void)hipFree(d);
@@ -526,7 +528,8 @@ int vk_volume_generate(vk_ctx *ctx, int kind, uint32_t nx, uint32_t ny, uint32_t
     const size_t n_vox = (size_t)nx * ny * nz;
     const size_t bpv = format == VK_FMT_R8_UNORM ? 1 : 2;
     void *d = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d, n_vox * bpv));
+    hipError_t e = ctx_alloc(ctx, &d, n_vox * bpv);
+    if (e != hipSuccess) return alloc_failed(ctx, e, "generator", "dense volume");
     // grid-stride kernels: a launch may not exceed 2^32 threads
     const uint64_t blocks = std::min<uint64_t>((n_vox + 255) / 256, 1ull << 22);
     if (kind == VK_GEN_BONSAI_STANDIN)
@@ -535,7 +538,7 @@ int vk_volume_generate(vk_ctx *ctx, int kind, uint32_t nx, uint32_t ny, uint32_t
         hipLaunchKernelGGL(generate_kernel<1>, dim3((uint32_t)blocks), dim3(256), 0, ctx->stream, d, nx, ny, nz, seed, lo, span, core);
     else
         hipLaunchKernelGGL(generate_kernel<0>, dim3((uint32_t)blocks), dim3(256), 0, ctx->stream, d, nx, ny, nz, seed, lo, span, core);
-    hipError_t e = hipGetLastError();
+    e = hipGetLastError();
     if (e != hipSuccess) { (void)hipFree(d); return fail(ctx, VK_ERR_HIP, std::string("generator launch: ") + hipGetErrorString(e)); }
     return build_from_dense(ctx, d, nullptr, true, nx, ny, nz, format, layout);
 }
@@ -549,9 +552,10 @@ int vk_volume_generate_xor(vk_ctx *ctx, uint32_t nx, uint32_t ny, uint32_t nz, f
     const size_t n_vox = (size_t)nx * ny * nz;
     if ((n_vox + 255) / 256 >= (1ull << 31)) return fail(ctx, VK_ERR_UNSUPPORTED, "volume too large");
     void *d = nullptr, *d2 = nullptr;
-    HIP_TRY(ctx, hipMalloc(&d, n_vox * 8));
-    hipError_t e = hipMalloc(&d2, n_vox * 8);
-    if (e != hipSuccess) { (void)hipFree(d); return fail(ctx, VK_ERR_OOM, std::string("xor normals: ") + hipGetErrorString(e)); }
+    hipError_t e = ctx_alloc(ctx, &d, n_vox * 8);
+    if (e != hipSuccess) return alloc_failed(ctx, e, "xor generator", "density");
+    e = ctx_alloc(ctx, &d2, n_vox * 8);
+    if (e != hipSuccess) { (void)hipFree(d); return alloc_failed(ctx, e, "xor generator", "normals"); }
     hipLaunchKernelGGL(xor_generate_kernel, dim3((uint32_t)((n_vox + 255) / 256)), dim3(256), 0, ctx->stream, (uint2 *)d, (uint2 *)d2, nx, ny, nz, time);
     e = hipGetLastError();
     if (e != hipSuccess) { (void)hipFree(d); (void)hipFree(d2); return fail(ctx, VK_ERR_HIP, std::string("xor generator launch: ") + hipGetErrorString(e)); }
@@ -597,8 +601,9 @@ int vk_set_transfer_function(vk_ctx *ctx, const float *rgba, uint32_t n, float l
     std::memcpy(blob.data(), rgba, (size_t)n * 16);
     std::memcpy(blob.data() + (size_t)n * 16, prefix.data(), prefix.size() * 4);
     float *d = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&d, blob.size()));
-    hipError_t e = hipMemcpy(d, blob.data(), blob.size(), hipMemcpyHostToDevice);
+    hipError_t e = ctx_alloc(ctx, (void **)&d, blob.size());
+    if (e != hipSuccess) return alloc_failed(ctx, e, "vk_set_transfer_function", "the table");
+    e = hipMemcpy(d, blob.data(), blob.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d); return fail(ctx, VK_ERR_HIP, std::string("vk_set_transfer_function: upload: ") + hipGetErrorString(e)); }
     if (!ctx->iso_on && (rc = rebuild_skip_maps(ctx, reinterpret_cast<const uint32_t *>(d + 4 * n), n, lo, hi, ctx->proj))) { (void)hipFree(d); return rc; }
     (void)hipFree(ctx->d_tf);
