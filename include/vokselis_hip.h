@@ -1031,6 +1031,89 @@ _Static_assert(sizeof(vk_skeleton_request) == 32 && sizeof(vk_skeleton_result) =
 int vk_skeletonize(vk_ctx *ctx, const vk_skeleton_request *req, const vk_voxel_box *box, uint8_t *class_out, void *dense_out,
                    vk_skeleton_result *result);
 
+/* Steady-state diffusion through a value range: the Laplace equation on the set S with no-flux walls,
+ * concentration 1 on one face of the box and 0 on the opposite one -- the effective diffusivity ratio D_eff / D0 and the tortuosity
+ * factor of a pore space.  The values are floats, and every one of them is defined bit for bit: a C loop that follows this comment
+ * reproduces the device, whatever the launch shape and the layout.  No operation is fused (no fma); every operation named below rounds
+ * once, to nearest even, in IEEE binary32 unless it says double.
+ * The set.  S, the box B, lo_k, hi_k and the integer spacing[3] (1 .. VK_DIST_MAX_SPACING) are exactly vk_geodesic_distance's; the box
+ * comes from `box`, from the clip box under VK_DIFF_CLIP_BOX, or is the whole volume.  A NaN texel is never in S.  axis a is 0, 1 or 2
+ * (x, y, z).  The inlet is B's first index along a, the outlet B's last; a voxel of S is "on the inlet" when its coordinate along a is
+ * the inlet's.  n_a is B's extent along a, n_b and n_c its other two.
+ * Weights.  w[c] = (float)(1.0 / (double)(spacing[c] * spacing[c])), c = 0, 1, 2 for a neighbour along x, y, z.  g = 2.0f * w[a]: the
+ * Dirichlet planes lie half a voxel outside the face voxels' centres.
+ * State.  One float c(v) per voxel of S, 0.5f at the start.  Off S there is no value: c_out holds VK_DIFF_OFF there.
+ * One voxel's update.  num = den = 0.0f.  For the six neighbours u of v in the order x-, x+, y-, y+, z-, z+, each one that lies in S
+ * (a neighbour outside the volume or outside B is not in S): num = num + w * c(u) (the product rounds, then the sum), den = den + w,
+ * with w the weight of the neighbour's axis.  If v is on the inlet, num = num + g and den = den + g; if v is on the outlet,
+ * den = den + g (a voxel may be on both when n_a == 1).  If den == 0 the voxel is never updated and keeps 0.5f.  Otherwise
+ * gs = num / den (correctly rounded), d = gs - c(v), c'(v) = c(v) + omega * d (the product rounds, then the sum).
+ * Sweep.  A sweep updates all voxels of S with ((x + y + z) & 1) == 0, on absolute volume indices, then all those with parity 1.  A
+ * voxel of one parity has neighbours of the other parity only, so the result of a sweep depends on no order.
+ * omega.  req->omega in (0, 2), or 0 for the automatic one: (float)(2.0 / (1.0 + 3.141592653589793 / (double)(n_a + 1))), plain double
+ * arithmetic, or the largest float below 2 where the conversion rounds to 2 (n_a above 10^8).  result->omega is the value used.
+ * Stopping.  Sweeps run in blocks of check_every (1 .. VK_DIFF_MAX_CHECK_EVERY); at most max_sweeps / check_every blocks run
+ * (max_sweeps >= check_every).  After a block:
+ *   delta   the largest fabsf(c'(v) - c(v)) (the difference rounds) over the voxels updated in the block's last sweep, 0 if none;
+ *   Fin_q   the sum of q(2.0f * (1.0f - c(v))) over the voxels of S on the inlet;
+ *   Fout_q  the sum of q(2.0f * c(v)) over the voxels of S on the outlet;
+ *   q(t) = (int64_t)(clamp(t) * 1073741824.0f), clamp(t) = t >= -1048576.0f ? (t <= 1048576.0f ? t : 1048576.0f) : -1048576.0f (a NaN
+ *   gives -1048576.0f); the product is exact, the conversion truncates, the sums are two's-complement 64-bit integers.
+ * The call has converged iff, in IEEE double, (double)delta <= (double)delta_tol and
+ * fabs((double)Fin_q - (double)Fout_q) <= (double)flux_tol * 0.5 * ((double)Fin_q + (double)Fout_q).  It stops after the first
+ * converged block or after the last permitted one.  sweeps = the blocks run * check_every: the number of sweeps run is exactly this
+ * rule's, however the implementation batches its launches.  A run that does not converge is VK_OK with converged == 0.
+ * result (may be NULL).  n_foreground = |S|; n_inlet, n_outlet = the voxels of S on the two faces; n_box = the voxels of B; sweeps;
+ * converged; delta, Fin_q, Fout_q of the last block; sum_c_q = the sum of q(c(v)) over S; omega and gain as used.
+ * What derives from the result, in double (the hosts compute these):
+ *   flux = ((double)Fin_q + (double)Fout_q) / 2147483648.0       the mean of the two faces' fluxes, in units of D0 * pitch
+ *   D_eff / D0 = flux * n_a / (n_b * n_c)                          the pitch cancels out of the ratio; it enters through the solve only
+ *   porosity = n_foreground / n_box                               0 for an empty box
+ *   tau = porosity / (D_eff / D0)                                 the tortuosity factor; inf when the flux is 0
+ *   flux mismatch = |Fin_q - Fout_q| / |0.5 (Fin_q + Fout_q)|     0 when both are 0; inf when they differ and their mean is 0
+ *   mean concentration = sum_c_q / (1073741824.0 n_foreground)    0 for an empty set
+ * Components of S that touch neither face are a pure-Neumann problem: they stay at 0.5 up to rounding and carry no flux, because
+ * flux is measured on the two faces only; they do count in the porosity.  vk_label_components with VK_LABEL_KEEP_SEEDS or
+ * KEEP_LARGEST removes them beforehand.  A component that touches one face only settles at that face's concentration.
+ * Outputs.  c_out (may be NULL): nx ny nz float, x fastest.  The dense value of a voxel of S is c(v) * gain (gain == 0 asks for 1),
+ * off S it is fill_out; both go through vk_label_components' fill rule F.  dense_out (may be NULL) and VK_DIFF_INSTALL behave exactly
+ * as vk_geodesic_distance's dense_out and VK_GEO_INSTALL.  Without VK_DIFF_INSTALL no context state changes.  The call blocks, runs
+ * on the context's current stream and allocates and frees its own buffers.
+ * VK_ERR_INVALID, decided before any launch, outputs untouched ("vk_steady_diffusion: ..."), in this order: a NULL request; lo or hi
+ * NaN; lo > hi; an axis above 2; an unknown flag; a spacing of 0 or above VK_DIST_MAX_SPACING; an omega that is not 0 and not inside
+ * (0, 2); check_every outside 1 .. VK_DIFF_MAX_CHECK_EVERY; max_sweeps < check_every; a delta_tol or flux_tol that is negative or not
+ * finite; a gain or fill_out that is not finite; none of c_out, dense_out, VK_DIFF_INSTALL and result requested; then VK_DIFF_INSTALL
+ * while a frame is being recorded; no volume; a box that is inverted or leaves the volume, a box together with VK_DIFF_CLIP_BOX.
+ * VK_ERR_UNSUPPORTED ("diffusion: ..."): a BRICKED / QUADS / STAGED or RGBA16F_PAIR volume; a volume of more than 2^32 - 2 voxels.
+ * VK_ERR_OOM: a buffer cannot be allocated.  A call that fails later may have written its outputs already; the context's volume is
+ * the old one whenever the call does not return VK_OK. */
+#define VK_DIFF_OFF 0x7FC00000u
+#define VK_DIFF_MAX_CHECK_EVERY 1024
+enum { VK_DIFF_CLIP_BOX = 1, VK_DIFF_INSTALL = 2 };
+typedef struct vk_diffusion_request {
+    float    lo, hi;                       /* the value range, formed exactly as vk_label_components forms lo_k, hi_k */
+    uint32_t axis, flags;                  /* 0, 1, 2 for x, y, z; VK_DIFF_CLIP_BOX | VK_DIFF_INSTALL */
+    uint32_t spacing[3];                   /* integer voxel pitch per axis x, y, z: 1 .. VK_DIST_MAX_SPACING */
+    float    omega;                        /* the over-relaxation factor in (0, 2); 0: automatic */
+    uint32_t check_every, max_sweeps;      /* sweeps per block, 1 .. VK_DIFF_MAX_CHECK_EVERY; the most sweeps, >= check_every */
+    float    delta_tol, flux_tol;          /* the two stopping bounds: finite, >= 0 */
+    float    gain, fill_out;               /* the dense value is c * gain (0: 1); the sample value off S */
+} vk_diffusion_request;                    /* 56 bytes */
+typedef struct vk_diffusion_result {
+    uint64_t n_foreground, n_inlet, n_outlet, n_box;
+    int64_t  Fin_q, Fout_q, sum_c_q;
+    uint32_t sweeps, converged;
+    float    delta, omega, gain;
+    uint32_t pad;
+} vk_diffusion_result;                     /* 80 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(vk_diffusion_request) == 56 && sizeof(vk_diffusion_result) == 80, "vk_diffusion_request: 56 bytes, vk_diffusion_result: 80 bytes");
+#else
+_Static_assert(sizeof(vk_diffusion_request) == 56 && sizeof(vk_diffusion_result) == 80, "vk_diffusion_request: 56 bytes, vk_diffusion_result: 80 bytes");
+#endif
+int vk_steady_diffusion(vk_ctx *ctx, const vk_diffusion_request *req, const vk_voxel_box *box, float *c_out, void *dense_out,
+                        vk_diffusion_result *result);
+
 /* The resample pass: a voxel box of the volume the context holds into a volume of caller-chosen dimensions, by
  * one of three rules, optionally mapped into another scalar format -- crop, resize, make isotropic, window 16-bit data into u8 --
  * without a trip through the host.  Every f32 operation below is rounded once; fmaf is fused where written and nowhere else.

@@ -17,6 +17,7 @@ Only the raycast hot path and the host surface that drives it live here (SURVEY.
   thickness  Thickness, thickness_request: the result and the request of Context.local_thickness
   geodesic   Geodesic, geodesic_request, geodesic_path: the result and the request of Context.geodesic_distance, and the path back to a source
   skeleton   Skeleton, skeleton_request: the result and the request of Context.skeletonize
+  diffusion  Diffusion, diffusion_request: the result and the request of Context.steady_diffusion
   resample   resample_request: the request of Context.resample_volume / crop_volume / downsample_volume / isotropic_volume
   dist       tile-parallel multi-GPU frame (one process per GPU, RCCL gather over xGMI)
 """
@@ -39,6 +40,7 @@ from ._native import (FMT_R8_UNORM, FMT_R16_FLOAT, FMT_RGBA16F_PAIR, FMT_R16_UNO
                       VkGeodesicRequest, VkGeodesicResult,
                       SKEL_CURVE, SKEL_KERNEL, SKEL_CLIP_BOX, SKEL_INSTALL, SKEL_FILL_IN, SKEL_OFF, SKEL_ISOLATED, SKEL_END, SKEL_REGULAR, SKEL_JUNCTION, SKEL_LINKS,
                       VkSkeletonRequest, VkSkeletonResult,
+                      DIFF_OFF, DIFF_MAX_CHECK_EVERY, DIFF_CLIP_BOX, DIFF_INSTALL, VkDiffusionRequest, VkDiffusionResult,
                       RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_AREA, RESAMPLE_INSTALL, RESAMPLE_CLIP_BOX, RESAMPLE_WINDOW, RESAMPLE_KEEP_FORMAT, RESAMPLE_MAX_RATIO,
                       VkResampleRequest, VkResampleResult)
 from .camera import Camera
@@ -53,6 +55,7 @@ from .measure import Measurements, measure_request
 from .thickness import Thickness, thickness_request
 from .geodesic import Geodesic, geodesic_path, geodesic_request
 from .skeleton import Skeleton, skeleton_request
+from .diffusion import Diffusion, diffusion_request
 from .resample import resample_request
 from .context import (Context, Demo, FrameCounter, HdrBackBuffer, Hit, ImageDimentions, RaycastPipeline, Uniform,
                       VolumeTexture, dispatch_optimal, partition_slots, render_batch, run_headless, transfer_table, untile_batch)
@@ -78,6 +81,7 @@ __all__ = [
     "VkGeodesicRequest", "VkGeodesicResult", "Geodesic", "geodesic_request", "geodesic_path",
     "SKEL_CURVE", "SKEL_KERNEL", "SKEL_CLIP_BOX", "SKEL_INSTALL", "SKEL_FILL_IN", "SKEL_OFF", "SKEL_ISOLATED", "SKEL_END", "SKEL_REGULAR", "SKEL_JUNCTION", "SKEL_LINKS",
     "VkSkeletonRequest", "VkSkeletonResult", "Skeleton", "skeleton_request",
+    "DIFF_OFF", "DIFF_MAX_CHECK_EVERY", "DIFF_CLIP_BOX", "DIFF_INSTALL", "VkDiffusionRequest", "VkDiffusionResult", "Diffusion", "diffusion_request",
     "RESAMPLE_NEAREST", "RESAMPLE_LINEAR", "RESAMPLE_AREA", "RESAMPLE_INSTALL", "RESAMPLE_CLIP_BOX", "RESAMPLE_WINDOW", "RESAMPLE_KEEP_FORMAT", "RESAMPLE_MAX_RATIO",
     "VkResampleRequest", "VkResampleResult", "resample_request",
 ]

@@ -305,6 +305,27 @@ class VkSkeletonResult(C.Structure):
 assert C.sizeof(VkSkeletonRequest) == 32 and C.sizeof(VkSkeletonResult) == 160
 
 
+DIFF_OFF, DIFF_MAX_CHECK_EVERY = 0x7FC00000, 1024
+DIFF_CLIP_BOX, DIFF_INSTALL = 1, 2
+
+
+class VkDiffusionRequest(C.Structure):
+    """vk_diffusion_request (56 bytes): the request of vk_steady_diffusion -- the value range, the axis (0, 1, 2), the flags, the integer
+    spacing per axis (x, y, z), omega (0: automatic), the sweeps per block and the most sweeps, the two stopping bounds, the gain of the
+    dense value (0: 1) and the fill of a voxel outside the set."""
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("axis", C.c_uint32), ("flags", C.c_uint32), ("spacing", C.c_uint32 * 3), ("omega", C.c_float), ("check_every", C.c_uint32),
+                ("max_sweeps", C.c_uint32), ("delta_tol", C.c_float), ("flux_tol", C.c_float), ("gain", C.c_float), ("fill_out", C.c_float)]
+
+
+class VkDiffusionResult(C.Structure):
+    """vk_diffusion_result (80 bytes): the totals of vk_steady_diffusion, the fluxes of its last block as integers, omega and the gain it used."""
+    _fields_ = [("n_foreground", C.c_uint64), ("n_inlet", C.c_uint64), ("n_outlet", C.c_uint64), ("n_box", C.c_uint64), ("Fin_q", C.c_int64), ("Fout_q", C.c_int64),
+                ("sum_c_q", C.c_int64), ("sweeps", C.c_uint32), ("converged", C.c_uint32), ("delta", C.c_float), ("omega", C.c_float), ("gain", C.c_float), ("pad", C.c_uint32)]
+
+
+assert C.sizeof(VkDiffusionRequest) == 56 and C.sizeof(VkDiffusionResult) == 80
+
+
 RESAMPLE_NEAREST, RESAMPLE_LINEAR, RESAMPLE_AREA = 0, 1, 2
 RESAMPLE_INSTALL, RESAMPLE_CLIP_BOX, RESAMPLE_WINDOW = 1, 2, 4
 RESAMPLE_KEEP_FORMAT = -1
@@ -390,6 +411,7 @@ SYMBOLS = {
     "vk_local_thickness": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_thickness_request *, const vk_voxel_box *, t2_out, dense_out, vk_thickness_result *
     "vk_geodesic_distance": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_geodesic_request *, const vk_voxel_box *, g_out, dense_out, vk_geodesic_result *
     "vk_skeletonize": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_skeleton_request *, const vk_voxel_box *, class_out, dense_out, vk_skeleton_result *
+    "vk_steady_diffusion": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),  # const vk_diffusion_request *, const vk_voxel_box *, c_out, dense_out, vk_diffusion_result *
     "vk_volume_resample": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, dense_out, vk_resample_result *
     "vk_resample_output": (C.c_int, [_vp, _vp, _vp, _vp]),  # const vk_resample_request *, const vk_voxel_box *, vk_resample_result *: the output's extents, format, layout and box, nothing launched
     "vk_volume_info": (C.c_int, [_vp, C.POINTER(_u32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_sz)]),

@@ -804,6 +804,38 @@ class Context:
                                                       dense.ctypes.data if dense is not None else None, C.byref(res)))
         return Geodesic(res, spacing, extent, arr, dense)
 
+    # -- steady-state diffusion through a value range: effective diffusivity, tortuosity factor (vk_steady_diffusion)
+    def steady_diffusion(self, lo, hi=float("inf"), axis="z", spacing=(1, 1, 1), omega: float = 0.0, check_every: int = 32, delta_tol: float = 1e-5, flux_tol: float = 1e-3,
+                         max_sweeps: int = 20000, gain: float = 0.0, fill_out: float = 0.0, box=None, install: bool = False, out: bool = False, c: bool = False):
+        """vk_steady_diffusion: the Laplace equation on the set S of voxels whose stored texel lies in [lo, hi] (inside box: None, "clip" or
+        ((x0, y0, z0), (x1, y1, z1))), with no-flux walls, concentration 1 on the box's first plane along `axis` ("x", "y", "z") and 0 on its
+        last, by red-black over-relaxation in float32 with the integer voxel pitch `spacing`.  omega: 0 picks the factor from the extent
+        along the axis; sweeps run in blocks of check_every until the largest change of a sweep is <= delta_tol and the fluxes through the
+        two faces agree to flux_tol (relative), or until max_sweeps.  The dense map stores c * gain (gain 0: 1) on S and fill_out
+        elsewhere; install (default False: the product is a number): it replaces the context's volume (outside frame_begin / frame_end).
+        Returns a Diffusion: porosity, flux, flux_mismatch, effective_diffusivity (D_eff / D0), tortuosity_factor, mean_concentration,
+        converged, sweeps and the raw totals, with c=True .c (float32 [nz, ny, nx], NaN off S), with out=True .dense [nz, ny, nx].
+        Blocks."""
+        from .diffusion import Diffusion, diffusion_request
+        from .label import voxel_box
+
+        req = diffusion_request(lo, hi, axis=axis, spacing=spacing, omega=omega, check_every=check_every, delta_tol=delta_tol, flux_tol=flux_tol, max_sweeps=max_sweeps, gain=gain,
+                                fill_out=fill_out, box=box, install=install)
+        vb = voxel_box(box)
+        dims, _ = self._volume_dtype()
+        extent = dims
+        if vb is not None:
+            extent = (vb.x1 - vb.x0, vb.y1 - vb.y0, vb.z1 - vb.z0)
+        elif box == "clip" and self.clip_box is not None:  # the voxels whose centre lies in the clip box, as the library counts them
+            cl, ch = self.clip_box
+            extent = tuple(sum(1 for i in range(n) if float(np.float32(l)) <= (i + 0.5) / n <= float(np.float32(h))) for l, h, n in zip(cl, ch, dims))
+        arr = np.zeros((dims[2], dims[1], dims[0]), np.float32) if c else None
+        dense = self._dense_out() if out else None
+        res = N.VkDiffusionResult()
+        N.check(self._h, N.lib().vk_steady_diffusion(self._h, C.byref(req), C.byref(vb) if vb is not None else None, arr.ctypes.data if arr is not None else None,
+                                                     dense.ctypes.data if dense is not None else None, C.byref(res)))
+        return Diffusion(res, req.axis, extent, arr, dense)
+
     # -- skeleton of a value range: topology-preserving thinning to centre lines (vk_skeletonize)
     def skeletonize(self, lo, hi=float("inf"), mode: str = "curve", max_iterations: int = 0, fill_in=None, fill_out: float = 0.0, box=None, install: bool = True, classes: bool = False,
                     out: bool = False):

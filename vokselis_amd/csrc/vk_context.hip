@@ -572,6 +572,9 @@ int vk_debug_set_param(vk_ctx *ctx, const char *name, double value) {
     else if (n == "geo_timing") ctx->geo_timing = (uint32_t)value;                // ... k: the call times its k-th phase alone (vk_timer_elapsed_ms); 9: round counts as the last message
     else if (n == "skel_max_blocks") ctx->skel_max_blocks = (uint32_t)value;      // vk_skeletonize: cap of its grids (0: none)
     else if (n == "skel_timing") ctx->skel_timing = (uint32_t)value;              // ... k: the call times its k-th phase alone (vk_timer_elapsed_ms); 9: iteration counts as the last message
+    else if (n == "diff_max_blocks") ctx->diff_max_blocks = (uint32_t)value;      // vk_steady_diffusion: cap of its grids (0: none)
+    else if (n == "diff_timing") ctx->diff_timing = (uint32_t)value;              // ... k: the call times its k-th phase alone (vk_timer_elapsed_ms); 9: block counts as the last message
+    else if (n == "diff_lds") ctx->diff_lds = (uint32_t)value;                    // ... 1: the sweeps stage their tiles in LDS (measurements, tests)
     else if (n == "resample_max_blocks") ctx->resample_max_blocks = (uint32_t)value;  // vk_volume_resample: cap of the grid (0: none)
     else if (n == "resample_area_passes") ctx->resample_area_passes = (uint32_t)value;  // ... 1: AREA as three axis passes (measurements, tests)
     else if (n == "resample_area_unroll") ctx->resample_area_unroll = (uint32_t)value;  // ... 0: no unrolled footprint at ratios 2 .. 4 (measurements, tests)

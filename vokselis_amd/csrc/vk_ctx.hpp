@@ -185,6 +185,9 @@ struct vk_ctx {
     uint32_t geo_timing = 0;         // ... k (measurements): the call brackets its k-th phase with the timer's events; 9: it leaves its round counts as the last message (vk_launch_geo.hip)
     uint32_t skel_max_blocks = 0;    // vk_skeletonize: cap of its grids (0: none) -- lets a small volume drive the grid-stride loops over tiles and voxels
     uint32_t skel_timing = 0;        // ... k (measurements): the call brackets its k-th phase with the timer's events; 9: it leaves its iteration counts as the last message (vk_launch_skel.hip)
+    uint32_t diff_max_blocks = 0;    // vk_steady_diffusion: cap of its grids (0: none) -- lets a small volume drive the grid-stride loops over tiles, voxels and face voxels
+    uint32_t diff_timing = 0;        // ... k (measurements): the call brackets its k-th phase with the timer's events; 9: it leaves its block counts as the last message (vk_launch_diff.hip)
+    uint32_t diff_lds = 0;           // ... 1 (measurements, tests): the sweeps stage each tile and its halo in LDS instead of loading neighbours from global memory; the same bits
     uint32_t resample_max_blocks = 0;  // vk_volume_resample: cap of the grid (0: none) -- lets a small volume drive the loop over tiles
     uint32_t resample_area_passes = 0; // ... 1 (measurements, tests): AREA as three axis passes through f32 intermediates instead of the fused footprint loop
     uint32_t resample_area_unroll = 1; // ... 0 (measurements, tests): AREA by an integer ratio of 2 .. 4 runs the table-driven footprint loops, not the unrolled ones

@@ -97,6 +97,12 @@
 //                                                            voxel takes the sample value of --label-fill (default 0).  Runs after --geodesic, as the last step that
 //                                                            replaces the volume; prints foreground, skeleton voxels, ends, junctions, isolated voxels and the length in
 //                                                            the units of --morph-spacing; --save-raw writes the skeleton
+//          [--diffusion AXIS [MAX_SWEEPS]] [--diffusion-install]   steady-state diffusion through that range (vk_steady_diffusion): the Laplace equation on the range with no-flux
+//                                                            walls, concentration 1 on the first plane along AXIS (x y z) and 0 on the last, in the pitch of
+//                                                            --morph-spacing, at most MAX_SWEEPS sweeps (default 20000).  Runs after --skeleton, as the last analysing
+//                                                            step; prints foreground, porosity, sweeps, "converged yes|no", the flux in and out, D_eff/D0 and the
+//                                                            tortuosity factor.  --diffusion-install: the concentration field replaces the volume (every voxel outside
+//                                                            the range takes --label-fill), so that --tf renders it and --save-raw writes it
 //          [--camera-blobs orbits.txt out.bin]              no GPU: one 144-byte CameraUniform per "zoom pitch yaw tx ty tz aspect" line
 #include <cstdio>
 #include <algorithm>
@@ -176,6 +182,8 @@ static int g_geo_axis = 0;                                                      
 static std::vector<std::array<uint32_t, 3>> g_geo_seeds;
 static bool g_skel_on = false;                                                   // --skeleton [curve|kernel] [MAX_ITER] (vk_skeletonize), on the same range
 static uint32_t g_skel_mode = VK_SKEL_CURVE, g_skel_max_iter = 0;
+static bool g_diff_on = false, g_diff_install = false, g_diff_save = false;      // --diffusion AXIS [MAX_SWEEPS], --diffusion-install (vk_steady_diffusion), on the same range; save: it fills --save-raw's file
+static uint32_t g_diff_axis = 0, g_diff_max_sweeps = 20000;
 static bool label_ops() { return !g_keep_largest.empty() || !g_drop_islands.empty() || !g_keep_voxels.empty() || !g_remove_voxels.empty() || !g_keep_picks.empty(); }
 
 // the context of a run that replaces the render: 8 x 8, or the frame's size under the render's camera when --keep-pick casts rays through it
@@ -195,7 +203,7 @@ static void apply_morph(Context &ctx) {
     int fmt = 0;
     check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !label_ops() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !label_ops() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on && !g_diff_save) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     const float fill_in = g_morph_fill_on ? g_morph_fill[0] : (std::isfinite(g_label_hi) ? g_label_hi : (std::isfinite(g_label_lo) ? std::max(g_label_lo, 1.0f) : 1.0f));
     for (size_t k = 0; k < g_morph.size(); k++) {
         const MorphOp &op = g_morph[k];
@@ -214,7 +222,7 @@ static void apply_split(Context &ctx) {
     int fmt = 0;
     check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !label_ops() && !g_thick_on && !g_geo_on && !g_skel_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !label_ops() && !g_thick_on && !g_geo_on && !g_skel_on && !g_diff_save) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     const Regions r = ctx.split_components(g_label_lo, g_label_hi, g_split_radius, g_morph_spacing, g_split_conn, nullptr, false, false, g_label_fill, true, dense.empty() ? nullptr : dense.data());
     std::printf("split: [%g, %g] radius %g connectivity %u: %llu regions (%llu markers of %llu voxels, %llu unreached regions of %llu voxels), %llu foreground voxels, %llu cut, %u rounds\n",
                 g_label_lo, g_label_hi, g_split_radius, g_split_conn, (unsigned long long)r.totals.n_regions, (unsigned long long)r.totals.n_markers, (unsigned long long)r.totals.n_marker_voxels,
@@ -270,7 +278,7 @@ static void apply_labels(Context &ctx) {
     for (uint64_t n : g_drop_islands) ops.push_back({"drop-islands", VK_LABEL_KEEP_MIN_SIZE, n, &none, false});
     for (uint64_t k : g_keep_largest) ops.push_back({"keep-largest", VK_LABEL_KEEP_LARGEST, k, &none, false});
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !g_thick_on && !g_geo_on && !g_skel_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !g_thick_on && !g_geo_on && !g_skel_on && !g_diff_save) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     for (size_t k = 0; k < ops.size(); k++) {
         const Op &op = ops[k];
         const vk_label_result r = ctx.keep_components(g_label_lo, g_label_hi, op.keep, op.count, *op.seeds, op.invert, g_label_fill, g_label_conn, nullptr, false, true,
@@ -307,7 +315,7 @@ static void apply_thickness(Context &ctx) {
     int fmt = 0;
     check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !g_geo_on && !g_skel_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !g_geo_on && !g_skel_on && !g_diff_save) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     const vk_thickness_result r = ctx.local_thickness(g_label_lo, g_label_hi, g_thick_radius, g_morph_spacing, nullptr, false, g_thick_gain, g_label_fill, true, dense.empty() ? nullptr : dense.data());
     std::printf("thickness: [%g, %g] cap %g spacing %u %u %u: %llu foreground voxels, largest thickness %.6g, %llu saturated voxels, gain %.9g\n", g_label_lo, g_label_hi, g_thick_radius,
                 g_morph_spacing[0], g_morph_spacing[1], g_morph_spacing[2], (unsigned long long)r.n_foreground, Context::thickness_of(r.max_t2), (unsigned long long)r.n_saturated, r.gain);
@@ -321,7 +329,7 @@ static void apply_geodesic(Context &ctx) {
     int fmt = 0;
     check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !g_skel_on) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !g_skel_on && !g_diff_save) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     const uint32_t conn = g_label_conn_on ? g_label_conn : 26u;
     const vk_geodesic_result r = ctx.geodesic_distance(g_label_lo, g_label_hi, g_geo_sources, g_geo_targets, g_geo_seeds, conn, g_morph_spacing, nullptr, false, 0.0f, g_label_fill, g_label_fill, true,
                                                        dense.empty() ? nullptr : dense.data());
@@ -347,7 +355,7 @@ static void apply_skeleton(Context &ctx) {
     int fmt = 0;
     check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty()) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    if (!g_save_raw.empty() && !g_diff_save) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
     const vk_skeleton_result r = ctx.skeletonize(g_label_lo, g_label_hi, g_skel_mode, g_skel_max_iter, nullptr, false, nullptr, g_label_fill, true, dense.empty() ? nullptr : dense.data());
     std::printf("skeleton: [%g, %g] %s spacing %u %u %u: %llu foreground voxels, %llu skeleton voxels, %llu ends, %llu junctions, %llu isolated voxels, length %.6g, %u iterations%s\n", g_label_lo,
                 g_label_hi, g_skel_mode == VK_SKEL_KERNEL ? "kernel" : "curve", g_morph_spacing[0], g_morph_spacing[1], g_morph_spacing[2], (unsigned long long)r.n_foreground,
@@ -356,12 +364,29 @@ static void apply_skeleton(Context &ctx) {
     if (!dense.empty()) write_dense(dense, "skeleton");
 }
 
+// --diffusion, after --skeleton: the last analysing step; with --diffusion-install it replaces the volume and takes over --save-raw's file
+static void apply_diffusion(Context &ctx) {
+    if (!g_diff_on) return;
+    uint32_t dims[3] = {0, 0, 0};
+    int fmt = 0;
+    check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
+    std::vector<unsigned char> dense;
+    if (g_diff_save) dense.resize((size_t)dims[0] * dims[1] * dims[2] * (fmt == VK_FMT_R8_UNORM ? 1u : 2u));
+    const vk_diffusion_result r = ctx.steady_diffusion(g_label_lo, g_label_hi, g_diff_axis, g_morph_spacing, 0.0f, 32u, 1e-5f, 1e-3f, g_diff_max_sweeps < 32u ? 32u : g_diff_max_sweeps, nullptr, false, 0.0f,
+                                                       g_label_fill, g_diff_install, dense.empty() ? nullptr : dense.data());
+    const Context::DiffusionValues v = Context::diffusion_values(r, g_diff_axis, dims);
+    std::printf("diffusion: [%g, %g] along %c spacing %u %u %u: %llu foreground voxels, porosity %.6g, %u sweeps, converged %s, flux in %.6g out %.6g, D_eff/D0 %.6g, tortuosity factor %.6g\n", g_label_lo,
+                g_label_hi, "xyz"[g_diff_axis], g_morph_spacing[0], g_morph_spacing[1], g_morph_spacing[2], (unsigned long long)r.n_foreground, v.porosity, r.sweeps, r.converged ? "yes" : "no", v.flux_in,
+                v.flux_out, v.effective_diffusivity, v.tortuosity_factor);
+    if (!dense.empty()) write_dense(dense, "diffusion");
+}
+
 // --crop, --resample, --downsample, --isotropic, --to-u8, --to-u16 in the order given, right after the volume is loaded; the last of them fills --save-raw's
 // file unless a filter, a --morph or a keep flag follows
 static void apply_resample(Context &ctx) {
     if (g_resample.empty()) return;
     static const char *const fmt_name[] = {"R8_UNORM", "R16_FLOAT", "RGBA16F_PAIR", "R16_UNORM"};
-    const bool save = !g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on;
+    const bool save = !g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on && !g_diff_save;
     std::vector<unsigned char> dense;
     for (size_t k = 0; k < g_resample.size(); k++) {
         const ResampleOp &op = g_resample[k];
@@ -387,9 +412,9 @@ static void apply_resample(Context &ctx) {
 // --median, then --smooth, once the volume is there and before anything reads it; the last of them also fills --save-raw's file (unless a keep flag follows)
 static void apply_filters(Context &ctx) {
     apply_resample(ctx);
-    if (!g_median && !g_smooth) { apply_labels(ctx); apply_measure(ctx); apply_thickness(ctx); apply_geodesic(ctx); apply_skeleton(ctx); return; }
+    if (!g_median && !g_smooth) { apply_labels(ctx); apply_measure(ctx); apply_thickness(ctx); apply_geodesic(ctx); apply_skeleton(ctx); apply_diffusion(ctx); return; }
     std::vector<unsigned char> dense;
-    if (!g_save_raw.empty() && !label_ops() && g_morph.empty() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on) {
+    if (!g_save_raw.empty() && !label_ops() && g_morph.empty() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on && !g_diff_save) {
         uint32_t dims[3] = {0, 0, 0};
         int fmt = 0;
         check(ctx.handle(), vk_volume_info(ctx.handle(), dims, &fmt, nullptr, nullptr));
@@ -404,6 +429,7 @@ static void apply_filters(Context &ctx) {
     apply_thickness(ctx);
     apply_geodesic(ctx);
     apply_skeleton(ctx);
+    apply_diffusion(ctx);
 }
 
 // --tf PATH: the whole file as little-endian f32 RGBA rows (the library checks n, finiteness and alpha)
@@ -969,6 +995,21 @@ int main(int argc, char **argv) {
                 g_skel_max_iter = (uint32_t)k;
             }
         }
+        else if (a == "--diffusion") {
+            if (g_diff_on) { std::fprintf(stderr, "bonsai: --diffusion: at most once\n"); return 2; }
+            g_diff_on = true;
+            const std::string axis = next();
+            if (axis != "x" && axis != "y" && axis != "z") { std::fprintf(stderr, "bonsai: --diffusion AXIS [MAX_SWEEPS]: AXIS is x, y or z\n"); return 2; }
+            g_diff_axis = (uint32_t)(axis[0] - 'x');
+            if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) {
+                const char *v = next();
+                char *end = nullptr;
+                const long long k = std::strtoll(v, &end, 10);
+                if (end == v || *end != '\0' || k < 32 || k > 0xffffffffll) { std::fprintf(stderr, "bonsai: --diffusion AXIS [MAX_SWEEPS]: MAX_SWEEPS is an integer >= 32 (a block of sweeps)\n"); return 2; }
+                g_diff_max_sweeps = (uint32_t)k;
+            }
+        }
+        else if (a == "--diffusion-install") g_diff_install = true;
         else if (a == "--measure") {
             g_measure_on = true;
             if (i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0) g_measure_csv = next();
@@ -1008,7 +1049,7 @@ int main(int argc, char **argv) {
     if (!mesh_path.empty() && (sl.on || hist || gpus > 0 || g_auto_window)) { std::fprintf(stderr, "bonsai: --mesh replaces the render: no --slice, --slice-plane, --histogram, --gpus or --auto-window\n"); return 2; }
     if (label_ops() && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel and --keep-pick need a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
     if (!g_keep_picks.empty() && !g_iso_on) { std::fprintf(stderr, "bonsai: --keep-pick needs --iso (the ray stops at the isosurface)\n"); return 2; }
-    if (g_label_fill_on && !label_ops() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on) { std::fprintf(stderr, "bonsai: --label-fill needs a flag that drops voxels: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel or --keep-pick\n"); return 2; }
+    if (g_label_fill_on && !label_ops() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on && !(g_diff_on && g_diff_install)) { std::fprintf(stderr, "bonsai: --label-fill needs a flag that drops voxels: --keep-largest, --drop-islands, --keep-voxel, --remove-voxel or --keep-pick\n"); return 2; }
     if (g_keep_voxels.size() + g_keep_picks.size() > 16u) { std::fprintf(stderr, "bonsai: --keep-voxel and --keep-pick: at most 16 seeds together\n"); return 2; }
     if ((g_components || label_ops()) && gpus > 0) { std::fprintf(stderr, "bonsai: --components and the keep flags run on one GPU\n"); return 2; }
     if (!g_morph.empty() && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --morph needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
@@ -1025,14 +1066,18 @@ int main(int argc, char **argv) {
     if (g_geo_on && gpus > 0) { std::fprintf(stderr, "bonsai: --geodesic runs on one GPU\n"); return 2; }
     if (g_skel_on && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --skeleton needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
     if (g_skel_on && gpus > 0) { std::fprintf(stderr, "bonsai: --skeleton runs on one GPU\n"); return 2; }
-    if (((g_morph_spacing_on && !g_split_on && !g_measure_on && !g_thick_on && !g_geo_on && !g_skel_on) || g_morph_fill_on) && g_morph.empty()) { std::fprintf(stderr, "bonsai: %s needs --morph\n", g_morph_spacing_on ? "--morph-spacing" : "--morph-fill"); return 2; }
+    if (g_diff_install && !g_diff_on) { std::fprintf(stderr, "bonsai: --diffusion-install needs --diffusion AXIS\n"); return 2; }
+    if (g_diff_on && !g_components && !g_iso_on) { std::fprintf(stderr, "bonsai: --diffusion needs a value range: --components LO HI, or --iso V for [V, inf)\n"); return 2; }
+    if (g_diff_on && gpus > 0) { std::fprintf(stderr, "bonsai: --diffusion runs on one GPU\n"); return 2; }
+    g_diff_save = g_diff_on && g_diff_install && !g_save_raw.empty();
+    if (((g_morph_spacing_on && !g_split_on && !g_measure_on && !g_thick_on && !g_geo_on && !g_skel_on && !g_diff_on) || g_morph_fill_on) && g_morph.empty()) { std::fprintf(stderr, "bonsai: %s needs --morph\n", g_morph_spacing_on ? "--morph-spacing" : "--morph-fill"); return 2; }
     if (!g_morph.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --morph runs on one GPU\n"); return 2; }
-    if ((label_ops() || !g_morph.empty() || g_split_on || g_measure_on || g_thick_on || g_geo_on || g_skel_on) && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
+    if ((label_ops() || !g_morph.empty() || g_split_on || g_measure_on || g_thick_on || g_geo_on || g_skel_on || g_diff_on) && !g_components) { g_label_lo = g_iso.iso; g_label_hi = INFINITY; g_label_conn = 6; }
     g_w = w; g_h = h;
     if (!g_resample.empty() && gpus > 0) { std::fprintf(stderr, "bonsai: --crop, --resample, --downsample, --isotropic, --to-u8 and --to-u16 run on one GPU\n"); return 2; }
     for (const ResampleOp &op : g_resample)
         if (op.kind == ResampleOp::CROP_CLIP && !g_clip_on) { std::fprintf(stderr, "bonsai: --crop clip needs --clip\n"); return 2; }
-    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && g_resample.empty() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
+    if (!g_save_raw.empty() && !g_median && !g_smooth && !label_ops() && g_morph.empty() && g_resample.empty() && !g_split_on && !g_thick_on && !g_geo_on && !g_skel_on && !g_diff_save) { std::fprintf(stderr, "bonsai: --save-raw writes the filtered volume: it needs --median or --smooth\n"); return 2; }
     if ((g_median || g_smooth) && gpus > 0) { std::fprintf(stderr, "bonsai: --median and --smooth run on one GPU\n"); return 2; }
     if (hist) return run_histogram(hist_bins, hist_lo, hist_hi);
     if (!mesh_path.empty()) return run_mesh(mesh_path, mesh_obj, mesh_iso_on ? mesh_iso : g_iso.iso, mesh_scale);

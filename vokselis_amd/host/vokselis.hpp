@@ -761,6 +761,38 @@ class Context {
         check(ctx_, vk_skeletonize(ctx_, &req, box, class_out, dense_out, &res));
         return res;
     }
+    // Steady-state diffusion (vk_steady_diffusion; blocks): the Laplace equation on S = the voxels in [lo, hi], no-flux walls, concentration 1 on the box's first
+    // plane along axis (0, 1, 2) and 0 on its last, by red-black over-relaxation in float32 with the integer pitch spacing (nullptr: 1 1 1).  omega: 0 picks
+    // the factor from the extent along the axis; sweeps run in blocks of check_every until the largest change of a block's last sweep is <= delta_tol and the
+    // two faces' fluxes agree to flux_tol, or until max_sweeps (converged == 0).  The dense map stores c * gain (gain 0: 1) on S and fill_out elsewhere.
+    // install (default false: the product is a number): it replaces the context's volume (outside frame_begin / frame_end); dense_out: nullptr, or host
+    // memory of nx ny nz elements of the volume's format; c_out: nullptr, or nx ny nz floats (the bits VK_DIFF_OFF off S).
+    vk_diffusion_result steady_diffusion(float lo, float hi = INFINITY, uint32_t axis = 2u, const uint32_t *spacing = nullptr, float omega = 0.0f, uint32_t check_every = 32u,
+                                         float delta_tol = 1e-5f, float flux_tol = 1e-3f, uint32_t max_sweeps = 20000u, const vk_voxel_box *box = nullptr, bool clip = false, float gain = 0.0f,
+                                         float fill_out = 0.0f, bool install = false, void *dense_out = nullptr, float *c_out = nullptr) {
+        vk_diffusion_request req{};
+        req.lo = lo; req.hi = hi; req.axis = axis; req.omega = omega; req.check_every = check_every; req.max_sweeps = max_sweeps; req.delta_tol = delta_tol; req.flux_tol = flux_tol;
+        req.gain = gain; req.fill_out = fill_out;
+        req.flags = (clip ? (uint32_t)VK_DIFF_CLIP_BOX : 0u) | (install ? (uint32_t)VK_DIFF_INSTALL : 0u);
+        for (int c = 0; c < 3; c++) req.spacing[c] = spacing ? spacing[c] : 1u;
+        vk_diffusion_result res{};
+        check(ctx_, vk_steady_diffusion(ctx_, &req, box, c_out, dense_out, &res));
+        return res;
+    }
+    // What the header derives from a result, in double.  extent: the box's extents x, y, z (the volume's dimensions without a box).
+    struct DiffusionValues { double flux, flux_in, flux_out, flux_mismatch, porosity, effective_diffusivity, tortuosity_factor, mean_concentration; };
+    static DiffusionValues diffusion_values(const vk_diffusion_result &r, uint32_t axis, const uint32_t extent[3]) {
+        DiffusionValues d{};
+        const double fi = (double)r.Fin_q, fo = (double)r.Fout_q, mean = 0.5 * (fi + fo);
+        d.flux_in = fi / 1073741824.0; d.flux_out = fo / 1073741824.0; d.flux = (fi + fo) / 2147483648.0;
+        d.flux_mismatch = mean != 0.0 ? std::fabs(fi - fo) / std::fabs(mean) : (fi != fo ? INFINITY : 0.0);
+        d.porosity = r.n_box ? (double)r.n_foreground / (double)r.n_box : 0.0;
+        const double cross = (double)extent[(axis + 1u) % 3u] * (double)extent[(axis + 2u) % 3u];
+        d.effective_diffusivity = cross > 0.0 ? d.flux * (double)extent[axis] / cross : 0.0;
+        d.tortuosity_factor = d.effective_diffusivity > 0.0 ? d.porosity / d.effective_diffusivity : INFINITY;
+        d.mean_concentration = r.n_foreground ? (double)r.sum_c_q / (1073741824.0 * (double)r.n_foreground) : 0.0;
+        return d;
+    }
     // sum_j links[j] sqrt(sum_c (spacing[c] d_c)^2) over the 13 offsets above the centre: the centre-line length in the units of the spacing (nullptr: 1 1 1).
     // Every adjacent pair counts, so the sum over-counts inside junction clumps.
     static double skeleton_length(const vk_skeleton_result &r, const uint32_t *spacing = nullptr) {
